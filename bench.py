@@ -18,12 +18,23 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.  Started bare wi
 environment itself -- before it has touched HIP in any way -- waits for them and
 exits non-zero if any of them fails; it never creates an engine and never re-execs.
 
-Extra objects on the same line:
+A plain run sets up, warms up, times the K steps and prints the line (headline `value`,
+`ms_per_step`, the workload and the device); nothing else is measured or checked.
+
+    --dump-outputs DIR  after the timed steps, write what the last timed step computed
+                        (mean, var, logml, status of every problem; ranks in order) as
+                        DIR/<name>.npy in float64.  The inputs are seeded: the same arguments
+                        give the same inputs, so two builds compare output for output.
+    --full              everything else, as extra objects on the same line:
+
+    parity        problem 0 against the CPU oracle (a failure voids `value`)
+    host_issue, ms_per_step_with_readback, n1_same_workload (N > 1), scale_point and
+                  ms_per_step_host_buffers (N = 1), probes
     roofline      the dominant kernel class of the timed workload
     rooflines     the two north-star lines: N=16384 Cholesky trailing update
-                  (fp64 MFMA) and N=4096 / N=16384 Gram build (HBM)
+                  (fp64 MFMA) and N=4096 / N=16384 Gram build (HBM)  [not with --no-extras]
     cpu_baseline  the CPU oracle (a port, OpenMP) on a bounded sample of the
-                  same workload, rank 0, N=1 only
+                  same workload, rank 0, N=1 only  [not with --no-cpu-baseline]
 """
 import argparse
 import json
@@ -127,13 +138,20 @@ def parse():
     ap.add_argument("--curve-batch", type=int, default=0,
                     help="problems per GPU of the scaling-curve workload (C5 shard) measured as "
                          "scale_point at N = 1 (0 = --batch when the workload is c5, else 64)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C3/C4 roofline runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the diagnostics, parity check, rooflines and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the C3/C4 roofline runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--nb", type=int, default=0, help="outer Cholesky block override")
     ap.add_argument("--inproc", action="store_true",
                     help="N > 1 in ONE process: an engine per device, a host thread each "
                          "(EnginePool), nothing spawned")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.workload is None:
         a.workload = "c2" if a.gpus == 1 else "c5"
     if not a.curve_batch:
@@ -309,14 +327,14 @@ def host_buffer_step(eng, wk, reps=10):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
-def run_main(eng, wk, steps, warmup, dist):
+def run_main(eng, wk, steps, warmup, dist, full):
     plan = eng.plan(wk["B"], wk["d"], wk["n"], wk["M"])
     plan.set_inputs(wk["x"], wk["y"], wk["xo"], wk["h"], wk["w"], wk["s"])
     for _ in range(warmup):
         plan.run()
     eng.sync()
     solo_ms = None
-    if dist.world > 1:
+    if full and dist.world > 1:
         # the N = 1 reference of the scaling line, in the same run: rank 0 passes over ITS
         # shard alone while the other ranks wait at the barrier (a few steps, untimed region)
         if dist.rank == 0:
@@ -341,6 +359,17 @@ def run_main(eng, wk, steps, warmup, dist):
                          "ms_per_step": (t1 - t0) / steps * 1e3,
                          "ms_per_step_hip_events": ev_ms / steps, "pid": os.getpid()})
     mean, var, logml, status = plan.results()
+    out = dict(wall=wall, ev_ms=ev_ms, mean=mean, var=var, logml=logml, status=status,
+               plan_bytes=plan.nbytes(), ranks=ranks, solo_ms=solo_ms)
+    if full:
+        out.update(step_diagnostics(eng, plan, steps, dist))
+    plan.close()
+    return out
+
+
+def step_diagnostics(eng, plan, steps, dist):
+    """--full: host issue time, steps with read-back and the per-class launch profile of the
+    plan just timed (more passes after the timed region; its outputs are already read)."""
     # host issue time of a step: how long the calls take to RETURN (nothing waited for), against
     # the device time of the same steps -- with N contexts driven from one node's cores the
     # launch rate must stay below the device's pace (VERDICT r03 item 9)
@@ -374,11 +403,30 @@ def run_main(eng, wk, steps, warmup, dist):
         prof[k]["ms"] /= ninstr
         prof[k]["work"] /= ninstr
         prof[k]["launches"] //= ninstr
-    nbytes = plan.nbytes()
-    plan.close()
-    return dict(wall=wall, ev_ms=ev_ms, rb_ms=rb_ms, prof=prof, mean=mean, var=var, logml=logml,
-                status=status, plan_bytes=nbytes, ranks=ranks, solo_ms=solo_ms,
-                ranks_issue=ranks_issue)
+    return dict(rb_ms=rb_ms, prof=prof, ranks_issue=ranks_issue)
+
+
+# --dump-outputs: at most this many bytes in all; a larger job writes a fixed, seeded sample of
+# its problems (every output of each problem kept) and their indices as problem_index.npy
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, parts):
+    """Write the outputs of the last timed step as DIR/<name>.npy (float64).  `parts`: one
+    (mean, var, logml, status) per rank, in rank order; problems are concatenated."""
+    names = ("mean", "var", "logml", "status")
+    arrs = {n: np.concatenate([np.asarray(p[i], dtype=np.float64) for p in parts])
+            for i, n in enumerate(names)}
+    nprob = arrs["logml"].shape[0]
+    per_problem = sum(a.nbytes for a in arrs.values()) // max(1, nprob)
+    if per_problem * nprob > DUMP_LIMIT_BYTES:
+        k = max(1, (DUMP_LIMIT_BYTES - 4096) // (per_problem + 8))  # (.npy headers, index)
+        idx = np.sort(np.random.RandomState(0).choice(nprob, k, replace=False))
+        arrs = {n: a[idx] for n, a in arrs.items()}
+        arrs["problem_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrs.items():
+        np.save(os.path.join(dirname, n + ".npy"), a)
 
 
 def parity_spotcheck(wk, res):
@@ -999,7 +1047,7 @@ def inproc_main(a):
             # the N = 1 point of the curve in the same run: rank 0 alone, the others wait
             solo_ms = None
             barrier.wait(timeout=600)
-            if rank == 0:
+            if a.full and rank == 0:
                 k = max(3, min(a.steps, 10))
                 eng.timer_start()
                 for _ in range(k):
@@ -1013,20 +1061,23 @@ def inproc_main(a):
             t1 = time.perf_counter()
             barrier.wait(timeout=600)
             mean, var, logml, status = plan.results()
-            # host issue time of a step beside its device time, all ranks' threads at once
-            ki = max(2, min(a.steps, 10))
-            barrier.wait(timeout=600)
-            ti0 = time.perf_counter()
-            for _ in range(ki):
-                plan.run()
-            ti1 = time.perf_counter()
-            eng.sync()
-            ti2 = time.perf_counter()
+            out = dict(rank=rank, device=eng.device, t0=t0, t1=t1, wk=wk, mean=mean, var=var,
+                       logml=logml, status=status, info=eng.info() if rank == 0 else None,
+                       solo_ms=solo_ms)
+            if a.full:
+                # host issue time of a step beside its device time, all ranks' threads at once
+                ki = max(2, min(a.steps, 10))
+                barrier.wait(timeout=600)
+                ti0 = time.perf_counter()
+                for _ in range(ki):
+                    plan.run()
+                ti1 = time.perf_counter()
+                eng.sync()
+                ti2 = time.perf_counter()
+                out.update(host_issue_ms_per_step=(ti1 - ti0) / ki * 1e3,
+                           device_ms_per_step=(ti2 - ti0) / ki * 1e3)
             plan.close()
-            return dict(rank=rank, device=eng.device, t0=t0, t1=t1, wk=wk, mean=mean, var=var,
-                        logml=logml, status=status, info=eng.info() if rank == 0 else None,
-                        solo_ms=solo_ms, host_issue_ms_per_step=(ti1 - ti0) / ki * 1e3,
-                        device_ms_per_step=(ti2 - ti0) / ki * 1e3)
+            return out
 
         def run(eng):
             # a rank that fails before a barrier (allocation, inputs, a HIP error on its device)
@@ -1047,6 +1098,8 @@ def inproc_main(a):
         pool.close()
         sys.exit(1)
     pool.close()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, [(r["mean"], r["var"], r["logml"], r["status"]) for r in res])
     wall = max(r["t1"] for r in res) - min(r["t0"] for r in res)
     wk = res[0]["wk"]
     nfail = int(sum((r["status"] != 0).sum() for r in res))
@@ -1062,19 +1115,121 @@ def inproc_main(a):
                    "launch_mode": "inproc: one process, an engine and a host thread per device",
                    "ranks": [{"rank": r["rank"], "device": r["device"],
                               "ms_per_step": (r["t1"] - r["t0"]) / a.steps * 1e3} for r in res]},
-        "host_issue": [{"rank": r["rank"], "host_issue_ms_per_step": r["host_issue_ms_per_step"],
-                        "device_ms_per_step": r["device_ms_per_step"]} for r in res],
         "failed_problems": nfail, "device": res[0]["info"],
-        "parity": parity_spotcheck(wk, res[0]),
     }
-    curve_fields(line, wk, res[0]["solo_ms"], a.gpus)
+    if a.full:
+        line["host_issue"] = [{"rank": r["rank"],
+                               "host_issue_ms_per_step": r["host_issue_ms_per_step"],
+                               "device_ms_per_step": r["device_ms_per_step"]} for r in res]
+        line["parity"] = parity_spotcheck(wk, res[0])
+        curve_fields(line, wk, res[0]["solo_ms"], a.gpus)
+        p = line["parity"]
+        if not (p["mean_rel"] < 1e-10 and p["var_rel_prior"] < 1e-10
+                and p["logml_rel"] < 1e-10) or nfail:
+            line["value"] = None
+            line["invalid"] = "parity check failed"
+    elif nfail:
+        line["value"] = None
+        line["invalid"] = "%d failed problems" % nfail
+    print(json.dumps(line))
+    sys.exit(0 if line["value"] is not None else 1)
+
+
+def dominant_roofline(prof, ev_step):
+    """--full: the dominant kernel class of the timed workload (instrumented pass) against its
+    roofline."""
+    dom = max(prof, key=lambda k: prof[k]["ms"])
+    dom_ms = prof[dom]["ms"]
+    per_launch_ms = dom_ms / max(1, prof[dom]["launches"])
+    if dom in ("gram", "reduce"):
+        ach = prof[dom]["work"] / (dom_ms * 1e-3) / 1e9
+        roof = {"kernel": dom, "bound": "hbm", "achieved": ach, "peak": PEAK_HBM_GBS,
+                "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": None}
+    else:
+        ach = prof[dom]["work"] / (dom_ms * 1e-3) / 1e12
+        roof = {"kernel": dom, "bound": "mfma", "achieved": ach, "peak": PEAK_FP64_TFLOPS,
+                "unit": "TFLOP/s", "frac": ach / PEAK_FP64_TFLOPS, "traffic": None}
+    dom_kernel = {"syrk_trailing_small": "slab_step_kernel<false, 8>",
+                  "syrk_trailing": TRAILING_KERNEL}.get(dom)
+    if dom_kernel:
+        roof["traffic"], roof["traffic_source"] = pmc_traffic(dom_kernel)
+        roof["kernel_symbol"] = dom_kernel
+    # The instrumented pass brackets every launch with HIP events, which stretches a chain of
+    # short launches beyond the step it belongs to.  The class time behind `achieved` is
+    # therefore the class's SHARE of the instrumented pass applied to the un-instrumented
+    # step (HIP events around the whole timed region): never more than ms_per_step.
+    tot_instr = sum(v["ms"] for v in prof.values())
+    dom_ms_step = dom_ms * min(1.0, ev_step / tot_instr) if tot_instr > 0 else dom_ms
+    scale = dom_ms / dom_ms_step if dom_ms_step > 0 else 1.0
+    roof["achieved"] *= scale
+    roof["frac"] *= scale
+    roof.update({"launches_per_step": prof[dom]["launches"],
+                 "ms_per_launch": dom_ms_step / max(1, prof[dom]["launches"]),
+                 "ms_per_launch_instrumented": per_launch_ms,
+                 "ms_per_step_in_class": dom_ms_step,
+                 "ms_per_step_in_class_instrumented": dom_ms,
+                 "time_basis": "class share of the instrumented pass x the un-instrumented "
+                               "step (HIP events over the timed region)",
+                 "algorithmic_work_per_step": prof[dom]["work"],
+                 "class_ms_per_step": {k: v["ms"] for k, v in prof.items()},
+                 "class_launches_per_step": {k: v["launches"] for k, v in prof.items()},
+                 "note": "dominant kernel class of the timed workload (HIP events on the "
+                         "engine stream, instrumented pass; the events' own overhead makes "
+                         "the class sum exceed ms_per_step).  A single C2 problem is a "
+                         "chain of 16 dependent one-launch steps, each bound by ONE "
+                         "workgroup's critical path (panel-row solve, tile update, the "
+                         "64-pivot diagonal factor: tools/c2_timeline.py), not by the "
+                         "chip's MFMA rate; the kernels with a roofline target are under "
+                         "'rooflines'"})
+    return roof
+
+
+def full_fields(line, a, eng, wk, res, value, nfail, dist):
+    """--full: everything on the line besides the headline measurement."""
+    line["host_issue"] = res["ranks_issue"]
+    line["ms_per_step_with_readback"] = res["rb_ms"]
+    line["roofline"] = dominant_roofline(res["prof"], res["ev_ms"] / a.steps)
+    curve_fields(line, wk, res["solo_ms"], dist.world)
+    line["parity"] = parity_spotcheck(wk, res)
+    if dist.world == 1:
+        # the N = 1 point of the C5 curve, whatever the headline workload is
+        if a.workload == CURVE_WORKLOAD:
+            line["scale_point"] = {
+                "workload": wk["desc"], "value": value, "unit": "problems/s",
+                "ms_per_step": res["wall"] / a.steps * 1e3, "n_gpus": 1,
+                "problems_per_gpu_per_step": wk["B"], "failed": int(nfail),
+                "note": "this line's own value: the headline workload is the curve workload"}
+        else:
+            line["scale_point"] = scale_point(eng, a.curve_batch)
+        line["ms_per_step_host_buffers"] = host_buffer_step(eng, wk)
+        line["ms_per_step_host_buffers_note"] = (
+            "one problem of config.workload through bq_fit_predict with host buffers: plan "
+            "creation + H2D + run + D2H + synchronisation per call (what a BQ user's call "
+            "costs); `value` / ms_per_step have the inputs resident")
+        try:
+            line["probes"] = {"mfma_f64_tflops": eng.probe_mfma_f64(),
+                              "mfma_f64_4x4x4_4b_tflops": eng.probe_mfma_variant(1, 8, 2),
+                              "fma_f64_tflops": eng.probe_fma_f64()}
+            wgb, cgb = eng.probe_hbm(1 << 30)
+            line["probes"].update({"hbm_write_gbs": wgb, "hbm_copy_gbs": cgb})
+            # the size of the N = 4096 Gram (134 MB, inside the 256 MiB Infinity Cache):
+            # what a kernel that only stores reaches on this box
+            wgb2, cgb2 = eng.probe_hbm(1 << 27)
+            line["probes"].update({"hbm_write_gbs_128MiB": wgb2, "hbm_copy_gbs_128MiB": cgb2})
+        except Exception as e:  # probes are informational
+            line["probes"] = {"error": str(e)}
+        if not a.no_extras:
+            line["rooflines"] = extras(eng, a.nb)
+            line["rooflines"]["fit_posterior_ms_at_n"] = fit_posterior_at_n(eng)
+            line["roofline"] = northstar_first(line["roofline"], line["rooflines"])
+        if not a.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(wk)
+            line["cpu_baseline"]["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
     p = line["parity"]
     if not (p["mean_rel"] < 1e-10 and p["var_rel_prior"] < 1e-10 and p["logml_rel"] < 1e-10) \
             or nfail:
         line["value"] = None
         line["invalid"] = "parity check failed"
-    print(json.dumps(line))
-    sys.exit(0 if line["value"] is not None else 1)
 
 
 def main():
@@ -1107,8 +1262,12 @@ def main():
     if a.nb:
         eng.set_block(a.nb)
     wk = make_workload(a.workload, a.batch, dist.rank)
-    res = run_main(eng, wk, a.steps, a.warmup, dist)
+    res = run_main(eng, wk, a.steps, a.warmup, dist, a.full)
     nfail = dist.sum(float((res["status"] != 0).sum()))
+    if a.dump_outputs:
+        parts = dist.gather(tuple(res[k] for k in ("mean", "var", "logml", "status")))
+        if dist.rank == 0:
+            dump_outputs(a.dump_outputs, parts)
     units = a.steps * wk["B"] * dist.world  # problems processed by the whole job
     value = units / res["wall"]
     line = None
@@ -1116,51 +1275,6 @@ def main():
         info = eng.info()
         npad = -(-wk["n"] // 64) * 64
         ntot = -(-(npad + wk["M"] + 1) // 64) * 64
-        prof = res["prof"]
-        dom = max(prof, key=lambda k: prof[k]["ms"])
-        dom_ms = prof[dom]["ms"]
-        per_launch_ms = dom_ms / max(1, prof[dom]["launches"])
-        if dom in ("gram", "reduce"):
-            ach = prof[dom]["work"] / (dom_ms * 1e-3) / 1e9
-            roof = {"kernel": dom, "bound": "hbm", "achieved": ach, "peak": PEAK_HBM_GBS,
-                    "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": None}
-        else:
-            ach = prof[dom]["work"] / (dom_ms * 1e-3) / 1e12
-            roof = {"kernel": dom, "bound": "mfma", "achieved": ach, "peak": PEAK_FP64_TFLOPS,
-                    "unit": "TFLOP/s", "frac": ach / PEAK_FP64_TFLOPS, "traffic": None}
-        dom_kernel = {"syrk_trailing_small": "slab_step_kernel<false, 8>",
-                      "syrk_trailing": TRAILING_KERNEL}.get(dom)
-        if dom_kernel:
-            roof["traffic"], roof["traffic_source"] = pmc_traffic(dom_kernel)
-            roof["kernel_symbol"] = dom_kernel
-        # The instrumented pass brackets every launch with HIP events, which stretches a chain of
-        # short launches beyond the step it belongs to.  The class time behind `achieved` is
-        # therefore the class's SHARE of the instrumented pass applied to the un-instrumented
-        # step (HIP events around the whole timed region): never more than ms_per_step.
-        ev_step = res["ev_ms"] / a.steps
-        tot_instr = sum(v["ms"] for v in prof.values())
-        dom_ms_step = dom_ms * min(1.0, ev_step / tot_instr) if tot_instr > 0 else dom_ms
-        scale = dom_ms / dom_ms_step if dom_ms_step > 0 else 1.0
-        roof["achieved"] *= scale
-        roof["frac"] *= scale
-        roof.update({"launches_per_step": prof[dom]["launches"],
-                     "ms_per_launch": dom_ms_step / max(1, prof[dom]["launches"]),
-                     "ms_per_launch_instrumented": per_launch_ms,
-                     "ms_per_step_in_class": dom_ms_step,
-                     "ms_per_step_in_class_instrumented": dom_ms,
-                     "time_basis": "class share of the instrumented pass x the un-instrumented "
-                                   "step (HIP events over the timed region)",
-                     "algorithmic_work_per_step": prof[dom]["work"],
-                     "class_ms_per_step": {k: v["ms"] for k, v in prof.items()},
-                     "class_launches_per_step": {k: v["launches"] for k, v in prof.items()},
-                     "note": "dominant kernel class of the timed workload (HIP events on the "
-                             "engine stream, instrumented pass; the events' own overhead makes "
-                             "the class sum exceed ms_per_step).  A single C2 problem is a "
-                             "chain of 16 dependent one-launch steps, each bound by ONE "
-                             "workgroup's critical path (panel-row solve, tile update, the "
-                             "64-pivot diagonal factor: tools/c2_timeline.py), not by the "
-                             "chip's MFMA rate; the kernels with a roofline target are under "
-                             "'rooflines'"})
         line = {
             "metric": "bq_fit_posterior_throughput",
             "value": value,
@@ -1192,56 +1306,17 @@ def main():
                        "bordered_system": ntot, "sharding": "independent problems per rank, "
                        "no data-path collective",
                        "ranks": res["ranks"]},
-            "host_issue": res["ranks_issue"],
             "ms_per_problem": res["wall"] / a.steps / wk["B"] * 1e3,
             "ms_per_step_hip_events": res["ev_ms"] / a.steps,
-            "ms_per_step_with_readback": res["rb_ms"],
             "failed_problems": int(nfail),
             "device": info,
             "plan_bytes": res["plan_bytes"],
-            "roofline": roof,
         }
-        curve_fields(line, wk, res["solo_ms"], dist.world)
-        line["parity"] = parity_spotcheck(wk, res)
-        if dist.world == 1:
-            # the N = 1 point of the C5 curve, whatever the headline workload is
-            if a.workload == CURVE_WORKLOAD:
-                line["scale_point"] = {
-                    "workload": wk["desc"], "value": value, "unit": "problems/s",
-                    "ms_per_step": res["wall"] / a.steps * 1e3, "n_gpus": 1,
-                    "problems_per_gpu_per_step": wk["B"], "failed": int(nfail),
-                    "note": "this line's own value: the headline workload is the curve workload"}
-            else:
-                line["scale_point"] = scale_point(eng, a.curve_batch)
-            line["ms_per_step_host_buffers"] = host_buffer_step(eng, wk)
-            line["ms_per_step_host_buffers_note"] = (
-                "one problem of config.workload through bq_fit_predict with host buffers: plan "
-                "creation + H2D + run + D2H + synchronisation per call (what a BQ user's call "
-                "costs); `value` / ms_per_step have the inputs resident")
-            try:
-                line["probes"] = {"mfma_f64_tflops": eng.probe_mfma_f64(),
-                                  "mfma_f64_4x4x4_4b_tflops": eng.probe_mfma_variant(1, 8, 2),
-                                  "fma_f64_tflops": eng.probe_fma_f64()}
-                wgb, cgb = eng.probe_hbm(1 << 30)
-                line["probes"].update({"hbm_write_gbs": wgb, "hbm_copy_gbs": cgb})
-                # the size of the N = 4096 Gram (134 MB, inside the 256 MiB Infinity Cache):
-                # what a kernel that only stores reaches on this box
-                wgb2, cgb2 = eng.probe_hbm(1 << 27)
-                line["probes"].update({"hbm_write_gbs_128MiB": wgb2, "hbm_copy_gbs_128MiB": cgb2})
-            except Exception as e:  # probes are informational
-                line["probes"] = {"error": str(e)}
-            if not a.no_extras:
-                line["rooflines"] = extras(eng, a.nb)
-                line["rooflines"]["fit_posterior_ms_at_n"] = fit_posterior_at_n(eng)
-                line["roofline"] = northstar_first(line["roofline"], line["rooflines"])
-            if not a.no_cpu_baseline:
-                line["cpu_baseline"] = cpu_baseline(wk)
-                line["cpu_baseline"]["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
-        p = line["parity"]
-        if not (p["mean_rel"] < 1e-10 and p["var_rel_prior"] < 1e-10 and p["logml_rel"] < 1e-10) \
-                or nfail:
+        if a.full:
+            full_fields(line, a, eng, wk, res, value, nfail, dist)
+        elif nfail:
             line["value"] = None
-            line["invalid"] = "parity check failed"
+            line["invalid"] = "%d failed problems" % nfail
     dist.barrier()
     if dist.rank == 0:
         print(json.dumps(line))

@@ -167,7 +167,7 @@ def test_bench_lines_carry_the_same_curve_workload():
         return subprocess.run([sys.executable, launcher] + args, env=env, capture_output=True,
                               text=True, timeout=600)
 
-    common = ["--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"]
     one = _line_of(run(["--gpus", "1", "--curve-batch", "2"] + common))
     two = _line_of(run(["--gpus", "2", "--batch", "2"] + common))
     # N = 1: the headline stays C2 (BASELINE configs[1]); the curve's point is beside it
@@ -189,6 +189,48 @@ def test_bench_lines_carry_the_same_curve_workload():
         assert line["value"] is not None and line["failed_problems"] == 0
         assert line["parity"]["logml_rel"] < 1e-10 and "unpinned" in line["parity"]["noise_form"]
         assert line["config"]["value_is"].endswith(line["config"]["workload"])
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path, oracle):
+    """Without --full the line carries the headline and none of the diagnostics; --dump-outputs
+    writes the last timed step's mean / var / logml / status in float64, every rank's problems in
+    rank order.  On the CPU through tests/bench_double_main.py."""
+    import subprocess
+    from bayesian_quadrature_amd import workloads as wl
+    launcher = os.path.join(ROOT, "tests", "bench_double_main.py")
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    for gpus, nprob in ((1, 1), (2, 4)):
+        out = tmp_path / ("g%d" % gpus)
+        args = ["--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+        if gpus > 1:
+            args += ["--batch", "2"]
+        r = subprocess.run([sys.executable, launcher] + args, env=env, capture_output=True,
+                           text=True, timeout=600)
+        line = _line_of(r)
+        assert line["metric"] == "bq_fit_posterior_throughput" and line["unit"] == "problems/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        for k in ("parity", "roofline", "rooflines", "host_issue", "ms_per_step_with_readback",
+                  "scale_point", "ms_per_step_host_buffers", "probes", "cpu_baseline",
+                  "n1_same_workload"):
+            assert k not in line, k
+        got = {f: np.load(str(out / (f + ".npy"))) for f in ("mean", "var", "logml", "status")}
+        assert sorted(p.name for p in out.iterdir()) == sorted(f + ".npy" for f in got)
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert got["mean"].shape == got["var"].shape == (nprob, 256)
+        assert got["logml"].shape == got["status"].shape == (nprob,)
+        assert (got["status"] == 0).all()
+        # the last problem: C2 itself, or problem 3 of C5 (rank 1's second)
+        if gpus == 1:
+            c = wl.c2()
+            x, y = c["x"], c["y"]
+        else:
+            c = wl.c5([nprob - 1])
+            x, y = c["x"][0], c["y"][0]
+        lm = oracle.gp_fit(x, y, c["h"], c["w"], c["s"])[2]
+        assert abs(got["logml"][-1] - lm) <= 1e-10 * abs(lm)
 
 
 def test_north_star_scalars_lead_the_roofline_object():
@@ -228,8 +270,8 @@ def test_bench_launches_its_own_ranks(engine):
     device and the line reports n_gpus 2 with two distinct ranks / processes."""
     import json
     ndev = engine.device_count()
-    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-extras",
-            "--no-cpu-baseline"]
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--full",
+            "--no-extras", "--no-cpu-baseline"]
     if ndev < 2:
         r = _run_bench(args, {})
         assert r.returncode != 0
@@ -248,6 +290,26 @@ def test_bench_launches_its_own_ranks(engine):
     assert line["n1_same_workload"]["workload"] == line["config"]["workload"]
     assert 0 < line["scaling_efficiency"] < 1.5
     assert line["parity"]["logml_rel"] < 1e-10
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_timed_plan_computed(engine, oracle, tmp_path):
+    """A plain ``bench.py --gpus 1 --dump-outputs DIR``: the C2 problem's mean / var / logml as
+    the timed plan left them match the CPU oracle at the 1e-10 bar."""
+    from bayesian_quadrature_amd import workloads as wl
+    line = _line_of(_run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1",
+                                "--dump-outputs", str(tmp_path)], {}))
+    assert line["steps"] == 3 and line["failed_problems"] == 0 and "parity" not in line
+    got = {f: np.load(str(tmp_path / (f + ".npy"))) for f in ("mean", "var", "logml", "status")}
+    assert got["mean"].shape == got["var"].shape == (1, 256) and got["logml"].shape == (1,)
+    assert (got["status"] == 0).all()
+    c = wl.c2()
+    L, a, lm = oracle.gp_fit(c["x"], c["y"], c["h"], c["w"], c["s"])
+    m, v = oracle.gp_predict(c["x"], c["h"], c["w"], L, a, c["xo"])
+    k0 = oracle.kernel_scale(1, c["h"], c["w"])
+    assert np.max(np.abs(got["mean"][0] - m)) <= 1e-10 * np.max(np.abs(m))
+    assert np.max(np.abs(got["var"][0] - v)) <= 1e-10 * k0
+    assert abs(got["logml"][0] - lm) <= 1e-10 * abs(lm)
 
 
 def test_engine_pool_partitions_and_propagates_errors(oracle):
@@ -371,7 +433,7 @@ def test_bench_inproc_mode(engine):
     nothing; loud failure without a second device, shared-device rehearsal otherwise."""
     import json
     ndev = engine.device_count()
-    args = ["--gpus", "2", "--inproc", "--steps", "2", "--warmup", "1", "--batch", "2"]
+    args = ["--gpus", "2", "--inproc", "--steps", "2", "--warmup", "1", "--batch", "2", "--full"]
     if ndev < 2:
         r = _run_bench(args, {})
         assert r.returncode != 0 and "needs 2 HIP devices" in r.stderr
@@ -394,7 +456,8 @@ def test_eight_rank_host_side_rehearsal(engine):
     the device time of the same steps: with the plan's launches replayed from a hipGraph a step
     costs the host one call, so the launch rate is not what limits eight contexts."""
     import json
-    for args in (["--gpus", "8", "--inproc"], ["--gpus", "5", "--no-extras", "--no-cpu-baseline"]):
+    for args in (["--gpus", "8", "--inproc", "--full"],
+                 ["--gpus", "5", "--full", "--no-extras", "--no-cpu-baseline"]):
         r = _run_bench(args + ["--steps", "4", "--warmup", "2", "--batch", "8"],
                        {"BQ_BENCH_SHARE_DEVICE": "1"})
         assert r.returncode == 0, r.stderr[-2000:]

@@ -5,7 +5,7 @@ committed under profiles/ (run on the GPU box; results come back through gpurun_
 
 Per pass P of tools/roofline_run.py (one rocprofv3 run each, never blended):
     <tag>_<P>_kernel_stats.csv     copy of the --stats summary of `t_<P>`
-    <tag>_bench_kernel_stats.csv   the same for `python3 bench.py --steps 200`
+    <tag>_bench_kernel_stats.csv   the same for `python3 bench.py --full --steps 200`
 and
     <tag>_trailing_dispatches.csv  one row per launch with trailing-update work of the sequential
                                    N=16384, tile-256 potrf (128-tile and 64-tile products, the

@@ -8,7 +8,7 @@ O=$PWD/gpurun_out/r06p
 mkdir -p $O
 export TMPDIR=/tmp
 T="rocprofv3 --kernel-trace --stats --output-format csv"
-$T -d $O/bench -o bench -- python3 bench.py --steps 200 --warmup 10 > $O/bench_under_rocprof.json 2> $O/bench.err || { echo bench-prof-failed; tail -5 $O/bench.err; }
+$T -d $O/bench -o bench -- python3 bench.py --full --steps 200 --warmup 10 > $O/bench_under_rocprof.json 2> $O/bench.err || { echo bench-prof-failed; tail -5 $O/bench.err; }
 echo bench-done
 for p in c2 gram potrf256 potrf256_dense potrf_engine trsv solve256 predict c5 c2x256 c3 calib fitpost_n1024 fitpost_n2048 fitpost_n4096 fitpost_n16384; do
   $T -d $O/t_$p -o t -- python3 tools/roofline_run.py $p > $O/t_$p.txt 2>&1 || echo trace-$p-failed
@@ -53,4 +53,4 @@ rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INS
 python3 tools/pmc_avg.py trsm_sweep $O/pmc_sweep_a $O/pmc_sweep_b > $O/panel_solve_pmc.txt 2>&1 || echo pmc-sweep-summary-failed
 python tools/xcd_hop.py > $O/xcd_hop.txt 2>&1 || echo xcd-hop-failed
 python tools/power_probe.py > $O/power_probe.txt 2>&1 || echo power-probe-failed
-python bench.py > $O/bench.json 2> $O/bench2.err; echo bench rc=$?
+python bench.py --full > $O/bench.json 2> $O/bench2.err; echo bench rc=$?
