@@ -1,4 +1,5 @@
-"""ctypes binding of libbqhip.so (the C ABI in include/bqhip.h).
+"""ctypes binding of libbqhip.so (the C ABI in include/bqhip.h) and of libbqhip_probe.so (the
+same library plus the hardware probes of include/bqhip_probe.h).
 
 There is no arithmetic in this module and no fallback: if the shared library
 is missing, fails to load, or no GPU is visible, the product raises.
@@ -11,6 +12,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BQHIP_LIBRARY: developer override used to A/B experimental builds of the same C ABI
 LIB_PATH = os.environ.get("BQHIP_LIBRARY") or os.path.join(_HERE, "libbqhip.so")
+# BQHIP_PROBE_LIBRARY: the same for the probe library (default: the _probe.so beside LIB_PATH)
+PROBE_LIB_PATH = os.environ.get("BQHIP_PROBE_LIBRARY") or \
+    os.path.splitext(LIB_PATH)[0] + "_probe.so"
 
 BQ_OK, BQ_ERR_NOT_PD, BQ_ERR_BAD_ARG, BQ_ERR_HIP, BQ_ERR_NOMEM = 0, 1, 2, 3, 4
 BQ_MAX_DIM = 8
@@ -89,23 +93,26 @@ SIGNATURES = {
     "bq_plan_results": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _i32p]),
     "bq_plan_bytes": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "bq_set_guard": (C.c_int, [C.c_int]),
-    "bq_probe_xcd_hop": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_double), _i32p,
-                                   C.POINTER(C.c_int64)]),
     "bq_plan_check_guards": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-    "bq_probe_mfma_f64": (C.c_int, [_vp, _dp]),
-    "bq_probe_fma_f64": (C.c_int, [_vp, _dp]),
     "bq_pair_create": (C.c_int, [_vp, _dp, _dp, _dp, _i64, _dp, _i64, _dp, _i64, _i64,
                                  C.POINTER(_vp)]),
     "bq_pair_destroy": (None, [_vp, _vp]),
     "bq_pair_llh": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _i32p]),
     "bq_pair_esm": (C.c_int, [_vp, _vp, _dp, _dp, _dbl, _dp, _dp, _dp, _dp, _i32p, _dp, _dp, _dp,
                               _i32p]),
+}
+
+# name -> (restype, argtypes); the hardware probes of include/bqhip_probe.h (libbqhip_probe.so)
+PROBE_SIGNATURES = {
+    "bq_probe_xcd_hop": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_double), _i32p,
+                                   C.POINTER(C.c_int64)]),
+    "bq_probe_mfma_f64": (C.c_int, [_vp, _dp]),
+    "bq_probe_fma_f64": (C.c_int, [_vp, _dp]),
     "bq_probe_hbm": (C.c_int, [_vp, C.c_size_t, _dp, _dp]),
     "bq_probe_hbm_read8": (C.c_int, [_vp, C.c_size_t, _i64, _dp]),
     "bq_probe_gemm": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _i64, C.c_int, _i64, _dp]),
     "bq_probe_mfma_variant": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
     "bq_probe_mfma444_layout": (C.c_int, [_vp, C.c_int, C.c_int, _i32p]),
-    "bq_probe_rsq": (C.c_int, [_vp, _dp, _i64, _dp]),
     "bq_probe_launch": (C.c_int, [_vp, _i64, _dp]),
     "bq_probe_c2_timeline": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _i64]),
     "bq_probe_exp": (C.c_int, [_vp, _dp, _i64, _dp]),
@@ -116,31 +123,46 @@ SIGNATURES = {
 }
 
 _lib = None
+_probe_lib = None
 
 
 class LibraryMissing(ImportError):
     pass
 
 
+def _load(path, tables, mode):
+    if not os.path.exists(path):
+        raise LibraryMissing(
+            "%s is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "or `make -C bayesian-quadrature_amd/csrc` (there is no CPU fallback)"
+            % os.path.basename(path))
+    try:
+        lib = C.CDLL(path, mode=mode)
+    except OSError as e:  # missing HIP runtime etc.
+        raise LibraryMissing("cannot load %s: %s" % (path, e))
+    for table in tables:
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError if the .so is stale
+            fn.restype = res
+            fn.argtypes = args
+    return lib
+
+
 def load_library():
     """Load libbqhip.so and declare every signature.  Raises LibraryMissing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise LibraryMissing(
-            "libbqhip.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "or `make -C bayesian-quadrature_amd/csrc` (there is no CPU fallback)")
-    try:
-        lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    except OSError as e:  # missing HIP runtime etc.
-        raise LibraryMissing("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so is stale
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _load(LIB_PATH, (SIGNATURES,), C.RTLD_GLOBAL)
+    return _lib
+
+
+def load_probe_library():
+    """Load libbqhip_probe.so and declare the product and the probe signatures.  Raises
+    LibraryMissing."""
+    global _probe_lib
+    if _probe_lib is None:
+        _probe_lib = _load(PROBE_LIB_PATH, (SIGNATURES, PROBE_SIGNATURES), C.RTLD_LOCAL)
+    return _probe_lib
 
 
 def dptr(a):

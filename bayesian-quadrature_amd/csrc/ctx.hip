@@ -107,54 +107,33 @@ static int ctx_init(bq_ctx *c, int device)
         c->flow_abort = static_cast<int *>(h);
         *c->flow_abort = 0;
     }
-    if (const char *e = std::getenv("BQ_TRSV_FLOW"))
-        c->trsv_flow = std::atoi(e);
-    if (const char *e = std::getenv("BQ_TRSV_FLOW_MIN"))
-        c->trsv_flow_min = std::atoi(e);
-    if (const char *e = std::getenv("BQ_LOOKAHEAD"))
-        c->lookahead = std::atoi(e);
-    if (const char *e = std::getenv("BQ_SPLIT"))
-        c->split_batch = std::atoi(e);
-    if (const char *e = std::getenv("BQ_DIAG_FIRST"))
-        c->diag_first = std::atoi(e);
-    if (const char *e = std::getenv("BQ_ASM_FUSE"))
-        c->asm_fuse = std::atoi(e);
-    if (const char *e = std::getenv("BQ_DF_SWEEP"))
-        c->df_sweep = std::atoi(e);
-    if (const char *e = std::getenv("BQ_DF_WG"))
-        c->df_wg = std::atoi(e);
-    if (const char *e = std::getenv("BQ_PAIR_BORDER"))
-        c->pair_border = std::atoi(e);
-    if (const char *e = std::getenv("BQ_DF_WG_ROWS"))
-        c->df_wg_rows = std::atoi(e);
-    if (const char *e = std::getenv("BQ_DF_EARLY"))
-        c->df_early = std::atoi(e);
-    if (const char *e = std::getenv("BQ_ROWS_TAIL"))
-        c->rows_tail = std::atoi(e);
-    if (const char *e = std::getenv("BQ_SOLVE_KCOPY"))
-        c->solve_kcopy = std::atoi(e);
-    if (const char *e = std::getenv("BQ_DF_SHARING"))
-        c->df_sharing = std::atoi(e);
-    if (const char *e = std::getenv("BQ_LA_MIN"))
-        c->la_min = std::atoi(e);
-    if (const char *e = std::getenv("BQ_GEMM_LDS"))
-        c->gemm_lds = std::atoi(e);
-    if (const char *e = std::getenv("BQ_GEMM_LDS64"))
-        c->gemm_lds64 = std::atoi(e);
-    if (const char *e = std::getenv("BQ_SLAB_NB_MAX"))
-        c->slab_nb_max = std::atoi(e);
-    if (const char *e = std::getenv("BQ_SLAB_MAX"))
-        c->slab_max = std::atoi(e);
-    if (const char *e = std::getenv("BQ_FOLD_READOUT"))
-        c->fold_readout = std::atoi(e);
-    if (const char *e = std::getenv("BQ_POTF2_8W"))
-        c->potf2_8w = std::atoi(e);
-    if (const char *e = std::getenv("BQ_GEMM_KSPLIT"))
-        c->gemm_ksplit = std::atoi(e);
-    if (const char *e = std::getenv("BQ_GEMM_TILE"))
-        c->gemm_tile = std::atoi(e);
-    if (const char *e = std::getenv("BQ_GRAPH"))
-        c->use_graph = std::atoi(e);
+    // environment switches: each selects a path that a GPU test compares the shipped one against
+    // (README lists them with their tests)
+    static const struct {
+        const char *name;
+        int bq_ctx::*field;
+    } switches[] = {
+        {"BQ_TRSV_FLOW", &bq_ctx::trsv_flow},
+        {"BQ_LOOKAHEAD", &bq_ctx::lookahead},
+        {"BQ_DIAG_FIRST", &bq_ctx::diag_first},
+        {"BQ_ASM_FUSE", &bq_ctx::asm_fuse},
+        {"BQ_DF_SWEEP", &bq_ctx::df_sweep},
+        {"BQ_DF_WG", &bq_ctx::df_wg},
+        {"BQ_PAIR_BORDER", &bq_ctx::pair_border},
+        {"BQ_DF_WG_ROWS", &bq_ctx::df_wg_rows},
+        {"BQ_DF_EARLY", &bq_ctx::df_early},
+        {"BQ_SOLVE_KCOPY", &bq_ctx::solve_kcopy},
+        {"BQ_LA_MIN", &bq_ctx::la_min},
+        {"BQ_GEMM_LDS", &bq_ctx::gemm_lds},
+        {"BQ_FOLD_READOUT", &bq_ctx::fold_readout},
+        {"BQ_POTF2_8W", &bq_ctx::potf2_8w},
+        {"BQ_GEMM_KSPLIT", &bq_ctx::gemm_ksplit},
+        {"BQ_GEMM_TILE", &bq_ctx::gemm_tile},
+        {"BQ_GRAPH", &bq_ctx::use_graph},
+    };
+    for (const auto &sw : switches)
+        if (const char *e = std::getenv(sw.name))
+            c->*sw.field = std::atoi(e);
     return BQ_OK;
 }
 

@@ -3,7 +3,8 @@
 // ABI (include/bqhip.h is); the library is built with hidden visibility and exports only
 // the extern "C" entry points.
 //
-// Translation units (Makefile):
+// Translation units (Makefile; all but probe.hip make libbqhip.so, all of them together
+// libbqhip_probe.so, whose extra entry points include/bqhip_probe.h declares):
 //   k_gram.hip   gram.h kernels                 launch_gram_sym / _cross
 //   k_gemm.hip   gemm.h kernels                 launch_gemm, launch_gemm_rows, launch_rows_step
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
@@ -17,7 +18,7 @@
 //   fit.hip      resident GP fits
 //   moments.hip  closed-form integrals, BQ moments, the acquisition entry points
 //   pair.hip     the stacked pair of GPs at S hyper-parameter sets in one batched pass
-//   probe.hip    hardware probes
+//   probe.hip    hardware probes (libbqhip_probe.so only)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,7 +117,6 @@ struct bq_ctx {
     hipStream_t cur = nullptr;    // stream the launch helpers enqueue on (stream or aux)
     hipEvent_t ev_panel = nullptr, ev_next = nullptr, ev_fork = nullptr, ev_top = nullptr;
     int lookahead = 1;
-    int split_batch = 1; // halves of a mid-sized batch on the two streams (BQ_SPLIT=0: lock-step)
     int diag_first = 1;  // batches: every outer block as diagonal factor, ONE panel solve, update
                          // (enqueue_potrf_dfirst; BQ_DIAG_FIRST=0: the recursive panels)
     int df_sweep = 1;    // the panel solve of an outer block in one launch (trsm_sweep_kernel; BQ_DF_SWEEP)
@@ -124,7 +124,6 @@ struct bq_ctx {
                          // batch size (potrf.hip, dfirst_wg), 0 / 1 forced (BQ_DF_WG)
     int trsv_flow = 1;   // single-vector sweeps as one launch each, hand-offs through memory
                          // (trsvflow.h; BQ_TRSV_FLOW=0: one launch per block column)
-    int trsv_flow_min = 2048; // ... from this many rows on (BQ_TRSV_FLOW_MIN)
     int *flow_abort = nullptr; // mapped host word a timed-out hand-off raises
     long n_flow_fallback = 0;  // solves re-issued on the per-block sweeps after such a time-out
                                // (bq_ctx_stats)
@@ -134,20 +133,14 @@ struct bq_ctx {
                          // below them: the factors an update hides (BQ_DF_WG_ROWS; 0: never)
     int df_early = 1;    // the diagonal-first sweep forks before the panel solve: the next diagonal block's
                          // rows are solved, updated and factored beside the rest of the solve (BQ_DF_EARLY)
-    int rows_tail = 128; // a large row sweep's last updates as split-k tiles: from this many LDS tiles down (BQ_ROWS_TAIL)
     int solve_kcopy = 1; // a one-vector solve's vector in / out and sentinel fill by kernels (BQ_SOLVE_KCOPY)
     double *hstage = nullptr; // mapped pinned staging of the small host-buffer calls (ctx_stage)
     size_t hstage_len = 0;
-    int df_sharing = 0;  // gemm_lds_tile's sharing mode while a diagonal factor runs beside an update
-                         // (0: the rule of a product alone -- C5 shard 5.73 ms against 6.05 with 1)
     int la_min = 3072;   // look-ahead only while the bulk update has at least this many rows (BQ_LA_MIN)
     DevBuf panel_ws;     // scratch panel columns of the eager linalg entry points
     DevBuf scratch;      // per-call temporaries of the acquisition / moment entry points, kept
                          // between calls (hipFree synchronises the device); bq_ctx_trim frees it
     int gemm_lds = 1;    // LDS-staged 128x128 trailing update (BQ_GEMM_LDS)
-    int gemm_lds64 = 1;  // its 64x64-tile form for products that cannot fill the chip (BQ_GEMM_LDS64)
-    int slab_nb_max = 3072; // one or two matrices below this size: one-launch steps throughout (BQ_SLAB_NB_MAX)
-    int slab_max = 4800;    // ... and the last rows of a larger one, from this many on (BQ_SLAB_MAX)
     int fold_readout = 1; // one-launch sweeps carry their read-out (SlabOut; BQ_FOLD_READOUT)
     SlabOut slab_out{};  // set (scal != nullptr) by a caller whose slab sweep carries its read-out
     int asm_fuse = 1;    // a batched plan assembles only the first outer block's columns; the rest of
@@ -221,10 +214,9 @@ inline long roundup(long v, long q) { return (v + q - 1) / q * q; }
 // under -- whichever setter, environment switch or probe changed a field.
 inline unsigned long long launch_config_key(const bq_ctx *c)
 {
-    const int f[] = {c->nb_override, c->lookahead, c->split_batch, c->la_min, c->gemm_lds,
-                     c->gemm_lds64, c->slab_nb_max, c->slab_max, c->fold_readout, c->potf2_8w,
-                     c->gemm_ksplit, c->gemm_tile, c->diag_first, c->df_sweep, c->df_wg,
-                     c->df_sharing, c->rows_tail, c->df_early, c->df_wg_rows};
+    const int f[] = {c->nb_override, c->lookahead, c->la_min,   c->gemm_lds,  c->fold_readout,
+                     c->potf2_8w,    c->gemm_ksplit, c->gemm_tile, c->diag_first, c->df_sweep,
+                     c->df_wg,       c->df_early,   c->df_wg_rows};
     unsigned long long h = 1469598103934665603ull;
     for (int v : f)
         h = (h ^ (unsigned long long)(unsigned)v) * 1099511628211ull;
@@ -469,11 +461,7 @@ struct WideInv {
 };
 inline int wide_block(int npad)
 {
-    // (BQ_WIDE_B: measurements)
-    static const int forced = std::getenv("BQ_WIDE_B") ? std::atoi(std::getenv("BQ_WIDE_B")) : 0;
-    if (forced > 0)
-        return std::min(npad, forced);
-    // (round 5, tools/wide_b_check.py, 256 against 512 on resident fits of 1024 / 1536 points:
+    // (round 5, profiles/r05_wide_b_check.txt, 256 against 512 on resident fits of 1024 / 1536 points:
     // posterior mean + variance at 256 points 0.064 -> 0.056 / 0.094 -> 0.073 ms, one-vector solve
     // 0.053 -> 0.039 / 0.070 -> 0.047 -- half the dependent steps --; the inverses cost 0.06 ms
     // more to rebuild after a refit: 0.43 -> 0.50 ms for refit + first posterior)
@@ -609,10 +597,9 @@ template <class F>
 int fit_replay(bq_ctx *c, bq_fit *f, int slot, F &&enqueue)
 {
     // (a one-launch sweep is two memsets and a kernel: enqueued directly it costs the host less
-    // than a graph launch does -- BQ_FLOW_GRAPH=1 replays it from a graph all the same)
-    static const bool flow_graph = std::getenv("BQ_FLOW_GRAPH") && std::atoi(std::getenv("BQ_FLOW_GRAPH"));
+    // than a graph launch does)
     if (!c->use_graph || c->prof || !c->own_stream || c->cur != c->stream ||
-        (!flow_graph && trsv_flow_ok(c, f->npad, wide_block(f->npad))))
+        trsv_flow_ok(c, f->npad, wide_block(f->npad)))
         return enqueue();
     // a graph captured with the one-launch sweeps inside is not what a fall-back retry (or a
     // caller that switched them off) asks for: such a call is enqueued eagerly
@@ -671,6 +658,7 @@ int with_flow_fallback(bq_ctx *c, F &&attempt)
 }
 // plan.hip: new kernel parameters for every problem of a plan, nothing else re-uploaded
 int plan_set_params(bq_ctx *c, bq_plan *p, const double *h, const double *w, const double *s);
-// plan.hip: the launch sequence of one pass of a plan (bq_probe_c2_timeline runs it eagerly)
+// plan.hip: the launch sequence of one pass of a plan (probe.hip, bq_probe_c2_timeline, runs it
+// eagerly)
 int plan_enqueue(bq_ctx *c, bq_plan *p);
 } // namespace bqh

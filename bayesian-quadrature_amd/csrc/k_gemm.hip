@@ -77,7 +77,7 @@ static int gemm_lds_tile(const bq_ctx *c, int m, int n, int k, int lower, int ba
         return per * batch;
     };
     const long a = tiles(128), a64 = tiles(64);
-    const bool can64 = c->gemm_lds64 && k >= 64, can128 = n >= 128;
+    const bool can64 = k >= 64, can128 = n >= 128;
     const int forced = c->gemm_tile;
     if (forced == 64 && can64)
         return 64;
@@ -190,8 +190,7 @@ int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const dou
                            cstride, P, ldp, pstride, Q, qsk, qstride, m, n, k, mode,
                            ccut > 0 ? ccut : 0x7fffffff);
     } else if (qsk == 1 && (qsj & 1) == 0 && fuse_j0 < 0 && (m % 64) == 0 &&
-               gemm_lds_tile(c, m, n, k, lower, batch) != 0 && c->gemm_lds64 &&
-               tiles(64) >= c->cus / 2) {
+               gemm_lds_tile(c, m, n, k, lower, batch) != 0 && tiles(64) >= c->cus / 2) {
         // Q given k-contiguous (the backward row sweep): the 64-tile kernel's transposed staging
         dim3 g = grid_for(64);
         hipLaunchKernelGGL((gemm_lds64_kernel<true, 1>), g, dim3(256), BQ_L64_BYTES, c->cur, C, ldc,
@@ -224,8 +223,7 @@ int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const dou
 // diagonal block those 64 columns are solved against and its record of block inverses.
 bool gemm_trsm_ok(const bq_ctx *c, int m, int n, int k)
 {
-    return c->gemm_lds64 && m > 0 && (m % 64) == 0 && n >= 64 && (n % 64) == 0 && k >= 32 &&
-           (k % 32) == 0;
+    return m > 0 && (m % 64) == 0 && n >= 64 && (n % 64) == 0 && k >= 32 && (k % 32) == 0;
 }
 
 int launch_gemm_trsm(bq_ctx *c, double *C, long ldc, long cstride, const double *P, long ldp,
@@ -253,15 +251,8 @@ int launch_trsm_sweep(bq_ctx *c, double *X, long ldx, long xstride, int m, const
         return fail(c, BQ_ERR_BAD_ARG, "trsm_sweep: m and kb must be multiples of 64");
     Bracket br(c, BQ_K_TRSM, (double)m * kb * kb * batch);
     const int nrb = m / 64;
-#ifdef BQ_TS_DBG
-    // ablation build (make DEFS=-DBQ_TS_DBG OUT=../libbqhip_dbg.so; tools/r06_ablate.sh)
-    static const int dbg = std::getenv("BQ_TS_DBG") ? std::atoi(std::getenv("BQ_TS_DBG")) : 0;
-    hipLaunchKernelGGL(trsm_sweep_kernel, dim3(8 * nrb * ((batch + 7) / 8)), dim3(256), BQ_L64_BYTES,
-                       c->cur, X, ldx, xstride, L11, ldl, lstride, rec, rstride, kb, nrb, batch, dbg);
-#else
     hipLaunchKernelGGL(trsm_sweep_kernel, dim3(8 * nrb * ((batch + 7) / 8)), dim3(256), BQ_L64_BYTES,
                        c->cur, X, ldx, xstride, L11, ldl, lstride, rec, rstride, kb, nrb, batch);
-#endif
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

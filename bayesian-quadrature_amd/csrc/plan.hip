@@ -588,33 +588,3 @@ extern "C" int bq_gp_logml_grid(bq_ctx *c, const double *x, const double *y, int
     }
     return logml_grid_core(c, x, y, d, n, h, w, s, G, chunk, out, nullptr, nullptr);
 }
-
-// One eager (not graph-replayed) pass of a plan with the profiling instantiation of the slab
-// step: stamps[160 * step + k] = s_memtime of workgroup 0 at (0) entry, (1) factor fragments
-// loaded, (2) panel rows solved, (3) tile loaded + Q in LDS, (4) tile updated, (5..9) the
-// diagonal factor's entry / block in registers / pivot chain done / sub-blocks in LDS / end.
-extern "C" int bq_probe_c2_timeline(bq_ctx *c, bq_plan *p, int64_t *stamps, int64_t nsteps)
-{
-    if (!c || !p || !stamps || nsteps < 1 || nsteps > 1024)
-        return BQ_ERR_BAD_ARG;
-    // only the one-launch slab sweep carries the stamped instantiation, and it stamps one
-    // record per step into the caller's nsteps (the sweep itself skips steps beyond them)
-    if (!sweep_is_slab(c, p->L.ntot, p->L.npad, p->nprob, p->panel.bytes / sizeof(double)))
-        return fail(c, BQ_ERR_BAD_ARG, "timeline: this plan does not sweep with the one-launch steps");
-    if (nsteps < p->L.npad / 64)
-        return fail(c, BQ_ERR_BAD_ARG, "timeline: %d steps, room for %d", p->L.npad / 64, (int)nsteps);
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf st;
-    HIPCHK(c, st.alloc(sizeof(long long) * 160 * (size_t)nsteps));
-    HIPCHK(c, hipMemsetAsync(st.p, 0, st.bytes, c->stream));
-    c->stamp_buf = static_cast<long long *>(st.p);
-    c->stamp_steps = (int)nsteps;
-    int rc = plan_enqueue(c, p);
-    c->stamp_buf = nullptr;
-    c->stamp_steps = 0;
-    BQCHK(rc);
-    HIPCHK(c, hipMemcpyAsync(stamps, st.p, st.bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BQ_OK;
-}
-

@@ -33,9 +33,6 @@ using Potf2F = Potf2FT<4>;
 // registers before the first panel is published --, then the four 16 x 16 diagonal
 // sub-blocks (1024 doubles)
 #define BQ_POTF2F_SLOTS (16 * 256)
-#ifndef BQ_POTF2F_EARLY
-#define BQ_POTF2F_EARLY 1
-#endif
 #define BQ_POTF2F_LDS_DOUBLES (BQ_POTF2F_SLOTS + 1024)
 
 // Factor panel P (columns 4P .. 4P+3, group QP = P >> 2) held by this wave and publish it.
@@ -119,7 +116,7 @@ __device__ __forceinline__ void potf2f_update(Potf2FT<NW> &st, const double *slo
 #define BQ_LATER(Q, NG) (((1 << (NG)) - 1) & ~((1 << ((Q) + 1)) - 1))
 
 // ---------------------------------------------------------------------------
-// The epilogue of a full block's factor (BQ_POTF2F_EARLY; tools/potf2_probe.py, potf2_waves.py).
+// The epilogue of a full block's factor (tools/potf2_probe.py, potf2_waves.py).
 // After the last pivot the factor used to copy the four 16 x 16 diagonal sub-blocks to LDS, pass a
 // barrier, and run the reciprocal pivots and the four block inverses beside the write-back: 6,000
 // cycles behind a chain of 13,000, most of them the inverses -- sixteen dependent steps, each lane
@@ -350,7 +347,7 @@ __device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, i
     // stamps[5] != 0 -- they cost the chain 2,500 cycles)
     // (only the assembly's first factor passes nreal -- a system of fewer than 64 points has no
     // other --: inside slab_step_kernel the second instantiation cost C2 0.4 us per step)
-    if (BQ_POTF2F_EARLY && nreal >= 64) {
+    if (nreal >= 64) {
         // (a full block: the epilogue straight out of the panels' slots)
         const double ld0 = logdet ? *logdet : 0.0; // one writer per launch, launches in order
         Potf2FSteps<0, NW, false, true>::run(
@@ -406,13 +403,8 @@ __device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, i
         BQ_STAMP(4);
         return;
     }
-    if (nreal < 64)
-        Potf2FSteps<0, NW, true>::run(st, slots, w, lane, nullptr, nreal > 0 ? nreal : 1);
-    else
-        Potf2FSteps<0, NW, false>::run(st, slots, w, lane,
-                                       (stamps && NW == 4 && stamps[5] != 0) ? stamps + 8
-                                                                              : nullptr,
-                                       64);
+    // (a block of fewer than 64 real columns: the padded steps, then the epilogue below)
+    Potf2FSteps<0, NW, true>::run(st, slots, w, lane, nullptr, nreal > 0 ? nreal : 1);
     BQ_STAMP(2);
     // the four 16 x 16 diagonal sub-blocks into LDS from registers:
     // blk[b][i + 16 k] = L[16 b + i][16 b + k]; my columns c = 4 (NW q + w) + sc: block c >> 4

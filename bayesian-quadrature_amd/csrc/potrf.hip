@@ -11,6 +11,11 @@ namespace bqh {
 // a factor to work on: 366 us alone against 236).  BQ_DF_WG = 0 / 1 forces either.
 static bool dfirst_wg(const bq_ctx *c, int batch) { return c->df_wg < 0 ? batch >= 96 : c->df_wg != 0; }
 
+// One or two matrices below kSlabNbMax rows run the one-launch steps throughout (auto_nb); the last
+// kSlabMax rows of a larger one are handed to them (enqueue_potrf_group)
+constexpr int kSlabNbMax = 3072;
+constexpr int kSlabMax = 4800;
+
 int auto_nb(const bq_ctx *c, int ntot, int batch)
 {
     if (c->nb_override > 0)
@@ -28,8 +33,8 @@ int auto_nb(const bq_ctx *c, int ntot, int batch)
         // blocks 64 / 256: N=2560 0.761 / 0.774, 3072 1.013 / 0.995, 3584 1.346 / 1.318, 4096
         // 1.776 / 1.617, 4608 2.311 / 1.967): from 3072 rows the first panels are blocked (with
         // the look-ahead once there is room for it) and the LAST rows go to the one-launch steps
-        // (slab_max / la_min, enqueue_potrf_group)
-        if (ntot < c->slab_nb_max)
+        // (kSlabMax / la_min, enqueue_potrf_group)
+        if (ntot < kSlabNbMax)
             return 64;
         // a wider block halves the trailing update's C traffic per flop (60 instead of 56
         // TFLOP/s at k = 512); it pays once the panel it lengthens hides behind the bulk
@@ -315,7 +320,7 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
         // The last rows of a large matrix are a small factorisation of their own -- the
         // Schur complement once this block's update is in --, and for one or two matrices
         // the one-launch steps are its shortest chain: hand the rest to the slab sweep.
-        const bool to_slab = batch <= 2 && ws && NB > 64 && r0 < ncols && ntot - r0 < c->slab_max;
+        const bool to_slab = batch <= 2 && ws && NB > 64 && r0 < ncols && ntot - r0 < kSlabMax;
         if (r0 < ntot) {
             const double *P = A + r0 + (long)K0 * lda;
             // the trailing update also factors the next diagonal block if there is one
@@ -405,7 +410,7 @@ static int enqueue_trsm_rec(bq_ctx *c, double *A, long lda, long astride, int ba
 int enqueue_panel_solve(bq_ctx *c, double *A, long lda, long astride, int batch, int r0, int m2,
                         int K0, int KB, const double *rec, long rstride)
 {
-    if (c->df_sweep && c->gemm_lds64)
+    if (c->df_sweep)
         return launch_trsm_sweep(c, A + r0 + (long)K0 * lda, lda, astride, m2,
                                  A + K0 + (long)K0 * lda, lda, astride, rec, rstride, KB, batch);
     return enqueue_trsm_rec(c, A, lda, astride, batch, r0, m2, K0, 0, KB, rec, rstride, false);
@@ -452,7 +457,9 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
                                   ws, K0, false, rstride);
     };
     BQCHK(diag(0, NB, recs[0]));
-    Sharing scope(c, la ? c->df_sharing : c->sharing);
+    // while a diagonal factor runs beside an update, gemm_lds_tile keeps the rule of a product
+    // alone (C5 shard 5.73 ms against 6.05 with the look-ahead's sharing mode 1)
+    Sharing scope(c, la ? 0 : c->sharing);
     // The caller assembled only the first NB columns (dfirst_seed_cols) and left the rest as a
     // GramSeed: block 0's three products are the first to touch everything right of them, and they
     // compute their tiles of the system instead of loading them -- the assembly of two thirds of a
@@ -580,8 +587,7 @@ int enqueue_potrf_partial(bq_ctx *c, double *A, long lda, long astride, int batc
     // panel chain only takes clock away (C3, 100 x N = 4096: 189.8 ms with the look-ahead,
     // 198 in two halves, 186.3 sequential; up to 32 matrices the look-ahead still gains 1-2 %)
     const bool big = ncols > NB && ntot - std::min(NB, ncols) >= c->la_min;
-    if (c->split_batch && c->lookahead && c->aux && c->cur == c->stream && batch >= 8 &&
-        NB >= 128 && !big) {
+    if (c->lookahead && c->aux && c->cur == c->stream && batch >= 8 && NB >= 128 && !big) {
         const int b0 = batch / 2, b1 = batch - b0;
         Sharing halves(c, 2);
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));

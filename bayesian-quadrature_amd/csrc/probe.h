@@ -1,5 +1,5 @@
-// probe.h -- hardware probes (MFMA / FMA rate, HBM bandwidth, MFMA layout, rsq accuracy)
-// Part of the libbqhip.so kernel set; compiled into probe.hip (host.h lists the units).
+// probe.h -- hardware probes (MFMA / FMA rate, HBM bandwidth, MFMA layout, exp accuracy)
+// Kernels of libbqhip_probe.so only; compiled into probe.hip (host.h lists the units).
 #pragma once
 #include "common.h"
 #include "potf2.h"
@@ -7,26 +7,6 @@
 // ---------------------------------------------------------------------------
 // hardware probes
 // ---------------------------------------------------------------------------
-// relative error of the raw v_rsq_f64 seed, of one and of two Newton steps, against
-// the correctly rounded 1/sqrt; out[3*i + k]
-__global__ void probe_rsq_kernel(const double *x, double *out, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const double d = x[i];
-    const double ref = 1.0 / sqrt(d);
-    double y = __builtin_amdgcn_rsq(d);
-    out[3 * i] = fabs(y - ref) / ref;
-    const double hd = 0.5 * d;
-    double t = __builtin_fma(-hd * y, y, 0.5);
-    y = __builtin_fma(y, t, y);
-    out[3 * i + 1] = fabs(y - ref) / ref;
-    t = __builtin_fma(-hd * y, y, 0.5);
-    y = __builtin_fma(y, t, y);
-    out[3 * i + 2] = fabs(y - ref) / ref;
-}
-
 // exp_gauss (common.h) on an array of arguments, for the per-element accuracy test
 __global__ void probe_exp_kernel(const double *x, double *out, int n)
 {

@@ -1,6 +1,12 @@
-// probe.hip -- hardware probes behind the C ABI (MFMA / FMA / HBM rates, launch latency,
-// operand layouts, the diagonal factor's timeline) and their kernels (probe.h).
+// probe.hip -- hardware probes of libbqhip_probe.so (MFMA / FMA / HBM rates, launch latency,
+// operand layouts, the diagonal factor's and a plan's timelines) and their kernels (probe.h).
+// Not linked into libbqhip.so (Makefile).
 #include "host.h"
+
+#pragma GCC visibility push(default)
+#include "../../include/bqhip_probe.h"
+#pragma GCC visibility pop
+
 #include "probe.h"
 
 using namespace bqh;
@@ -259,24 +265,6 @@ extern "C" int bq_probe_exp(bq_ctx *c, const double *x, int64_t n, double *out)
     return BQ_OK;
 }
 
-extern "C" int bq_probe_rsq(bq_ctx *c, const double *x, int64_t n, double *err3)
-{
-    if (!c || !x || !err3 || n < 1)
-        return BQ_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf xd, od;
-    HIPCHK(c, xd.alloc(sizeof(double) * n));
-    HIPCHK(c, od.alloc(sizeof(double) * 3 * n));
-    HIPCHK(c, hipMemcpyAsync(xd.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(probe_rsq_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                       xd.d(), od.d(), (int)n);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(err3, od.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BQ_OK;
-}
-
 // The diagonal factor alone: A (64 x 64 host, column-major) is factored `reps` times from a
 // resident copy; L_out / dinv_out (BQ_DINV_HALF doubles) / info_out are the last launch's
 // results, us_per_launch the HIP-event average, stamps5 the in-kernel s_memtime stamps
@@ -432,6 +420,8 @@ extern "C" int bq_probe_panel_solve(bq_ctx *c, int64_t m, int64_t kb, int64_t ba
 {
     if (!c || !L || !X || m < 64 || (m & 63) || kb < 64 || (kb & 63) || batch < 1)
         return c ? fail(c, BQ_ERR_BAD_ARG, "panel_solve: m, kb multiples of 64") : BQ_ERR_BAD_ARG;
+    if (mode < 0 || mode > 2)
+        return fail(c, BQ_ERR_BAD_ARG, "panel_solve: mode must be 0, 1 or 2");
     HIPCHK(c, hipSetDevice(c->device));
     const long lda = (long)(kb + m), astride = lda * (long)kb;
     const long rstride = (long)(kb / 64) * BQ_DINV_HALF;
@@ -472,6 +462,35 @@ extern "C" int bq_probe_panel_solve(bq_ctx *c, int64_t m, int64_t kb, int64_t ba
         HIPCHK(c, hipMemcpy2DAsync(X + b * m * kb, sizeof(double) * m, A.d() + b * astride + kb,
                                    sizeof(double) * lda, sizeof(double) * m, kb,
                                    hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+
+// One eager (not graph-replayed) pass of a plan with the profiling instantiation of the slab
+// step: stamps[160 * step + k] = s_memtime of workgroup 0 at (0) entry, (1) factor fragments
+// loaded, (2) panel rows solved, (3) tile loaded + Q in LDS, (4) tile updated, (5..9) the
+// diagonal factor's entry / block in registers / pivot chain done / sub-blocks in LDS / end.
+extern "C" int bq_probe_c2_timeline(bq_ctx *c, bq_plan *p, int64_t *stamps, int64_t nsteps)
+{
+    if (!c || !p || !stamps || nsteps < 1 || nsteps > 1024)
+        return BQ_ERR_BAD_ARG;
+    // only the one-launch slab sweep carries the stamped instantiation, and it stamps one
+    // record per step into the caller's nsteps (the sweep itself skips steps beyond them)
+    if (!sweep_is_slab(c, p->L.ntot, p->L.npad, p->nprob, p->panel.bytes / sizeof(double)))
+        return fail(c, BQ_ERR_BAD_ARG, "timeline: this plan does not sweep with the one-launch steps");
+    if (nsteps < p->L.npad / 64)
+        return fail(c, BQ_ERR_BAD_ARG, "timeline: %d steps, room for %d", p->L.npad / 64, (int)nsteps);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf st;
+    HIPCHK(c, st.alloc(sizeof(long long) * 160 * (size_t)nsteps));
+    HIPCHK(c, hipMemsetAsync(st.p, 0, st.bytes, c->stream));
+    c->stamp_buf = static_cast<long long *>(st.p);
+    c->stamp_steps = (int)nsteps;
+    int rc = plan_enqueue(c, p);
+    c->stamp_buf = nullptr;
+    c->stamp_steps = 0;
+    BQCHK(rc);
+    HIPCHK(c, hipMemcpyAsync(stamps, st.p, st.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BQ_OK;
 }

@@ -172,7 +172,7 @@ static bool rows_small(const bq_ctx *c, int mrows, int npad, const WideInv &w)
     // 66 us with round 5's 512-column steps)
     return (mrows % 32) == 0 && (w.B % 64) == 0 &&
            (long)(mrows / 32) * (npad / 32) <= 4L * c->cus &&
-           ((mrows % 64) != 0 || !c->gemm_lds64 || npad < 2048 ||
+           ((mrows % 64) != 0 || npad < 2048 ||
             (long)(mrows / 64) * (npad / 64) < c->cus / 2);
 }
 
@@ -229,13 +229,13 @@ static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long l
         }
         // The last steps' updates are few 64 x 64 tiles of one k loop each (22 us however few):
         // there the update goes out as 32 x 32 split-k tiles too (rows_step_kernel), a quarter of
-        // a tile's k loop per wave.  rows_tail: from how many LDS tiles down in the forward sweep
-        // (0: never); the backward sweep's Q is strided across a tile's columns there and gains
-        // only from a quarter of that on (N = 4096, 256 rows, step times in us, forward 30 26 26 25
-        // 17 -> 29 23 21 17 16, backward 28 26 26 25 19 -> 28 26 26 19 19; tools/rows_tail_check.py).
+        // a tile's k loop per wave.  kRowsTail: from how many LDS tiles down in the forward sweep;
+        // the backward sweep's Q is strided across a tile's columns there and gains only from a
+        // quarter of that on (N = 4096, 256 rows, step times in us, forward 30 26 26 25 17 -> 29 23
+        // 21 17 16, backward 28 26 26 25 19 -> 28 26 26 19 19; docs/LABBOOK.md, round 5 item 5).
+        constexpr long kRowsTail = 128;
         const long lds_tiles = (long)(mrows / 64) * (nu / 64);
-        if (!first && nu > 0 && c->rows_tail > 0 &&
-            lds_tiles <= (forward ? c->rows_tail : c->rows_tail / 4) &&
+        if (!first && nu > 0 && lds_tiles <= (forward ? kRowsTail : kRowsTail / 4) &&
             (mrows % 32) == 0 && (nu % 32) == 0 && (bp % 16) == 0) {
             RowsJob b = a;
             b.C = Cu;
@@ -325,7 +325,7 @@ int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mro
         }
         return BQ_OK;
     }
-    if (c->gemm_lds64 && (mrows % 64) == 0 && (w.B % 64) == 0 && (ldl & 1) == 0)
+    if ((mrows % 64) == 0 && (w.B % 64) == 0 && (ldl & 1) == 0)
         return rows_fused(c, true, Xin, Xout, ldx, mrows, L, ldl, npad, w);
     HIPCHK(c, hipMemsetAsync(Xout, 0, sizeof(double) * (size_t)ldx * npad, c->cur));
     for (int J = 0; J < npad; J += w.B) {
@@ -346,8 +346,7 @@ int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mro
 int enqueue_backward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
                           const double *L, long ldl, int npad, WideInv w)
 {
-    if (!rows_small(c, mrows, npad, w) && c->gemm_lds64 && (mrows % 64) == 0 &&
-        (w.B % 64) == 0 && (ldl & 1) == 0)
+    if (!rows_small(c, mrows, npad, w) && (mrows % 64) == 0 && (w.B % 64) == 0 && (ldl & 1) == 0)
         return rows_fused(c, false, Xin, Xout, ldx, mrows, L, ldl, npad, w);
     HIPCHK(c, hipMemsetAsync(Xout, 0, sizeof(double) * (size_t)ldx * npad, c->cur));
     const int last = (npad - 1) / w.B * w.B;

@@ -30,15 +30,8 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
                                                             long lstride,
                                                             const double *__restrict__ rec,
                                                             long rstride, int kb, int nrb,
-                                                            int batch
-#ifdef BQ_TS_DBG
-                                                            , int dbg // ablations (measurements only)
-#endif
-)
+                                                            int batch)
 {
-#ifndef BQ_TS_DBG
-    constexpr int dbg = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int slot = blockIdx.x >> 3;
     const int b = (int)(blockIdx.x & 7) + 8 * (slot / nrb);
@@ -59,7 +52,7 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
     // (dma row) + 8 (i >> 5) -- gemm_lds64_body's layout
     const bool stq = wave >= 2;
     const int dma0 = 4 * (wave & 1);
-    const double *gp = X + ((dbg & 4) ? 0 : R0) + 2 * (lane & 31) + (long)(dma0 + 8 * (lane >> 5)) * ldx;
+    const double *gp = X + R0 + 2 * (lane & 31) + (long)(dma0 + 8 * (lane >> 5)) * ldx;
     const double *gq0 = L11 + 2 * (lane & 31) + (long)(dma0 + 8 * (lane >> 5)) * ldl;
     const int srow = ((stq ? 8 : 0) + dma0) * BQ_LDS_ROW;
     const unsigned char *pview = smem + l4 * BQ_LDS_ROW + (wr + l15) * 8;
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
         qview[s] = smem + (8 + l4) * BQ_LDS_ROW + (wc + ((l15 - 4 * s) & 15)) * 8;
 
 #define BQ_TS_FILL(BUF_, CH_)                                                                      \
-    if (!(dbg & 8)) {                                                                              \
+    {                                                                                              \
         const double *g_ = gsrc + (long)(CH_) * 16 * sld;                                          \
         _Pragma("unroll") for (int r = 0; r < 4; ++r) __builtin_amdgcn_global_load_lds(            \
             (global_cvoid_t *)(g_ + (long)r * sld),                                                \
@@ -105,7 +98,6 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
             if (tn == 1 && j < 7)                                                                  \
                 BQ_TS_READ_P(BUF_, st + 1, pf[(st + 1) & 1])                                       \
             __builtin_amdgcn_sched_barrier(0);                                                     \
-            if (!(dbg & 16))                                                                       \
             _Pragma("unroll") for (int tm = 0; tm < 2; ++tm)                                       \
                 _Pragma("unroll") for (int s = 0; s < 4; ++s) acc[tm][tn][s] =                     \
                     __builtin_amdgcn_mfma_f64_4x4x4f64(qf[j & 1][s], pf[st & 1][tm],               \
@@ -156,19 +148,15 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
             double4_t a4 = {-Tw[64 * (16 * c)], -Tw[64 * (16 * c + 4)], -Tw[64 * (16 * c + 8)],
                             -Tw[64 * (16 * c + 12)]};
             double4_t xc = {0.0, 0.0, 0.0, 0.0};
-            if (!(dbg & 1)) {
 #pragma unroll
-                for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                            Lss[16 * c + (long)(16 * bb + 4 * r) * ldl], x[bb][r], a4, 0, 0, 0);
+            for (int bb = 0; bb < c; ++bb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    xc = __builtin_amdgcn_mfma_f64_16x16x4f64(-W[256 * c + 64 * r], a4[r], xc, 0, 0, 0);
-            } else {
-                xc = -a4 * 1e-3;
-            }
+                    a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                        Lss[16 * c + (long)(16 * bb + 4 * r) * ldl], x[bb][r], a4, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                xc = __builtin_amdgcn_mfma_f64_16x16x4f64(-W[256 * c + 64 * r], a4[r], xc, 0, 0, 0);
             x[c] = xc;
 #pragma unroll
             for (int r = 0; r < 4; ++r)

@@ -35,8 +35,10 @@ def _wvec(w, d):
 class Engine(object):
     """A device context.  Not thread-safe; use one per thread / per GPU."""
 
-    def __init__(self, device=0, stream=None):
-        self._lib = L.load_library()
+    def __init__(self, device=0, stream=None, probes=False):
+        """probes: run on libbqhip_probe.so (the same engine plus the hardware probes)."""
+        self._probe_eng = self if probes else None
+        self._lib = L.load_probe_library() if probes else L.load_library()
         self._ctx = C.c_void_p()
         n = C.c_int(0)
         self._lib.bq_device_count(C.byref(n))
@@ -56,6 +58,10 @@ class Engine(object):
 
     # -- plumbing ---------------------------------------------------------
     def close(self):
+        pe = getattr(self, "_probe_eng", None)
+        if pe is not None and pe is not self:
+            pe.close()
+            self._probe_eng = None
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
             self._lib.bq_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -398,49 +404,65 @@ class Engine(object):
         return Pair(self, x_s, tl_s, l_s, x_c, x_a, S)
 
     # -- probes ----------------------------------------------------------------
+    def probe_engine(self):
+        """The engine the probe_* methods run on: this one if it was created with probes=True,
+        else an engine on libbqhip_probe.so for the same device, created on first use and closed
+        with this one (its own context: the probes see the environment's switches, not this
+        engine's setters)."""
+        if self._probe_eng is None:
+            self._probe_eng = Engine(self.device, probes=True)
+        return self._probe_eng
+
     def probe_mfma_f64(self):
+        e = self.probe_engine()
         v = C.c_double()
-        self._check(self._lib.bq_probe_mfma_f64(self._ctx, C.cast(C.byref(v), _dp)))
+        e._check(e._lib.bq_probe_mfma_f64(e._ctx, C.cast(C.byref(v), _dp)))
         return float(v.value)
 
     def probe_mfma_variant(self, kind, nacc=8, waves_per_simd=2):
         """TFLOP/s of back-to-back independent MFMAs: kind 0 = v_mfma_f64_16x16x4_f64,
         1 = v_mfma_f64_4x4x4_4b_f64."""
+        e = self.probe_engine()
         v = C.c_double()
-        self._check(self._lib.bq_probe_mfma_variant(self._ctx, int(kind), int(nacc),
-                                                    int(waves_per_simd), C.cast(C.byref(v), _dp)))
+        e._check(e._lib.bq_probe_mfma_variant(e._ctx, int(kind), int(nacc),
+                                              int(waves_per_simd), C.cast(C.byref(v), _dp)))
         return v.value
 
     def probe_fma_f64(self):
+        e = self.probe_engine()
         v = C.c_double()
-        self._check(self._lib.bq_probe_fma_f64(self._ctx, C.cast(C.byref(v), _dp)))
+        e._check(e._lib.bq_probe_fma_f64(e._ctx, C.cast(C.byref(v), _dp)))
         return float(v.value)
 
     def probe_hbm(self, nbytes=1 << 30):
+        e = self.probe_engine()
         a, b = C.c_double(), C.c_double()
-        self._check(self._lib.bq_probe_hbm(self._ctx, int(nbytes), C.cast(C.byref(a), _dp),
-                                           C.cast(C.byref(b), _dp)))
+        e._check(e._lib.bq_probe_hbm(e._ctx, int(nbytes), C.cast(C.byref(a), _dp),
+                                     C.cast(C.byref(b), _dp)))
         return float(a.value), float(b.value)
 
     def probe_hbm_read8(self, nbytes=1 << 30, reps=4):
         """GB/s of a read-only pass with the single-vector sweeps' access pattern (8 B per
         lane); under ``rocprofv3 --pmc FETCH_SIZE`` a known byte count for that counter."""
+        e = self.probe_engine()
         v = C.c_double()
-        self._check(self._lib.bq_probe_hbm_read8(self._ctx, int(nbytes), int(reps),
-                                                 C.cast(C.byref(v), _dp)))
+        e._check(e._lib.bq_probe_hbm_read8(e._ctx, int(nbytes), int(reps),
+                                           C.cast(C.byref(v), _dp)))
         return float(v.value)
 
     def probe_gemm(self, m, n, k, lower=0, batch=1, qt=False, reps=20):
         """ms per launch of C (m x n) -= P Q^T (k columns) through the engine's kernel selection."""
+        e = self.probe_engine()
         v = C.c_double()
-        self._check(self._lib.bq_probe_gemm(self._ctx, int(m), int(n), int(k), int(lower),
-                                            int(batch), 1 if qt else 0, int(reps),
-                                            C.cast(C.byref(v), _dp)))
+        e._check(e._lib.bq_probe_gemm(e._ctx, int(m), int(n), int(k), int(lower),
+                                      int(batch), 1 if qt else 0, int(reps),
+                                      C.cast(C.byref(v), _dp)))
         return float(v.value)
 
     def probe_panel_solve(self, Lfac, X, mode=0, reps=0):
         """X L^-T for a batch of lower-triangular kb x kb factors L (batch, kb, kb) and row blocks
         X (batch, m, kb) through the batched factorisation's panel-solve launches."""
+        e = self.probe_engine()
         L_ = np.asarray(Lfac, dtype=np.float64)
         X_ = np.asarray(X, dtype=np.float64)
         batch, kb, _ = L_.shape
@@ -449,32 +471,35 @@ class Engine(object):
         Lf = np.ascontiguousarray(np.transpose(L_, (0, 2, 1)))
         Xf = np.ascontiguousarray(np.transpose(X_, (0, 2, 1)))
         ms = C.c_double()
-        self._check(self._lib.bq_probe_panel_solve(self._ctx, int(m), int(kb), int(batch),
-                                                   L.dptr(Lf), L.dptr(Xf), int(mode), int(reps),
-                                                   C.cast(C.byref(ms), _dp)))
+        e._check(e._lib.bq_probe_panel_solve(e._ctx, int(m), int(kb), int(batch),
+                                             L.dptr(Lf), L.dptr(Xf), int(mode), int(reps),
+                                             C.cast(C.byref(ms), _dp)))
         if reps > 0:
             return float(ms.value)  # ms per call
         return np.transpose(Xf, (0, 2, 1)).copy()
 
     def probe_xcd_hop(self, mode, iters=2000, kib=1):
         """(ns per hand-off, XCC ids of the 16 workgroups, stale payload words) -- see
-        bq_probe_xcd_hop in include/bqhip.h."""
+        bq_probe_xcd_hop in include/bqhip_probe.h."""
+        e = self.probe_engine()
         ns, bad = C.c_double(), C.c_int64()
         xcc = np.zeros(16, dtype=np.int32)
-        self._check(self._lib.bq_probe_xcd_hop(self._ctx, int(mode), int(iters), int(kib),
-                                               C.byref(ns),
-                                               xcc.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               C.byref(bad)))
+        e._check(e._lib.bq_probe_xcd_hop(e._ctx, int(mode), int(iters), int(kib),
+                                         C.byref(ns),
+                                         xcc.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         C.byref(bad)))
         return float(ns.value), xcc, int(bad.value)
 
     def probe_launch(self, n=2000):
+        e = self.probe_engine()
         v = C.c_double()
-        self._check(self._lib.bq_probe_launch(self._ctx, int(n), C.cast(C.byref(v), _dp)))
+        e._check(e._lib.bq_probe_launch(e._ctx, int(n), C.cast(C.byref(v), _dp)))
         return float(v.value)
 
     def probe_mfma_layout(self):
+        e = self.probe_engine()
         out = np.empty(256)
-        self._check(self._lib.bq_probe_mfma_layout(self._ctx, L.dptr(out)))
+        e._check(e._lib.bq_probe_mfma_layout(e._ctx, L.dptr(out)))
         return out.reshape(64, 4)
 
 

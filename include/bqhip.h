@@ -3,7 +3,8 @@
  * GP engine.  This is the drop-in boundary: plain pointers and sizes, no
  * torch / numpy types.  The Python host package binds it with ctypes
  * (bayesian-quadrature_amd/_lib.py); INTEGRATION.md shows the stub a
- * maintainer of the reference would add.
+ * maintainer of the reference would add.  The hardware probes are not part
+ * of it: they live in libbqhip_probe.so (bqhip_probe.h).
  *
  * Reference interfaces replaced (jhamrick/bayesian-quadrature v0.2.0):
  *   bq_cho_factor      <- linalg_c.pyx:55-93   cho_factor(C, L)
@@ -303,71 +304,6 @@ int bq_plan_bytes(bq_plan *plan, size_t *bytes);
  * factors in place); this checks that the batched sweep's block rules size theirs correctly. */
 int bq_set_guard(int on);
 int bq_plan_check_guards(bq_ctx *ctx, bq_plan *plan, int64_t *guarded, int64_t *damaged);
-
-/* ---- hardware probes (tools/probe.py, bench.py peak denominators) --- */
-/* sustained v_mfma_f64_16x16x4_f64 rate in TFLOP/s over all CUs */
-int bq_probe_mfma_f64(bq_ctx *ctx, double *tflops);
-/* sustained v_fma_f64 rate in TFLOP/s */
-int bq_probe_fma_f64(bq_ctx *ctx, double *tflops);
-/* streaming fp64 write / copy bandwidth in GB/s over `bytes` */
-int bq_probe_hbm(bq_ctx *ctx, size_t bytes, double *write_gbs, double *copy_gbs);
-/* ns per hand-off between two one-wave workgroups (eight ping-pong pairs, the slowest pair):
- * mode 0 = partners on one XCD, plain payload stores + sc1 flag, sc1 loads (no cache maintenance);
- * 1 = partners on different XCDs behind agent-scope release / acquire; 2 = as 1 on one XCD.  kib:
- * KiB of payload per hand-off.  xcc16: the XCC id each of the 16 workgroups ran on; bad_words:
- * payload words that arrived stale.  Bounded spins (status 3 if a partner never answers).
- * Measurement behind docs/LABBOOK.md round 6 (the C2 chain as one launch); no reference
- * counterpart (linalg_c.pyx:55-93 is one LAPACK call). */
-int bq_probe_xcd_hop(bq_ctx *ctx, int mode, int64_t iters, int64_t kib, double *ns_per_hop,
-                     int32_t *xcc16, int64_t *bad_words);
-/* C (m x n) -= P (m x k) Q (n x k)^T on scratch operands through the engine's own kernel
- * selection (lower: only the lower trapezoid; qt: Q given k-contiguous): average ms over `reps`
- * back-to-back launches -- the tuning probe behind tools/gemm_probe.py */
-int bq_probe_gemm(bq_ctx *ctx, int64_t m, int64_t n, int64_t k, int lower, int64_t batch, int qt,
-                  int64_t reps, double *ms);
-/* `reps` read-only passes over `bytes` with 8-byte-per-lane loads, 512 contiguous bytes per
- * wave (the access pattern of the single-vector sweeps): a known byte count for calibrating
- * the profiler's FETCH_SIZE counter on that pattern; read_gbs may be NULL */
-int bq_probe_hbm_read8(bq_ctx *ctx, size_t bytes, int64_t reps, double *read_gbs);
-/* MFMA issue study: kind 0 = v_mfma_f64_16x16x4_f64, 1 = v_mfma_f64_4x4x4_4b_f64; nacc
- * independent accumulators per wave (1,2,4,8); blocks_per_cu = waves per SIMD */
-int bq_probe_mfma_variant(bq_ctx *ctx, int kind, int nacc, int blocks_per_cu, double *tflops);
-/* operand map of v_mfma_f64_4x4x4_4b_f64 under the CBSZ / ABID broadcast controls:
- * out[2*(la*64 + lb) + {0,1}] = low / high half of the 64-bit mask of D lanes fed by A lane la
- * and B lane lb */
-int bq_probe_mfma444_layout(bq_ctx *ctx, int cbsz, int abid, int32_t *out8192);
-/* relative error of v_rsq_f64 raw / after one / after two Newton steps at x[0..n):
- * err3[3*i + {0,1,2}] */
-int bq_probe_rsq(bq_ctx *ctx, const double *x, int64_t n, double *err3);
-/* out[i] = the Gram kernels' own exp (exp_gauss, csrc/common.h) of x[i] <= 0: per-element
- * accuracy probe (tests/test_gpu_parity.py::test_exp_gauss_accuracy). */
-int bq_probe_exp(bq_ctx *ctx, const double *x, int64_t n, double *out);
-/* device time per launch of a chain of n empty, dependent kernels (us) */
-int bq_probe_launch(bq_ctx *ctx, int64_t n, double *us_per_launch);
-/* One eager pass of a plan (one or two problems, outer block 64) with the profiling
- * instantiation of the one-launch slab step: 160 s_memtime stamps of workgroup 0 per step
- * (10 phase boundaries, then the diagonal factor's per-wave barrier stamps). */
-int bq_probe_c2_timeline(bq_ctx *ctx, bq_plan *plan, int64_t *stamps, int64_t nsteps);
-/* The 64 x 64 diagonal factor alone (the launch that heads every panel step): A is a
- * 64 x 64 host matrix, factored `reps` times from a resident copy (from_lds != 0: handed
- * over through LDS as the one-launch steps do).  Last launch's factor, its
- * BQ_DINV_HALF-double record (64 reciprocal pivots + four 16 x 16 block inverses), info,
- * HIP-event microseconds per launch and 136 in-kernel s_memtime stamps (5 phase
- * boundaries, then per panel and wave the arrival at / release from the panel barrier). */
-int bq_probe_potf2(bq_ctx *ctx, const double *A, int from_lds, int64_t reps, double *L_out,
-                   double *dinv_out, int32_t *info_out, double *us_per_launch,
-                   int64_t *stamps136);
-/* The batched panel solve of one outer block alone (potrf.hip, enqueue_panel_solve): X (m x kb per
- * problem, column-major, in / out) <- X L^-T against `batch` dense lower-triangular kb x kb
- * factors L; mode 0: as the context is configured, 1: recursive products + 64-column solves,
- * 2: the one-launch sweep (trsm_sweep_kernel).  m, kb multiples of 64.  reps > 0: the call is
- * repeated reps times on its own output and timed (HIP events, ms per call); X is then not
- * written back. */
-int bq_probe_panel_solve(bq_ctx *ctx, int64_t m, int64_t kb, int64_t batch, const double *L,
-                         double *X, int mode, int64_t reps, double *ms_per_call);
-/* dump of the f64 MFMA D-register layout: out[64*4] receives, for lane l and
- * register r, the value row*16+col of the D element it holds */
-int bq_probe_mfma_layout(bq_ctx *ctx, double *out256);
 
 #ifdef __cplusplus
 }

@@ -1,19 +1,28 @@
 """The C-ABI library loads without a GPU and exports every symbol that
-include/bqhip.h declares; the ctypes table covers all of them; the product
-fails loudly (no fallback) when no device is present."""
+include/bqhip.h declares and no hardware probe; the probe library exports those
+and every probe of include/bqhip_probe.h; the ctypes tables cover exactly them;
+both are linked -Bsymbolic; the product fails loudly (no fallback) when no
+device is present."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "bqhip.h")).read()
+def _declared(header="bqhip.h"):
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(bq_[A-Za-z0-9_]+)\s*\(", text)))
+
+
+def _exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True,
+                         check=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
 
 
 def test_header_symbols_exported():
@@ -23,11 +32,33 @@ def test_header_symbols_exported():
     assert len(names) >= 40
     for n in names:
         assert hasattr(lib, n), "libbqhip.so does not export %s" % n
+    assert not [n for n in _exported(_lib.LIB_PATH) if n.startswith("bq_probe_")]
+
+
+def test_probe_library_exports_both_headers():
+    from bayesian_quadrature_amd import _lib
+    lib = _lib.load_probe_library()
+    probes = _declared("bqhip_probe.h")
+    assert probes and all(n.startswith("bq_probe_") for n in probes)
+    for n in _declared() + probes:
+        assert hasattr(lib, n), "libbqhip_probe.so does not export %s" % n
 
 
 def test_ctypes_table_matches_header():
     from bayesian_quadrature_amd import _lib
     assert sorted(_lib.SIGNATURES) == _declared()
+    assert sorted(_lib.PROBE_SIGNATURES) == _declared("bqhip_probe.h")
+
+
+def test_libraries_bind_their_own_symbols():
+    """DT_FLAGS SYMBOLIC (-Wl,-Bsymbolic): calls between a library's own entry points stay inside
+    it although both libraries export the bqhip.h names and libbqhip.so is loaded RTLD_GLOBAL."""
+    from bayesian_quadrature_amd import _lib
+    for path in (_lib.LIB_PATH, _lib.PROBE_LIB_PATH):
+        dyn = subprocess.run(["readelf", "-d", path], capture_output=True, text=True,
+                             check=True).stdout
+        flags = [ln for ln in dyn.splitlines() if "(FLAGS)" in ln]
+        assert flags and "SYMBOLIC" in flags[0].split(), (path, flags)
 
 
 def test_device_count_and_loud_failure():

@@ -1,15 +1,40 @@
 """GPU parity: every hot-path entry point of the C ABI against the CPU oracle on
 the same seeded inputs (SURVEY.md section 8d bars), plus size-independent
-properties at the full BASELINE sizes.  All calls go through libbqhip.so."""
+properties at the full BASELINE sizes.  All calls go through libbqhip.so (the hardware probes
+through libbqhip_probe.so)."""
+import contextlib
+import os
+
 import numpy as np
 import pytest
 
 from conftest import rand_spd
+from bayesian_quadrature_amd import Engine
 from bayesian_quadrature_amd import workloads as wl
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10  # north_star: posterior mean/variance and log-ML within 1e-10 relative fp64
+
+
+@contextlib.contextmanager
+def _engine_env(env):
+    """A second Engine(0) created with the environment switches `env` set -- a context reads them
+    when it is created --, the environment restored at once; the engine is closed on exit."""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        eng = Engine(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    try:
+        yield eng
+    finally:
+        eng.close()
 
 
 def relmax(a, b, scale=None):
@@ -28,7 +53,7 @@ def test_mfma_f64_layout(engine):
             assert lay[l, r] == 16 * row + col, (l, r, lay[l, r])
 
 
-def test_exp_gauss_accuracy(engine):
+def test_exp_gauss_accuracy_on_probe_library(engine):
     """The Gram kernels' hand-written exp (csrc/common.h: ln 2 hi/lo reduction, degree-13
     polynomial, v_ldexp_f64) per element: within 1 ulp of the true exp -- taken in x87
     extended precision -- over 10^6 arguments of [-745.2, 0], the subnormal results
@@ -41,7 +66,8 @@ def test_exp_gauss_accuracy(engine):
                         np.array([0.0, -0.0, -1e-300, -708.396418532264, -745.1332191019411,
                                   -745.1332191019412, -746.0, -800.0, -1e4])])
     out = np.empty_like(x)
-    engine._check(engine._lib.bq_probe_exp(engine._ctx, L.dptr(x), x.size, L.dptr(out)))
+    pe = engine.probe_engine()
+    pe._check(pe._lib.bq_probe_exp(pe._ctx, L.dptr(x), x.size, L.dptr(out)))
     truth = np.exp(x.astype(np.longdouble))
     ref = truth.astype(np.float64)
     ulp = np.spacing(np.maximum(np.abs(ref), np.finfo(np.float64).tiny * 2.0 ** -52))
@@ -53,7 +79,7 @@ def test_exp_gauss_accuracy(engine):
     # more than the one ulp the accuracy bound allows
     xs = np.sort(x[:200000])
     o2 = np.empty_like(xs)
-    engine._check(engine._lib.bq_probe_exp(engine._ctx, L.dptr(xs), xs.size, L.dptr(o2)))
+    pe._check(pe._lib.bq_probe_exp(pe._ctx, L.dptr(xs), xs.size, L.dptr(o2)))
     assert (np.diff(o2) >= -np.spacing(o2[1:])).all()
 
 
@@ -468,6 +494,29 @@ def test_plan_rerun_is_deterministic(engine):
     plan.close()
 
 
+def test_plan_without_graph_replay_same_bits(engine):
+    """BQ_GRAPH=0 (read when a context is created) enqueues a plan's launches one by one instead of
+    replaying them from a captured hipGraph: the same kernels in the same order, so a C2 plan and a
+    small batched plan give the same bits either way."""
+    c2 = wl.c2()
+    c5 = wl.c5([0, 1, 2], n=300, m=40)
+    cases = ((1, 1024, 256, c2["x"][None], c2["y"][None], c2["xo"][None], c2["h"], c2["w"],
+              c2["s"]),
+             (3, 300, 40, c5["x"], c5["y"], c5["xo"], c5["h"], c5["w"] * 10, c5["s"]))
+    with _engine_env({"BQ_GRAPH": "0"}) as eager:
+        for B, n, M, x, y, xo, h, w, s in cases:
+            res = []
+            for eng in (engine, eager):
+                plan = eng.plan(B, 1, n, M)
+                plan.set_inputs(x, y, xo, h, w, s)
+                plan.run()  # (the graph-replaying engine: captured here, replayed from here on)
+                plan.run()
+                res.append(plan.results())
+                plan.close()
+            for u, v in zip(*res):
+                assert np.array_equal(u, v), (B, n, M)
+
+
 # ---- golden fixtures ----------------------------------------------------------------
 def test_golden_c1(engine):
     import os
@@ -637,26 +686,12 @@ def test_trailing_update_variants_agree(engine, env, nb, la):
     kept beside the shipped trailing update (BQ_GEMM_LDS=0, read when a context is created),
     gives the same factor of an N = 4480 system -- a
     size that is a multiple of 64 but not of 128, large enough for the 128 x 128 tiles."""
-    import os
-    from bayesian_quadrature_amd import Engine
     n = 4480
     c = wl.c4(n)
     x = np.ascontiguousarray(c["x"])
     K, Lref = _potrf_dev(engine, x, c, n)
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = Engine(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    try:
+    with _engine_env(env) as eng:
         K2, L2 = _potrf_dev(eng, x, c, n, nb, la)
-    finally:
-        eng.close()
     assert np.array_equal(K, K2)
     assert _resid(K, L2, np.random.RandomState(3), nvec=2) < 1e-14 * n
     # the variants differ only in summation order
@@ -1164,18 +1199,7 @@ def test_kernel_copies_match_the_copy_engine_route(engine):
     linalg_c drop-ins are one launch.  The same calls with BQ_SOLVE_KCOPY=0 give the same bits where
     the same kernels do the arithmetic, and agree to rounding where the one-launch forms replace
     them (cho_solve up to 64 rows)."""
-    import os
-    from bayesian_quadrature_amd import Engine
-    old = os.environ.get("BQ_SOLVE_KCOPY")
-    os.environ["BQ_SOLVE_KCOPY"] = "0"
-    try:
-        eng0 = Engine(0)
-    finally:
-        if old is None:
-            os.environ.pop("BQ_SOLVE_KCOPY", None)
-        else:
-            os.environ["BQ_SOLVE_KCOPY"] = old
-    try:
+    with _engine_env({"BQ_SOLVE_KCOPY": "0"}) as eng0:
         rs = np.random.RandomState(4)
         # a resident fit: one-vector solves (one-launch sweeps and the per-block route), posterior
         for n in (700, 1500, 2100):
@@ -1215,11 +1239,9 @@ def test_kernel_copies_match_the_copy_engine_route(engine):
             if n > 64:
                 assert np.array_equal(xa, xb)
             assert engine.logdet(La) == eng0.logdet(La)
-    finally:
-        eng0.close()
 
 
-def test_diagonal_factor_block_inverses_and_pivots(engine):
+def test_diagonal_factor_block_inverses_and_pivots_on_probe_library(engine):
     """The 64 x 64 diagonal factor alone (bq_probe_potf2: four and eight waves, the block read from
     global memory and handed over through LDS): L against LAPACK, the reciprocal pivots, and the four
     16 x 16 block inverses every panel solve multiplies by -- W_b L_bb = I to rounding --; the four
@@ -1227,6 +1249,7 @@ def test_diagonal_factor_block_inverses_and_pivots(engine):
     operations in the substitution's order); a non-positive pivot is reported at its column."""
     import ctypes as C
     from bayesian_quadrature_amd import _lib as L
+    pe = engine.probe_engine()
 
     def probe(A, flags):
         A = np.asfortranarray(A, dtype=np.float64)
@@ -1235,9 +1258,8 @@ def test_diagonal_factor_block_inverses_and_pivots(engine):
         info = C.c_int32(0)
         us = C.c_double(0)
         st = (C.c_int64 * 136)()
-        engine._check(engine._lib.bq_probe_potf2(engine._ctx, L.dptr(A), flags, 2, L.dptr(Lo),
-                                                 L.dptr(dv), C.byref(info),
-                                                 C.cast(C.byref(us), L._dp), st))
+        pe._check(pe._lib.bq_probe_potf2(pe._ctx, L.dptr(A), flags, 2, L.dptr(Lo), L.dptr(dv),
+                                         C.byref(info), C.cast(C.byref(us), L._dp), st))
         return np.tril(Lo), dv, info.value
 
     rs = np.random.RandomState(11)
@@ -1278,18 +1300,7 @@ def test_potf2_eight_waves_is_the_same_factor(engine):
     potf2f_body<8>; BQ_POTF2_8W, read when a context is created) applies the same updates to
     every column in the same order as the four-wave form: a C2 pass and a small failing
     system give bit-identical results."""
-    import os
-    from bayesian_quadrature_amd import Engine
-    old = os.environ.get("BQ_POTF2_8W")
-    os.environ["BQ_POTF2_8W"] = "0"
-    try:
-        eng4 = Engine(0)
-    finally:
-        if old is None:
-            os.environ.pop("BQ_POTF2_8W", None)
-        else:
-            os.environ["BQ_POTF2_8W"] = old
-    try:
+    with _engine_env({"BQ_POTF2_8W": "0"}) as eng4:
         c = wl.c2()
         res = []
         for eng in (engine, eng4):
@@ -1311,8 +1322,6 @@ def test_potf2_eight_waves_is_the_same_factor(engine):
                 eng.gp_fit(x, y, 1.0, 0.2, 0.0)
             res.append(str(ei.value))
         assert res[-1] == res[-2]
-    finally:
-        eng4.close()
 
 
 def test_folded_readout_matches_finalize(engine, oracle):
@@ -1321,18 +1330,7 @@ def test_folded_readout_matches_finalize(engine, oracle):
     finalize launch; BQ_FOLD_READOUT=0 (read when a context is created) gives the stand-alone
     form.  Plans (one and several problems, with and without prediction points) and the
     resident fit agree between the two and with the oracle."""
-    import os
-    from bayesian_quadrature_amd import Engine
-    old = os.environ.get("BQ_FOLD_READOUT")
-    os.environ["BQ_FOLD_READOUT"] = "0"
-    try:
-        eng0 = Engine(0)
-    finally:
-        if old is None:
-            os.environ.pop("BQ_FOLD_READOUT", None)
-        else:
-            os.environ["BQ_FOLD_READOUT"] = old
-    try:
+    with _engine_env({"BQ_FOLD_READOUT": "0"}) as eng0:
         rs = np.random.RandomState(11)
         for B, n, M in ((1, 1024, 256), (3, 200, 33), (5, 40, 0), (2, 64, 64), (1, 63, 1)):
             dx = 10.0 / n
@@ -1368,8 +1366,6 @@ def test_folded_readout_matches_finalize(engine, oracle):
             lm.append(fit.logml)
             fit.close()
         assert abs(lm[0] - lm[2]) <= 1e-13 * abs(lm[0]) and abs(lm[1] - lm[3]) <= 1e-13 * abs(lm[1])
-    finally:
-        eng0.close()
 
 
 def test_ksplit_variants_agree(engine):
@@ -1377,18 +1373,7 @@ def test_ksplit_variants_agree(engine):
     rows_fused_kernel<., 2>; BQ_GEMM_KSPLIT, read when a context is created) against the
     four-wave forms: a posterior variance at C2's size and a 256-column solve on an N = 4096
     factor differ only in summation order."""
-    import os
-    from bayesian_quadrature_amd import Engine
-    old = os.environ.get("BQ_GEMM_KSPLIT")
-    os.environ["BQ_GEMM_KSPLIT"] = "0"
-    try:
-        eng4 = Engine(0)
-    finally:
-        if old is None:
-            os.environ.pop("BQ_GEMM_KSPLIT", None)
-        else:
-            os.environ["BQ_GEMM_KSPLIT"] = old
-    try:
+    with _engine_env({"BQ_GEMM_KSPLIT": "0"}) as eng4:
         c = wl.c2()
         xo = np.linspace(-5.0, 5.0, 256) + 1e-3
         res = []
@@ -1408,8 +1393,6 @@ def test_ksplit_variants_agree(engine):
             X.append(fit.solve(B))
             fit.close()
         assert relmax(X[0], X[1]) < 1e-9  # (cond(K) ~ 1e6: both are within it of the solution)
-    finally:
-        eng4.close()
 
 
 def test_cho_solve_mat_square_multi_block(engine, oracle):
@@ -1526,8 +1509,6 @@ def test_pair_esm_routes_agree(engine):
     against the S M full bordered systems (BQ_PAIR_BORDER=0), incl. a candidate on top of a
     candidate point (both jitters) and a set whose GP2 is numerically singular (its elements'
     status non-zero on both routes)."""
-    import os
-    from bayesian_quadrature_amd import Engine
     ns, S, M = 200, 6, 14
     xs, ls, xc, dx, rs = _pair_problem(ns, 9, 3 * ns + M)
     x_a = np.sort(np.concatenate([rs.uniform(-7, 7, M - 2), xc[:1] + 0.05, xc[-1:]]))
@@ -1537,17 +1518,10 @@ def test_pair_esm_routes_agree(engine):
     pair = engine.pair(xs, np.log(ls), ls, xc, x_a, S)
     r = pair.esm(p_tl, p_l, 0.5, MU1, COV1)
     pair.close()
-    os.environ["BQ_PAIR_BORDER"] = "0"
-    try:
-        e2 = Engine(0)
-    finally:
-        del os.environ["BQ_PAIR_BORDER"]
-    try:
+    with _engine_env({"BQ_PAIR_BORDER": "0"}) as e2:
         pair2 = e2.pair(xs, np.log(ls), ls, xc, x_a, S)
         r2 = pair2.esm(p_tl, p_l, 0.5, MU1, COV1)
         pair2.close()
-    finally:
-        e2.close()
     assert ((r["status"] != 0) == (r2["status"] != 0)).all() and (r["status"][3] != 0).all()
     ok = r["status"] == 0
     assert ok.sum() >= (S - 1) * M - 2
@@ -1602,8 +1576,6 @@ def test_batch_dense_vs_oracle_and_variants(engine, oracle, batch, n, m):
     the batched sweep against the default on the same inputs: the recursive panels of rounds 1-3
     (BQ_DIAG_FIRST=0), either form of the diagonal factor, the recursive panel solve, the fork
     after instead of before the panel solve, no second stream."""
-    import os
-    from bayesian_quadrature_amd import Engine
     x, y, xo, h, w, s = _dense_batch(batch, n, m)
     mean, var, logml, status = engine.batch_fit_predict(x, y, h, w, s, xo)
     assert (status == 0).all()
@@ -1616,16 +1588,8 @@ def test_batch_dense_vs_oracle_and_variants(engine, oracle, batch, n, m):
     for env in ({"BQ_DIAG_FIRST": "0"}, {"BQ_DF_WG": "0"}, {"BQ_DF_WG": "1"}, {"BQ_DF_SWEEP": "0"},
                 {"BQ_DF_EARLY": "0"}, {"BQ_DF_WG_ROWS": "0"}, {"BQ_DF_WG_ROWS": "300"},
                 {"BQ_LOOKAHEAD": "0"}):
-        os.environ.update(env)
-        try:
-            e2 = Engine(0)
-        finally:
-            for k in env:
-                del os.environ[k]
-        try:
+        with _engine_env(env) as e2:
             m2, v2, l2, st2 = e2.batch_fit_predict(x, y, h, w, s, xo)
-        finally:
-            e2.close()
         assert (st2 == 0).all(), env
         assert relmax(m2, mean) < 1e-12 and relmax(l2, logml) < 1e-12, env
         assert relmax(v2, var, scale=oracle.kernel_scale(2, h, w)) < 1e-12, env
@@ -1727,8 +1691,6 @@ def test_fused_assembly_same_bits(engine, oracle, batch, n, m, d):
     that goes to a register-streaming kernel), its region is assembled right in front of it.
     Either way the results carry the bits of the full assembly (BQ_ASM_FUSE=0), and problem 0
     agrees with the oracle."""
-    import os
-    from bayesian_quadrature_amd import Engine
     rs = np.random.RandomState(batch + n + d)
     x = rs.uniform(-3, 3, (batch, d, n))
     xo = rs.uniform(-3, 3, (batch, d, m))
@@ -1737,15 +1699,8 @@ def test_fused_assembly_same_bits(engine, oracle, batch, n, m, d):
     w = np.full(d, 6.0 / n ** (1.0 / d) * 1.5)
     mean, var, logml, status = engine.batch_fit_predict(x, y, h, w, s, xo)
     assert (status == 0).all()
-    os.environ["BQ_ASM_FUSE"] = "0"
-    try:
-        e2 = Engine(0)
-    finally:
-        del os.environ["BQ_ASM_FUSE"]
-    try:
+    with _engine_env({"BQ_ASM_FUSE": "0"}) as e2:
         m2, v2, l2, st2 = e2.batch_fit_predict(x, y, h, w, s, xo)
-    finally:
-        e2.close()
     assert np.array_equal(mean, m2) and np.array_equal(var, v2) and np.array_equal(logml, l2)
     assert np.array_equal(status, st2)
     Lo, ao, lmo = oracle.gp_fit(x[0], y[0], h, w, s)
@@ -1782,8 +1737,6 @@ def test_flow_sweeps_same_bits_as_per_block_launches(engine, n):
     one grid, values handed over through sentinel-filled slots) against the one-launch-per-block
     sweeps (BQ_TRSV_FLOW=0): the same arithmetic in the same order, so the same bits; and the
     residual K x - b."""
-    import os
-    from bayesian_quadrature_amd import Engine
     c = wl.c4(n)
     y = wl.norm_logpdf(c["x"])
     b = np.random.RandomState(n).randn(n)
@@ -1791,17 +1744,10 @@ def test_flow_sweeps_same_bits_as_per_block_launches(engine, n):
     x1, a1 = fit.solve(b), fit.alpha()
     K = fit.K()
     fit.close()
-    os.environ["BQ_TRSV_FLOW"] = "0"
-    try:
-        e2 = Engine(0)
-    finally:
-        del os.environ["BQ_TRSV_FLOW"]
-    try:
+    with _engine_env({"BQ_TRSV_FLOW": "0"}) as e2:
         f2 = e2.gp_fit(c["x"], y, c["h"], c["w"] * 3.0, c["s"])
         x0, a0 = f2.solve(b), f2.alpha()
         f2.close()
-    finally:
-        e2.close()
     assert np.array_equal(x1, x0) and np.array_equal(a1, a0)
     # (w = 3 dx: a wider band than C4's, cond(K) ~ 1e8 -- the bar is the residual with the device's
     # own Gram matrix, as in test_fit_solve_at_benched_sizes)

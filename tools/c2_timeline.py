@@ -14,7 +14,7 @@ NAMES = ["entry", "frags_loaded", "rows_solved", "tile_loaded", "tile_updated", 
          "potf2_loaded", "potf2_chain", "potf2_blocks", "potf2_end"]
 
 if __name__ == "__main__":
-    e = Engine(0)
+    e = Engine(0, probes=True)
     c = wl.c2()
     plan = e.plan(1, 1, 1024, 256)
     plan.set_inputs(c["x"][None], c["y"][None], c["xo"][None], c["h"], c["w"], c["s"])
@@ -27,7 +27,7 @@ if __name__ == "__main__":
     t = np.array(list(st), dtype=np.int64).reshape(nsteps, 160)[:, :10]
     d = np.diff(t, axis=1)                       # phase lengths per step
     gap = t[1:, 0] - t[:-1, 9]                   # end of a step's factor -> next step's entry
-    out = {"library": L.LIB_PATH, "unit": "s_memtime ticks",
+    out = {"library": L.PROBE_LIB_PATH, "unit": "s_memtime ticks",
            "phases_mean_steps_1_14": {NAMES[i + 1]: float(d[1:15, i].mean()) for i in range(9)},
            "phases_step_5": {NAMES[i + 1]: int(d[5, i]) for i in range(9)},
            "step_total_mean": float((t[1:15, 9] - t[1:15, 0]).mean()),

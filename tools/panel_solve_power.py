@@ -19,7 +19,7 @@ def smi():
     return (int(v[1]), v[0]) if v else (-1, -1.0)
 
 
-modes = [int(v) for v in sys.argv[1:]] or [2, 18]
+modes = [int(v) for v in sys.argv[1:]] or [2]
 m, kb, batch = (int(v) for v in os.environ.get("SHAPE", "2048,448,64").split(","))
 rs = np.random.RandomState(0)
 # unit diagonal + a small strictly lower part: thousands of solves of the solve's own output stay

@@ -36,9 +36,9 @@ def check(A, Lo, dv):
 
 
 if __name__ == "__main__":
-    e = Engine(0)
+    e = Engine(0, probes=True)
     rs = np.random.RandomState(0)
-    out = {"library": L.LIB_PATH}
+    out = {"library": L.PROBE_LIB_PATH}
     # a C2-like diagonal block (Gaussian kernel, w = dx, s = 1e-3) and a random SPD block
     x = np.linspace(-5, 5, 1024)[:64]
     dx = 10.0 / 1023

@@ -3,7 +3,7 @@ accumulators per wave and waves per SIMD."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bayesian_quadrature_amd import Engine, _lib as L
-e = Engine(0)
+e = Engine(0, probes=True)
 for kind, name in ((0, "16x16x4"), (1, "4x4x4_4b")):
     for nacc in (1, 2, 4, 8):
         row = []

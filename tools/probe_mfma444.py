@@ -4,7 +4,7 @@ import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bayesian_quadrature_amd import Engine, _lib as L
-e = Engine(0)
+e = Engine(0, probes=True)
 
 
 def table(cbsz, abid):

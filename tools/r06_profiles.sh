@@ -38,7 +38,6 @@ du -sh $O
 python tools/c5_time.py all > $O/c5_time.txt 2>&1 || echo c5-time-failed
 for w in c5 c2x256 c3chunk; do python tools/plan_timeline.py $w v > $O/plan_timeline_$w.txt 2>&1 || echo timeline-$w-failed; done
 python tools/predict_time.py > $O/predict_time.txt 2>&1 || echo predict-time-failed
-python tools/wide_b_check.py > $O/wide_b_check.txt 2>&1 || echo wide-b-failed
 python tools/panel_solve_time.py > $O/panel_solve_time.txt 2>&1 || echo panel-solve-time-failed
 python tools/trsv_flow_check.py 2048 4096 16384 > $O/trsv_flow_check.txt 2>&1 || echo trsv-flow-failed
 python tools/choose_next_time.py > $O/choose_next_time.txt 2>&1 || echo choose-next-failed
@@ -46,7 +45,6 @@ python tools/fit_hypers_time.py > $O/fit_hypers_time.txt 2>&1 || echo fit-hypers
 # round 6: the panel solve under the socket's power cap (sustained rates, clock, watts), its
 # ablations (debug build), and what a hand-off costs inside one XCD
 bash tools/r06_shapes.sh > /dev/null 2>&1; cp gpurun_out/r06s/power5.txt $O/panel_solve_power.txt 2>/dev/null || echo shapes-failed
-(cd bayesian-quadrature_amd/csrc && make -j8 DEFS=-DBQ_TS_DBG OUT=../libbqhip_dbg.so > /dev/null 2>&1) && bash tools/r06_ablate.sh > /dev/null 2>&1; cp gpurun_out/r06s/ablate.txt $O/panel_solve_ablate.txt 2>/dev/null || echo ablate-failed
 rm -f bayesian-quadrature_amd/libbqhip_dbg.so
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_MFMA --output-format csv -d $O/pmc_sweep_a -o p -- python3 tools/panel_solve_one.py 2 2048 448 64 4 > $O/pmc_sweep_a.txt 2>&1 || echo pmc-sweep-a-failed
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sweep_b -o p -- python3 tools/panel_solve_one.py 2 2048 448 64 4 > $O/pmc_sweep_b.txt 2>&1 || echo pmc-sweep-b-failed
