@@ -25,6 +25,7 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     f->have_zc = false;
     f->have_wide = false;
     f->have_dw = false;
+    f->have_y = false;
     // pinned staging: [0, 136) results, then the kernel parameters, then border points
     constexpr size_t HF_PAR = 8 + 128, HF_PTS = HF_PAR + (sizeof(GaussParams) + 7) / 8;
     if (!f->hfit)
@@ -279,6 +280,7 @@ extern "C" int bq_gp_set_y(bq_ctx *c, bq_fit *f, const double *y)
     f->stale = true; // the factor is intact, z / alpha / log-ML belong to the old targets
     f->have_alpha = false;
     f->have_zc = false;
+    f->have_y = false;
     HIPCHK(c, hipMemcpyAsync(f->y.p, y, sizeof(double) * f->n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // y is the caller's buffer
     return BQ_OK;
@@ -348,6 +350,62 @@ extern "C" int bq_gp_logml(bq_ctx *c, bq_fit *f, double *out)
     if (!out)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     *out = f->logml;
+    return BQ_OK;
+}
+
+// d log p / d theta = 1/2 sum_ij G_ij dKxx_ij / d theta, G = alpha alpha^T - Kxx^-1, with
+// Kxx^-1 = Y Y^T, Y = L^-T: the triangular inverse by the forward row sweep on I (kept until the
+// next (re)fit), then one MFMA product over the lower tiles of Y Y^T seeded with alpha alpha^T whose
+// tiles are reduced against the kernel's derivatives instead of stored (gemm_lds_grad_kernel)
+extern "C" int bq_gp_logml_grad(bq_ctx *c, bq_fit *f, double *grad)
+{
+    BQCHK(check_fit(c, f));
+    if (!grad)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad;
+    BQCHK(fit_alpha(c, f));
+    if (!f->have_y) {
+        WideInv w;
+        BQCHK(fit_wide(c, f, w));
+        const size_t bytes = sizeof(double) * (size_t)npad * npad;
+        if (f->gY.bytes < bytes || f->gX.bytes < bytes) {
+            // both buffers or neither: a failed allocation leaves no half-made workspace for the
+            // next call to run on.  The sweep never writes Y's strict lower triangle and the
+            // product reads it in diagonal tiles: cleared once, here
+            hipError_t e = f->gY.alloc(bytes);
+            if (e == hipSuccess)
+                e = f->gX.alloc(bytes);
+            if (e == hipSuccess)
+                e = hipMemsetAsync(f->gY.p, 0, bytes, c->stream);
+            if (e != hipSuccess) {
+                f->gY.release();
+                f->gX.release();
+                return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                            "gradient workspace (2 x %zu bytes): %s", bytes, hipGetErrorString(e));
+            }
+        }
+        BQCHK(enqueue_inverse_rows(c, f->gX.d(), f->gY.d(), f->A.d(), f->ldl, npad, w));
+        f->have_y = true;
+    }
+    const size_t np = grad_parts(npad, d);
+    if (f->gpart.bytes < sizeof(double) * (np + BQ_MAXD + 2))
+        HIPCHK(c, f->gpart.alloc(sizeof(double) * (np + BQ_MAXD + 2)));
+    GradJob gj;
+    gj.alpha = f->alpha.d();
+    gj.pts = f->pts.d();
+    gj.part = f->gpart.d();
+    gj.g = f->g;
+    gj.n = f->n;
+    GradScale sc{};
+    sc.f[0] = 1.0 / f->h;
+    for (int k = 0; k < d; ++k)
+        sc.f[1 + k] = 0.5 / f->w[k];
+    sc.f[d + 1] = f->s;
+    double *gd = f->gpart.d() + np;
+    BQCHK(launch_logml_grad(c, d, f->gY.d(), npad, gj, sc, gd));
+    HIPCHK(c, hipMemcpyAsync(grad, gd, sizeof(double) * (d + 2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return BQ_OK;
 }
 

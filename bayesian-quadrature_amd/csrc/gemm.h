@@ -487,14 +487,109 @@ __global__ __launch_bounds__(256) void gemm_k64_kernel(double *__restrict__ C, l
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void global_cvoid_t;
 
+// The log-ML gradient's accumulators start at -alpha_i alpha_j (Tile444's rotated-quad layout)
+template <int TM, int TN>
+__device__ __forceinline__ void grad_seed_neg(double (&acc)[TM][TN][4],
+                                              const double *__restrict__ alpha, int row0, int col0,
+                                              int lane)
+{
+    const int l15 = lane & 15, l4 = lane >> 4, blk = (lane >> 2) & 3;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+        const double ai = alpha[row0 + 16 * tm + l15];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                acc[tm][tn][s] = -(ai * alpha[col0 + 16 * tn + 4 * ((blk - s) & 3) + l4]);
+    }
+}
+
+// The log-ML gradient's tile reduction (GD = d > 0 in gemm_lds_body / gemm_lds64_body): with acc = -G on the wave
+// tile (rows row0.., columns col0..), the d + 2 sums of the gradient over its entries with i, j < n,
+//   S_K = sum G k,  S_k = sum G k (r_k^2 / w_k^2 - 1),  S_s = sum_i G_ii,
+// weighted 2 off the diagonal (the tile stands for its mirror too), one partial per workgroup.
+// (TM = TN = 4: the 128-tile's 64 x 64 wave tiles; 2: the 64-tile's 32 x 32 ones)
+template <int D, int TM, int TN>
+__device__ __forceinline__ void grad_tile_reduce(const double (&acc)[TM][TN][4], const GradJob &gj,
+                                                 unsigned char *smem, int row0, int col0,
+                                                 bool active, int lane, int wave)
+{
+    constexpr int NC = D + 2;
+    double sum[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        sum[c] = 0.0;
+    if (active) {
+        const int l15 = lane & 15, l4 = lane >> 4, blk = (lane >> 2) & 3;
+        const GaussParams &g = gj.g;
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) {
+            const int i = row0 + 16 * tm + l15;
+            if (i >= gj.n)
+                continue;
+            double xi[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+                xi[k] = gj.pts[k + (long)i * D];
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int j = col0 + 16 * tn + 4 * ((blk - s) & 3) + l4;
+                    if (j >= gj.n)
+                        continue;
+                    const double G = -acc[tm][tn][s];
+                    double r2[D], q = 0.0; // gauss_q's arithmetic
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const double t = xi[k] - gj.pts[k + (long)j * D];
+                        r2[k] = t * t;
+                        q += r2[k] * g.nh[k];
+                    }
+                    const double gk = G * (g.c * exp_gauss(q));
+                    sum[0] += gk;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) // r^2 / w^2 = -2 nh r^2
+                        sum[1 + k] += gk * ((-2.0 * g.nh[k]) * r2[k] - 1.0);
+                    if (i == j)
+                        sum[D + 1] += G;
+                }
+        }
+        const double wt = row0 == col0 ? 1.0 : 2.0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            sum[c] *= wt;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            sum[c] += __shfl_xor(sum[c], off);
+    // the staging buffers are free once every wave is past its last chunk
+    double *red = reinterpret_cast<double *>(smem);
+    __syncthreads();
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            red[wave * NC + c] = sum[c];
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < NC)
+        gj.part[(long)blockIdx.x * NC + t] = ((red[t] + red[NC + t]) + red[2 * NC + t]) + red[3 * NC + t];
+}
+
 // SD > 0: C has not been written yet -- the accumulators start as minus the bordered system's own
 // entries (gram_seed_neg<SD>, points of dimension SD) instead of minus a loaded tile
-template <int SD>
+// GD > 0: the log-ML gradient (gemm_lds_grad_kernel): P = Q = Y = L^-T, upper triangular, so a
+// lower tile's k range starts at its first row; the accumulators start at -alpha_i alpha_j, end at
+// -G = Y Y^T - alpha alpha^T, and are reduced (grad_tile_reduce<GD>) instead of stored
+template <int SD, int GD = 0>
 __device__ __forceinline__ void gemm_lds_body(double *__restrict__ C, long ldc, long cstride,
                                               const double *__restrict__ P, long ldp, long pstride,
                                               const double *__restrict__ Q, long ldq, long qstride,
                                               int m, int n, int k, int lower, int ncut,
-                                              const GramSeed *sd)
+                                              const GramSeed *sd, const GradJob *gj = nullptr)
 {
     // ncut: columns >= ncut of C are left alone (the border x border block of a bordered
     // system, which nothing reads: see plan_readout_kernel)
@@ -512,6 +607,11 @@ __device__ __forceinline__ void gemm_lds_body(double *__restrict__ C, long ldc, 
     const int R0 = bx * 128, C0 = by * 128;
     if (C0 >= ncut)
         return; // (the whole workgroup, before any barrier)
+    if constexpr (GD > 0) { // Y[i, k] = 0 for k < i: the terms before the tile's first row vanish
+        P += (long)R0 * ldp;
+        Q += (long)R0 * ldq;
+        k -= R0;
+    }
     const int wr = (wave & 1) * 64, wc = (wave >> 1) * 64; // this wave's 64 x 64 sub-tile
     const int row0 = R0 + wr, col0 = C0 + wc;
     const bool active = row0 < m && col0 < n && col0 < ncut && !(lower && col0 >= row0 + 64);
@@ -591,7 +691,9 @@ __device__ __forceinline__ void gemm_lds_body(double *__restrict__ C, long ldc, 
     BQ_LDS_FILL(0, 0)
     const Tile444<4, 4> ct(C, ldc, row0, col0, lane);
     if (active) {
-        if (SD > 0)
+        if constexpr (GD > 0)
+            grad_seed_neg<4, 4>(acc, gj->alpha, row0, col0, lane);
+        else if (SD > 0)
             gram_seed_neg<(SD > 0 ? SD : 1), 4, 4>(acc, *sd, b, row0, col0, lane);
         else
             ct.load_neg(acc);
@@ -606,6 +708,10 @@ __device__ __forceinline__ void gemm_lds_body(double *__restrict__ C, long ldc, 
 #undef BQ_LDS_CHUNK
 #undef BQ_LDS_FILL
 
+    if constexpr (GD > 0) {
+        grad_tile_reduce<GD, 4, 4>(acc, *gj, smem, row0, col0, active, lane, wave);
+        return;
+    }
     if (!active)
         return;
     ct.store_neg(acc, lower);
@@ -619,6 +725,41 @@ __global__ __launch_bounds__(256, 2) void gemm_lds_kernel(double *__restrict__ C
                                                           int lower, int ncut)
 {
     gemm_lds_body<0>(C, ldc, cstride, P, ldp, pstride, Q, ldq, qstride, m, n, k, lower, ncut, nullptr);
+}
+
+// The log-ML gradient's product over the lower 128-tiles of Y Y^T (1-D triangular grid, m = n =
+// k = npad; Y = L^-T column-major, ld ldy), each workgroup's d + 2 partial sums to gj.part
+template <int D>
+__global__ __launch_bounds__(256, 2) void gemm_lds_grad_kernel(const double *__restrict__ Y, long ldy,
+                                                               int npad, GradJob gj)
+{
+    gemm_lds_body<0, D>(const_cast<double *>(Y), ldy, 0, Y, ldy, 0, Y, ldy, 0, npad, npad, npad, 2,
+                        0x7fffffff, nullptr, &gj);
+}
+
+// Sums the partials of gemm_lds(64)_grad_kernel in a fixed order (same bits on every call) and scales
+// them into the gradient: grad = [S_K / h, S_k / (2 w_k), s S_s]
+__global__ __launch_bounds__(256) void grad_finalize_kernel(const double *__restrict__ part,
+                                                            int nwg, int nc, GradScale sc,
+                                                            double *__restrict__ grad)
+{
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    for (int c = 0; c < nc; ++c) {
+        double v = 0.0;
+        for (int i = t; i < nwg; i += 256)
+            v += part[(long)i * nc + c];
+        red[t] = v;
+        __syncthreads();
+        for (int h = 128; h > 0; h >>= 1) {
+            if (t < h)
+                red[t] += red[t + h];
+            __syncthreads();
+        }
+        if (t == 0)
+            grad[c] = red[0] * sc.f[c];
+        __syncthreads();
+    }
 }
 
 // ... its tile of C computed, not loaded (the first product over a region the assembly left out)
@@ -666,7 +807,8 @@ __global__ __launch_bounds__(256, 2) void gemm_lds_seed_kernel(
 // trsm_blk_kernel scheme applied to the tile on its way out (through LDS into that kernel's
 // 16-rows-per-wave operand form): one launch and one pass over the slab less per 64 columns.
 // Lss: the slab's factored 64 x 64 diagonal block, wrec: its record of block inverses.
-template <bool QT, int KS = 1, bool TRSM = false, int SD = 0>
+// GD > 0: the log-ML gradient in 64 x 64 workgroup tiles (gemm_lds64_grad_kernel; see gemm_lds_body)
+template <bool QT, int KS = 1, bool TRSM = false, int SD = 0, int GD = 0>
 __device__ __forceinline__ void gemm_lds64_body(unsigned char *smem, double *__restrict__ C,
                                                 long ldc, const double *__restrict__ P, long ldp,
                                                 const double *__restrict__ Q, long ldq, int m,
@@ -674,7 +816,8 @@ __device__ __forceinline__ void gemm_lds64_body(unsigned char *smem, double *__r
                                                 const double *__restrict__ Lss = nullptr,
                                                 long ldl = 0,
                                                 const double *__restrict__ wrec = nullptr,
-                                                const GramSeed *sd = nullptr, int sb = 0)
+                                                const GramSeed *sd = nullptr, int sb = 0,
+                                                const GradJob *gj = nullptr)
 {
     const int t = threadIdx.x, lane = t & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -682,6 +825,11 @@ __device__ __forceinline__ void gemm_lds64_body(unsigned char *smem, double *__r
     const int R0 = bx * 64, C0 = by * 64;
     if (C0 >= ncut)
         return; // (the whole workgroup, before any barrier)
+    if constexpr (GD > 0) { // Y[i, k] = 0 for k < i: the terms before the tile's first row vanish
+        P += (long)R0 * ldp;
+        Q += (long)R0 * ldq;
+        k -= R0;
+    }
     const int wr = (wave & 1) * 32, wc = (wave >> 1) * 32;
     const int row0 = R0 + wr, col0 = C0 + wc;
     const bool active = row0 < m && col0 < n && col0 < ncut && !(lower && col0 >= row0 + 32);
@@ -779,7 +927,9 @@ __device__ __forceinline__ void gemm_lds64_body(unsigned char *smem, double *__r
     // of a CU's rate whether four waves walk it or eight; what the eight gain is the job tiles')
     BQ_L64_FILL(0, 0)
     if (active && (KS == 1 || grp == 0)) {
-        if (SD > 0) // (the tile computed from the problem's points: see gemm_lds_body)
+        if constexpr (GD > 0)
+            grad_seed_neg<2, 2>(acc, gj->alpha, row0, col0, lane);
+        else if (SD > 0) // (the tile computed from the problem's points: see gemm_lds_body)
             gram_seed_neg<(SD > 0 ? SD : 1), 2, 2>(acc, *sd, sb, row0, col0, lane);
         else
             ct.load_neg(acc);
@@ -803,6 +953,10 @@ __device__ __forceinline__ void gemm_lds64_body(unsigned char *smem, double *__r
 #undef BQ_L64_OFF
 #undef BQ_L64_QOFF
 
+    if constexpr (GD > 0) {
+        grad_tile_reduce<GD, 2, 2>(acc, *gj, smem, row0, col0, active, lane, wave);
+        return;
+    }
     if (KS == 2) {
         // group 1's partial sums -> LDS (16 doubles per lane, 32 KiB: the staging buffers are
         // free once every wave is past its last chunk) -> group 0
@@ -923,6 +1077,21 @@ __global__ __launch_bounds__(256, 4) void gemm_lds64_seed_kernel(
     gemm_lds64_body<false, 1, false, SD>(smem, C + (long)b * cstride, ldc, P + (long)b * pstride,
                                          ldp, Q + (long)b * qstride, ldq, m, n, k, lower, ncut, bx,
                                          by, nullptr, 0, nullptr, &sd, b);
+}
+
+// the log-ML gradient's product in 64 x 64 tiles: four times the workgroups of
+// gemm_lds_grad_kernel for the systems whose 128-tiles cannot fill the chip.  (Three waves per
+// SIMD at the least, not four: at d = 8 the epilogue spilled under the 128-VGPR cap of four.)
+template <int D>
+__global__ __launch_bounds__(256, 3) void gemm_lds64_grad_kernel(const double *__restrict__ Y,
+                                                                 long ldy, int npad, GradJob gj)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int bx, by;
+    tri_decode(blockIdx.x, bx, by);
+    gemm_lds64_body<false, 1, false, 0, D>(smem, const_cast<double *>(Y), ldy, Y, ldy, Y, ldy, npad,
+                                           npad, npad, 2, 0x7fffffff, bx, by, nullptr, 0, nullptr,
+                                           nullptr, 0, &gj);
 }
 
 

@@ -362,6 +362,10 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
 // ---- k_gemm.hip -----------------------------------------------------------------------
 int gemm_init(bq_ctx *c); // function attributes of the LDS-staged kernels, once per context
 bool gemm_uses_lds(const bq_ctx *c, int m, int n, int k, int lower, int batch);
+// the log-ML gradient's product and finalize (gemm_lds_grad_kernel, grad_finalize_kernel)
+size_t grad_parts(int npad, int d);
+int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob &gj,
+                      const GradScale &sc, double *grad);
 // C(m x n) -= P(m x k) Q(n x k)^T; see k_gemm.hip
 int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const double *P, long ldp,
                 long pstride, const double *Q, long qsj, long qsk, long qstride, int m, int n,
@@ -484,6 +488,11 @@ int enqueue_backward_vec(bq_ctx *c, double *x, double *y, const double *L, long 
                          WideInv w, double *ws = nullptr);
 int enqueue_forward_rows_blk(bq_ctx *c, double *X, long ldx, int mrows, const double *L, long ldl,
                              int npad, const double *dw);
+// Y <- L^-T (npad x npad, ld npad); X: workspace of the same size.  Rows at or beyond a step's
+// block are still unit vectors and sit out (N^3 / 3 flops); Y's strict lower triangle is not
+// written (the caller clears it once)
+int enqueue_inverse_rows(bq_ctx *c, double *X, double *Y, const double *L, long ldl, int npad,
+                         WideInv w);
 int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
                          const double *L, long ldl, int npad, WideInv w);
 int enqueue_backward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
@@ -542,6 +551,11 @@ struct bq_fit {
                   // of bq_gp_refit_predict (one read-back for all of it)
     DevBuf alpha; // npad, valid if have_alpha
     bool have_alpha = false;
+    // the log-ML gradient (bq_gp_logml_grad): Y = L^-T (npad x npad, zero below its diagonal) and
+    // the sweep's partial sums (npad x npad), allocated on the first gradient; the product's
+    // partials and the d + 2 results
+    DevBuf gY, gX, gpart;
+    bool have_y = false;
     bool have_zc = false; // wz holds z = L^-1 y contiguously (gathered from the factor's y row on
                           // the first posterior after a (re)fit: the row reductions then read one
                           // line per 8 entries instead of one per entry)

@@ -25,6 +25,22 @@ int gemm_init(bq_ctx *c)
     BQ_L64_ATTR(gemm_lds_seed_kernel<2>, BQ_LDS_BYTES);
     BQ_L64_ATTR(gemm_lds64_seed_kernel<1>, BQ_L64_BYTES);
     BQ_L64_ATTR(gemm_lds64_seed_kernel<2>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<1>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<2>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<3>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<4>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<5>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<6>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<7>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds_grad_kernel<8>, BQ_LDS_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<1>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<2>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<3>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<4>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<5>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<6>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<7>, BQ_L64_BYTES);
+    BQ_L64_ATTR(gemm_lds64_grad_kernel<8>, BQ_L64_BYTES);
 #undef BQ_L64_ATTR
     return BQ_OK;
 }
@@ -214,6 +230,65 @@ int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const dou
             BQ_GEMM_SUB(1, 1, 32);
     }
 #undef BQ_GEMM_SUB
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// The log-ML gradient from Y = L^-T (npad x npad, ld npad, zero below its diagonal) and the fit's
+// alpha: the lower tiles of G = alpha alpha^T - Y Y^T, each reduced against the kernel's
+// derivatives into d + 2 partials (gemm_lds(64)_grad_kernel), then one workgroup sums them in a
+// fixed order and scales them (grad_finalize_kernel).  part: grad_parts(npad, d) doubles; grad: d + 2.
+//
+// Workgroup tile: 128 x 128 once the lower 128-tiles number at least kGrad128PerCu per CU, else
+// 64 x 64 (four times the workgroups).  BQ_GEMM_TILE=64|128 forces one (measurements).
+static int grad_tile(const bq_ctx *c, int npad)
+{
+    constexpr long kGrad128PerCu = 2;
+    if (c->gemm_tile == 64 || c->gemm_tile == 128)
+        return c->gemm_tile;
+    const long gm = (npad + 127) / 128;
+    return gm * (gm + 1) / 2 >= kGrad128PerCu * c->cus ? 128 : 64;
+}
+
+size_t grad_parts(int npad, int d)
+{
+    const size_t gm = (size_t)(npad + 63) / 64; // (the 64-tiles: more workgroups than 128-tiles)
+    return gm * (gm + 1) / 2 * (size_t)(d + 2);
+}
+
+int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob &gj,
+                      const GradScale &sc, double *grad)
+{
+    if (d < 1 || d > BQ_MAXD || (npad % 64))
+        return fail(c, BQ_ERR_BAD_ARG, "logml_grad: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    const int t = grad_tile(c, npad);
+    const unsigned gm = (unsigned)(npad + t - 1) / t, nwg = gm * (gm + 1) / 2;
+    {
+        // (the N^3 / 3 of the lower tiles' k ranges, the flops the kernel has to do)
+        Bracket br(c, BQ_K_GEMM, (double)npad * npad * npad / 3.0);
+#define BQ_GRAD(D_)                                                                                \
+    if (t == 128)                                                                                  \
+        hipLaunchKernelGGL(gemm_lds_grad_kernel<D_>, dim3(nwg), dim3(256), BQ_LDS_BYTES, c->cur, Y, \
+                           (long)npad, npad, gj);                                                  \
+    else                                                                                           \
+        hipLaunchKernelGGL(gemm_lds64_grad_kernel<D_>, dim3(nwg), dim3(256), BQ_L64_BYTES, c->cur,  \
+                           Y, (long)npad, npad, gj)
+        switch (d) {
+        case 1: BQ_GRAD(1); break;
+        case 2: BQ_GRAD(2); break;
+        case 3: BQ_GRAD(3); break;
+        case 4: BQ_GRAD(4); break;
+        case 5: BQ_GRAD(5); break;
+        case 6: BQ_GRAD(6); break;
+        case 7: BQ_GRAD(7); break;
+        default: BQ_GRAD(8); break;
+        }
+#undef BQ_GRAD
+        HIPCHK(c, hipGetLastError());
+    }
+    Bracket br(c, BQ_K_REDUCE);
+    hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, c->cur, gj.part, (int)nwg,
+                       d + 2, sc, grad);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -183,13 +183,16 @@ static bool rows_small(const bq_ctx *c, int mrows, int npad, const WideInv &w)
 // depend on the PREVIOUS step only, not on each other: they share a launch, and a step costs
 // the longer of the two instead of their sum plus a launch gap.  (On two streams with events
 // the small product waited for workgroup slots behind the big one: slower than in sequence.)
-static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long ldx, int mrows,
-                      const double *L, long ldl, int npad, const WideInv &w)
+// tri (forward only): Xin = I, and row r enters at the step that holds column r -- rows at or
+// beyond J + bJ are still unit vectors with nothing to subtract (the triangular inverse)
+static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long ldx, int mrows_all,
+                      const double *L, long ldl, int npad, const WideInv &w, bool tri = false)
 {
     const int last = (npad - 1) / w.B * w.B;
     for (int step = 0; step * w.B < npad; ++step) {
         const int J = forward ? step * w.B : last - step * w.B;
         const int bJ = std::min(w.B, npad - J);
+        const int mrows = tri ? std::min(mrows_all, J + bJ) : mrows_all;
         const int Jp = forward ? J - w.B : J + w.B; // the block solved one step earlier
         const bool first = step == 0;
         const int bp = first ? 0 : std::min(w.B, npad - Jp);
@@ -257,6 +260,15 @@ static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long l
                                 2.0 * mrows * ((double)bJ * (a.k1 + a.k2) + (double)nu * bp)));
     }
     return BQ_OK;
+}
+
+int enqueue_inverse_rows(bq_ctx *c, double *X, double *Y, const double *L, long ldl, int npad,
+                         WideInv w)
+{
+    BQCHK(launch_pad_identity(c, X, npad, 0, npad)); // X = I (the last call left partial sums)
+    if ((w.B % 64) == 0 && (ldl & 1) == 0)
+        return rows_fused(c, true, X, Y, npad, npad, L, ldl, npad, w, true);
+    return enqueue_forward_rows(c, X, Y, npad, npad, L, ldl, npad, w);
 }
 
 // Xout <- Xin L^-T; Xin is overwritten with partial sums

@@ -41,6 +41,22 @@ struct GramSeed {
     int d, r, c;
 };
 
+// The log-ML gradient's product (gemm.h, gemm_lds_grad_kernel): the tile of G = alpha alpha^T -
+// Kxx^-1 is reduced against the kernel's derivatives instead of being stored.  part: d + 2 partial
+// sums per workgroup.
+struct GradJob {
+    const double *alpha; // npad
+    const double *pts;   // d x n
+    double *part;
+    GaussParams g;
+    int n;
+};
+
+// the scalings of the gradient's d + 2 sums (grad_finalize_kernel)
+struct GradScale {
+    double f[BQ_MAXD + 2];
+};
+
 // Read-out of a bordered system folded into the one-launch sweep (slab.h): the diagonal factors
 // add their share of log|K| to scal[4b + 1] as they go, and the LAST step's tiles -- the Schur
 // complement of the border -- store what finalize_kernel would read from it (no launch of its own).

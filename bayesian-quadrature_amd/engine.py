@@ -568,6 +568,14 @@ class Fit(object):
         e._check(e._lib.bq_gp_logml(e._ctx, self._handle(), C.cast(C.byref(v), _dp)))
         return float(v.value)
 
+    def logml_grad(self):
+        """Gradient of the log marginal likelihood, (d + 2,): [d/dh, d/dw_1 .. d/dw_d, d/ds]
+        (bq_gp_logml_grad)."""
+        g = np.empty(self.d + 2)
+        e = self._eng
+        e._check(e._lib.bq_gp_logml_grad(e._ctx, self._handle(), L.dptr(g)))
+        return g
+
     def _get(self, which, shape):
         out = np.empty(shape, order="F")
         e = self._eng

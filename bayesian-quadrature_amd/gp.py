@@ -15,7 +15,9 @@ Formulas: Gaussian kernel ``h^2 N(x1 | x2, w^2)``,
 import copy as _copy
 
 import numpy as np
+import scipy.optimize as optim
 
+from . import util
 from .engine import get_engine
 
 DTYPE = np.float64
@@ -224,6 +226,65 @@ class GP(object):
     @property
     def log_lh(self):
         return self._memo("log_lh", lambda: self._device_fit().logml)
+
+    @property
+    def dloglh_dtheta(self):
+        """Gradient of ``log_lh`` in the order of ``params``, [d/dh, d/dw, d/ds], from the
+        device fit (bq_gp_logml_grad); memoised like ``log_lh``."""
+        return self._memo("dloglh_dtheta", lambda: self._device_fit().logml_grad())
+
+    def fit_MLII(self, params, method="L-BFGS-B", ntry=10):
+        """Maximise ``log_lh`` over the named subset of ("h", "w", "s") with the exact gradient
+        (util.find_good_parameters with ``logpdf_grad``).
+
+        Positivity by reparametrisation: the search runs over log h, log w and log s, so every
+        point it evaluates has h, w, s > 0 and none lies on the edge s = 0, where Kxx of close
+        points is singular.  An optimum at s = 0 is therefore only approached, never reached.
+        An s that starts at exactly 0 has no logarithm: it is searched as it is, under the
+        L-BFGS-B bound s >= 0.  Leaves the GP at the optimum and returns the optimiser's summary
+        (x in the parameters' own units); RuntimeError when no optimum is found."""
+        names = ("h", "w", "s")
+        params = list(params)
+        if not params or any(p not in names for p in params) or len(set(params)) != len(params):
+            raise ValueError("params: a subset of %s" % (names,))
+        idx = [names.index(p) for p in params]
+        th0 = np.array([self.get_param(p) for p in params], dtype=DTYPE)
+        logp = th0 > 0
+        u0 = np.where(logp, np.log(np.where(logp, th0, 1.0)), th0)
+        bounds = [(None, None) if lg else (0.0, None) for lg in logp]
+
+        def theta(u):
+            return np.where(logp, np.exp(u), u)
+
+        def set_all(t):
+            for p, v in zip(params, t):
+                self.set_param(p, v)
+
+        def logpdf(u):
+            try:
+                set_all(theta(u))
+                return self.log_lh
+            except (ValueError, np.linalg.LinAlgError):
+                return -np.inf
+
+        def logpdf_grad(u):
+            f = logpdf(u)
+            if not np.isfinite(f):
+                return f, np.zeros(len(params))
+            t = theta(u)
+            return f, self.dloglh_dtheta[idx] * np.where(logp, t, 1.0)
+
+        u = util.find_good_parameters(logpdf, u0, method, ntry=ntry, logpdf_grad=logpdf_grad,
+                                      bounds=bounds if method == "L-BFGS-B" else None)
+        if u is None:
+            set_all(th0)
+            raise RuntimeError("couldn't find good parameters")
+        x = theta(u)
+        set_all(x)
+        opt = util.LAST_OPT
+        return optim.OptimizeResult(x=x, fun=-self.log_lh, success=opt.get("success", False),
+                                    nfev=opt.get("nfev", -1), nit=opt.get("nit", -1),
+                                    attempts=opt.get("attempts", -1))
 
     def Kxoxo(self, xo):
         return self.K(xo, xo)

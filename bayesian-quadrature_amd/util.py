@@ -55,7 +55,8 @@ def cd_points(x0):
 LAST_OPT = {}
 
 
-def find_good_parameters(logpdf, x0, method, ntry=10, logpdf_batch=None):
+def find_good_parameters(logpdf, x0, method, ntry=10, logpdf_batch=None, logpdf_grad=None,
+                         bounds=None):
     """Up to ``ntry`` restarts of scipy.optimize.minimize on -logpdf; returns the
     first optimum whose log-pdf exceeds MIN, else None.
 
@@ -70,8 +71,17 @@ def find_good_parameters(logpdf, x0, method, ntry=10, logpdf_batch=None):
     and noise both ~1e-8.  NOT the reference's trajectory -- a better-conditioned one over the
     same objective: it ends at least as high (round 5's forward-difference batch ended at -1.114
     where the sequential run reached -0.940 on the reference's fixture; tests/test_bq_object.py
-    bounds the gap now)."""
+    bounds the gap now).
+
+    ``logpdf_grad`` (x -> (log-pdf, gradient)) gives the exact gradient instead: scipy gets both
+    with ``jac=True``, one evaluation per point (gp.GP.fit_MLII).  ``bounds`` go to scipy as
+    they are."""
     batched = logpdf_batch is not None
+    kw = {} if bounds is None else {"bounds": bounds}
+
+    def fun_and_exact_grad(x):
+        f, g = logpdf_grad(x)
+        return -float(f), -np.asarray(g, dtype=np.float64)
 
     def fun_and_grad(x):
         X, span = cd_points(x)
@@ -89,14 +99,17 @@ def find_good_parameters(logpdf, x0, method, ntry=10, logpdf_batch=None):
 
     for i in range(ntry):
         logger.debug("Attempt #%d with %s", i + 1, method)
-        if batched:
-            res = optim.minimize(fun=fun_and_grad, x0=x0, method=method, jac=True)
+        if logpdf_grad is not None:
+            res = optim.minimize(fun=fun_and_exact_grad, x0=x0, method=method, jac=True, **kw)
+        elif batched:
+            res = optim.minimize(fun=fun_and_grad, x0=x0, method=method, jac=True, **kw)
         else:
-            res = optim.minimize(fun=lambda x: -logpdf(x), x0=x0, method=method)
+            res = optim.minimize(fun=lambda x: -logpdf(x), x0=x0, method=method, **kw)
         p = logpdf(res["x"])
         LAST_OPT.clear()
         LAST_OPT.update({"attempts": i + 1, "nit": int(res.get("nit", -1)),
-                         "nfev": int(res.get("nfev", -1)), "logpdf": float(p)})
+                         "nfev": int(res.get("nfev", -1)), "logpdf": float(p),
+                         "success": bool(res.get("success", False))})
         if p > MIN:
             return res["x"]
         if logpdf(x0) < p:

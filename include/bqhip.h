@@ -168,6 +168,11 @@ int bq_gp_refit_predict(bq_ctx *ctx, bq_fit *fit, double h, const double *w, dou
                         const double *xo, int64_t M, double *mean, double *var);
 void bq_fit_destroy(bq_ctx *ctx, bq_fit *fit);
 int bq_gp_logml(bq_ctx *ctx, bq_fit *fit, double *out);
+/* gradient of the fit's log marginal likelihood with respect to its hyper-parameters:
+ * grad[0] = d/dh, grad[1..d] = d/dw_k, grad[d+1] = d/ds (host, d + 2 entries).
+ * Same status rules as bq_gp_logml (stale / not-PD / null handle).  The first call after a
+ * (re)fit builds L^-T: 2 npad^2 doubles of device memory, kept with the fit. */
+int bq_gp_logml_grad(bq_ctx *ctx, bq_fit *fit, double *grad);
 /* which: 0 = L (n x n, strict upper zeroed), 1 = alpha = Kxx^-1 y (n),
  * 2 = z = L^-1 y (n), 3 = Kxx (n x n, recomputed) */
 int bq_gp_get(bq_ctx *ctx, bq_fit *fit, int which, double *out_host);
