@@ -16,7 +16,6 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
                       double *hpost = nullptr, // hpost: host copy of misc[8 .. 8 + 128) on return
                       size_t npts_words = 0)
 {
-    const int ntot = f->L.ntot;
     int *info = f->misc.i();
     double *scal = f->misc.d() + 2;
     f->valid = false;
@@ -51,31 +50,11 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
                                      sizeof(double) * npts_words, hipMemcpyHostToDevice,
                                      c->stream));
     }
-    double *scratch = f->dinv.d() + f->npad;
-    FirstStep fs;
-    const bool fuse = sweep_is_slab(c, ntot, f->npad, 1, f->panel.bytes / sizeof(double));
-    if (fuse) {
-        fs.S0 = f->panel.d();
-        fs.lds = ntot;
-        fs.sstride = 64L * ntot;
-        fs.dinv = scratch;
-        fs.info = info;
-        fs.scal = c->fold_readout ? scal : nullptr;
-    } else {
-        HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int), c->stream));
-    }
-    BQCHK(launch_assemble(c, f->d, f->pts.d(), 0, f->y.d(), 0, static_cast<GaussParams *>(f->gp.p),
-                          0, f->A.d(), f->ldl, 0, f->L, 1, fs));
-    const bool folded = fuse && f->L.yrow >= 0 && c->fold_readout;
-    if (folded) // the one-launch sweep carries the read-out (SlabOut)
-        c->slab_out = SlabOut{scal, pm, pv, 64L, f->L.n, f->L.npad, f->L.M, f->L.yrow};
-    const int st_sweep = enqueue_potrf_partial(c, f->A.d(), f->ldl, 0, 1, ntot, f->npad, scratch,
-                                               info, f->panel.d(),
-                                               f->panel.bytes / sizeof(double), fuse);
-    c->slab_out = SlabOut{};
-    BQCHK(st_sweep);
-    if (!folded)
-        BQCHK(launch_finalize(c, f->A.d(), f->ldl, 0L, f->L, scal, pm, pv, 64L, 1));
+    const GramSeed sys{f->pts.d(), 0, f->y.d(), 0, static_cast<const GaussParams *>(f->gp.p), 0,
+                       f->L, f->d, 0, 0};
+    BQCHK(enqueue_bordered(c, sys, 1, f->A.d(), f->ldl, 0, f->dinv.d() + f->npad, info,
+                           f->panel.d(), f->panel.bytes / sizeof(double), scal, pm, pv, 64L, false,
+                           0.0));
     // one read-back: misc = [info (int, 8 bytes) | pad | scal[4] | pad | mean[64] | var[64]]
     double *hm = f->hfit;
     if (hmap)
@@ -216,8 +195,7 @@ extern "C" int bq_gp_fit(bq_ctx *c, const double *x, const double *y, int64_t d,
     A(f->y, sizeof(double) * (size_t)f->npad);
     A(f->gp, sizeof(GaussParams));
     A(f->dinv, sizeof(double) * ((size_t)f->npad + BQ_DINV_STRIDE));
-    A(f->panel, panel_ws_useful(c, f->L.ntot, 1) ? sizeof(double) * panel_ws_doubles(f->L.ntot, 1)
-                                                 : 0);
+    A(f->panel, sizeof(double) * sweep_route(c, f->L.ntot, f->L.ntot, 1).ws_doubles);
     A(f->dw, sizeof(double) * BQ_DINV_HALF * (size_t)(f->npad / 64));
     A(f->misc, sizeof(double) * (8 + 128));
     A(f->alpha, sizeof(double) * (size_t)f->npad);

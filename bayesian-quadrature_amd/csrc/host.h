@@ -10,7 +10,8 @@
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
 //   k_reduce.hip reduce.h trsv.h kernels        read-outs, single-vector sweeps, utilities
-//   potrf.hip    the blocked factorisation's launch sequences (no kernels of its own)
+//   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
+//                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
 //   ctx.hip      contexts, device memory, timers, the launch profiler
 //   linalg.hip   linalg_c drop-ins, Gram entry points, bq_potrf_dev
@@ -142,12 +143,9 @@ struct bq_ctx {
                          // between calls (hipFree synchronises the device); bq_ctx_trim frees it
     int gemm_lds = 1;    // LDS-staged 128x128 trailing update (BQ_GEMM_LDS)
     int fold_readout = 1; // one-launch sweeps carry their read-out (SlabOut; BQ_FOLD_READOUT)
-    SlabOut slab_out{};  // set (scal != nullptr) by a caller whose slab sweep carries its read-out
     int asm_fuse = 1;    // a batched plan assembles only the first outer block's columns; the rest of
                          // the system is computed inside the first products that touch it
                          // (GramSeed; BQ_ASM_FUSE=0: the whole system is assembled first)
-    GramSeed gram_seed{}; // set (pts != nullptr) by a caller that assembled only dfirst_seed_cols()
-                         // columns: enqueue_potrf_dfirst seeds the first block's products with it
     int potf2_8w = 1;    // the one-launch steps' diagonal factor on eight waves where a step's workgroups
                          // have a CU each (BQ_POTF2_8W)
     int gemm_ksplit = 1; // eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT)
@@ -174,8 +172,6 @@ struct bq_ctx {
     GaussParams gbuf_host{};
     bool gbuf_valid = false;
     DevBuf dinv64; // potf2 reciprocal-diagonal scratch
-    long long *stamp_buf = nullptr; // bq_probe_c2_timeline: 160 stamps per slab step
-    int stamp_steps = 0;            // slab steps stamp_buf has room for
 };
 
 namespace bqh {
@@ -357,7 +353,8 @@ int launch_slab_first(bq_ctx *c, double *A, long lda, long astride, int batch, d
 int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, double *Sin,
                      double *Sout, long lds, long sstride, int ntot, int j0, double *dinv_in,
                      double *dinv_out, int fnext, int last, int *info, int col0,
-                     long long *stamps, double work, long dstride = BQ_DINV_STRIDE);
+                     const SlabOut &out, long long *stamps, double work,
+                     long dstride = BQ_DINV_STRIDE);
 
 // ---- k_gemm.hip -----------------------------------------------------------------------
 int gemm_init(bq_ctx *c); // function attributes of the LDS-staged kernels, once per context
@@ -438,20 +435,41 @@ int flow_check(bq_ctx *c);
 
 // ---- potrf.hip ------------------------------------------------------------------------
 int auto_nb(const bq_ctx *c, int ntot, int batch);
-// columns a caller of enqueue_potrf_partial has to assemble before it when it hands the rest over
-// as c->gram_seed (the first outer block's), 0: the whole system (another sweep will run)
-int dfirst_seed_cols(const bq_ctx *c, int ntot, int ncols, int batch, size_t panel_ws_len);
-size_t panel_ws_doubles(int ntot, int batch);
-size_t sweep_ws_doubles(const bq_ctx *c, int ntot, int batch);
-bool panel_ws_useful(const bq_ctx *c, int ntot, int batch);
-bool sweep_is_slab(const bq_ctx *c, int ntot, int ncols, int batch, size_t panel_ws_len);
-int enqueue_potrf_partial(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot,
-                          int ncols, double *dinv, int *info, double *panel_ws = nullptr,
-                          size_t panel_ws_len = 0, bool first_done = false,
-                          bool skip_border = false);
+// How the first ncols columns of `batch` matrices of ntot rows are eliminated, decided in ONE place
+// (sweep_route): every enqueue asks again with the workspace on hand (a setter may have changed the
+// answer since), every workspace is sized by the ws_doubles of the unlimited answer.
+struct SweepRoute {
+    // Slab: one launch per 64-column step (slab.h); Blocked: outer blocks of nb, look-ahead, the
+    // slab tail of one or two matrices; Halves: two half-batches of it on the two streams;
+    // DiagFirst: batches, diagonal block first (enqueue_potrf_dfirst)
+    enum Kind { Slab, Blocked, Halves, DiagFirst } kind;
+    int ntot, ncols, batch;
+    int nb;                 // outer block (auto_nb)
+    size_t ws_doubles;      // workspace the route uses (0: none)
+    bool first_in_assembly; // Slab: an assembly launch can carry step 0 (FirstStep)
+    int seed_cols;          // DiagFirst: columns to assemble before a seeded sweep (0: all)
+    bool border_rows;       // a bordered system's results can come off its border rows
+};
+SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch,
+                       size_t ws_on_hand = SIZE_MAX);
+// what a caller tells the sweep besides its route
+struct SweepArgs {
+    bool first_done = false;     // the assembly carried step 0 (SweepRoute::first_in_assembly)
+    bool skip_border = false;    // the results come off the border rows (SweepRoute::border_rows)
+    SlabOut out{};               // Slab: the last step stores the read-out (scal != nullptr)
+    GramSeed seed{};             // DiagFirst: only SweepRoute::seed_cols columns were assembled
+    long long *stamps = nullptr; // Slab: bq_probe_c2_timeline's 160 stamps per step, for
+    int stamped_steps = 0;       // this many steps
+};
+int enqueue_potrf_partial(bq_ctx *c, const SweepRoute &r, double *A, long lda, long astride,
+                          double *dinv, int *info, double *ws, const SweepArgs &a = SweepArgs());
+int enqueue_bordered(bq_ctx *c, const GramSeed &sys, int batch, double *A, long lda, long astride,
+                     double *dinv, int *info, double *ws, size_t ws_len, double *scal, double *mean,
+                     double *var, long mstride, bool rows, double work, long long *stamps = nullptr,
+                     int stamped_steps = 0);
 
 int enqueue_panel_solve(bq_ctx *c, double *A, long lda, long astride, int batch, int r0, int m2,
-                        int K0, int KB, const double *rec, long rstride);
+                        int K0, int KB, const double *rec, long rstride, bool one_launch);
 
 // ---- sweeps.hip -----------------------------------------------------------------------
 struct WideInv {
@@ -673,6 +691,6 @@ int with_flow_fallback(bq_ctx *c, F &&attempt)
 // plan.hip: new kernel parameters for every problem of a plan, nothing else re-uploaded
 int plan_set_params(bq_ctx *c, bq_plan *p, const double *h, const double *w, const double *s);
 // plan.hip: the launch sequence of one pass of a plan (probe.hip, bq_probe_c2_timeline, runs it
-// eagerly)
-int plan_enqueue(bq_ctx *c, bq_plan *p);
+// eagerly with its stamps)
+int plan_enqueue(bq_ctx *c, bq_plan *p, long long *stamps = nullptr, int stamped_steps = 0);
 } // namespace bqh

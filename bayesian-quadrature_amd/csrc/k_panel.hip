@@ -156,12 +156,12 @@ int launch_slab_first(bq_ctx *c, double *A, long lda, long astride, int batch, d
     return BQ_OK;
 }
 
-// one 64-column step of a small system in one launch (slab_step_kernel); stamps: the
-// profiling instantiation (bq_probe_c2_timeline)
+// one 64-column step of a small system in one launch (slab_step_kernel); out: the read-out the
+// last step stores (SlabOut); stamps: the profiling instantiation (bq_probe_c2_timeline)
 int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, double *Sin,
                      double *Sout, long lds, long sstride, int ntot, int j0, double *dinv_in,
                      double *dinv_out, int fnext, int last, int *info, int col0,
-                     long long *stamps, double work, long dstride)
+                     const SlabOut &out, long long *stamps, double work, long dstride)
 {
     const int T = (ntot - j0 - 64) / 64;
     Bracket br(c, BQ_K_SYRK_SMALL, work);
@@ -170,22 +170,22 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
     if (stamps && w8)
         hipLaunchKernelGGL((slab_step_kernel<true, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512), 0,
                            c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
-                           dinv_out, dstride, fnext, last, info, col0, stamps, c->slab_out);
+                           dinv_out, dstride, fnext, last, info, col0, stamps, out);
     else if (stamps)
         hipLaunchKernelGGL((slab_step_kernel<true, 4>), dim3(T * (T + 1) / 2, 1, batch), dim3(256), 0,
                            c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
-                           dinv_out, dstride, fnext, last, info, col0, stamps, c->slab_out);
+                           dinv_out, dstride, fnext, last, info, col0, stamps, out);
     else if (w8)
         // a CU per workgroup: 512 threads, the diagonal factor on eight waves
         hipLaunchKernelGGL((slab_step_kernel<false, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512),
                            0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
                            dinv_out, dstride, fnext, last, info, col0,
-                           (long long *)nullptr, c->slab_out);
+                           (long long *)nullptr, out);
     else
         hipLaunchKernelGGL((slab_step_kernel<false, 4>), dim3(T * (T + 1) / 2, 1, batch), dim3(256),
                            0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
                            dinv_out, dstride, fnext, last, info, col0,
-                           (long long *)nullptr, c->slab_out);
+                           (long long *)nullptr, out);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -22,6 +22,23 @@ static int upload_padded(bq_ctx *c, const double *H, int n, DevBuf &A, int &ntot
     return BQ_OK;
 }
 
+// the context's panel scratch, grown to what the sweep of one ntot x ntot matrix uses
+static int grow_panel_ws(bq_ctx *c, int ntot)
+{
+    const size_t bytes = sizeof(double) * sweep_route(c, ntot, ntot, 1).ws_doubles;
+    if (c->panel_ws.bytes < bytes)
+        HIPCHK(c, c->panel_ws.alloc(bytes));
+    return BQ_OK;
+}
+
+// factor one ntot x ntot matrix (bq_cho_factor, bq_potrf_dev)
+static int potrf_one(bq_ctx *c, double *A, long lda, int ntot, double *dinv, int *info)
+{
+    BQCHK(grow_panel_ws(c, ntot));
+    const SweepRoute r = sweep_route(c, ntot, ntot, 1, c->panel_ws.bytes / sizeof(double));
+    return enqueue_potrf_partial(c, r, A, lda, 0, dinv, info, c->panel_ws.d());
+}
+
 extern "C" int bq_cho_factor(bq_ctx *c, const double *C, double *L, int64_t n, int64_t *info_out)
 {
     if (!c)
@@ -40,8 +57,7 @@ extern "C" int bq_cho_factor(bq_ctx *c, const double *C, double *L, int64_t n, i
         // ([flag | the block with its identity padding]), one launch, one synchronisation
         double *hs = nullptr, *ds = nullptr;
         BQCHK(ctx_stage(c, 1 + 4096, &hs, &ds));
-        if (c->panel_ws.bytes < sizeof(double) * panel_ws_doubles(64, 1))
-            HIPCHK(c, c->panel_ws.alloc(sizeof(double) * panel_ws_doubles(64, 1)));
+        BQCHK(grow_panel_ws(c, 64));
         hs[0] = 0.0; // (the flag is its first four bytes)
         double *blk = hs + 1;
         std::memset(blk, 0, sizeof(double) * 4096);
@@ -88,10 +104,7 @@ extern "C" int bq_cho_factor(bq_ctx *c, const double *C, double *L, int64_t n, i
         BQCHK(upload_padded(c, C, (int)n, A, ntot, lda));
         HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int), c->stream));
     }
-    if (c->panel_ws.bytes < sizeof(double) * panel_ws_doubles(ntot, 1))
-        HIPCHK(c, c->panel_ws.alloc(sizeof(double) * panel_ws_doubles(ntot, 1)));
-    BQCHK(enqueue_potrf_partial(c, A.d(), lda, 0, 1, ntot, ntot, dinv, info, c->panel_ws.d(),
-                                c->panel_ws.bytes / sizeof(double)));
+    BQCHK(potrf_one(c, A.d(), lda, ntot, dinv, info));
     int hinfo = 0;
     if (small) {
         BQCHK(launch_mat_out(c, ds, A.d(), lda, (int)n, info));
@@ -340,8 +353,5 @@ extern "C" int bq_potrf_dev(bq_ctx *c, double *A_dev, int64_t n, int64_t lda, in
     if (!c->dinv64.p)
         HIPCHK(c, c->dinv64.alloc(BQ_DINV_STRIDE * sizeof(double)));
     HIPCHK(c, hipMemsetAsync(info_dev, 0, sizeof(int32_t), c->stream));
-    if (c->panel_ws.bytes < sizeof(double) * panel_ws_doubles((int)n, 1))
-        HIPCHK(c, c->panel_ws.alloc(sizeof(double) * panel_ws_doubles((int)n, 1)));
-    return enqueue_potrf_partial(c, A_dev, lda, 0, 1, (int)n, (int)n, c->dinv64.d(), info_dev,
-                                 c->panel_ws.d(), c->panel_ws.bytes / sizeof(double));
+    return potrf_one(c, A_dev, lda, (int)n, c->dinv64.d(), info_dev);
 }

@@ -539,7 +539,8 @@ extern "C" int bq_esm_batch(bq_ctx *c, const double *x_sc, const double *l_sc, i
     const long lda = pick_ld(L.ntot);
     // per candidate: the bordered matrix, the panel scratch of the one-launch sweep, the
     // diagonal factor's record, failure flag and outputs
-    const size_t per = sizeof(double) * ((size_t)lda * L.ntot + panel_ws_doubles(L.ntot, 1) +
+    const size_t per = sizeof(double) * ((size_t)lda * L.ntot +
+                                         sweep_route(c, L.ntot, L.ntot, 1).ws_doubles +
                                          BQ_DINV_STRIDE + 2) + sizeof(int);
     size_t freeb = 0, totalb = 0;
     HIPCHK(c, hipMemGetInfo(&freeb, &totalb));
@@ -570,7 +571,8 @@ extern "C" int bq_esm_batch(bq_ctx *c, const double *x_sc, const double *l_sc, i
     HIPCHK(c, dj2.alloc(sizeof(double) * M));
     HIPCHK(c, Ad.alloc(sizeof(double) * (size_t)lda * L.ntot * (size_t)chunk));
     HIPCHK(c, dinv.alloc(sizeof(double) * BQ_DINV_STRIDE * (size_t)chunk));
-    HIPCHK(c, panel.alloc(sizeof(double) * sweep_ws_doubles(c, L.ntot, (int)chunk)));
+    HIPCHK(c,
+           panel.alloc(sizeof(double) * sweep_route(c, L.ntot, L.ntot, (int)chunk).ws_doubles));
     HIPCHK(c, info.alloc(sizeof(int) * (size_t)chunk));
     HIPCHK(c, outd.alloc(sizeof(double) * 2 * (size_t)chunk));
     HIPCHK(c, hipMemcpyAsync(xs.p, x_sc, sizeof(double) * nsc, hipMemcpyHostToDevice, c->stream));
@@ -599,9 +601,9 @@ extern "C" int bq_esm_batch(bq_ctx *c, const double *x_sc, const double *l_sc, i
                                dj2.d() + a0, thresh, g, Ad.d(), lda, lda * (long)L.ntot, L);
             HIPCHK(c, hipGetLastError());
         }
-        BQCHK(enqueue_potrf_partial(c, Ad.d(), lda, lda * (long)L.ntot, nb, L.ntot, L.npad,
-                                    dinv.d(), info.i(), panel.d(),
-                                    panel.bytes / sizeof(double)));
+        const SweepRoute route = sweep_route(c, L.ntot, L.npad, nb, panel.bytes / sizeof(double));
+        BQCHK(enqueue_potrf_partial(c, route, Ad.d(), lda, lda * (long)L.ntot, dinv.d(), info.i(),
+                                    panel.d()));
         hipLaunchKernelGGL(esm_finalize_kernel, dim3((nb + 255) / 256), dim3(256), 0, c->stream,
                            Ad.d(), lda, lda * (long)L.ntot, L, nb, outd.d());
         HIPCHK(c, hipGetLastError());

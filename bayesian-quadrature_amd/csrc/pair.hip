@@ -379,11 +379,13 @@ static int pair_esm_border(bq_ctx *c, bq_pair *pr, int p, double thresh, double 
         };
         A(pr->bdinv, sizeof(double) * BQ_DINV_STRIDE * (size_t)sch);
         A(pr->binfo, sizeof(int) * (size_t)sch);
-        A(pr->bws, sizeof(double) * sweep_ws_doubles(c, ntot, (int)sch));
+        // (sized for the whole matrix although stage 1 eliminates p columns: sizing for p would
+        // change its route)
+        A(pr->bws, sizeof(double) * sweep_route(c, ntot, ntot, (int)sch).ws_doubles);
         A(pr->sA, sizeof(double) * (size_t)asstride * ech);
         A(pr->sdinv, sizeof(double) * BQ_DINV_STRIDE * (size_t)ech);
         A(pr->sinfo, sizeof(int) * (size_t)ech);
-        A(pr->sws, sizeof(double) * sweep_ws_doubles(c, Ls.ntot, (int)ech));
+        A(pr->sws, sizeof(double) * sweep_route(c, Ls.ntot, Ls.ntot, (int)ech).ws_doubles);
         A(pr->sout, sizeof(double) * 2 * (size_t)ech);
         if (e != hipSuccess) {
             for (DevBuf *b : {&pr->bA, &pr->bdinv, &pr->binfo, &pr->bws, &pr->sA, &pr->sdinv,
@@ -411,8 +413,9 @@ static int pair_esm_border(bq_ctx *c, bq_pair *pr, int p, double thresh, double 
             HIPCHK(c, hipGetLastError());
         }
         // the first p columns of every set, the whole trailing block kept up to date
-        BQCHK(enqueue_potrf_partial(c, pr->bA.d(), lda, astride, nb, ntot, p, pr->bdinv.d(),
-                                    pr->binfo.i(), pr->bws.d(), pr->bws.bytes / sizeof(double)));
+        const SweepRoute r1 = sweep_route(c, ntot, p, nb, pr->bws.bytes / sizeof(double));
+        BQCHK(enqueue_potrf_partial(c, r1, pr->bA.d(), lda, astride, pr->bdinv.d(), pr->binfo.i(),
+                                    pr->bws.d()));
         {
             Bracket br(c, BQ_K_GRAM, 8.0 * Ls.ntot * Ls.ntot * ne);
             hipLaunchKernelGGL(esmb_gather_kernel, dim3((Ls.ntot + 63) / 64, Ls.ntot / 64, ne),
@@ -421,9 +424,9 @@ static int pair_esm_border(bq_ctx *c, bq_pair *pr, int p, double thresh, double 
                                (long)s0, (long)s0 * ma, pr->sA.d(), ldas, asstride, Ls);
             HIPCHK(c, hipGetLastError());
         }
-        BQCHK(enqueue_potrf_partial(c, pr->sA.d(), ldas, asstride, ne, Ls.ntot, Ls.npad,
-                                    pr->sdinv.d(), pr->sinfo.i(), pr->sws.d(),
-                                    pr->sws.bytes / sizeof(double)));
+        const SweepRoute r2 = sweep_route(c, Ls.ntot, Ls.npad, ne, pr->sws.bytes / sizeof(double));
+        BQCHK(enqueue_potrf_partial(c, r2, pr->sA.d(), ldas, asstride, pr->sdinv.d(), pr->sinfo.i(),
+                                    pr->sws.d()));
         hipLaunchKernelGGL(esm_multi_finalize_kernel, dim3((ne + 255) / 256), dim3(256), 0,
                            c->stream, pr->sA.d(), ldas, asstride, Ls, ne, pr->sout.d());
         HIPCHK(c, hipGetLastError());
@@ -497,7 +500,8 @@ extern "C" int bq_pair_esm(bq_ctx *c, bq_pair *pr, const double *p_tl, const dou
     L.ntot = L.npad + 64;
     const long lda = pick_ld(L.ntot);
     const int64_t E = (int64_t)S * ma;
-    const size_t per = sizeof(double) * ((size_t)lda * L.ntot + panel_ws_doubles(L.ntot, 1) +
+    const size_t per = sizeof(double) * ((size_t)lda * L.ntot +
+                                         sweep_route(c, L.ntot, L.ntot, 1).ws_doubles +
                                          BQ_DINV_STRIDE + 2) + sizeof(int);
     if (!pr->esm_small) {
         HIPCHK(c, pr->gpd.alloc(sizeof(GaussParams) * S));
@@ -524,7 +528,8 @@ extern "C" int bq_pair_esm(bq_ctx *c, bq_pair *pr, const double *p_tl, const dou
         if (e == hipSuccess)
             e = pr->dinv.alloc(sizeof(double) * BQ_DINV_STRIDE * (size_t)ch);
         if (e == hipSuccess)
-            e = pr->panel.alloc(sizeof(double) * sweep_ws_doubles(c, L.ntot, (int)ch));
+            e = pr->panel.alloc(sizeof(double) *
+                                sweep_route(c, L.ntot, L.ntot, (int)ch).ws_doubles);
         if (e == hipSuccess)
             e = pr->info.alloc(sizeof(int) * (size_t)ch);
         if (e == hipSuccess)
@@ -593,8 +598,9 @@ extern "C" int bq_pair_esm(bq_ctx *c, bq_pair *pr, const double *p_tl, const dou
                                lda * (long)L.ntot, L);
             HIPCHK(c, hipGetLastError());
         }
-        BQCHK(enqueue_potrf_partial(c, Ad.d(), lda, lda * (long)L.ntot, nb, L.ntot, L.npad,
-                                    dinv.d(), info.i(), panel.d(), panel.bytes / sizeof(double)));
+        const SweepRoute route = sweep_route(c, L.ntot, L.npad, nb, panel.bytes / sizeof(double));
+        BQCHK(enqueue_potrf_partial(c, route, Ad.d(), lda, lda * (long)L.ntot, dinv.d(), info.i(),
+                                    panel.d()));
         hipLaunchKernelGGL(esm_multi_finalize_kernel, dim3((nb + 255) / 256), dim3(256), 0,
                            c->stream, Ad.d(), lda, lda * (long)L.ntot, L, nb, outd.d());
         HIPCHK(c, hipGetLastError());

@@ -38,7 +38,7 @@ extern "C" int bq_plan_create(bq_ctx *c, int64_t nprob, int64_t d, int64_t n, in
     A(p->y, sizeof(double) * (size_t)p->L.npad * nprob);
     A(p->gp, sizeof(GaussParams) * (size_t)nprob);
     A(p->dinv, sizeof(double) * BQ_DINV_STRIDE * (size_t)nprob);
-    A(p->panel, sizeof(double) * sweep_ws_doubles(c, p->L.ntot, (int)nprob));
+    A(p->panel, sizeof(double) * sweep_route(c, p->L.ntot, p->L.ntot, (int)nprob).ws_doubles);
     A(p->info, sizeof(int) * (size_t)nprob);
     A(p->scal, sizeof(double) * 4 * (size_t)nprob);
     A(p->mean, sizeof(double) * (size_t)std::max<int64_t>(M, 1) * nprob);
@@ -237,59 +237,14 @@ int plan_set_params(bq_ctx *c, bq_plan *p, const double *h, const double *w, con
     return BQ_OK;
 }
 
-int plan_enqueue(bq_ctx *c, bq_plan *p)
+int plan_enqueue(bq_ctx *c, bq_plan *p, long long *stamps, int stamped_steps)
 {
-    // a small system's first sweep launch (and the clearing of the failure flags) rides in
-    // the assembly
-    FirstStep fs;
-    const bool fuse = sweep_is_slab(c, p->L.ntot, p->L.npad, p->nprob,
-                                    p->panel.bytes / sizeof(double));
-    if (fuse) {
-        fs.S0 = p->panel.d();
-        fs.lds = p->L.ntot;
-        fs.sstride = 64L * p->L.ntot;
-        fs.dinv = p->dinv.d();
-        fs.info = p->info.i();
-        fs.scal = c->fold_readout ? p->scal.d() : nullptr;
-    } else {
-        HIPCHK(c, hipMemsetAsync(p->info.p, 0, sizeof(int) * p->nprob, c->stream));
-    }
-    // a batch that sweeps diagonal block first assembles only its first outer block's columns: the
-    // first products that touch the rest compute it themselves (GramSeed, potrf.hip)
-    const int jcols = fuse ? 0
-                           : dfirst_seed_cols(c, p->L.ntot, p->L.npad, p->nprob,
-                                              p->panel.bytes / sizeof(double));
-    BQCHK(launch_assemble(c, p->d, p->pts.d(), (long)p->d * p->L.ntot, p->y.d(), p->L.npad,
-                          static_cast<GaussParams *>(p->gp.p), 1, p->A.d(), p->lda, p->astride,
-                          p->L, p->nprob, fs, jcols));
-    if (jcols > 0)
-        c->gram_seed = GramSeed{p->pts.d(), (long)p->d * p->L.ntot, p->y.d(), (long)p->L.npad,
-                                static_cast<const GaussParams *>(p->gp.p), 1, p->L, p->d, 0, 0};
-    // A blocked sweep (outer block >= 128) reads its results off the border rows and skips the
-    // border x border block in its trailing updates; the one-launch steps of small systems
-    // update everything and read the Schur complement.
-    const bool by_rows = !fuse && p->L.yrow >= 0 && auto_nb(c, p->L.ntot, p->nprob) >= 128;
-    // a sweep of one-launch steps carries the read-out itself (SlabOut: no finalize launch)
-    const bool folded = fuse && p->L.yrow >= 0 && c->fold_readout;
-    if (folded)
-        c->slab_out = SlabOut{p->scal.d(), p->mean.d(), p->var.d(), (long)std::max(p->M, 1),
-                              p->L.n, p->L.npad, p->L.M, p->L.yrow};
-    const int st_sweep =
-        enqueue_potrf_partial(c, p->A.d(), p->lda, p->astride, p->nprob, p->L.ntot, p->L.npad,
-                              p->dinv.d(), p->info.i(), p->panel.d(),
-                              p->panel.bytes / sizeof(double), fuse, by_rows);
-    c->slab_out = SlabOut{};
-    c->gram_seed = GramSeed{};
-    BQCHK(st_sweep);
-    if (folded)
-        return BQ_OK;
-    if (by_rows)
-        return launch_plan_readout(c, p->A.d(), p->lda, p->astride, p->L,
-                                   static_cast<const GaussParams *>(p->gp.p), p->scal.d(),
-                                   p->mean.d(), p->var.d(), (long)std::max(p->M, 1), p->nprob);
-    return launch_finalize(c, p->A.d(), p->lda, p->astride, p->L, p->scal.d(), p->mean.d(),
-                           p->var.d(), (long)std::max(p->M, 1), p->nprob,
-                           8.0 * (p->n + 2.0 * p->M) * p->nprob);
+    const GramSeed sys{p->pts.d(), (long)p->d * p->L.ntot, p->y.d(), (long)p->L.npad,
+                       static_cast<const GaussParams *>(p->gp.p), 1, p->L, p->d, 0, 0};
+    return enqueue_bordered(c, sys, p->nprob, p->A.d(), p->lda, p->astride, p->dinv.d(),
+                            p->info.i(), p->panel.d(), p->panel.bytes / sizeof(double), p->scal.d(),
+                            p->mean.d(), p->var.d(), (long)std::max(p->M, 1), true,
+                            8.0 * (p->n + 2.0 * p->M) * p->nprob, stamps, stamped_steps);
 }
 
 } // namespace bqh

@@ -1,6 +1,7 @@
-// potrf.hip -- the launch sequences of the blocked right-looking Cholesky: block sizes,
-// recursive panels, the one-launch sweeps of small systems, the two-stream look-ahead and the
-// two half-batches of mid-sized batches.  No kernels of its own (k_panel.hip, k_gemm.hip).
+// potrf.hip -- the launch sequences of the blocked right-looking Cholesky: block sizes and the
+// route of a sweep (sweep_route), recursive panels, the one-launch sweeps of small systems, the
+// two-stream look-ahead, two half-batches, diagonal block first, and the bordered pass of plans
+// and fits.  No kernels of its own (k_panel.hip, k_gemm.hip).
 #include "host.h"
 
 namespace bqh {
@@ -70,6 +71,62 @@ int auto_nb(const bq_ctx *c, int ntot, int batch)
     return 64;
 }
 
+// doubles of scratch the one-launch slab sweep needs (two panel columns per problem)
+static size_t panel_ws_doubles(int ntot, int batch) { return ((size_t)2 * 64 * ntot + 4096) * batch; }
+// the block-inverse records of one outer block's diagonal factor (enqueue_potrf_dfirst)
+static size_t dfirst_rec_doubles(int nb, int batch) { return (size_t)(nb / 64) * BQ_DINV_HALF * batch; }
+
+// the look-ahead pays up to this many matrices per batch (enqueue_potrf_group)
+#define BQ_LA_MAX_BATCH 48
+
+SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch, size_t ws_on_hand)
+{
+    SweepRoute r{};
+    r.ntot = ntot;
+    r.ncols = ncols;
+    r.batch = batch;
+    r.nb = auto_nb(c, ntot, batch);
+    // A blocked sweep (outer block >= 128) reads a bordered system's results off the border rows
+    // and skips the border x border block in its trailing updates; the one-launch steps of small
+    // systems update everything and read the Schur complement.
+    r.border_rows = r.nb >= 128;
+    if (c->diag_first && batch >= 3 && ncols >= 128 && r.nb >= 128) {
+        // (two sets of records: with the early fork the next block's diagonal factor writes its own
+        // while the rest of this block's panel solve still reads this block's)
+        const int nb = std::min(r.nb, ncols);
+        const size_t need = panel_ws_doubles(nb, batch) + 2 * dfirst_rec_doubles(nb, batch);
+        if (ws_on_hand >= need) {
+            r.kind = SweepRoute::DiagFirst;
+            r.ws_doubles = need;
+            // (with one outer block there is no product that could seed what lies right of it)
+            r.seed_cols = c->asm_fuse && nb < ncols ? nb : 0;
+            return r;
+        }
+    }
+    const size_t panel = panel_ws_doubles(ntot, batch);
+    if (r.nb == 64 && ncols >= 64 && ws_on_hand >= panel) {
+        r.kind = SweepRoute::Slab;
+        r.ws_doubles = panel;
+        r.first_in_assembly = ntot > 64;
+        return r;
+    }
+    // large systems (a look-ahead's size) in a batch that fills the chip many times over run
+    // as ONE sequential group: the product is power-bound (docs/LABBOOK.md section 4), beside it the
+    // panel chain only takes clock away (C3, 100 x N = 4096: 189.8 ms with the look-ahead,
+    // 198 in two halves, 186.3 sequential; up to 32 matrices the look-ahead still gains 1-2 %)
+    const bool big = ncols > r.nb && ntot - std::min(r.nb, ncols) >= c->la_min;
+    if (c->lookahead && c->aux && c->cur == c->stream && batch >= 8 && r.nb >= 128 && !big) {
+        r.kind = SweepRoute::Halves;
+        return r;
+    }
+    r.kind = SweepRoute::Blocked;
+    // (a batch fills the chip without the panel steps and the slab tail: only one or two
+    // matrices use the scratch)
+    if (batch <= 2 && ws_on_hand >= panel)
+        r.ws_doubles = panel;
+    return r;
+}
+
 // Columns [j0, j0 + w) of a panel, recursively: the left half, ONE update of the right half's
 // columns with the whole left half, the right half.  Same flops as the left-looking slab
 // order (each 64-column slab updated with everything before it, n = 64 per launch), but two
@@ -102,13 +159,12 @@ static int enqueue_panel_rec(bq_ctx *c, double *A, long lda, long astride, int b
 // factor, panel solve -- enqueued on c->cur.  With fusion on, the diagonal factor of a
 // slab rides in the launch that last updates it (the slab update here, or the
 // trailing update of the previous block: `diag_done`).
-// With a scratch column pair `ws` (panel_ws_doubles) every step is ONE launch
-// (panel_step_kernel, slab.h): the workgroups solve the rows they need themselves.
+// With a scratch column pair `ws` (panel_ws_doubles; one or two matrices) every step is ONE
+// launch (panel_step_kernel, slab.h): the workgroups solve the rows they need themselves.
 static int enqueue_panel(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot, int K0,
                   int KB, double *dinv, int *info, bool diag_done, double *ws = nullptr)
 {
-    // (a batch fills the chip without this: the redundant solves then only cost throughput)
-    if (ws && batch <= 2) {
+    if (ws) {
         if (!diag_done)
             BQCHK(launch_potf2(c, A, lda, astride, K0, dinv, BQ_DINV_STRIDE, info, batch));
         if (ntot - K0 - 64 <= 0)
@@ -136,28 +192,9 @@ static int enqueue_panel(bq_ctx *c, double *A, long lda, long astride, int batch
     return enqueue_panel_rec(c, A, lda, astride, batch, ntot, K0, KB, dinv, info, diag_done);
 }
 
-// Eliminate the first ncols columns (multiple of 64) of the ntot x ntot lower
-// matrix (ntot multiple of 64), batched.  dinv: BQ_DINV_STRIDE doubles per problem.
-//
-// With more than one outer block and a wide block the factorisation runs with a
-// look-ahead of one panel on two streams.  The main stream carries only the bulk
-// trailing updates (everything right of the next panel), back to back; the
-// high-priority aux stream updates the next panel's columns and factors that
-// panel meanwhile.  The two meet through events: update k+1 waits for panel k+1,
-// the panel-column update k+1 waits for trailing update k (which last wrote
-// those columns).
-// doubles of scratch the one-launch slab sweep needs (two panel columns per problem)
-size_t panel_ws_doubles(int ntot, int batch) { return ((size_t)2 * 64 * ntot + 4096) * batch; }
-
-// whether a sweep over `batch` matrices of size ntot can use that scratch at all (with the
-// block size in force now): callers that own long-lived workspaces skip the allocation else
-bool panel_ws_useful(const bq_ctx *c, int ntot, int batch)
-{
-    return batch <= 2 || auto_nb(c, ntot, batch) == 64;
-}
-
 // Outer block 64 (small systems): one launch per 64-column step (slab.h) after the first
-// diagonal factor and the staging of panel 0.
+// diagonal factor and the staging of panel 0.  a: the route's read-out, step 0 in the assembly
+// and the probe's stamps (SweepRoute::Slab; the sweeps inside other routes pass none).
 // col0: global column of A's first column (a sweep over the trailing block of a larger
 // factorisation reports failures in the larger matrix's numbering)
 // rstride > 0: `dinv` is a row of RECORDS per problem (rstride doubles apart), one BQ_DINV_HALF
@@ -165,8 +202,8 @@ bool panel_ws_useful(const bq_ctx *c, int ntot, int batch)
 // record of its own diagonal block (the batched panel solve reads them: enqueue_potrf_dfirst);
 // else the two halves of a BQ_DINV_STRIDE ping-pong.
 static int enqueue_slab_sweep(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot,
-                       int ncols, double *dinv, int *info, double *ws, int col0 = 0,
-                       bool first_done = false, long rstride = 0)
+                       int ncols, double *dinv, int *info, double *ws, const SweepArgs &a,
+                       int col0 = 0, long rstride = 0)
 {
     const long dstride = rstride > 0 ? rstride : (long)BQ_DINV_STRIDE;
     if (ntot <= 64)
@@ -174,7 +211,7 @@ static int enqueue_slab_sweep(bq_ctx *c, double *A, long lda, long astride, int 
                             info, batch);
     const long sstride = 64L * ntot;
     double *S[2] = {ws, ws + sstride * batch};
-    if (!first_done)
+    if (!a.first_done)
         // the first diagonal factor and the staging of panel 0 share a launch (or ride in the
         // assembly: assemble_first_kernel)
         BQCHK(launch_slab_first(c, A, lda, astride, batch, S[0], (long)ntot, sstride, ntot, dinv,
@@ -186,22 +223,18 @@ static int enqueue_slab_sweep(bq_ctx *c, double *A, long lda, long astride, int 
         const int fnext = r0 < ncols;
         const double m = (double)(ntot - r0);
         // only batch element 0 is stamped, and only while the probe's buffer has room
-        long long *stamps = (c->stamp_buf && j0 / 64 < c->stamp_steps)
-                                ? c->stamp_buf + 160 * (j0 / 64)
-                                : nullptr;
+        long long *stamps =
+            (a.stamps && j0 / 64 < a.stamped_steps) ? a.stamps + 160 * (j0 / 64) : nullptr;
         // the tile updates (lower half of 2 m^2 64) and the solve of the panel (m 64^2)
         const long din = rstride > 0 ? (long)(j0 / 64) * BQ_DINV_HALF : (long)par * BQ_DINV_HALF;
         const long dout =
             rstride > 0 ? (long)(j0 / 64 + 1) * BQ_DINV_HALF : (long)(par ^ 1) * BQ_DINV_HALF;
         BQCHK(launch_slab_step(c, A, lda, astride, batch, S[par], S[par ^ 1], (long)ntot, sstride,
-                               ntot, j0, dinv + din, dinv + dout, fnext, !fnext, info, col0, stamps,
-                               (m * m * 64.0 + m * 64.0 * 64.0) * batch, dstride));
+                               ntot, j0, dinv + din, dinv + dout, fnext, !fnext, info, col0, a.out,
+                               stamps, (m * m * 64.0 + m * 64.0 * 64.0) * batch, dstride));
     }
     return BQ_OK;
 }
-
-// the look-ahead pays up to this many matrices per batch (enqueue_potrf_partial)
-#define BQ_LA_MAX_BATCH 48
 
 // (tile choice while two streams share the chip: gemm_lds_tile)
 struct Sharing {
@@ -211,25 +244,23 @@ struct Sharing {
     ~Sharing() { c->sharing = prev; }
 };
 
-// nb_forced: the outer block of the whole batch when this call factors one half of it
-// whether a factorisation of these sizes goes to the one-launch slab sweep from its first column
-bool sweep_is_slab(const bq_ctx *c, int ntot, int ncols, int batch, size_t panel_ws_len)
-{
-    return auto_nb(c, ntot, batch) == 64 && panel_ws_len >= panel_ws_doubles(ntot, batch) &&
-           ncols >= 64 && ntot > 64;
-}
-
+// Eliminate the first ncols columns (multiple of 64) of the ntot x ntot lower
+// matrix (ntot multiple of 64), batched, with outer block NB.  dinv: BQ_DINV_STRIDE doubles per
+// problem.  ws: the slab sweep's scratch (SweepRoute::Blocked of one or two matrices, else null):
+// one-launch panel steps and the last rows on the one-launch steps.
+//
+// With more than one outer block and a wide block the factorisation runs with a
+// look-ahead of one panel on two streams.  The main stream carries only the bulk
+// trailing updates (everything right of the next panel), back to back; the
+// high-priority aux stream updates the next panel's columns and factors that
+// panel meanwhile.  The two meet through events: update k+1 waits for panel k+1,
+// the panel-column update k+1 waits for trailing update k (which last wrote
+// those columns).
 // skip_border: the caller reads its results off the border ROWS (plan_readout_kernel), so the
 // trailing updates leave the border x border block alone
 static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot,
-                        int ncols, double *dinv, int *info, double *panel_ws, size_t panel_ws_len,
-                        int nb_forced, bool first_done = false, bool skip_border = false)
+                        int ncols, double *dinv, int *info, double *ws, int NB, bool skip_border)
 {
-    const int NB = nb_forced > 0 ? nb_forced : auto_nb(c, ntot, batch);
-    double *ws = (panel_ws && panel_ws_len >= panel_ws_doubles(ntot, batch)) ? panel_ws : nullptr;
-    if (NB == 64 && ws && ncols >= 64)
-        return enqueue_slab_sweep(c, A, lda, astride, batch, ntot, ncols, dinv, info, ws, 0,
-                                  first_done);
     const bool la = c->lookahead && c->aux && NB >= 128 && ncols > NB && batch <= BQ_LA_MAX_BATCH;
     int K0 = 0;
     bool panel_done = false; // panel K0 was already factored by the look-ahead phase
@@ -320,7 +351,7 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
         // The last rows of a large matrix are a small factorisation of their own -- the
         // Schur complement once this block's update is in --, and for one or two matrices
         // the one-launch steps are its shortest chain: hand the rest to the slab sweep.
-        const bool to_slab = batch <= 2 && ws && NB > 64 && r0 < ncols && ntot - r0 < kSlabMax;
+        const bool to_slab = ws && NB > 64 && r0 < ncols && ntot - r0 < kSlabMax;
         if (r0 < ntot) {
             const double *P = A + r0 + (long)K0 * lda;
             // the trailing update also factors the next diagonal block if there is one
@@ -335,7 +366,7 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
         }
         if (to_slab)
             return enqueue_slab_sweep(c, A + r0 + (long)r0 * lda, lda, astride, batch, ntot - r0,
-                                      ncols - r0, dinv, info, ws, r0);
+                                      ncols - r0, dinv, info, ws, SweepArgs(), r0);
     }
     return BQ_OK;
 }
@@ -356,26 +387,6 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
 //        and its factorisation D, hidden beside the rest of the update.
 // The whole batch moves in lock-step through launches that each fill the chip.
 // ---------------------------------------------------------------------------------------------
-static size_t dfirst_rec_doubles(int nb, int batch) { return (size_t)(nb / 64) * BQ_DINV_HALF * batch; }
-// (two sets of records: with the early fork the next block's diagonal factor writes its own while
-// the rest of this block's panel solve still reads this block's)
-static size_t dfirst_ws_doubles(int nb, int batch)
-{
-    return panel_ws_doubles(nb, batch) + 2 * dfirst_rec_doubles(nb, batch);
-}
-
-static bool dfirst_applies(const bq_ctx *c, int ntot, int ncols, int batch)
-{
-    return c->diag_first && batch >= 3 && ncols >= 128 && auto_nb(c, ntot, batch) >= 128;
-}
-
-size_t sweep_ws_doubles(const bq_ctx *c, int ntot, int batch)
-{
-    if (dfirst_applies(c, ntot, ntot, batch))
-        return dfirst_ws_doubles(std::min(auto_nb(c, ntot, batch), ntot), batch);
-    return panel_ws_useful(c, ntot, batch) ? panel_ws_doubles(ntot, batch) : 0;
-}
-
 // X = rows [rx, rx + m) of the panel that starts at column K0: columns [j0, j0 + w) (relative
 // to K0) solved against L11 = A[K0.., K0..]; rec: the records of L11's 64 x 64 diagonal blocks.
 // solved: the launch that last updated slab j0 solved it as well.
@@ -406,33 +417,22 @@ static int enqueue_trsm_rec(bq_ctx *c, double *A, long lda, long astride, int ba
     return enqueue_trsm_rec(c, A, lda, astride, batch, rx, m, K0, j0 + wl, wr, rec, rstride, fuse);
 }
 
-// the panel solve of one outer block as enqueue_potrf_dfirst issues it (also bq_probe_panel_solve)
+// the panel solve of one outer block as enqueue_potrf_dfirst issues it (also bq_probe_panel_solve);
+// one_launch: trsm_sweep_kernel (c->df_sweep), else the recursive products and solves
 int enqueue_panel_solve(bq_ctx *c, double *A, long lda, long astride, int batch, int r0, int m2,
-                        int K0, int KB, const double *rec, long rstride)
+                        int K0, int KB, const double *rec, long rstride, bool one_launch)
 {
-    if (c->df_sweep)
+    if (one_launch)
         return launch_trsm_sweep(c, A + r0 + (long)K0 * lda, lda, astride, m2,
                                  A + K0 + (long)K0 * lda, lda, astride, rec, rstride, KB, batch);
     return enqueue_trsm_rec(c, A, lda, astride, batch, r0, m2, K0, 0, KB, rec, rstride, false);
 }
 
-// (the condition under which enqueue_potrf_partial takes enqueue_potrf_dfirst, and the sweep has at
-// least two outer blocks: with one there is no product that could seed what lies right of it)
-int dfirst_seed_cols(const bq_ctx *c, int ntot, int ncols, int batch, size_t panel_ws_len)
+static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long lda, long astride,
+                                int *info, double *ws, const SweepArgs &a)
 {
-    if (!c->asm_fuse || (ntot & 63) || (ncols & 63) || ncols > ntot ||
-        !dfirst_applies(c, ntot, ncols, batch))
-        return 0;
-    const int NB = std::min(auto_nb(c, ntot, batch), ncols);
-    if (panel_ws_len < dfirst_ws_doubles(NB, batch) || NB >= ncols)
-        return 0;
-    return NB;
-}
-
-static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot,
-                                int ncols, int *info, double *ws, bool skip_border)
-{
-    const int NB = std::min(auto_nb(c, ntot, batch), ncols);
+    const int batch = r.batch, ntot = r.ntot, ncols = r.ncols, NB = std::min(r.nb, ncols);
+    const bool skip_border = a.skip_border, one_launch = c->df_sweep;
     double *recs[2] = {ws + panel_ws_doubles(NB, batch),
                        ws + panel_ws_doubles(NB, batch) + dfirst_rec_doubles(NB, batch)};
     const long rstride = (long)(NB / 64) * BQ_DINV_HALF;
@@ -454,20 +454,20 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
             return launch_potrf_wg(c, A + K0 + (long)K0 * lda, lda, astride, KB, rec, rstride, info,
                                    K0, batch);
         return enqueue_slab_sweep(c, A + K0 + (long)K0 * lda, lda, astride, batch, KB, KB, rec, info,
-                                  ws, K0, false, rstride);
+                                  ws, SweepArgs(), K0, rstride);
     };
     BQCHK(diag(0, NB, recs[0]));
     // while a diagonal factor runs beside an update, gemm_lds_tile keeps the rule of a product
     // alone (C5 shard 5.73 ms against 6.05 with the look-ahead's sharing mode 1)
     Sharing scope(c, la ? 0 : c->sharing);
-    // The caller assembled only the first NB columns (dfirst_seed_cols) and left the rest as a
+    // The caller assembled only the first NB columns (SweepRoute::seed_cols) and left the rest as a
     // GramSeed: block 0's three products are the first to touch everything right of them, and they
     // compute their tiles of the system instead of loading them -- the assembly of two thirds of a
     // C5 system (an HBM-write-bound launch) and its read-back disappear.
-    const bool seeded = c->gram_seed.pts != nullptr;
-    auto seed_at = [&](int r, int cc) {
-        GramSeed sd = c->gram_seed;
-        sd.r = r;
+    const bool seeded = a.seed.pts != nullptr;
+    auto seed_at = [&](int rr, int cc) {
+        GramSeed sd = a.seed;
+        sd.r = rr;
         sd.c = cc;
         return sd;
     };
@@ -480,7 +480,8 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
         const double *P = A + r0 + (long)K0 * lda;
         const int nw = r0 < ncols ? std::min(NB, ncols - r0) : 0;
         if (nw == 0) {
-            BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r0, m2, K0, KB, rec, rstride));
+            BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r0, m2, K0, KB, rec, rstride,
+                                      one_launch));
             // what is left is the Schur complement of the border: nobody reads it when the
             // results come off the border rows
             if (!skip_border)
@@ -490,7 +491,8 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
         }
         const int r1 = r0 + nw;
         if (!early)
-            BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r0, m2, K0, KB, rec, rstride));
+            BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r0, m2, K0, KB, rec, rstride,
+                                      one_launch));
         // the next diagonal block: (its rows of the panel solved,) updated and factored -- on the
         // second stream, beside the rest
         if (la) {
@@ -500,7 +502,8 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
         }
         int st = BQ_OK;
         if (early) {
-            st = enqueue_panel_solve(c, A, lda, astride, batch, r0, nw, K0, KB, rec, rstride);
+            st = enqueue_panel_solve(c, A, lda, astride, batch, r0, nw, K0, KB, rec, rstride,
+                                     one_launch);
             // (no early return while c->cur is the second stream: a failed record falls through
             // to the block below that restores it -- ADVICE r05)
             if (st == BQ_OK && hipEventRecord(c->ev_top, c->aux) != hipSuccess)
@@ -525,7 +528,7 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
             const double *P1 = A + r1 + (long)K0 * lda;
             if (early) {
                 BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r1, ntot - r1, K0, KB, rec,
-                                          rstride));
+                                          rstride, one_launch));
                 // the column update reads the top rows as its Q operand
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_top, 0));
             }
@@ -554,59 +557,99 @@ static int enqueue_potrf_dfirst(bq_ctx *c, double *A, long lda, long astride, in
     return BQ_OK;
 }
 
-// Eliminate the first ncols columns of `batch` matrices.  A batch of mid-sized matrices
-// (config C5: 64 x N = 2048) sweeps in lock-step: every 64-column panel step is two short
-// dependent launches that leave most of the chip idle, and a third of the sweep's time is
-// such panel work.  The batch is therefore cut in two halves on the two streams: one half's
-// panel chain runs beside the other half's MFMA trailing update (C5 shard: 7.21 -> 6.78 ms;
-// three or four groups on more streams were slower, 7.8 / 7.5 ms).  (Large single matrices
-// use the second stream for the look-ahead instead, small ones the one-launch steps.)
-int enqueue_potrf_partial(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot,
-                          int ncols, double *dinv, int *info, double *panel_ws,
-                          size_t panel_ws_len, bool first_done, bool skip_border)
+// Eliminate the first r.ncols columns of r.batch matrices along the route sweep_route chose.  ws:
+// at least r.ws_doubles of scratch.
+int enqueue_potrf_partial(bq_ctx *c, const SweepRoute &r, double *A, long lda, long astride,
+                          double *dinv, int *info, double *ws, const SweepArgs &a)
 {
+    const int batch = r.batch, ntot = r.ntot, ncols = r.ncols;
     if ((ntot & 63) || (ncols & 63) || ncols > ntot)
         return fail(c, BQ_ERR_BAD_ARG, "potrf: sizes must be multiples of 64");
-    const int NB = auto_nb(c, ntot, batch);
-    if (dfirst_applies(c, ntot, ncols, batch) && panel_ws &&
-        panel_ws_len >= dfirst_ws_doubles(std::min(NB, ncols), batch)) {
-        // (Two half-batches on the two streams, each in lock-step with its diagonal factors on its
-        // own stream, were measured in rounds 4 and 5 -- in phase: C5 shard 5.77 ms / 256 x C2 4.33
-        // against 5.67 / 4.21 for the whole batch in lock-step; out of phase, the second half
-        // starting when the first half's first panel solve is through, so that one half's
-        // panel-solve workgroups and diagonal chains run beside the other half's update tiles:
-        // 5.87 / 4.52-4.81, C3 186-188 against 177 -- and removed: every launch of a half fills
-        // the chip half as well, and two MFMA-bound kernels gain nothing from sharing CUs.)
-        return enqueue_potrf_dfirst(c, A, lda, astride, batch, ntot, ncols, info, panel_ws,
-                                    skip_border);
-    }
-    if (c->gram_seed.pts)
+    if (a.seed.pts && r.kind != SweepRoute::DiagFirst)
         return fail(c, BQ_ERR_BAD_ARG, "potrf: a partly assembled system on a sweep that cannot seed it");
-    // large systems (a look-ahead's size) in a batch that fills the chip many times over run
-    // as ONE sequential group: the product is power-bound (docs/LABBOOK.md section 4), beside it the
-    // panel chain only takes clock away (C3, 100 x N = 4096: 189.8 ms with the look-ahead,
-    // 198 in two halves, 186.3 sequential; up to 32 matrices the look-ahead still gains 1-2 %)
-    const bool big = ncols > NB && ntot - std::min(NB, ncols) >= c->la_min;
-    if (c->lookahead && c->aux && c->cur == c->stream && batch >= 8 && NB >= 128 && !big) {
-        const int b0 = batch / 2, b1 = batch - b0;
-        Sharing halves(c, 2);
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-        c->cur = c->aux;
-        int st = enqueue_potrf_group(c, A + (long)b0 * astride, lda, astride, b1, ntot, ncols,
-                                     dinv + (long)b0 * BQ_DINV_STRIDE, info + b0, nullptr, 0, NB,
-                                     false, skip_border);
-        c->cur = c->stream;
-        if (st != BQ_OK)
-            return st;
-        HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
-        BQCHK(enqueue_potrf_group(c, A, lda, astride, b0, ntot, ncols, dinv, info, nullptr, 0, NB,
-                                  false, skip_border));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_panel, 0));
-        return BQ_OK;
+    if (r.kind == SweepRoute::Slab)
+        return enqueue_slab_sweep(c, A, lda, astride, batch, ntot, ncols, dinv, info, ws, a);
+    if (r.kind == SweepRoute::Blocked)
+        return enqueue_potrf_group(c, A, lda, astride, batch, ntot, ncols, dinv, info,
+                                   r.ws_doubles ? ws : nullptr, r.nb, a.skip_border);
+    // (Two half-batches on the two streams, each in lock-step with its diagonal factors on its
+    // own stream, were measured in rounds 4 and 5 -- in phase: C5 shard 5.77 ms / 256 x C2 4.33
+    // against 5.67 / 4.21 for the whole batch in lock-step; out of phase, the second half
+    // starting when the first half's first panel solve is through, so that one half's
+    // panel-solve workgroups and diagonal chains run beside the other half's update tiles:
+    // 5.87 / 4.52-4.81, C3 186-188 against 177 -- and removed: every launch of a half fills
+    // the chip half as well, and two MFMA-bound kernels gain nothing from sharing CUs.)
+    if (r.kind == SweepRoute::DiagFirst)
+        return enqueue_potrf_dfirst(c, r, A, lda, astride, info, ws, a);
+    // Halves: a batch of mid-sized matrices (config C5: 64 x N = 2048) sweeps in lock-step: every
+    // 64-column panel step is two short dependent launches that leave most of the chip idle, and a
+    // third of the sweep's time is such panel work.  The batch is therefore cut in two halves on
+    // the two streams: one half's panel chain runs beside the other half's MFMA trailing update
+    // (C5 shard: 7.21 -> 6.78 ms; three or four groups on more streams were slower, 7.8 / 7.5 ms).
+    // Both halves keep the whole batch's outer block.
+    const int b0 = batch / 2, b1 = batch - b0;
+    Sharing halves(c, 2);
+    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
+    c->cur = c->aux;
+    int st = enqueue_potrf_group(c, A + (long)b0 * astride, lda, astride, b1, ntot, ncols,
+                                 dinv + (long)b0 * BQ_DINV_STRIDE, info + b0, nullptr, r.nb,
+                                 a.skip_border);
+    c->cur = c->stream;
+    if (st != BQ_OK)
+        return st;
+    HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
+    BQCHK(enqueue_potrf_group(c, A, lda, astride, b0, ntot, ncols, dinv, info, nullptr, r.nb,
+                              a.skip_border));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_panel, 0));
+    return BQ_OK;
+}
+
+// One pass over `batch` bordered systems (plan_enqueue, fit_factor): the assembly, the sweep over
+// the first L.npad columns and the read-out of log-ML and of the posterior at the M border points.
+// sys: the systems' points, targets, kernel parameters and layout; rows: the read-out may come off
+// the border rows (plan_readout_kernel); work: the finalize launch's figure for the profiler.
+int enqueue_bordered(bq_ctx *c, const GramSeed &sys, int batch, double *A, long lda, long astride,
+                     double *dinv, int *info, double *ws, size_t ws_len, double *scal, double *mean,
+                     double *var, long mstride, bool rows, double work, long long *stamps,
+                     int stamped_steps)
+{
+    const Layout &L = sys.L;
+    const SweepRoute r = sweep_route(c, L.ntot, L.npad, batch, ws_len);
+    SweepArgs a;
+    a.stamps = stamps;
+    a.stamped_steps = stamped_steps;
+    // a small system's first sweep launch (and the clearing of the failure flags) rides in
+    // the assembly
+    FirstStep fs;
+    if (r.first_in_assembly) {
+        fs.S0 = ws;
+        fs.lds = L.ntot;
+        fs.sstride = 64L * L.ntot;
+        fs.dinv = dinv;
+        fs.info = info;
+        fs.scal = c->fold_readout ? scal : nullptr;
+        a.first_done = true;
+    } else {
+        HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int) * batch, c->stream));
     }
-    return enqueue_potrf_group(c, A, lda, astride, batch, ntot, ncols, dinv, info, panel_ws,
-                               panel_ws_len, 0, first_done, skip_border);
+    // a batch that sweeps diagonal block first assembles only its first outer block's columns: the
+    // first products that touch the rest compute it themselves (GramSeed)
+    BQCHK(launch_assemble(c, sys.d, sys.pts, sys.pstride, sys.y, sys.ystride, sys.gp, sys.gpstride,
+                          A, lda, astride, L, batch, fs, r.seed_cols));
+    if (r.seed_cols > 0)
+        a.seed = sys;
+    a.skip_border = rows && L.yrow >= 0 && r.border_rows;
+    // a sweep of one-launch steps carries the read-out itself (SlabOut: no finalize launch)
+    const bool folded = r.first_in_assembly && L.yrow >= 0 && c->fold_readout;
+    if (folded)
+        a.out = SlabOut{scal, mean, var, mstride, L.n, L.npad, L.M, L.yrow};
+    BQCHK(enqueue_potrf_partial(c, r, A, lda, astride, dinv, info, ws, a));
+    if (folded)
+        return BQ_OK;
+    if (a.skip_border)
+        return launch_plan_readout(c, A, lda, astride, L, sys.gp, scal, mean, var, mstride, batch);
+    return launch_finalize(c, A, lda, astride, L, scal, mean, var, mstride, batch, work);
 }
 
 } // namespace bqh

@@ -437,26 +437,20 @@ extern "C" int bq_probe_panel_solve(bq_ctx *c, int64_t m, int64_t kb, int64_t ba
                                    hipMemcpyHostToDevice, c->stream));
         BQCHK(launch_diag_winv(c, A.d() + b * astride, lda, (int)kb, rec.d() + b * rstride));
     }
-    const int keep = c->df_sweep;
-    if (mode == 1)
-        c->df_sweep = 0;
-    if (mode == 2)
-        c->df_sweep = 1;
+    const bool one_launch = mode == 0 ? c->df_sweep != 0 : mode == 2;
     const int st = enqueue_panel_solve(c, A.d(), lda, astride, (int)batch, (int)kb, (int)m, 0,
-                                       (int)kb, rec.d(), rstride);
+                                       (int)kb, rec.d(), rstride, one_launch);
     if (st == BQ_OK && reps > 0 && ms_per_call) {
         // timing: the same call again and again on its own (now solved, still finite) output
         float ms = 0;
         BQCHK(bq_timer_start(c));
         for (int64_t r = 0; r < reps; ++r)
             (void)enqueue_panel_solve(c, A.d(), lda, astride, (int)batch, (int)kb, (int)m, 0,
-                                      (int)kb, rec.d(), rstride);
+                                      (int)kb, rec.d(), rstride, one_launch);
         BQCHK(bq_timer_stop_ms(c, &ms));
         *ms_per_call = ms / (double)reps;
-        c->df_sweep = keep;
         return BQ_OK; // (X is not downloaded: it has been solved reps + 1 times)
     }
-    c->df_sweep = keep;
     BQCHK(st);
     for (int64_t b = 0; b < batch; ++b)
         HIPCHK(c, hipMemcpy2DAsync(X + b * m * kb, sizeof(double) * m, A.d() + b * astride + kb,
@@ -476,7 +470,8 @@ extern "C" int bq_probe_c2_timeline(bq_ctx *c, bq_plan *p, int64_t *stamps, int6
         return BQ_ERR_BAD_ARG;
     // only the one-launch slab sweep carries the stamped instantiation, and it stamps one
     // record per step into the caller's nsteps (the sweep itself skips steps beyond them)
-    if (!sweep_is_slab(c, p->L.ntot, p->L.npad, p->nprob, p->panel.bytes / sizeof(double)))
+    if (sweep_route(c, p->L.ntot, p->L.npad, p->nprob, p->panel.bytes / sizeof(double)).kind !=
+        SweepRoute::Slab)
         return fail(c, BQ_ERR_BAD_ARG, "timeline: this plan does not sweep with the one-launch steps");
     if (nsteps < p->L.npad / 64)
         return fail(c, BQ_ERR_BAD_ARG, "timeline: %d steps, room for %d", p->L.npad / 64, (int)nsteps);
@@ -484,12 +479,7 @@ extern "C" int bq_probe_c2_timeline(bq_ctx *c, bq_plan *p, int64_t *stamps, int6
     DevBuf st;
     HIPCHK(c, st.alloc(sizeof(long long) * 160 * (size_t)nsteps));
     HIPCHK(c, hipMemsetAsync(st.p, 0, st.bytes, c->stream));
-    c->stamp_buf = static_cast<long long *>(st.p);
-    c->stamp_steps = (int)nsteps;
-    int rc = plan_enqueue(c, p);
-    c->stamp_buf = nullptr;
-    c->stamp_steps = 0;
-    BQCHK(rc);
+    BQCHK(plan_enqueue(c, p, static_cast<long long *>(st.p), (int)nsteps));
     HIPCHK(c, hipMemcpyAsync(stamps, st.p, st.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BQ_OK;

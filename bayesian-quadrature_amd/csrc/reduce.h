@@ -160,18 +160,6 @@ __global__ __launch_bounds__(256) void predict_mean_kernel(const double *__restr
         mean[i] = g.c * s;
 }
 
-// dst(rows x cols, ld ldd) <- src(rows x cols, ld lds); optional transpose
-__global__ void copy2d_kernel(double *__restrict__ dst, long ldd, const double *__restrict__ src,
-                              long lds, int rows, int cols, int transpose_src)
-{
-    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int j0 = blockIdx.y * 16 + (threadIdx.x >> 6) * 4;
-    if (i >= rows)
-        return;
-    for (int j = j0; j < j0 + 4 && j < cols; ++j)
-        dst[i + (long)j * ldd] = transpose_src ? src[j + (long)i * lds] : src[i + (long)j * lds];
-}
-
 // A <- identity on the padding square [n, ntot) and zero in the padding
 // rows/cols of the lower triangle (used by the linalg drop-ins)
 __global__ void pad_identity_kernel(double *__restrict__ A, long lda, int n, int ntot)
