@@ -460,6 +460,49 @@ extern "C" int bq_probe_panel_solve(bq_ctx *c, int64_t m, int64_t kb, int64_t ba
     return BQ_OK;
 }
 
+// The batched sweep on the caller's own matrices (a plan takes points, not matrices): the first
+// ncols columns of `batch` lower ntot x ntot matrices are eliminated along the route sweep_route
+// picks for them, with the workspace sized as plan_create sizes it and default SweepArgs (nothing
+// seeded, no folded read-out, the border x border Schur complement computed).  The whole buffer --
+// padding rows and the gaps between matrices included -- goes up and comes back verbatim.
+extern "C" int bq_probe_potrf_batch(bq_ctx *c, int64_t batch, int64_t ntot, int64_t ncols,
+                                    int64_t lda, int64_t astride, double *A, int32_t *info,
+                                    int32_t *route)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (!A || !info || !route || batch < 1 || batch > (1 << 20) || ntot < 64 || ntot > 65536 ||
+        (ntot & 63) || ncols < 64 || (ncols & 63) || ncols > ntot)
+        return fail(c, BQ_ERR_BAD_ARG, "potrf_batch: ntot, ncols multiples of 64, ncols <= ntot");
+    if (lda == 0)
+        lda = pick_ld(ntot);
+    if (astride == 0)
+        astride = lda * ntot;
+    if (lda < ntot || (lda & 1) || astride < lda * ntot || (astride & 1))
+        return fail(c, BQ_ERR_BAD_ARG, "potrf_batch: lda >= ntot, astride >= lda ntot, both even");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf Ad, dinv, ws, inf;
+    const size_t abytes = sizeof(double) * (size_t)astride * (size_t)batch;
+    HIPCHK(c, Ad.alloc(abytes));
+    HIPCHK(c, dinv.alloc(sizeof(double) * BQ_DINV_STRIDE * (size_t)batch));
+    HIPCHK(c, ws.alloc(sizeof(double) *
+                       sweep_route(c, (int)ntot, (int)ntot, (int)batch).ws_doubles));
+    HIPCHK(c, inf.alloc(sizeof(int) * (size_t)batch));
+    const SweepRoute r =
+        sweep_route(c, (int)ntot, (int)ncols, (int)batch, ws.bytes / sizeof(double));
+    route[0] = (int32_t)r.kind;
+    route[1] = r.nb;
+    route[2] = r.ws_doubles != 0;
+    HIPCHK(c, hipMemcpyAsync(Ad.p, A, abytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(inf.p, 0, sizeof(int) * (size_t)batch, c->stream));
+    BQCHK(enqueue_potrf_partial(c, r, Ad.d(), (long)lda, (long)astride, dinv.d(), inf.i(), ws.d()));
+    HIPCHK(c, hipMemcpyAsync(A, Ad.p, abytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(info, inf.p, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+
 // One eager (not graph-replayed) pass of a plan with the profiling instantiation of the slab
 // step: stamps[160 * step + k] = s_memtime of workgroup 0 at (0) entry, (1) factor fragments
 // loaded, (2) panel rows solved, (3) tile loaded + Q in LDS, (4) tile updated, (5..9) the

@@ -478,6 +478,33 @@ class Engine(object):
             return float(ms.value)  # ms per call
         return np.transpose(Xf, (0, 2, 1)).copy()
 
+    SWEEP_KINDS = ("slab", "blocked", "halves", "diag_first")
+
+    def probe_potrf_batch(self, buf, batch, ntot, ncols=None, lda=0, astride=0):
+        """The batched Cholesky sweep on the caller's matrices (bq_probe_potrf_batch): buf is a
+        flat float64 array of batch * astride doubles (column-major matrices of leading dimension
+        lda; 0 = the plans' own strides), factored in place.  Returns (info per matrix,
+        (route kind, outer block, scratch used))."""
+        e = self.probe_engine()
+        if buf.dtype != np.float64 or buf.ndim != 1 or not buf.flags.c_contiguous:
+            raise ValueError("buf must be a flat contiguous float64 array")
+        ld = int(lda) if lda else self.plan_ld(ntot)
+        stride = int(astride) if astride else ld * int(ntot)
+        if buf.shape[0] != stride * int(batch):
+            raise ValueError("buf holds %d doubles, the batch %d" % (buf.shape[0], stride * batch))
+        info = np.full(int(batch), -1, dtype=np.int32)
+        route = np.full(3, -1, dtype=np.int32)
+        e._check(e._lib.bq_probe_potrf_batch(
+            e._ctx, int(batch), int(ntot), int(ntot if ncols is None else ncols), int(lda),
+            int(astride), L.dptr(buf), info.ctypes.data_as(L._i32p),
+            route.ctypes.data_as(L._i32p)))
+        return info, (self.SWEEP_KINDS[route[0]], int(route[1]), bool(route[2]))
+
+    @staticmethod
+    def plan_ld(ntot):
+        """Leading dimension of a plan's ntot-row systems (csrc/host.h, pick_ld)."""
+        return int(ntot) + (64 if ntot >= 1024 and ntot % 512 == 0 else 0)
+
     def probe_xcd_hop(self, mode, iters=2000, kib=1):
         """(ns per hand-off, XCC ids of the 16 workgroups, stale payload words) -- see
         bq_probe_xcd_hop in include/bqhip_probe.h."""

@@ -120,7 +120,9 @@ int bq_profile_timeline(bq_ctx *ctx, int keep, double *out, int64_t max_rows, in
 /* L <- lower Cholesky factor of C (n x n, ld = n).  C == L allowed (in place).
  * The strict upper triangle of L is left as it was in C ("upper values could
  * be anything", linalg_c.pyx:58-59).  BQ_ERR_NOT_PD when dpotrf would fail;
- * *info (may be NULL) receives the 1-based failing column. */
+ * *info (may be NULL) receives the 1-based failing column: the first column whose pivot is not a
+ * positive finite number.  (A NaN or +inf pivot fails too, where LAPACK's dpotrf carries on; the
+ * same rule holds for bq_potrf_dev's flag and for the status of the batched entry points.) */
 int bq_cho_factor(bq_ctx *ctx, const double *C, double *L, int64_t n, int64_t *info);
 /* X <- (L L^T)^-1 B, B and X are n x nrhs, ld = n.  B == X allowed. */
 int bq_cho_solve(bq_ctx *ctx, const double *L, const double *B, double *X, int64_t n,

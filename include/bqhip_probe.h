@@ -74,6 +74,21 @@ int bq_probe_potf2(bq_ctx *ctx, const double *A, int from_lds, int64_t reps, dou
  * written back. */
 int bq_probe_panel_solve(bq_ctx *ctx, int64_t m, int64_t kb, int64_t batch, const double *L,
                          double *X, int mode, int64_t reps, double *ms_per_call);
+/* The batched Cholesky sweep on the caller's own matrices (potrf.hip, enqueue_potrf_partial; a plan
+ * takes points, so nothing else can hand a batched route a dense or a deliberately indefinite
+ * matrix): the first ncols columns of `batch` lower ntot x ntot matrices (column-major, leading
+ * dimension lda, astride doubles apart; 0 = the plans' own padded lda / lda * ntot) are
+ * eliminated along the route the engine picks for (ntot, ncols, batch), with its workspace sized
+ * as a plan's and nothing seeded or skipped: L11 and L21 replace the first ncols columns, the
+ * lower triangle of the Schur complement the rest.  A (host, batch * astride doubles) is uploaded
+ * and downloaded whole -- rows ntot .. lda - 1 and the gaps between matrices must come back as
+ * they went.  info[b]: 0 or the 1-based failing column of matrix b.  route[0..2]: the sweep that
+ * ran (0 one-launch steps, 1 blocked, 2 two half-batches, 3 diagonal block first), its outer
+ * block, and whether it used scratch.  ntot, ncols multiples of 64, ncols <= ntot, lda >= ntot and
+ * even, astride >= lda * ntot and even; anything else is BQ_ERR_BAD_ARG.
+ * (tests/test_cholesky_contracts.py) */
+int bq_probe_potrf_batch(bq_ctx *ctx, int64_t batch, int64_t ntot, int64_t ncols, int64_t lda,
+                         int64_t astride, double *A, int32_t *info, int32_t *route);
 /* dump of the f64 MFMA D-register layout: out[64*4] receives, for lane l and
  * register r, the value row*16+col of the D element it holds */
 int bq_probe_mfma_layout(bq_ctx *ctx, double *out256);
