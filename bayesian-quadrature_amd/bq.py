@@ -108,6 +108,11 @@ class BQ(object):
         kernel = self.options["kernel"]
         self._drop_pairs()
         self.gp_log_l = GP(kernel(*params_tl[:-1]), self.x_s, self.tl_s, s=params_tl[-1])
+        self._init_rest(params_l)
+
+    def _init_rest(self, params_l):
+        """Everything of ``init`` behind the log-GP: candidates, the second GP, the grids."""
+        kernel = self.options["kernel"]
         self.gp_log_l.jitter = np.zeros(self.ns, dtype=DTYPE)
         self._choose_candidates()
         self.gp_l = GP(kernel(*params_l[:-1]), self.x_sc, self.l_sc, s=params_l[-1])
@@ -471,6 +476,16 @@ class BQ(object):
             self.l_s = np.append(self.l_s, float(l_a))
             self.tl_s = np.append(self.tl_s, np.log(float(l_a)))
             self.ns += 1
+            # the log-GP keeps its object and its resident factor and grows by one row
+            # (gp.GP.append); the rest is init's, in init's order
+            try:
+                self.gp_log_l.append(float(x_a), np.log(float(l_a)))
+            except np.linalg.LinAlgError:
+                pass  # a singular system shows where it always has: at the new GP's first use
+            else:
+                self._drop_pairs()
+                self._init_rest(self.gp_l.params)
+                return
         self.init(self.gp_log_l.params, self.gp_l.params)
 
     # ------------------------------------------------------- pickling, copying

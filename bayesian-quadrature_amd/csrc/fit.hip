@@ -8,6 +8,11 @@
 // ===========================================================================
 namespace bqh {
 
+// a fit's pinned staging (bq_fit::hfit): [0, 136) results, then the kernel parameters, then 64
+// points of the largest dimension (the border points of a refit, the observations of an append)
+constexpr size_t HF_PAR = 8 + 128, HF_PTS = HF_PAR + (sizeof(GaussParams) + 7) / 8;
+constexpr size_t HF_NPTS = 64 * BQ_MAXD;
+
 // pm / pv: device buffers for the posterior mean / variance of the layout's M border points
 // (bq_gp_refit_predict), or null
 // npts_words: that many doubles of border points wait in the staging buffer (hfit + HF_PTS) for
@@ -26,10 +31,9 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     f->have_dw = false;
     f->have_y = false;
     // pinned staging: [0, 136) results, then the kernel parameters, then border points
-    constexpr size_t HF_PAR = 8 + 128, HF_PTS = HF_PAR + (sizeof(GaussParams) + 7) / 8;
     if (!f->hfit)
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
-                                sizeof(double) * (HF_PTS + 64 * BQ_MAXD)));
+                                sizeof(double) * (HF_PTS + HF_NPTS)));
     std::memcpy(f->hfit + HF_PAR, &f->g, sizeof f->g);
     // The call's small transfers -- kernel parameters (and border points) in, the record out -- go
     // through one kernel each on the mapped staging buffer: a copy-engine operation costs the
@@ -294,10 +298,9 @@ extern "C" int bq_gp_refit_predict(bq_ctx *c, bq_fit *f, double h, const double 
     f->g = make_params(f->d, h, w, s);
     f->L = make_layout(f->n, (int)M, true); // same ntot: the points share the y row's block
     {
-        constexpr size_t HF_PTS = 8 + 128 + (sizeof(GaussParams) + 7) / 8;
         if (!f->hfit)
             HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
-                                    sizeof(double) * (HF_PTS + 64 * BQ_MAXD)));
+                                    sizeof(double) * (HF_PTS + HF_NPTS)));
         std::memcpy(f->hfit + HF_PTS, xo, sizeof(double) * f->d * M);
     }
     double hv[128];
@@ -308,6 +311,204 @@ extern "C" int bq_gp_refit_predict(bq_ctx *c, bq_fit *f, double h, const double 
         if (var)
             var[i] = hv[64 + i];
     }
+    return BQ_OK;
+}
+
+// Append k observations to a resident fit under its current hyper-parameters: O(k n^2), no Gram
+// of the old points, no refactorisation (append.h has the arithmetic).  V, S, L_S and z_new live in
+// the context's scratch; a grown layout is built in buffers of its own beside the old one.  The
+// fit is touched by the last kernel alone, and only when every pivot of S was positive: a failed
+// append -- not positive definite, out of memory -- leaves the handle exactly as it was.
+extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const double *y_new,
+                            int64_t k64)
+{
+    BQCHK(check_fit(c, f));
+    if (!x_new || !y_new || k64 < 1)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    BQCHK(check_dims(c, f->d, (int64_t)f->n + k64));
+    const int d = f->d, n = f->n, k = (int)k64, npad = f->npad;
+    for (int64_t i = 0; i < (int64_t)d * k; ++i)
+        if (!std::isfinite(x_new[i]))
+            return fail(c, BQ_ERR_BAD_ARG, "append: points must be finite");
+    for (int i = 0; i < k; ++i)
+        if (!std::isfinite(y_new[i]))
+            return fail(c, BQ_ERR_BAD_ARG, "append: targets must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int kp = (int)roundup(k, 64);
+    const bool small = k <= 64;
+
+    // ---- a layout that holds n + k points, in buffers of its own until the append has succeeded
+    const bool grow = n + k > npad;
+    Layout L2 = f->L;
+    long ldl2 = f->ldl;
+    DevBuf nA, npts, ny, ndinv, ndw, nalpha, npanel;
+    if (grow) {
+        L2 = make_layout(n + k, 0, true);
+        ldl2 = pick_ld(L2.ntot);
+        hipError_t e = hipSuccess;
+        auto A = [&](DevBuf &b, size_t bytes) {
+            if (e == hipSuccess)
+                e = b.alloc(bytes);
+        };
+        A(nA, sizeof(double) * (size_t)ldl2 * L2.ntot);
+        A(npts, sizeof(double) * (size_t)d * L2.ntot);
+        A(ny, sizeof(double) * (size_t)L2.npad);
+        A(ndinv, sizeof(double) * ((size_t)L2.npad + BQ_DINV_STRIDE));
+        A(npanel, sizeof(double) * sweep_route(c, L2.ntot, L2.ntot, 1).ws_doubles);
+        A(ndw, sizeof(double) * BQ_DINV_HALF * (size_t)(L2.npad / 64));
+        A(nalpha, sizeof(double) * (size_t)L2.npad);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                        "append: growing the fit to %d points failed: %s", n + k,
+                        hipGetErrorString(e));
+        }
+    }
+
+    // ---- side buffers
+    Scratch sc(c);
+    const size_t oV = sc.take((size_t)kp * npad), oS = sc.take((size_t)kp * kp),
+                 oX = sc.take((size_t)64 * kp), ox = sc.take((size_t)d * k), oy = sc.take((size_t)k),
+                 oout = sc.take(8), oinfo = sc.take(8),
+                 opart = sc.take(small ? append_part_doubles(npad) : 0),
+                 odw = sc.take(small ? 0 : BQ_DINV_HALF * (size_t)(kp / 64)),
+                 ovz = sc.take(small ? 0 : (size_t)kp);
+    BQCHK(sc.commit());
+    double *V = sc.at(oV), *S = sc.at(oS), *X = sc.at(oX), *xn = sc.at(ox), *yn = sc.at(oy),
+           *out = sc.at(oout);
+    int *info = reinterpret_cast<int *>(sc.at(oinfo));
+
+    // ---- the observations in: through the fit's mapped staging when they fit in it
+    double *hmap = nullptr;
+    if (c->solve_kcopy && f->hfit)
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hfit, 0));
+    const size_t nx = (size_t)d * k;
+    if (hmap && nx + k <= HF_NPTS) {
+        std::memcpy(f->hfit + HF_PTS, x_new, sizeof(double) * nx);
+        std::memcpy(f->hfit + HF_PTS + nx, y_new, sizeof(double) * k);
+        BQCHK(launch_copy_words2(c, xn, hmap + HF_PTS, nx, yn, hmap + HF_PTS + nx, (size_t)k));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(xn, x_new, sizeof(double) * nx, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(yn, y_new, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
+    }
+
+    // ---- V = K(x_new, x_old) L^-T: the 64-column sweep with the 16 x 16 inverses, in place (S
+    // cancels when a new point lies near old ones: enqueue_forward_rows_blk says what the wide
+    // inverses lose there).  Columns n .. npad of V stay zero: the padding is the identity.
+    BQCHK(launch_gram_cross_pad(c, d, xn, k, kp, f->pts.d(), n, npad, f->g, V, kp));
+    BQCHK(fit_dw(c, f));
+    BQCHK(enqueue_forward_rows_blk(c, V, kp, kp, f->A.d(), f->ldl, npad, f->dw.d()));
+    const double *zold = f->A.d() + f->L.yrow;
+
+    // ---- L_S and z_new.  A pivot counts as positive above the factorisation's own backward error
+    // (append.h, append_factor_kernel)
+    const double tol = 4.0 * (n + k + 1.0) * std::numeric_limits<double>::epsilon() *
+                       (f->g.c + f->g.s2);
+    long zstride = 1;
+    if (small) {
+        BQCHK(launch_append_small(c, V, npad, k, zold, f->ldl, sc.at(opart), xn, yn, d, f->g, tol, S,
+                                  X, info));
+    } else {
+        // S = K(x_new, x_new) + s^2 I (identity on its padding) - V V^T, the device Cholesky,
+        // then one more 64-column sweep for z_new = L_S^-1 (y_new - V z) as row 0 of X
+        double *vz = sc.at(ovz), *dwS = sc.at(odw);
+        BQCHK(launch_gram_sym(c, d, xn, 0, static_cast<GaussParams *>(f->gp.p), 0, S, kp, 0, k, 1));
+        if (kp > k)
+            BQCHK(launch_pad_identity(c, S, kp, k, kp));
+        BQCHK(launch_gemm(c, BQ_K_GEMM, S, kp, 0, V, kp, 0, V, 1, kp, 0, kp, kp, npad, 0, 1));
+        if (!c->dinv64.p)
+            HIPCHK(c, c->dinv64.alloc(BQ_DINV_STRIDE * sizeof(double)));
+        HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int), c->stream));
+        BQCHK(potrf_one(c, S, kp, kp, c->dinv64.d(), info));
+        BQCHK(launch_rowdot(c, V, (long)kp, k, kp, npad, zold, 0.0, vz, nullptr, f->ldl));
+        HIPCHK(c, hipMemsetAsync(X, 0, sizeof(double) * (size_t)64 * kp, c->stream));
+        BQCHK(launch_append_rhs(c, yn, vz, k, X, S, kp, tol, info));
+        BQCHK(launch_diag_winv(c, S, kp, kp, dwS));
+        BQCHK(enqueue_forward_rows_blk(c, X, 64, 64, S, kp, kp, dwS));
+        zstride = 64;
+    }
+
+    // ---- the grown layout: the old factor and its z, the identity on the new padding
+    if (grow) {
+        HIPCHK(c, hipMemcpy2DAsync(nA.p, sizeof(double) * ldl2, f->A.p, sizeof(double) * f->ldl,
+                                   sizeof(double) * npad, npad, hipMemcpyDeviceToDevice,
+                                   c->stream));
+        BQCHK(launch_append_grow(c, nA.d(), ldl2, npad, L2.ntot, L2.yrow, f->A.d(), f->ldl,
+                                 f->L.yrow, npad));
+        HIPCHK(c, hipMemsetAsync(npts.p, 0, npts.bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(ny.p, 0, ny.bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(ndinv.p, 0, ndinv.bytes, c->stream));
+        HIPCHK(c, hipMemcpyAsync(npts.p, f->pts.p, sizeof(double) * (size_t)d * n,
+                                 hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ny.p, f->y.p, sizeof(double) * n, hipMemcpyDeviceToDevice,
+                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(ndinv.p, f->dinv.p, sizeof(double) * npad,
+                                 hipMemcpyDeviceToDevice, c->stream));
+    }
+
+    // ---- the commit: the only launch that writes into the fit
+    AppendJob job{};
+    job.V = V, job.S = S, job.zn = X, job.zstride = zstride, job.xn = xn, job.yn = yn;
+    job.info = info;
+    job.A = grow ? nA.d() : f->A.d();
+    job.ldl = ldl2;
+    job.pts = grow ? npts.d() : f->pts.d();
+    job.y = grow ? ny.d() : f->y.d();
+    job.dinv = grow ? ndinv.d() : f->dinv.d();
+    job.out = out;
+    job.logdet = f->logdet, job.qf = f->qf;
+    job.d = d, job.n = n, job.k = k, job.kp = kp, job.yrow = L2.yrow;
+    BQCHK(launch_append_commit(c, job));
+    double *hm = f->hfit;
+    if (hmap)
+        BQCHK(launch_copy_words2(c, hmap, out, 6, nullptr, nullptr, 0));
+    else
+        HIPCHK(c, hipMemcpyAsync(hm, out, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int hinfo = 0;
+    std::memcpy(&hinfo, hm, sizeof hinfo);
+    if (hinfo != 0)
+        return fail(c, BQ_ERR_NOT_PD,
+                    "append: the Schur complement of the new points is not positive definite");
+
+    // ---- bookkeeping: a fit of n + k points in every respect
+    if (grow) {
+        auto take = [](DevBuf &dst, DevBuf &src) {
+            std::swap(dst.p, src.p);
+            std::swap(dst.bytes, src.bytes);
+            std::swap(dst.guard, src.guard);
+        };
+        take(f->A, nA), take(f->pts, npts), take(f->y, ny), take(f->dinv, ndinv);
+        take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
+        // everything sized by the old npad goes; the captured sweeps hold the old pointers
+        for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart})
+            b->release();
+        if (f->hvec)
+            (void)hipHostFree(f->hvec);
+        f->hvec = nullptr;
+        for (int i = 0; i < 3; ++i) {
+            if (f->vgexec[i])
+                (void)hipGraphExecDestroy(f->vgexec[i]);
+            if (f->vgraph[i])
+                (void)hipGraphDestroy(f->vgraph[i]);
+            f->vgexec[i] = nullptr;
+            f->vgraph[i] = nullptr;
+            f->vg_failed[i] = false;
+        }
+        f->L = L2;
+        f->npad = L2.npad;
+        f->ldl = ldl2;
+    }
+    f->n = n + k;
+    f->L.n = n + k;
+    f->have_alpha = false;
+    f->have_zc = false;
+    f->have_y = false;
+    f->have_wide = false;
+    f->have_dw = false;
+    f->logml = hm[2];
+    f->logdet = hm[3];
+    f->qf = hm[4];
     return BQ_OK;
 }
 

@@ -9,7 +9,8 @@
 //   k_gemm.hip   gemm.h kernels                 launch_gemm, launch_gemm_rows, launch_rows_step
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
-//   k_reduce.hip reduce.h trsv.h kernels        read-outs, single-vector sweeps, utilities
+//   k_reduce.hip reduce.h trsv.h append.h        read-outs, single-vector sweeps, utilities, the
+//                kernels                        finishing kernels of an append
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -432,6 +433,18 @@ int launch_plan_gather(bq_ctx *c, double *out, const double *scal, const int *in
 int launch_copy_words2(bq_ctx *c, void *d1, const void *s1, size_t n1, void *d2, const void *s2,
                        size_t n2);
 int flow_check(bq_ctx *c);
+// growing a resident fit by k observations (append.h): the finishing path of k <= 64, the pieces
+// of the blocked one, the one kernel that writes into the fit, the border strip of a grown layout
+size_t append_part_doubles(int npad);
+int launch_append_small(bq_ctx *c, const double *V, int npad, int k, const double *z, long zstride,
+                        double *part, const double *xn, const double *yn, int d,
+                        const GaussParams &g, double tol, double *S, double *zn,
+                        int *info);
+int launch_append_rhs(bq_ctx *c, const double *yn, const double *vz, int k, double *X,
+                      const double *S, int kp, double tol, int *info);
+int launch_append_commit(bq_ctx *c, const AppendJob &a);
+int launch_append_grow(bq_ctx *c, double *A, long lda, int r0, int ntot, int yrow,
+                       const double *Aold, long ldold, int yold, int ncopy);
 
 // ---- potrf.hip ------------------------------------------------------------------------
 int auto_nb(const bq_ctx *c, int ntot, int batch);
@@ -517,6 +530,10 @@ int enqueue_backward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mr
                           const double *L, long ldl, int npad, WideInv w);
 int solve_rows_host(bq_ctx *c, const double *L, long ldl, int n, int npad, WideInv w,
                     const double *B, int64_t nrhs, double *X);
+
+// ---- linalg.hip -----------------------------------------------------------------------
+// factor one ntot x ntot device matrix on the context's panel scratch (dinv: BQ_DINV_STRIDE)
+int potrf_one(bq_ctx *c, double *A, long lda, int ntot, double *dinv, int *info);
 
 } // namespace bqh
 

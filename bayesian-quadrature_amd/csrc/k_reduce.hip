@@ -4,6 +4,7 @@
 #include "reduce.h"
 #include "trsv.h"
 #include "trsvflow.h"
+#include "append.h"
 
 namespace bqh {
 
@@ -110,6 +111,62 @@ int launch_transpose_blocks(bq_ctx *c, const double *src, double *dst, int B, lo
 int launch_neg_sumsq(bq_ctx *c, const double *v, int n, double *out)
 {
     hipLaunchKernelGGL(neg_sumsq_kernel, dim3(1), dim3(256), 0, c->stream, v, n, out);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// ---- growing a resident fit (append.h; fit.hip, bq_gp_append) ----
+size_t append_parts(int npad) { return (size_t)((npad + BQ_APPEND_CHUNK - 1) / BQ_APPEND_CHUNK); }
+size_t append_part_doubles(int npad) { return append_parts(npad) * BQ_APPEND_PART; }
+
+// k <= 64: the partial products over V's column chunks, then the one-workgroup factor of S
+int launch_append_small(bq_ctx *c, const double *V, int npad, int k, const double *z, long zstride,
+                        double *part, const double *xn, const double *yn, int d,
+                        const GaussParams &g, double tol, double *S, double *zn,
+                        int *info)
+{
+    if (k < 1 || k > 64 || npad <= 0 || (npad & 63))
+        return fail(c, BQ_ERR_BAD_ARG, "append: 1 <= k <= 64 rows over whole 64-column blocks");
+    const int np = (int)append_parts(npad);
+    {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * 64 * npad);
+        hipLaunchKernelGGL(append_part_kernel, dim3(np), dim3(256), 0, c->stream, V, npad, k, z,
+                           zstride, part);
+        HIPCHK(c, hipGetLastError());
+    }
+    Bracket br(c, BQ_K_POTF2, (double)k * k * k / 3.0);
+    hipLaunchKernelGGL(append_factor_kernel, dim3(1), dim3(256), 0, c->stream, part, np, xn, yn, d,
+                       k, g, tol, S, zn, info);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_append_rhs(bq_ctx *c, const double *yn, const double *vz, int k, double *X,
+                      const double *S, int kp, double tol, int *info)
+{
+    hipLaunchKernelGGL(append_rhs_kernel, dim3(1), dim3(256), 0, c->stream, yn, vz, k, X, S, kp, tol,
+                       info);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_append_commit(bq_ctx *c, const AppendJob &a)
+{
+    Bracket br(c, BQ_K_REDUCE, 16.0 * a.k * (a.n + a.k));
+    const long words = (long)a.k * (a.n + a.k);
+    const int wgs = (int)std::max(1L, std::min((long)c->cus, (words + 4095) / 4096));
+    hipLaunchKernelGGL(append_commit_kernel, dim3(wgs), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_append_grow(bq_ctx *c, double *A, long lda, int r0, int ntot, int yrow,
+                       const double *Aold, long ldold, int yold, int ncopy)
+{
+    if (r0 >= ntot)
+        return BQ_OK;
+    hipLaunchKernelGGL(append_grow_kernel, dim3((ntot - r0 + 255) / 256, ntot), dim3(256), 0,
+                       c->stream, A, lda, r0, ntot, yrow, Aold, ldold, yold, ncopy);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -31,8 +31,8 @@ static int grow_panel_ws(bq_ctx *c, int ntot)
     return BQ_OK;
 }
 
-// factor one ntot x ntot matrix (bq_cho_factor, bq_potrf_dev)
-static int potrf_one(bq_ctx *c, double *A, long lda, int ntot, double *dinv, int *info)
+// factor one ntot x ntot matrix (bq_cho_factor, bq_potrf_dev, bq_gp_append)
+int bqh::potrf_one(bq_ctx *c, double *A, long lda, int ntot, double *dinv, int *info)
 {
     BQCHK(grow_panel_ws(c, ntot));
     const SweepRoute r = sweep_route(c, ntot, ntot, 1, c->panel_ws.bytes / sizeof(double));

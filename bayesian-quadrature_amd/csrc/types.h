@@ -57,6 +57,25 @@ struct GradScale {
     double f[BQ_MAXD + 2];
 };
 
+// Growing a resident fit by k observations (append.h): what append_commit_kernel reads and writes.
+struct AppendJob {
+    // side buffers
+    const double *V;    // kp x npad (ld kp): the swept rows
+    const double *S;    // kp x kp (ld kp): L_S in its lower triangle
+    const double *zn;   // z_new[i] at zn[i * zstride]
+    long zstride;
+    const double *xn;   // d x k new points
+    const double *yn;   // k new targets
+    const int *info;    // 0: every pivot of S was positive
+    // the fit (after growth: the new buffers)
+    double *A;
+    long ldl;
+    double *pts, *y, *dinv;
+    double *out;        // [info | - | logml, logdet, qf]: the words a (re)fit reads back
+    double logdet, qf;  // of the n old points
+    int d, n, k, kp, yrow;
+};
+
 // Read-out of a bordered system folded into the one-launch sweep (slab.h): the diagonal factors
 // add their share of log|K| to scal[4b + 1] as they go, and the LAST step's tiles -- the Schur
 // complement of the border -- store what finalize_kernel would read from it (no launch of its own).

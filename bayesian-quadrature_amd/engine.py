@@ -574,6 +574,21 @@ class Fit(object):
         e = self._eng
         e._check(e._lib.bq_gp_set_y(e._ctx, self._handle(), L.dptr(y)))
 
+    def append(self, x_new, y_new):
+        """Append k observations under the current hyper-parameters (bq_gp_append): O(k n^2) on
+        the resident factor, no refactorisation.  x_new is (d, k), or (k,) for d = 1; y_new is
+        (k,).  LinAlgError (the new points make the system singular) leaves the fit as it was."""
+        x_new = _pts(x_new)
+        if x_new.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        k = x_new.shape[1]
+        y_new = np.ascontiguousarray(y_new, dtype=np.float64)
+        if k < 1 or y_new.shape != (k,):
+            raise ValueError("y has invalid shape")
+        e = self._eng
+        e._check(e._lib.bq_gp_append(e._ctx, self._handle(), L.dptr(x_new), L.dptr(y_new), k))
+        self.n += k
+
     def refit_predict(self, h, w, s, xo):
         """New hyper-parameters and the posterior mean / marginal variance at xo in one sweep
         (bq_gp_refit_predict: the hyper-parameter loop's body)."""

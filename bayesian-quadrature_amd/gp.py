@@ -163,6 +163,40 @@ class GP(object):
             self._invalidate()
         self._y = val
 
+    def append(self, x, y):
+        """Add observations: observably the same as assigning the concatenated ``x`` and ``y``,
+        but a device fit whose parameters are current grows in place (engine.Fit.append, O(k n^2)
+        on the resident factor) instead of being dropped and rebuilt from nothing -- the
+        ``add_observation`` half of the active-sampling loop.  A LinAlgError (the new points make
+        Kxx singular) leaves the GP as it was."""
+        x = np.atleast_1d(np.array(x, dtype=DTYPE, copy=True))
+        y = np.atleast_1d(np.array(y, dtype=DTYPE, copy=True))
+        if x.ndim != 1:
+            raise ValueError("x must be one-dimensional")
+        if y.ndim != 1:
+            raise ValueError("y must be one-dimensional")
+        if x.shape != y.shape:
+            raise ValueError("shape mismatch for x and y")
+        if x.size == 0:
+            return
+        new_x = np.concatenate([self._x, x])
+        new_y = np.concatenate([self._y, y])
+        fit = getattr(self, "_fit", None)
+        params = (self.K.h, self.K.w, self._s)
+        if fit is not None and self._fit_params == params and hasattr(fit, "append"):
+            try:
+                fit.append(x, y)
+            except np.linalg.LinAlgError:
+                raise  # the fit and the data are what they were
+            except (ValueError, RuntimeError, MemoryError):  # the engine's error types
+                self._invalidate()
+            else:
+                self._memoized = {}
+        else:
+            self._invalidate()
+        self._x = new_x
+        self._y = new_y
+
     @property
     def s(self):
         return self._s

@@ -168,6 +168,13 @@ int bq_gp_set_y(bq_ctx *ctx, bq_fit *fit, const double *y);
  * M > 63 falls back to bq_gp_refit + bq_gp_predict. */
 int bq_gp_refit_predict(bq_ctx *ctx, bq_fit *fit, double h, const double *w, double s,
                         const double *xo, int64_t M, double *mean, double *var);
+/* Append k observations (x_new: d x k column-major points, y_new: k targets) to a resident fit
+ * under its current hyper-parameters.  Afterwards the handle is a fit of n + k points in every
+ * respect.  O(k n^2): no Gram of the old points, no refactorisation.
+ * BQ_ERR_NOT_PD: the Schur complement of the new points is not positive definite; the fit is
+ * left exactly as it was (n, factor, z, log-ML, alpha: same bits).
+ * BQ_ERR_BAD_ARG: stale fit ("refit required", as every consumer), null / k < 1 / non-finite. */
+int bq_gp_append(bq_ctx *ctx, bq_fit *fit, const double *x_new, const double *y_new, int64_t k);
 void bq_fit_destroy(bq_ctx *ctx, bq_fit *fit);
 int bq_gp_logml(bq_ctx *ctx, bq_fit *fit, double *out);
 /* gradient of the fit's log marginal likelihood with respect to its hyper-parameters:
