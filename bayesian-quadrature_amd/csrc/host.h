@@ -149,6 +149,8 @@ struct bq_ctx {
                          // (GramSeed; BQ_ASM_FUSE=0: the whole system is assembled first)
     int potf2_8w = 1;    // the one-launch steps' diagonal factor on eight waves where a step's workgroups
                          // have a CU each (BQ_POTF2_8W)
+    int slab8_rounds = 1 << 20; // ... and a slab step's 512-thread form while the step has at most this many
+                         // workgroups per CU (launch_slab_step: no limit shipped; BQ_SLAB8_ROUNDS, 0: one)
     int gemm_ksplit = 1; // eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT)
     int gemm_tile = 0;   // 64 / 128: force the LDS kernel's workgroup tile (BQ_GEMM_TILE; measurements)
     int sharing = 0;     // how the chip is shared while the launches being queued run (gemm_lds_tile):
@@ -213,7 +215,7 @@ inline unsigned long long launch_config_key(const bq_ctx *c)
 {
     const int f[] = {c->nb_override, c->lookahead, c->la_min,   c->gemm_lds,  c->fold_readout,
                      c->potf2_8w,    c->gemm_ksplit, c->gemm_tile, c->diag_first, c->df_sweep,
-                     c->df_wg,       c->df_early,   c->df_wg_rows};
+                     c->df_wg,       c->df_early,   c->df_wg_rows, c->slab8_rounds};
     unsigned long long h = 1469598103934665603ull;
     for (int v : f)
         h = (h ^ (unsigned long long)(unsigned)v) * 1099511628211ull;

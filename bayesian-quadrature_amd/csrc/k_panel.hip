@@ -138,9 +138,22 @@ int launch_panel_step(bq_ctx *c, double *A, long lda, long astride, int batch, i
                       int *info, double work)
 {
     Bracket br(c, BQ_K_GEMM, work);
-    hipLaunchKernelGGL(panel_step_kernel, dim3(nrb, 1, batch), dim3(256), 0, c->cur, A, lda,
-                       astride, Sin, Sout, lds, sstride, K0, j0, dinv_in, dinv_out,
-                       (long)BQ_DINV_STRIDE, has_next, first, SL, info);
+    // Eight waves where every workgroup of the step has a CU to itself: the second row-block
+    // solve and the next diagonal factor on waves 4-7.  Not beside a look-ahead's bulk update
+    // (sharing): eight waves of 244 VGPRs need a CU's whole register file, which no retiring
+    // workgroup of the update frees -- N = 16384 lost 2.5 us per step, 0.65 ms, to the wait.
+    // The update occupies the chip for about m^2 NB / 50 TFLOP/s and the panel's chain lasts
+    // NB / 64 x 21 us: from m = 4,000 rows down (64 row blocks) the chain out-lasts the update
+    // it sits beside, finds free CUs for most of its steps, and takes the eight waves again.
+    const bool beside_bulk = c->sharing != 0 && (long)nrb * batch > 64;
+    if (c->potf2_8w && !beside_bulk && (long)nrb * batch <= c->cus)
+        hipLaunchKernelGGL(panel_step_kernel<8>, dim3(nrb, 1, batch), dim3(512), 0, c->cur, A, lda,
+                           astride, Sin, Sout, lds, sstride, K0, j0, dinv_in, dinv_out,
+                           (long)BQ_DINV_STRIDE, has_next, first, SL, info);
+    else
+        hipLaunchKernelGGL(panel_step_kernel<4>, dim3(nrb, 1, batch), dim3(256), 0, c->cur, A, lda,
+                           astride, Sin, Sout, lds, sstride, K0, j0, dinv_in, dinv_out,
+                           (long)BQ_DINV_STRIDE, has_next, first, SL, info);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -156,6 +169,26 @@ int launch_slab_first(bq_ctx *c, double *A, long lda, long astride, int batch, d
     return BQ_OK;
 }
 
+// The most workgroups a step may have and still run in its 512-thread form, whose waves 4-7 idle
+// through a diagonal tile's update: slab8_rounds rounds of one workgroup per CU.  Shipped: no
+// limit -- us per step, 512 / 256 threads (tools/slab_step_time.py, medians of 7; LABBOOK,
+// "Wave groups of the one-launch steps"):
+//     workgroups      one matrix         5 x N = 1024      16 x N = 768
+//        ~50        16.5 / 17.2        17.1 / 18.0        18.0 / 18.7
+//        ~250       18.5 / 18.8        20.4 / 22.3        20.6 / 22.0
+//        ~280       21.8 / 22.6        22.6 / 23.8        25.9 / 28.0 (336)
+//        ~500       23.4 / 23.7        26.4 / 29.1        25.7 / 27.4
+//        ~600       26.6 / 27.7        28.2 / 30.4        30.2 / 31.6
+//        ~950       33.3 / 34.7             --            38.3 / 40.2
+//        ~2150      53.5 / 53.4             --                 --
+//        ~2550      52.6 / 52.5             --                 --
+// The 512-thread form is 0.3 - 1.4 us ahead up to 1,000 workgroups (more in a stacked batch) and
+// level from 1,700; the 3 - 4 us a step gains with every 256 workgroups are the same in both.
+static long slab8_limit(const bq_ctx *c)
+{
+    return (long)(c->slab8_rounds > 1 ? c->slab8_rounds : 1) * c->cus;
+}
+
 // one 64-column step of a small system in one launch (slab_step_kernel); out: the read-out the
 // last step stores (SlabOut); stamps: the profiling instantiation (bq_probe_c2_timeline)
 int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, double *Sin,
@@ -166,7 +199,7 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
     const int T = (ntot - j0 - 64) / 64;
     Bracket br(c, BQ_K_SYRK_SMALL, work);
     const long wgs = (long)T * (T + 1) / 2 * batch;
-    const bool w8 = c->potf2_8w && fnext && wgs <= c->cus;
+    const bool w8 = c->potf2_8w && fnext && wgs <= slab8_limit(c);
     if (stamps && w8)
         hipLaunchKernelGGL((slab_step_kernel<true, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512), 0,
                            c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
@@ -176,7 +209,7 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
                            c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
                            dinv_out, dstride, fnext, last, info, col0, stamps, out);
     else if (w8)
-        // a CU per workgroup: 512 threads, the diagonal factor on eight waves
+        // 512 threads: both row-block solves at once, the diagonal factor on eight waves
         hipLaunchKernelGGL((slab_step_kernel<false, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512),
                            0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
                            dinv_out, dstride, fnext, last, info, col0,

@@ -64,6 +64,27 @@ __device__ __forceinline__ void slab_solve16(const double (&t)[4][4], const doub
     }
 }
 
+// The A fragments of a step's solves out of the workgroup's LDS staging area: Fs holds the six
+// blocks (c, bb), c > bb, below L_jj's diagonal at 256 ((c (c - 1)) / 2 + bb), then the four
+// negated block inverses as they lie in global memory.
+__device__ __forceinline__ void slab_frags(const double *Fs, int l15, int l4, double (&la)[4][3][4],
+                                           double (&wneg)[4][4])
+{
+    const double *Ws = Fs + 6 * 256;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            wneg[c][r] = Ws[256 * c + 64 * r + l15 + 16 * l4];
+#pragma unroll
+    for (int c = 1; c < 4; ++c)
+#pragma unroll
+        for (int bb = 0; bb < c; ++bb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                la[c][bb][r] = Fs[256 * ((c * (c - 1)) / 2 + bb) + l15 + 16 * (l4 + 4 * r)];
+}
+
 // The ten lower 16 x 16 blocks (rb, cb) of a diagonal tile dealt to the four waves:
 //   wave 0: (0,0) (1,0) (1,1)   wave 1: (2,0) (2,1) (2,2)   wave 2: (3,0) (3,1)   wave 3: (3,2) (3,3)
 // Every wave issues THREE MFMAs per k-step: waves 2 and 3 repeat their second block into an
@@ -78,9 +99,10 @@ __device__ __forceinline__ void slab_solve16(const double (&t)[4][4], const doub
 
 // STAMP: a profiling instantiation (tools/c2_timeline.py) whose workgroup 0 records s_memtime
 // at its phase boundaries; the shipped launches use STAMP = false and carry no stamp code.
-// NW = 8 (launched when a step's workgroups have a CU each): 512 threads; waves 4-7 take no part
-// in the tile update -- they pass its barriers -- and in workgroup 0 join the diagonal factor as
-// its second wave per SIMD (potf2f_body<8>: the chain 16.5 k -> 13.2 k cycles).
+// NW = 8 (launch_slab_step has the rule): 512 threads; in an off-diagonal tile waves 4-7 solve the
+// Q rows while waves 0-3 solve the P rows; in a diagonal tile they pass the update's barriers,
+// and in workgroup 0 they join the diagonal factor as its second wave per SIMD (potf2f_body<8>:
+// the chain 16.5 k -> 13.2 k cycles).
 template <bool STAMP, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(double *__restrict__ A, long lda,
                                                         long astride,
@@ -129,6 +151,27 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     if (NW == 8 && wave >= 4) {
         // the barriers of the tile update below, in their order: fragments staged; Q rows
         // written; and for workgroup 0 with a next factor: Q rows read; diagonal block in LDS
+        if (bx != by) {
+            // off-diagonal tile: the Q rows (row block by) are solved HERE, beside waves 0-3's
+            // solve of the P rows -- the two are independent, and one after the other they were
+            // 2 x 3,300 cycles of every such workgroup.  Same MFMAs on the same operands in the
+            // same order as the four-wave form does them on waves 0-3.
+            const int wq = wave - 4;
+            double tq[4][4];
+            slab_load16(Sin + Cb + 16 * wq + l15 + (long)l4 * lds, lds, tq);
+            __syncthreads();
+            double la[4][3][4], wneg[4][4];
+            slab_frags(plds + 4096, l15, l4, la, wneg);
+            double4_t xq[4];
+            slab_solve16(tq, la, wneg, xq);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wq + l15] = xq[c][r];
+            __syncthreads();
+            return; // (workgroup 0 is a diagonal tile)
+        }
         __syncthreads();
         __syncthreads();
         if (blockIdx.x == 0 && factor_next) {
@@ -167,7 +210,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 wv[q] = din[64 + 256 * q + t];
-            if (bx != by)
+            if (NW == 4 && bx != by)
                 slab_load16(Sin + Cb + 16 * wave + l15 + (long)l4 * lds, lds, tq);
             slab_load16(Sin + Rb + 16 * wave + l15 + (long)l4 * lds, lds, tp);
             // C tile (negated: the MFMAs add Q P^T).  Off-diagonal tiles: rows 16 wave .. +15,
@@ -202,23 +245,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
                 Ws[256 * q + t] = -wv[q];
         }
         __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                wneg[c][r] = Ws[256 * c + 64 * r + l15 + 16 * l4];
-#pragma unroll
-        for (int c = 1; c < 4; ++c)
-#pragma unroll
-            for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    la[c][bb][r] = Fs[256 * ((c * (c - 1)) / 2 + bb) + l15 + 16 * (l4 + 4 * r)];
+        slab_frags(Fs, l15, l4, la, wneg);
     }
     BQ_SSTAMP(1, la[3][2][3] + wneg[3][3])
-    // Q rows (row block by) -> LDS; P rows (row block bx) stay in registers
+    // Q rows (row block by) -> LDS (eight waves: by waves 4-7, above); P rows (row block bx)
+    // stay in registers
     double4_t xp[4];
-    if (bx != by) {
+    if (NW == 4 && bx != by) {
         double4_t xq[4];
         slab_solve16(tq, la, wneg, xq);
 #pragma unroll
@@ -435,10 +468,14 @@ __global__ __launch_bounds__(256) void slab_first_kernel(double *__restrict__ A,
 //     ALL slabs 0 .. s of the panel (left-looking, k = 64 (s + 1): the earlier slabs' L from
 //     A, slab s from registers / LDS); the result goes to the scratch column Sout, the input
 //     of step s + 1 -- except in workgroup 0, whose rows ARE row block s + 1: its result is
-//     the next diagonal block, handed through LDS to the 4-wave potf2.
-// Nothing waits on another workgroup.  grid: ((ntot - j0 - 64) / 64, 1, batch); block 256.
+//     the next diagonal block, handed through LDS to potf2_body<NW>.
+// Nothing waits on another workgroup.  grid: ((ntot - j0 - 64) / 64, 1, batch); block 64 NW.
+// NW = 8 (launch_panel_step has the rule): waves 4-7 solve the rows of row
+// block s + 1 beside waves 0-3's solve of the workgroup's own rows, and join workgroup 0's
+// diagonal factor (potf2f_body<8>); the left-looking product stays on waves 0-3, in its k order.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void panel_step_kernel(double *__restrict__ A, long lda,
+template <int NW = 4>
+__global__ __launch_bounds__(64 * NW) void panel_step_kernel(double *__restrict__ A, long lda,
                                                          long astride,
                                                          const double *__restrict__ Sin,
                                                          double *__restrict__ Sout, long lds,
@@ -476,8 +513,19 @@ __global__ __launch_bounds__(256) void panel_step_kernel(double *__restrict__ A,
     const long ldsp = first ? lda : lds;
     if (!first && j0 - K0 == 64 && blockIdx.x == 0) {
         double *dst = A + j0 + (long)(j0 - 64) * lda;
-        for (int e = threadIdx.x; e < 4096; e += 256)
+        for (int e = threadIdx.x; e < 4096; e += 64 * NW)
             dst[(e & 63) + (long)(e >> 6) * lda] = SL[e];
+    }
+    if (NW == 8 && wave >= 4 && (!has_next || blockIdx.x == 0)) {
+        // no second row block to solve: the barriers of waves 0-3 below, in their order, and
+        // workgroup 0's diagonal factor
+        if (!has_next)
+            return;
+        __syncthreads();
+        __syncthreads();
+        __syncthreads();
+        potf2_body<8>(A + r0 + (long)r0 * lda, lda, r0, dout, info + b, plds, Ts, 64);
+        return;
     }
 
     double la[4][3][4], wneg[4][4];
@@ -498,16 +546,21 @@ __global__ __launch_bounds__(256) void panel_step_kernel(double *__restrict__ A,
                     la[c][bb][r] = L11[16 * c + (long)(16 * bb + 4 * r) * lda];
     }
     double4_t xp[4];
-    if (has_next && blockIdx.x != 0) {
+    if (has_next && blockIdx.x != 0 && (NW == 4 || wave >= 4)) {
+        const int wq = wave & 3;
         double4_t xq[4];
         double tq[4][4];
-        slab_load16(Sp + r0 + 16 * wave + l15 + (long)l4 * ldsp, ldsp, tq);
+        slab_load16(Sp + r0 + 16 * wq + l15 + (long)l4 * ldsp, ldsp, tq);
         slab_solve16(tq, la, wneg, xq);
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xq[c][r];
+                Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wq + l15] = xq[c][r];
+        if (NW == 8) {
+            __syncthreads(); // (the one in front of the slab-s product below)
+            return;
+        }
     }
     {
         double tp[4][4];
@@ -597,7 +650,7 @@ __global__ __launch_bounds__(256) void panel_step_kernel(double *__restrict__ A,
             for (int r = 0; r < 4; ++r)
                 Ts[16 * wave + l15 + 64 * (16 * cb + l4 + 4 * r)] = -acc[cb][r];
         __syncthreads();
-        potf2_body(A + r0 + (long)r0 * lda, lda, r0, dout, info + b, plds, Ts, 64);
+        potf2_body<NW>(A + r0 + (long)r0 * lda, lda, r0, dout, info + b, plds, Ts, 64);
         return;
     }
     double *Cout = Sout + Rb + 16 * wave + l15 + (long)l4 * lds;
