@@ -30,6 +30,7 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     f->have_wide = false;
     f->have_dw = false;
     f->have_y = false;
+    f->have_hess = false;
     // pinned staging: [0, 136) results, then the kernel parameters, then border points
     if (!f->hfit)
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
@@ -263,6 +264,7 @@ extern "C" int bq_gp_set_y(bq_ctx *c, bq_fit *f, const double *y)
     f->have_alpha = false;
     f->have_zc = false;
     f->have_y = false;
+    f->have_hess = false;
     HIPCHK(c, hipMemcpyAsync(f->y.p, y, sizeof(double) * f->n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // y is the caller's buffer
     return BQ_OK;
@@ -481,7 +483,8 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
         take(f->A, nA), take(f->pts, npts), take(f->y, ny), take(f->dinv, ndinv);
         take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
         // everything sized by the old npad goes; the captured sweeps hold the old pointers
-        for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart})
+        for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart,
+                          &f->hB})
             b->release();
         if (f->hvec)
             (void)hipHostFree(f->hvec);
@@ -504,6 +507,7 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
     f->have_alpha = false;
     f->have_zc = false;
     f->have_y = false;
+    f->have_hess = false;
     f->have_wide = false;
     f->have_dw = false;
     f->logml = hm[2];
@@ -532,6 +536,37 @@ extern "C" int bq_gp_logml(bq_ctx *c, bq_fit *f, double *out)
     return BQ_OK;
 }
 
+// Y = L^-T in gY (the gradient's and the Hessian's operand), built on its first use after a (re)fit
+static int fit_y(bq_ctx *c, bq_fit *f)
+{
+    if (f->have_y)
+        return BQ_OK;
+    const int npad = f->npad;
+    WideInv w;
+    BQCHK(fit_wide(c, f, w));
+    const size_t bytes = sizeof(double) * (size_t)npad * npad;
+    if (f->gY.bytes < bytes || f->gX.bytes < bytes) {
+        // both buffers or neither: a failed allocation leaves no half-made workspace for the
+        // next call to run on.  The sweep never writes Y's strict lower triangle and the
+        // product reads it in diagonal tiles: cleared once, here
+        hipError_t e = f->gY.alloc(bytes);
+        if (e == hipSuccess)
+            e = f->gX.alloc(bytes);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(f->gY.p, 0, bytes, c->stream);
+        if (e != hipSuccess) {
+            f->gY.release();
+            f->gX.release();
+            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                        "gradient workspace (2 x %zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+    }
+    BQCHK(enqueue_inverse_rows(c, f->gX.d(), f->gY.d(), f->A.d(), f->ldl, npad, w));
+    f->have_y = true;
+    f->have_hess = false; // (Kxx^-1 lived in the sweep's workspace)
+    return BQ_OK;
+}
+
 // d log p / d theta = 1/2 sum_ij G_ij dKxx_ij / d theta, G = alpha alpha^T - Kxx^-1, with
 // Kxx^-1 = Y Y^T, Y = L^-T: the triangular inverse by the forward row sweep on I (kept until the
 // next (re)fit), then one MFMA product over the lower tiles of Y Y^T seeded with alpha alpha^T whose
@@ -544,29 +579,7 @@ extern "C" int bq_gp_logml_grad(bq_ctx *c, bq_fit *f, double *grad)
     HIPCHK(c, hipSetDevice(c->device));
     const int d = f->d, npad = f->npad;
     BQCHK(fit_alpha(c, f));
-    if (!f->have_y) {
-        WideInv w;
-        BQCHK(fit_wide(c, f, w));
-        const size_t bytes = sizeof(double) * (size_t)npad * npad;
-        if (f->gY.bytes < bytes || f->gX.bytes < bytes) {
-            // both buffers or neither: a failed allocation leaves no half-made workspace for the
-            // next call to run on.  The sweep never writes Y's strict lower triangle and the
-            // product reads it in diagonal tiles: cleared once, here
-            hipError_t e = f->gY.alloc(bytes);
-            if (e == hipSuccess)
-                e = f->gX.alloc(bytes);
-            if (e == hipSuccess)
-                e = hipMemsetAsync(f->gY.p, 0, bytes, c->stream);
-            if (e != hipSuccess) {
-                f->gY.release();
-                f->gX.release();
-                return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                            "gradient workspace (2 x %zu bytes): %s", bytes, hipGetErrorString(e));
-            }
-        }
-        BQCHK(enqueue_inverse_rows(c, f->gX.d(), f->gY.d(), f->A.d(), f->ldl, npad, w));
-        f->have_y = true;
-    }
+    BQCHK(fit_y(c, f));
     const size_t np = grad_parts(npad, d);
     if (f->gpart.bytes < sizeof(double) * (np + BQ_MAXD + 2))
         HIPCHK(c, f->gpart.alloc(sizeof(double) * (np + BQ_MAXD + 2)));
@@ -585,6 +598,75 @@ extern "C" int bq_gp_logml_grad(bq_ctx *c, bq_fit *f, double *grad)
     BQCHK(launch_logml_grad(c, d, f->gY.d(), npad, gj, sc, gd));
     HIPCHK(c, hipMemcpyAsync(grad, gd, sizeof(double) * (d + 2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+
+// d^2 log p / d theta^2 in the gradient's parameter order (hess.h has the formula): Kxx^-1 = Y Y^T
+// into the sweep's idle workspace, one MFMA product Kxx^-1 dK/dw_k per length scale with the
+// derivative generated from the points, tile sums and the quadratic terms on the device; the
+// (d + 2)^2 entries are put together here from those sums.  Kept until the fit changes.
+extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
+{
+    BQCHK(check_fit(c, f));
+    if (!hess)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad, np = d + 2;
+    if (!f->have_hess) {
+        BQCHK(fit_alpha(c, f));
+        BQCHK(fit_y(c, f));
+        const size_t bytes = sizeof(double) * hess_ws_doubles(npad, d);
+        if (f->hB.bytes < bytes) {
+            f->hB.release();
+            hipError_t e = f->hB.alloc(bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                            "Hessian workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
+            }
+        }
+        HessJob hj;
+        hj.pts = f->pts.d();
+        hj.alpha = f->alpha.d();
+        hj.g = f->g;
+        for (int k = 0; k < BQ_MAXD; ++k)
+            hj.iw[k] = k < d ? 1.0 / f->w[k] : 0.0;
+        hj.n = f->n;
+        hj.npad = npad;
+        const double *sums = nullptr;
+        BQCHK(launch_logml_hess(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h, f->s,
+                                &sums));
+        const int ng = hess_ng(d), nt = hess_nt(d), nq = hess_nq(d);
+        double hs[hess_ng(BQ_MAXD) + hess_nt(BQ_MAXD) + hess_nq(BQ_MAXD)];
+        HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof(double) * (ng + nt + nq), hipMemcpyDeviceToHost,
+                                 c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const double *G = hs, *T = hs + ng, *Q = hs + ng + nt;
+        const double h = f->h, s = f->s;
+        double *H = f->hess;
+        // 1/2 sum(G o D_pq) + 1/2 tr(Ki D_p Ki D_q), upper triangle
+        for (int i = 0; i < np * np; ++i)
+            H[i] = 0.0;
+        H[0] = G[0] / (h * h) + 2.0 * T[0] / (h * h);
+        H[np - 1] = 2.0 * s * T[1] / h;
+        H[(np - 1) * np + np - 1] = G[ng - 1] + 2.0 * (s * s) * T[2];
+        for (int k = 0; k < d; ++k) {
+            H[1 + k] = G[1 + k] / h + T[3 + k] / h;
+            H[(1 + k) * np + np - 1] = s * T[3 + d + k];
+            for (int l = k; l < d; ++l)
+                H[(1 + k) * np + 1 + l] =
+                    0.5 * G[1 + d + hess_pair(d, k, l)] + 0.5 * T[3 + 2 * d + hess_pair(d, k, l)];
+        }
+        // - (D_p a)^T Ki (D_q a), and the mirror
+        for (int p = 0, o = 0; p < np; ++p)
+            for (int q = p; q < np; ++q, ++o) {
+                H[p * np + q] -= Q[o];
+                H[q * np + p] = H[p * np + q];
+            }
+        f->have_hess = true;
+    }
+    for (int i = 0; i < np * np; ++i)
+        hess[i] = f->hess[i];
     return BQ_OK;
 }
 

@@ -366,6 +366,13 @@ bool gemm_uses_lds(const bq_ctx *c, int m, int n, int k, int lower, int batch);
 size_t grad_parts(int npad, int d);
 int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob &gj,
                       const GradScale &sc, double *grad);
+// ---- k_hess.hip ----------------------------------------------------------------------
+// the log-ML Hessian's sums (hess.h) into the workspace; *sums: where they are on the device
+size_t hess_ws_doubles(int npad, int d);
+int launch_logml_hess(bq_ctx *c, int d, const double *Y, double *Ki, double *ws, const HessJob &hj,
+                      const double *y, double h, double s, const double **sums);
+
+// ---- k_gemm.hip (continued) -----------------------------------------------------------
 // C(m x n) -= P(m x k) Q(n x k)^T; see k_gemm.hip
 int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const double *P, long ldp,
                 long pstride, const double *Q, long qsj, long qsk, long qstride, int m, int n,
@@ -593,6 +600,12 @@ struct bq_fit {
     // partials and the d + 2 results
     DevBuf gY, gX, gpart;
     bool have_y = false;
+    // the log-ML Hessian (bq_gp_logml_hess): Kxx^-1 takes gX once the sweep is done with it; the d
+    // products Kxx^-1 dK/dw_k, the vectors and the partial sums (hess_ws_doubles) in hB, allocated
+    // on the first Hessian; the result until the next (re)fit, new targets or append
+    DevBuf hB;
+    bool have_hess = false;
+    double hess[(BQ_MAXD + 2) * (BQ_MAXD + 2)] = {0};
     bool have_zc = false; // wz holds z = L^-1 y contiguously (gathered from the factor's y row on
                           // the first posterior after a (re)fit: the row reductions then read one
                           // line per 8 entries instead of one per entry)

@@ -57,6 +57,29 @@ struct GradScale {
     double f[BQ_MAXD + 2];
 };
 
+// The log-ML Hessian (hess.h): what its kernels read of the fit
+struct HessJob {
+    const double *pts;   // d x n
+    const double *alpha; // npad
+    GaussParams g;
+    double iw[BQ_MAXD];  // 1 / w_k
+    int n, npad;
+};
+
+// the sums' places (D = d): [G sums | trace sums | quadratic terms]
+//   G:     S_K, S_k (d), S_kl (k <= l, row by row), S_ss
+//   trace: sum C o C, sum C o Ki, sum Ki o Ki, sum C o B_k (d), sum Ki o B_k (d), sum B_k o B_l^T (k <= l)
+//   quad:  (D_p a)^T Ki (D_q a), p <= q over the d + 2 parameters, row by row
+constexpr int hess_npair(int d) { return d * (d + 1) / 2; }
+constexpr int hess_ng(int d) { return 2 + d + hess_npair(d); }
+constexpr int hess_nt(int d) { return 3 + 2 * d + hess_npair(d); }
+constexpr int hess_nq(int d) { return hess_npair(d + 2); }
+// place of the pair (k, l), k <= l < d, in a row-by-row upper triangle
+constexpr int hess_pair(int d, int k, int l)
+{
+    return k * d - k * (k - 1) / 2 + (l - k);
+}
+
 // Growing a resident fit by k observations (append.h): what append_commit_kernel reads and writes.
 struct AppendJob {
     // side buffers

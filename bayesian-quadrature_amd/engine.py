@@ -618,6 +618,14 @@ class Fit(object):
         e._check(e._lib.bq_gp_logml_grad(e._ctx, self._handle(), L.dptr(g)))
         return g
 
+    def logml_hess(self):
+        """Hessian of the log marginal likelihood, (d + 2, d + 2), symmetric, in the order of
+        ``logml_grad``: [h, w_1 .. w_d, s] (bq_gp_logml_hess)."""
+        H = np.empty((self.d + 2, self.d + 2))
+        e = self._eng
+        e._check(e._lib.bq_gp_logml_hess(e._ctx, self._handle(), L.dptr(H)))
+        return H
+
     def _get(self, which, shape):
         out = np.empty(shape, order="F")
         e = self._eng

@@ -267,6 +267,31 @@ class GP(object):
         device fit (bq_gp_logml_grad); memoised like ``log_lh``."""
         return self._memo("dloglh_dtheta", lambda: self._device_fit().logml_grad())
 
+    @property
+    def d2loglh_dtheta2(self):
+        """Hessian of ``log_lh`` in the order of ``params``, 3 x 3 over [h, w, s], from the
+        device fit (bq_gp_logml_hess: analytic, nothing differenced); memoised like
+        ``dloglh_dtheta``."""
+        return self._memo("d2loglh_dtheta2", lambda: self._device_fit().logml_hess())
+
+    def hyper_cov(self, params):
+        """Laplace covariance of the named subset of ("h", "w", "s") at the current parameters:
+        the inverse of minus the Hessian of ``log_lh`` restricted to them, in their own units
+        and their given order.  The other parameters are held fixed, not marginalised.
+        numpy.linalg.LinAlgError when that block of -H is not positive definite: the point is not
+        a maximum over these parameters (a saddle, a ridge, or an optimum not yet reached)."""
+        names = ("h", "w", "s")
+        params = list(params)
+        if not params or any(p not in names for p in params) or len(set(params)) != len(params):
+            raise ValueError("params: a subset of %s" % (names,))
+        idx = [names.index(p) for p in params]
+        A = -self.d2loglh_dtheta2[np.ix_(idx, idx)]
+        if not np.all(np.isfinite(A)):
+            raise np.linalg.LinAlgError("the Hessian is not finite")
+        np.linalg.cholesky(A)  # LinAlgError unless positive definite
+        C = np.linalg.inv(A)
+        return 0.5 * (C + C.T)
+
     def fit_MLII(self, params, method="L-BFGS-B", ntry=10):
         """Maximise ``log_lh`` over the named subset of ("h", "w", "s") with the exact gradient
         (util.find_good_parameters with ``logpdf_grad``).

@@ -182,6 +182,15 @@ int bq_gp_logml(bq_ctx *ctx, bq_fit *fit, double *out);
  * Same status rules as bq_gp_logml (stale / not-PD / null handle).  The first call after a
  * (re)fit builds L^-T: 2 npad^2 doubles of device memory, kept with the fit. */
 int bq_gp_logml_grad(bq_ctx *ctx, bq_fit *fit, double *grad);
+/* Hessian of the fit's log marginal likelihood with respect to its hyper-parameters, in the
+ * gradient's order [h, w_1 .. w_d, s]: hess is (d + 2) x (d + 2) on the host, written in full,
+ * hess[p][q] == hess[q][p] bit for bit.  Analytic: Kxx^-1 once and one n x n x n product per
+ * length scale, nothing differenced.  Same status rules as bq_gp_logml_grad (stale / not-PD /
+ * null handle or pointer; BQ_ERR_NOMEM when the workspace cannot be allocated, with nothing
+ * half-made left behind).  The first call builds what the gradient keeps (L^-T) if it is not
+ * there, and d npad^2 doubles of device memory more, kept with the fit; the result is kept until
+ * the next (re)fit, bq_gp_set_y or bq_gp_append.  The fit itself is not disturbed. */
+int bq_gp_logml_hess(bq_ctx *ctx, bq_fit *fit, double *hess);
 /* which: 0 = L (n x n, strict upper zeroed), 1 = alpha = Kxx^-1 y (n),
  * 2 = z = L^-1 y (n), 3 = Kxx (n x n, recomputed) */
 int bq_gp_get(bq_ctx *ctx, bq_fit *fit, int which, double *out_host);
