@@ -124,6 +124,7 @@ PROBE_SIGNATURES = {
     "bq_probe_mfma_layout": (C.c_int, [_vp, _dp]),
     "bq_probe_panel_solve": (C.c_int, [_vp, _i64, _i64, _i64, _dp, _dp, C.c_int, _i64, _dp]),
     "bq_probe_potrf_batch": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _dp, _i32p, _i32p]),
+    "bq_probe_sweep": (C.c_int, [_vp, C.c_int, _i64, _dp, _i64, _i64, _i64, _dp, _i32p]),
 }
 
 _lib = None

@@ -519,6 +519,24 @@ inline size_t wide_alloc_doubles(int npad)
     return 5 * wide_doubles(npad) + B * B;
 }
 WideInv wide_views(const double *base, int npad);
+// How a row sweep over a resident factor goes out, decided in ONE place each (sweeps.hip): the kind
+// of the whole sweep (rows_route) and the form of a fused step's update (rows_update).  The sweeps
+// ask these and report what they ran (bq_probe_sweep passes it on).
+struct RowsRoute {
+    // Step: one rows_step_kernel launch per block, split-k tiles (small systems, forward);
+    // Fused: one launch per block, the update in LDS-staged or split-k tiles (rows_fused_kernel);
+    // Gemm: two gemm_rows products per block (what neither takes, and every small backward sweep)
+    enum Kind { Step, Fused, Gemm } kind;
+    int B;        // columns per step (wide_block)
+    int n_lds;    // Fused: steps whose update went out as 64 x 64 LDS-staged tiles ...
+    int n_splitk; // ... and as 32 x 32 split-k tiles
+};
+enum class RowsUpdate { None, Lds, SplitK };
+// tri: the triangular inverse (enqueue_inverse_rows: mrows = npad, forward)
+RowsRoute rows_route(const bq_ctx *c, bool forward, int mrows, int npad, long ldl,
+                     bool tri = false);
+// the update of a fused step: mrows x nu entries, bp columns of the block solved one step earlier
+RowsUpdate rows_update(bool forward, int mrows, int nu, int bp);
 int compute_wide_inverses(bq_ctx *c, const double *L, long ldl, int npad, const double *dw,
                           double *nr);
 // ws: trsv_flow_ws_doubles(npad, w.B) doubles for the one-launch form (nullptr: a launch per block)
@@ -532,11 +550,12 @@ int enqueue_forward_rows_blk(bq_ctx *c, double *X, long ldx, int mrows, const do
 // block are still unit vectors and sit out (N^3 / 3 flops); Y's strict lower triangle is not
 // written (the caller clears it once)
 int enqueue_inverse_rows(bq_ctx *c, double *X, double *Y, const double *L, long ldl, int npad,
-                         WideInv w);
+                         WideInv w, RowsRoute *ran = nullptr);
+// ran: the route the sweep took (rows_route, and the fused steps' update forms)
 int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
-                         const double *L, long ldl, int npad, WideInv w);
+                         const double *L, long ldl, int npad, WideInv w, RowsRoute *ran = nullptr);
 int enqueue_backward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
-                          const double *L, long ldl, int npad, WideInv w);
+                          const double *L, long ldl, int npad, WideInv w, RowsRoute *ran = nullptr);
 int solve_rows_host(bq_ctx *c, const double *L, long ldl, int n, int npad, WideInv w,
                     const double *B, int64_t nrhs, double *X);
 

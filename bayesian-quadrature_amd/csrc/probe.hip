@@ -503,6 +503,119 @@ extern "C" int bq_probe_potrf_batch(bq_ctx *c, int64_t batch, int64_t ntot, int6
     return BQ_OK;
 }
 
+// ONE sweep over a resident factor on the caller's own factor and right-hand sides (a fit takes
+// points, bq_cho_solve always runs both sweeps): L (n x n host, column-major, lower) goes up with
+// leading dimension ldl, the 16 x 16 and the wide inverses are built as bq_cho_solve builds them,
+// the sweep `which` runs on X (right-hand sides as ROWS, X[r + j ldx]) and the whole ldx x n buffer
+// comes back.  route: what the sweep reported it ran (RowsRoute), not a second opinion.
+extern "C" int bq_probe_sweep(bq_ctx *c, int which, int64_t n, const double *L, int64_t ldl,
+                              int64_t mrows, int64_t ldx, double *X, int32_t *route)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (!L || !X || !route)
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: null pointer");
+    if (which < BQ_SWEEP_FORWARD_ROWS || which > BQ_SWEEP_BACKWARD_VEC_FLOW)
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: which must be 0 .. %d", BQ_SWEEP_BACKWARD_VEC_FLOW);
+    if (n < 64 || n > 65536 || (n & 63))
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: n must be a multiple of 64 in [64, 65536]");
+    if (ldl == 0)
+        ldl = pick_ld(n);
+    if (ldl < n)
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: ldl >= n (0: the engine's own)");
+    const bool vec = which >= BQ_SWEEP_FORWARD_VEC, flow = which >= BQ_SWEEP_FORWARD_VEC_FLOW;
+    const bool inverse = which == BQ_SWEEP_INVERSE_ROWS;
+    if (vec ? mrows != 1 : (mrows < 32 || (mrows & 31) || mrows > 65536))
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: mrows a multiple of 32 (single-vector sweeps: 1)");
+    if (ldx < mrows || ldx > 65536)
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: ldx >= mrows");
+    if (inverse && (mrows != n || ldx != n))
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: the triangular inverse has mrows = ldx = n");
+    const int npad = (int)n, B = wide_block(npad);
+    if (flow && !trsv_flow_ok(c, npad, B))
+        return fail(c, BQ_ERR_BAD_ARG, "sweep: no one-launch single-vector sweep at n = %d", npad);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf A, dw, wide;
+    HIPCHK(c, A.alloc(sizeof(double) * (size_t)ldl * npad));
+    HIPCHK(c, dw.alloc(sizeof(double) * BQ_DINV_HALF * (size_t)(npad / 64)));
+    HIPCHK(c, wide.alloc(sizeof(double) * wide_alloc_doubles(npad)));
+    HIPCHK(c, hipMemsetAsync(A.p, 0, A.bytes, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(A.p, sizeof(double) * ldl, L, sizeof(double) * n, sizeof(double) * n,
+                               n, hipMemcpyHostToDevice, c->stream));
+    BQCHK(launch_diag_winv(c, A.d(), ldl, npad, dw.d()));
+    BQCHK(compute_wide_inverses(c, A.d(), ldl, npad, dw.d(), wide.d()));
+    const WideInv w = wide_views(wide.d(), npad);
+    RowsRoute ran{RowsRoute::Gemm, B, 0, 0};
+    int kind = -1;
+    if (vec) {
+        // the vector is row 0 of X: X[j ldx]
+        std::vector<double> h((size_t)npad);
+        for (int j = 0; j < npad; ++j)
+            h[(size_t)j] = X[(size_t)j * ldx];
+        DevBuf Xd;
+        HIPCHK(c, Xd.alloc(sizeof(double) *
+                           (2 * (size_t)npad + (flow ? trsv_flow_ws_doubles(npad, B) : 0))));
+        double *x = Xd.d(), *y = Xd.d() + npad, *fw = flow ? Xd.d() + 2 * (size_t)npad : nullptr;
+        const bool forward = which == BQ_SWEEP_FORWARD_VEC || which == BQ_SWEEP_FORWARD_VEC_FLOW;
+        // (as bq_cho_solve: a timed-out hand-off re-issues the sweep on the per-block kernels)
+        BQCHK(with_flow_fallback(c, [&]() -> int {
+            HIPCHK(c, hipMemsetAsync(Xd.p, 0, sizeof(double) * 2 * (size_t)npad, c->stream));
+            HIPCHK(c, hipMemcpyAsync(x, h.data(), sizeof(double) * npad, hipMemcpyHostToDevice,
+                                     c->stream));
+            if (forward)
+                BQCHK(enqueue_forward_vec(c, x, y, A.d(), ldl, npad, w, fw));
+            else
+                BQCHK(enqueue_backward_vec(c, x, y, A.d(), ldl, npad, w, fw));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            return BQ_OK;
+        }));
+        HIPCHK(c, hipMemcpy(h.data(), y, sizeof(double) * npad, hipMemcpyDeviceToHost));
+        for (int j = 0; j < npad; ++j)
+            X[(size_t)j * ldx] = h[(size_t)j];
+        kind = flow ? BQ_SWEEP_KIND_VEC_FLOW : BQ_SWEEP_KIND_VEC_BLOCK;
+    } else {
+        // both buffers start as the caller's: whichever holds the result, its rows mrows .. ldx - 1
+        // are the caller's bits unless a kernel wrote them
+        DevBuf X1, X2;
+        const size_t xbytes = sizeof(double) * (size_t)ldx * npad;
+        HIPCHK(c, X1.alloc(xbytes));
+        HIPCHK(c, X2.alloc(xbytes));
+        double *res = X2.d();
+        if (inverse) {
+            // (Y's strict lower triangle is not written: cleared as fit_y clears it)
+            HIPCHK(c, hipMemsetAsync(X2.p, 0, xbytes, c->stream));
+            BQCHK(enqueue_inverse_rows(c, X1.d(), X2.d(), A.d(), ldl, npad, w, &ran));
+            kind = (int)ran.kind;
+        } else {
+            HIPCHK(c, hipMemcpyAsync(X1.p, X, xbytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(X2.p, X, xbytes, hipMemcpyHostToDevice, c->stream));
+            if (which == BQ_SWEEP_FORWARD_ROWS) {
+                BQCHK(enqueue_forward_rows(c, X1.d(), X2.d(), ldx, (int)mrows, A.d(), ldl, npad, w,
+                                           &ran));
+                kind = (int)ran.kind;
+            } else if (which == BQ_SWEEP_BACKWARD_ROWS) {
+                BQCHK(enqueue_backward_rows(c, X1.d(), X2.d(), ldx, (int)mrows, A.d(), ldl, npad, w,
+                                            &ran));
+                kind = (int)ran.kind;
+            } else {
+                BQCHK(enqueue_forward_rows_blk(c, X1.d(), ldx, (int)mrows, A.d(), ldl, npad,
+                                               dw.d()));
+                res = X1.d();
+                ran.B = 64;
+                kind = BQ_SWEEP_KIND_BLK;
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(X, res, xbytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    route[0] = kind;
+    route[1] = ran.B;
+    route[2] = ran.n_lds;
+    route[3] = ran.n_splitk;
+    route[4] = (int32_t)c->n_flow_fallback;
+    return BQ_OK;
+}
+
 // One eager (not graph-replayed) pass of a plan with the profiling instantiation of the slab
 // step: stamps[160 * step + k] = s_memtime of workgroup 0 at (0) entry, (1) factor fragments
 // loaded, (2) panel rows solved, (3) tile loaded + Q in LDS, (4) tile updated, (5..9) the

@@ -163,17 +163,61 @@ int enqueue_forward_rows_blk(bq_ctx *c, double *X, long ldx, int mrows, const do
     return BQ_OK;
 }
 
-// whether the one-launch steps of rows_step_kernel (32 x 32 split-k tiles for everything) serve
-// a row sweep: systems too small to give 64 x 64 LDS-staged tiles half a chip of workgroups
-static bool rows_small(const bq_ctx *c, int mrows, int npad, const WideInv &w)
+// the gemm_rows products accumulate into Xout: its mrows x npad entries start at zero (rows
+// mrows .. ldx - 1 are not the sweep's)
+static int clear_rows(bq_ctx *c, double *Xout, long ldx, int mrows, int npad)
 {
+    if (ldx == mrows)
+        HIPCHK(c, hipMemsetAsync(Xout, 0, sizeof(double) * (size_t)ldx * npad, c->cur));
+    else
+        HIPCHK(c, hipMemset2DAsync(Xout, sizeof(double) * ldx, 0, sizeof(double) * mrows, npad,
+                                   c->cur));
+    return BQ_OK;
+}
+
+// The route of a row sweep (host.h), decided here and nowhere else.  Step: the one-launch steps of
+// rows_step_kernel (32 x 32 split-k tiles for everything) serve systems too small to give 64 x 64
+// LDS-staged tiles half a chip of workgroups -- forward only; the backward sweep of such a system
+// goes out as gemm_rows products, whose small form is the same split-k tile.  Fused: whole 64-row
+// tiles and an even ldl (the LDS-DMA moves 16 bytes).  tri (the triangular inverse) is fused
+// whatever its size.
+RowsRoute rows_route(const bq_ctx *c, bool forward, int mrows, int npad, long ldl, bool tri)
+{
+    const int B = wide_block(npad);
     // (below 2048 rows the split-k tiles stay ahead: the posterior at 1000 points over N = 1024
     // took 77 us with them, 90 us with the fused large-system steps -- round 3, 256-column steps;
     // 66 us with round 5's 512-column steps)
-    return (mrows % 32) == 0 && (w.B % 64) == 0 &&
-           (long)(mrows / 32) * (npad / 32) <= 4L * c->cus &&
-           ((mrows % 64) != 0 || npad < 2048 ||
-            (long)(mrows / 64) * (npad / 64) < c->cus / 2);
+    const bool small = (mrows % 32) == 0 && (B % 64) == 0 &&
+                       (long)(mrows / 32) * (npad / 32) <= 4L * c->cus &&
+                       ((mrows % 64) != 0 || npad < 2048 ||
+                        (long)(mrows / 64) * (npad / 64) < c->cus / 2);
+    const bool fusable = (B % 64) == 0 && (ldl & 1) == 0;
+    RowsRoute r{RowsRoute::Gemm, B, 0, 0};
+    if (tri && fusable)
+        r.kind = RowsRoute::Fused;
+    else if (forward && small)
+        r.kind = RowsRoute::Step;
+    else if (!small && (mrows % 64) == 0 && fusable)
+        r.kind = RowsRoute::Fused;
+    return r;
+}
+
+// The form of a fused step's update, C (mrows x nu) -= Y_Jp (mrows x bp) Q^T.  The last steps'
+// updates are few 64 x 64 tiles of one k loop each (22 us however few): there the update goes out
+// as 32 x 32 split-k tiles too (rows_step_kernel), a quarter of a tile's k loop per wave.  The
+// threshold: from how many LDS tiles down in the forward sweep; the backward sweep's Q is strided
+// across a tile's columns there and gains only from a quarter of that on (N = 4096, 256 rows, step
+// times in us, forward 30 26 26 25 17 -> 29 23 21 17 16, backward 28 26 26 25 19 -> 28 26 26 19
+// 19; docs/LABBOOK.md, round 5 item 5).
+RowsUpdate rows_update(bool forward, int mrows, int nu, int bp)
+{
+    const long kRowsTail = forward ? 128 : 128 / 4;
+    if (bp <= 0 || nu <= 0)
+        return RowsUpdate::None; // the first step, and the last one's empty remainder
+    const long lds_tiles = (long)(mrows / 64) * (nu / 64);
+    if (lds_tiles <= kRowsTail && (mrows % 32) == 0 && (nu % 32) == 0 && (bp % 16) == 0)
+        return RowsUpdate::SplitK;
+    return RowsUpdate::Lds;
 }
 
 // A large system's sweep, one launch per step (rows_fused_kernel).  With T_J = W_J L[J, J-B]
@@ -186,7 +230,8 @@ static bool rows_small(const bq_ctx *c, int mrows, int npad, const WideInv &w)
 // tri (forward only): Xin = I, and row r enters at the step that holds column r -- rows at or
 // beyond J + bJ are still unit vectors with nothing to subtract (the triangular inverse)
 static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long ldx, int mrows_all,
-                      const double *L, long ldl, int npad, const WideInv &w, bool tri = false)
+                      const double *L, long ldl, int npad, const WideInv &w, RowsRoute &ran,
+                      bool tri = false)
 {
     const int last = (npad - 1) / w.B * w.B;
     for (int step = 0; step * w.B < npad; ++step) {
@@ -230,16 +275,10 @@ static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long l
                 Qu = L + Jp;
             }
         }
-        // The last steps' updates are few 64 x 64 tiles of one k loop each (22 us however few):
-        // there the update goes out as 32 x 32 split-k tiles too (rows_step_kernel), a quarter of
-        // a tile's k loop per wave.  kRowsTail: from how many LDS tiles down in the forward sweep;
-        // the backward sweep's Q is strided across a tile's columns there and gains only from a
-        // quarter of that on (N = 4096, 256 rows, step times in us, forward 30 26 26 25 17 -> 29 23
-        // 21 17 16, backward 28 26 26 25 19 -> 28 26 26 19 19; docs/LABBOOK.md, round 5 item 5).
-        constexpr long kRowsTail = 128;
-        const long lds_tiles = (long)(mrows / 64) * (nu / 64);
-        if (!first && nu > 0 && lds_tiles <= (forward ? kRowsTail : kRowsTail / 4) &&
-            (mrows % 32) == 0 && (nu % 32) == 0 && (bp % 16) == 0) {
+        const RowsUpdate upd = rows_update(forward, mrows, nu, bp);
+        ran.n_lds += upd == RowsUpdate::Lds;
+        ran.n_splitk += upd == RowsUpdate::SplitK;
+        if (upd == RowsUpdate::SplitK) {
             RowsJob b = a;
             b.C = Cu;
             b.P1 = Pu;
@@ -263,20 +302,26 @@ static int rows_fused(bq_ctx *c, bool forward, double *Xin, double *Xout, long l
 }
 
 int enqueue_inverse_rows(bq_ctx *c, double *X, double *Y, const double *L, long ldl, int npad,
-                         WideInv w)
+                         WideInv w, RowsRoute *ran)
 {
     BQCHK(launch_pad_identity(c, X, npad, 0, npad)); // X = I (the last call left partial sums)
-    if ((w.B % 64) == 0 && (ldl & 1) == 0)
-        return rows_fused(c, true, X, Y, npad, npad, L, ldl, npad, w, true);
-    return enqueue_forward_rows(c, X, Y, npad, npad, L, ldl, npad, w);
+    RowsRoute mine, &r = ran ? *ran : mine;
+    r = rows_route(c, true, npad, npad, ldl, true);
+    if (r.kind != RowsRoute::Fused)
+        return enqueue_forward_rows(c, X, Y, npad, npad, L, ldl, npad, w, ran);
+    return rows_fused(c, true, X, Y, npad, npad, L, ldl, npad, w, r, true);
 }
 
 // Xout <- Xin L^-T; Xin is overwritten with partial sums
 int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
-                         const double *L, long ldl, int npad, WideInv w)
+                         const double *L, long ldl, int npad, WideInv w, RowsRoute *ran)
 {
+    RowsRoute mine, &r = ran ? *ran : mine;
+    r = rows_route(c, true, mrows, npad, ldl);
+    if (r.kind == RowsRoute::Fused)
+        return rows_fused(c, true, Xin, Xout, ldx, mrows, L, ldl, npad, w, r);
     // small systems: one launch per step (rows_step_kernel), every entry of Xout written
-    if (rows_small(c, mrows, npad, w)) {
+    if (r.kind == RowsRoute::Step) {
         for (int J = 0; J < npad; J += w.B) {
             const int bJ = std::min(w.B, npad - J), rest = npad - J - bJ;
             RowsJob a{}, b{};
@@ -337,9 +382,7 @@ int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mro
         }
         return BQ_OK;
     }
-    if ((mrows % 64) == 0 && (w.B % 64) == 0 && (ldl & 1) == 0)
-        return rows_fused(c, true, Xin, Xout, ldx, mrows, L, ldl, npad, w);
-    HIPCHK(c, hipMemsetAsync(Xout, 0, sizeof(double) * (size_t)ldx * npad, c->cur));
+    BQCHK(clear_rows(c, Xout, ldx, mrows, npad));
     for (int J = 0; J < npad; J += w.B) {
         const int bJ = std::min(w.B, npad - J);
         // (NR[k, j] read through its transposed copy: unit stride across the output columns)
@@ -356,11 +399,13 @@ int enqueue_forward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mro
 
 // Xout <- Xin L^-1 (the L^T sweep of dpotrs in row form); Xin is overwritten
 int enqueue_backward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mrows,
-                          const double *L, long ldl, int npad, WideInv w)
+                          const double *L, long ldl, int npad, WideInv w, RowsRoute *ran)
 {
-    if (!rows_small(c, mrows, npad, w) && (mrows % 64) == 0 && (w.B % 64) == 0 && (ldl & 1) == 0)
-        return rows_fused(c, false, Xin, Xout, ldx, mrows, L, ldl, npad, w);
-    HIPCHK(c, hipMemsetAsync(Xout, 0, sizeof(double) * (size_t)ldx * npad, c->cur));
+    RowsRoute mine, &r = ran ? *ran : mine;
+    r = rows_route(c, false, mrows, npad, ldl);
+    if (r.kind == RowsRoute::Fused)
+        return rows_fused(c, false, Xin, Xout, ldx, mrows, L, ldl, npad, w, r);
+    BQCHK(clear_rows(c, Xout, ldx, mrows, npad));
     const int last = (npad - 1) / w.B * w.B;
     for (int J = last; J >= 0; J -= w.B) {
         const int bJ = std::min(w.B, npad - J);

@@ -500,6 +500,31 @@ class Engine(object):
             route.ctypes.data_as(L._i32p)))
         return info, (self.SWEEP_KINDS[route[0]], int(route[1]), bool(route[2]))
 
+    SWEEPS = ("forward_rows", "backward_rows", "forward_rows_blk", "inverse_rows", "forward_vec",
+              "backward_vec", "forward_vec_flow", "backward_vec_flow")
+    ROWS_KINDS = ("step", "fused", "gemm_rows", "blk", "vec_block", "vec_flow")
+
+    def probe_sweep(self, which, Lfac, X, mrows=None, ldl=0):
+        """ONE sweep over a resident factor on the caller's factor (bq_probe_sweep).  Lfac: n x n
+        lower factor, n a multiple of 64; X: the right-hand sides as rows, a Fortran-ordered
+        (ldx, n) float64 array whose first mrows rows (default: all) are solved in place, the others
+        only travel; ldl: the factor's leading dimension on the device (0: the engine's own).
+        Returns the route: {"kind", "B", "lds", "splitk", "flow_fallbacks"}."""
+        e = self.probe_engine()
+        Lf = L.f64(Lfac)
+        n = Lf.shape[0]
+        if Lf.shape != (n, n):
+            raise ValueError("Lfac must be square")
+        if X.dtype != np.float64 or X.ndim != 2 or not X.flags.f_contiguous or X.shape[1] != n:
+            raise ValueError("X must be a Fortran-ordered float64 (ldx, n) array")
+        ldx = X.shape[0]
+        route = np.full(5, -1, dtype=np.int32)
+        e._check(e._lib.bq_probe_sweep(
+            e._ctx, self.SWEEPS.index(which), n, L.dptr(Lf), int(ldl),
+            int(ldx if mrows is None else mrows), ldx, L.dptr(X), route.ctypes.data_as(L._i32p)))
+        return {"kind": self.ROWS_KINDS[route[0]], "B": int(route[1]), "lds": int(route[2]),
+                "splitk": int(route[3]), "flow_fallbacks": int(route[4])}
+
     @staticmethod
     def plan_ld(ntot):
         """Leading dimension of a plan's ntot-row systems (csrc/host.h, pick_ld)."""

@@ -89,6 +89,48 @@ int bq_probe_panel_solve(bq_ctx *ctx, int64_t m, int64_t kb, int64_t batch, cons
  * (tests/test_cholesky_contracts.py) */
 int bq_probe_potrf_batch(bq_ctx *ctx, int64_t batch, int64_t ntot, int64_t ncols, int64_t lda,
                          int64_t astride, double *A, int32_t *info, int32_t *route);
+/* ONE triangular sweep over a resident factor on the caller's own factor and right-hand sides
+ * (csrc/sweeps.hip; bq_cho_solve always runs a forward and a backward sweep, a fit takes points).
+ * L: n x n lower factor (host, column-major, ld n), uploaded with leading dimension ldl (0: the
+ * engine's own; >= n, may be odd); the 16 x 16 and the wide block inverses are built from it as
+ * bq_cho_solve builds them.  X: the right-hand sides as ROWS, X[r + j ldx], mrows x n, in and out;
+ * the whole ldx x n buffer is uploaded and downloaded, rows mrows .. ldx - 1 must come back as they
+ * went.  which:
+ *   BQ_SWEEP_FORWARD_ROWS       X <- X L^-T (enqueue_forward_rows)
+ *   BQ_SWEEP_BACKWARD_ROWS      X <- X L^-1 (enqueue_backward_rows)
+ *   BQ_SWEEP_FORWARD_ROWS_BLK   X <- X L^-T in 64-column steps from the 16 x 16 inverses
+ *   BQ_SWEEP_INVERSE_ROWS       X <- L^-T, its strict lower triangle zero (X ignored on input;
+ *                               mrows = ldx = n)
+ *   BQ_SWEEP_FORWARD_VEC / BQ_SWEEP_BACKWARD_VEC             one vector (mrows = 1: X[j ldx]),
+ *                               x <- L^-1 x / L^-T x, one launch per block column
+ *   BQ_SWEEP_FORWARD_VEC_FLOW / BQ_SWEEP_BACKWARD_VEC_FLOW   the same as one launch, with
+ *                               bq_cho_solve's fall-back; BQ_ERR_BAD_ARG where the engine has no
+ *                               one-launch sweep for n
+ * route[0..4]: the kind that ran (BQ_SWEEP_KIND_*), the columns per step, the fused steps whose
+ * update went out as LDS-staged tiles and as split-k tiles, and the context's count of one-launch
+ * sweeps re-issued after a timed-out hand-off.  n a multiple of 64, mrows a multiple of 32 (1 for
+ * the single-vector sweeps), ldx >= mrows, ldl >= n; anything else is BQ_ERR_BAD_ARG.
+ * (tests/test_sweep_contracts.py) */
+enum {
+    BQ_SWEEP_FORWARD_ROWS = 0,
+    BQ_SWEEP_BACKWARD_ROWS = 1,
+    BQ_SWEEP_FORWARD_ROWS_BLK = 2,
+    BQ_SWEEP_INVERSE_ROWS = 3,
+    BQ_SWEEP_FORWARD_VEC = 4,
+    BQ_SWEEP_BACKWARD_VEC = 5,
+    BQ_SWEEP_FORWARD_VEC_FLOW = 6,
+    BQ_SWEEP_BACKWARD_VEC_FLOW = 7
+};
+enum {
+    BQ_SWEEP_KIND_STEP = 0,      /* one split-k launch per block (small systems, forward) */
+    BQ_SWEEP_KIND_FUSED = 1,     /* one launch per block, solve and update side by side */
+    BQ_SWEEP_KIND_GEMM_ROWS = 2, /* two products per block */
+    BQ_SWEEP_KIND_BLK = 3,
+    BQ_SWEEP_KIND_VEC_BLOCK = 4,
+    BQ_SWEEP_KIND_VEC_FLOW = 5
+};
+int bq_probe_sweep(bq_ctx *ctx, int which, int64_t n, const double *L, int64_t ldl, int64_t mrows,
+                   int64_t ldx, double *X, int32_t *route);
 /* dump of the f64 MFMA D-register layout: out[64*4] receives, for lane l and
  * register r, the value row*16+col of the D element it holds */
 int bq_probe_mfma_layout(bq_ctx *ctx, double *out256);
