@@ -417,7 +417,12 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
         BQCHK(launch_gram_sym(c, d, xn, 0, static_cast<GaussParams *>(f->gp.p), 0, S, kp, 0, k, 1));
         if (kp > k)
             BQCHK(launch_pad_identity(c, S, kp, k, kp));
-        BQCHK(launch_gemm(c, BQ_K_GEMM, S, kp, 0, V, kp, 0, V, 1, kp, 0, kp, kp, npad, 0, 1));
+        GemmJob vvt;
+        vvt.C = S, vvt.ldc = kp;
+        vvt.P = V, vvt.ldp = kp;
+        vvt.Q = V, vvt.qsj = 1, vvt.qsk = kp;
+        vvt.m = kp, vvt.n = kp, vvt.k = npad;
+        BQCHK(launch_gemm(c, BQ_K_GEMM, vvt));
         if (!c->dinv64.p)
             HIPCHK(c, c->dinv64.alloc(BQ_DINV_STRIDE * sizeof(double)));
         HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int), c->stream));
@@ -803,8 +808,12 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
             HIPCHK(c, hipMemcpyAsync(gd.p, &g0, sizeof g0, hipMemcpyHostToDevice, c->stream));
             BQCHK(launch_gram_sym(c, d, xod.d(), 0, static_cast<GaussParams *>(gd.p), 0, Cd.d(),
                                   Mp, 0, (int)M, 1));
-            BQCHK(launch_gemm(c, BQ_K_GEMM, Cd.d(), Mp, 0, V.d(), Mp, 0, V.d(), 1, Mp, 0, Mp, Mp,
-                              npad, 0, 1));
+            GemmJob vvt;
+            vvt.C = Cd.d(), vvt.ldc = Mp;
+            vvt.P = V.d(), vvt.ldp = Mp;
+            vvt.Q = V.d(), vvt.qsj = 1, vvt.qsk = Mp;
+            vvt.m = Mp, vvt.n = Mp, vvt.k = npad;
+            BQCHK(launch_gemm(c, BQ_K_GEMM, vvt));
             HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(double) * M, Cd.p, sizeof(double) * Mp,
                                        sizeof(double) * M, M, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream)); // Cd goes out of scope

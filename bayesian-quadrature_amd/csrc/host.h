@@ -153,7 +153,7 @@ struct bq_ctx {
                          // workgroups per CU (launch_slab_step: no limit shipped; BQ_SLAB8_ROUNDS, 0: one)
     int gemm_ksplit = 1; // eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT)
     int gemm_tile = 0;   // 64 / 128: force the LDS kernel's workgroup tile (BQ_GEMM_TILE; measurements)
-    int sharing = 0;     // how the chip is shared while the launches being queued run (gemm_lds_tile):
+    int sharing = 0;     // how the chip is shared while the launches being queued run (gemm_route):
                          // 0 alone, 1 the two streams of a look-ahead, 2 the two halves of a batch
     int use_graph = 1;   // replay plans from a captured hipGraph (BQ_GRAPH=0 disables)
     bool own_stream = false;
@@ -361,8 +361,8 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
 
 // ---- k_gemm.hip -----------------------------------------------------------------------
 int gemm_init(bq_ctx *c); // function attributes of the LDS-staged kernels, once per context
-bool gemm_uses_lds(const bq_ctx *c, int m, int n, int k, int lower, int batch);
 // the log-ML gradient's product and finalize (gemm_lds_grad_kernel, grad_finalize_kernel)
+int grad_tile(const bq_ctx *c, int npad); // 128 / 64: its workgroup tile (the Hessian's follows it)
 size_t grad_parts(int npad, int d);
 int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob &gj,
                       const GradScale &sc, double *grad);
@@ -373,12 +373,45 @@ int launch_logml_hess(bq_ctx *c, int d, const double *Y, double *Ki, double *ws,
                       const double *y, double h, double s, const double **sums);
 
 // ---- k_gemm.hip (continued) -----------------------------------------------------------
-// C(m x n) -= P(m x k) Q(n x k)^T; see k_gemm.hip
-int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const double *P, long ldp,
-                long pstride, const double *Q, long qsj, long qsk, long qstride, int m, int n,
-                int k, int lower, int batch, int fuse_j0 = -1, double *dinv = nullptr,
-                long dstride = 0, int *info = nullptr, int ccut = 0,
-                const GramSeed *seed = nullptr);
+// One product C(m x n) -= P(m x k) Q(n x k)^T per batch element, as operands and a shape.
+struct GemmJob {
+    double *C = nullptr;
+    long ldc = 0, cstride = 0;
+    const double *P = nullptr;
+    long ldp = 0, pstride = 0;
+    const double *Q = nullptr; // Q(j, k) at Q[j qsj + k qsk]
+    long qsj = 0, qsk = 0, qstride = 0;
+    int m = 0, n = 0, k = 0;
+    int lower = 0; // only the lower trapezoid of C is needed
+    int batch = 1;
+    int ccut = 0;  // > 0: columns >= ccut of C need no update (honoured by the LDS-staged kernels)
+    const GramSeed *seed = nullptr; // C was left out of the assembly: compute it from the points
+    // request: also factor the leading 64 x 64 block of C (global column j0) in the same launch;
+    // dinv / info as for launch_potf2.  Whether the launch carried it: GemmRoute::fused
+    struct Fuse {
+        int j0 = -1;
+        double *dinv = nullptr;
+        long dstride = 0;
+        int *info = nullptr;
+    } fuse;
+    bool rows = false; // a sweep's product (one matrix, few rows, a long k): split-k tiles allowed
+};
+// Which kernel takes a product, decided in ONE place (gemm_route, k_gemm.hip) -- the third routing
+// function beside sweep_route and rows_route.  launch_gemm asks it once and reports what it ran.
+struct GemmRoute {
+    // Lds128 / Lds64: gemm_lds_kernel / gemm_lds64_kernel (QT: Q k-contiguous); Sub128 / 64 / 32:
+    // gemm_sub_kernel<4 | 2 | 1>; K64x64 / K64x32: gemm_k64_kernel<2 | 1>; SplitK: gemm_splitk_kernel
+    enum Kernel { Lds128, Lds64, Lds64QT, Sub128, Sub64, Sub32, K64x64, K64x32, SplitK } kernel;
+    int mfma;            // Sub*: 4 (the 4x4x4 four-block MFMA) or 16 (16x16x4); else 0
+    dim3 grid;
+    bool fused;          // the launch carries the diagonal factor GemmJob::fuse asked for
+    bool seeded;         // the kernel computes its own C tile from the points (GemmJob::seed)
+    bool assemble_first; // a seed was given but the kernel cannot seed: the region is assembled first
+    int syrk_cls;        // profile class of a BQ_K_SYRK product: BQ_K_SYRK_SMALL below a chip of 128-tiles
+};
+GemmRoute gemm_route(const bq_ctx *c, const GemmJob &g);
+// ran: the route the launch took
+int launch_gemm(bq_ctx *c, int cls, const GemmJob &g, GemmRoute *ran = nullptr);
 bool gemm_trsm_ok(const bq_ctx *c, int m, int n, int k);
 int launch_gemm_trsm(bq_ctx *c, double *C, long ldc, long cstride, const double *P, long ldp,
                      long pstride, const double *Q, long ldq, long qstride, int m, int n, int k,
@@ -456,6 +489,13 @@ int launch_append_grow(bq_ctx *c, double *A, long lda, int r0, int ntot, int yro
                        const double *Aold, long ldold, int yold, int ncopy);
 
 // ---- potrf.hip ------------------------------------------------------------------------
+// scope of bq_ctx::sharing: how the chip is shared while the launches queued inside it run
+struct Sharing {
+    bq_ctx *c;
+    int prev;
+    Sharing(bq_ctx *c_, int how) : c(c_), prev(c_->sharing) { c->sharing = how; }
+    ~Sharing() { c->sharing = prev; }
+};
 int auto_nb(const bq_ctx *c, int ntot, int batch);
 // How the first ncols columns of `batch` matrices of ntot rows are eliminated, decided in ONE place
 // (sweep_route): every enqueue asks again with the workspace on hand (a setter may have changed the

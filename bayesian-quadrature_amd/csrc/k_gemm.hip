@@ -45,18 +45,7 @@ int gemm_init(bq_ctx *c)
     return BQ_OK;
 }
 
-// C(m x n) -= P(m x k) Q(n x k)^T; tile shape from the amount of parallelism
-// fuse_j0 >= 0: also factor the leading 64x64 block of C (global column fuse_j0) in the
-// same launch (see gemm_sub_kernel); dinv / info as for launch_potf2
-// whether C(m x n) -= P Q^T with unit-stride Q rows goes to the LDS-staged 128 x 128 kernel:
-// whole 64 x 64 wave tiles, k in chunks of 32, and at least BQ_LDS_MIN_TILES workgroup tiles.
-// (Round 1 asked for a full chip of tiles, 256.  The look-ahead's update of the next panel --
-// m x 512 columns, 100-250 tiles, on the second stream BESIDE the bulk update -- then went to
-// the register-streaming kernel at ~12 TFLOP/s and sat on the panel chain: with the LDS
-// kernel N = 16384 takes 26.5 instead of 27.1 ms, 12288 13.17 instead of 13.35; the smaller
-// sizes and the batched configs do not move.)
-// Such an update never carries the fused diagonal factor (the factor would ride on the
-// register-streaming kernel, which is slower by more than a potf2 launch costs).
+// fewest workgroup tiles the LDS-staged 128 x 128 kernel is worth (gemm_route)
 #define BQ_LDS_MIN_TILES 96
 // 0: no; 128 / 64: the workgroup tile of the LDS-staged kernel that takes the product.
 //
@@ -111,125 +100,154 @@ static int gemm_lds_tile(const bq_ctx *c, int m, int n, int k, int lower, int ba
     return (can128 && a >= BQ_LDS_MIN_TILES) ? 128 : 0;
 }
 
-bool gemm_uses_lds(const bq_ctx *c, int m, int n, int k, int lower, int batch)
+// The ONE place that picks the kernel of a product C(m x n) -= P(m x k) Q(n x k)^T; the tile shape
+// follows the amount of parallelism.
+//   * An LDS-staged kernel takes the product where gemm_lds_tile has a tile for it: unit-stride Q
+//     rows, whole 64 x 64 wave tiles, k in chunks of 32 and, for the 128 x 128 kernel, at least
+//     BQ_LDS_MIN_TILES workgroup tiles.  (Round 1 asked for a full chip of tiles, 256.  The
+//     look-ahead's update of the next panel -- m x 512 columns, 100-250 tiles, on the second stream
+//     BESIDE the bulk update -- then went to the register-streaming kernel at ~12 TFLOP/s and sat on
+//     the panel chain: with the LDS kernel N = 16384 takes 26.5 instead of 27.1 ms, 12288 13.17
+//     instead of 13.35; the smaller sizes and the batched configs do not move.)  Q given
+//     k-contiguous (the backward row sweep) goes to the 64-tile kernel's transposed staging.
+//   * The fusion rule: a requested diagonal factor (GemmJob::fuse: the leading 64 x 64 block of C
+//     factored in the same launch, see gemm_sub_kernel) is carried exactly when NO LDS-staged kernel
+//     takes the product.  The factor rides on the register-streaming kernels only, and those are
+//     slower than an LDS-staged one by more than a potf2 launch costs.  The caller reads
+//     GemmRoute::fused and factors the block itself where it is false.
+//   * C left out of the assembly (GemmJob::seed): the LDS-staged kernels compute their tile of it
+//     from the problem's points (d <= 2); anything else gets the region written first.
+//   * Else the register-streaming kernels, 128 / 64 / 32-row workgroup tiles by what fills the chip;
+//     k = 64 has kernels of its own below 128.
+//   * A sweep's product (GemmJob::rows; small ones: the posterior variance at C2 size) goes out in
+//     split-k tiles, gemm_splitk_kernel -- unless the LDS-staged tiles already get half a chip of
+//     workgroups.
+GemmRoute gemm_route(const bq_ctx *c, const GemmJob &g)
 {
-    return gemm_lds_tile(c, m, n, k, lower, batch) != 0;
-}
-
-int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const double *P, long ldp,
-                long pstride, const double *Q, long qsj, long qsk, long qstride, int m, int n,
-                int k, int lower, int batch, int fuse_j0, double *dinv, long dstride, int *info,
-                int ccut, const GramSeed *seed)
-{
-    // ccut > 0: columns >= ccut of C need no update (honoured by the LDS-staged kernel only)
-    if (m <= 0 || n <= 0 || k <= 0)
-        return BQ_OK;
-    if ((m & 15) || (n & 15) || (k & 7))
-        return fail(c, BQ_ERR_BAD_ARG, "gemm: m,n must be multiples of 16 and k of 8");
-    if (seed) {
-        // a product that cannot seed its own accumulators: its region of C is assembled first
-        const bool f444s = qsj == 1 && (m % 64) == 0 && (n % 64) == 0;
-        const int t = (f444s && fuse_j0 < 0) ? gemm_lds_tile(c, m, n, k, lower, batch) : 0;
-        if (!((t == 128 || t == 64) && (seed->d == 1 || seed->d == 2))) {
-            const int ncol = ccut > 0 ? std::min(n, ccut) : n;
-            BQCHK(launch_assemble_region(c, *seed, C - seed->r - (long)seed->c * ldc, ldc, cstride, m,
-                                         (ncol + 63) / 64 * 64, batch));
-            seed = nullptr;
-        }
-    }
+    const int m = g.m, n = g.n, k = g.k, lower = g.lower, batch = g.batch;
+    GemmRoute r{};
     auto tiles = [&](int t) {
         long a = (long)((m + t - 1) / t) * ((n + t - 1) / t) * batch;
         return lower ? a / 2 + 1 : a;
     };
-    // algorithmic flops: full product 2mnk; lower trapezoid of a trailing block
-    // 2k(mn - n^2/2), i.e. m^2 k for the square update
-    const double flops = (lower ? 2.0 * k * ((double)m * n - 0.5 * (double)n * n)
-                                : 2.0 * (double)m * n * k) * batch;
-    if (cls == BQ_K_SYRK && tiles(128) < c->cus)
-        cls = BQ_K_SYRK_SMALL;
-    Bracket br(c, cls, flops);
-    const long cu = c->cus;
+    r.syrk_cls = tiles(128) < c->cus ? BQ_K_SYRK_SMALL : BQ_K_SYRK;
     // square trailing updates launch only their lower workgroup tiles (mode 2)
     const bool tri = lower && m == n;
-    const int mode = tri ? 2 : lower;
     auto grid_for = [&](int t) {
         const unsigned gm = (unsigned)((m + t - 1) / t), gn = (unsigned)((n + t - 1) / t);
         return tri ? dim3(gm * (gm + 1) / 2, 1, batch) : dim3(gm, gn, batch);
     };
     // the 4x4x4 four-block MFMA sustains ~1.5x the rate of the 16x16x4 form on gfx950; it
     // needs unit-stride Q rows and whole wave tiles (every padded system here has them)
-    const bool f444 = qsj == 1 && (m % 64) == 0 && (n % 64) == 0;
-#define BQ_GEMM_SUB(TM_, TN_, T_)                                                                  \
-    do {                                                                                           \
-        if (f444)                                                                                  \
-            hipLaunchKernelGGL((gemm_sub_kernel<TM_, TN_, 1>), grid_for(T_), dim3(256), 0, c->cur, \
-                               C, ldc, cstride, P, ldp, pstride, Q, qsj, qsk, qstride, m, n, k,    \
-                               mode, fuse_j0, dinv, dstride, info);                                \
-        else                                                                                       \
-            hipLaunchKernelGGL((gemm_sub_kernel<TM_, TN_, 0>), grid_for(T_), dim3(256), 0, c->cur, \
-                               C, ldc, cstride, P, ldp, pstride, Q, qsj, qsk, qstride, m, n, k,    \
-                               mode, fuse_j0, dinv, dstride, info);                                \
-    } while (0)
-    // a 64-column slab has no use for 128-column workgroup tiles (half of their waves idle)
-    const int ldst = (f444 && fuse_j0 < 0) ? gemm_lds_tile(c, m, n, k, lower, batch) : 0;
-    // C left out of the assembly (seed): the LDS-staged kernels compute their tile of it from the
-    // problem's points (d <= 2); anything else gets the region written first
-    if (seed) {
-        const bool can = (ldst == 128 || ldst == 64) && (seed->d == 1 || seed->d == 2);
-        if (can) {
-            const int cut = ccut > 0 ? ccut : 0x7fffffff;
-            const dim3 g = grid_for(ldst);
-#define BQ_GEMM_SEED(K_, BYTES_)                                                                   \
-    hipLaunchKernelGGL(K_, g, dim3(256), BYTES_, c->cur, C, ldc, cstride, P, ldp, pstride, Q, qsk,  \
-                       qstride, m, n, k, mode, cut, *seed)
-            if (ldst == 128 && seed->d == 1)
-                BQ_GEMM_SEED(gemm_lds_seed_kernel<1>, BQ_LDS_BYTES);
-            else if (ldst == 128)
-                BQ_GEMM_SEED(gemm_lds_seed_kernel<2>, BQ_LDS_BYTES);
-            else if (seed->d == 1)
-                BQ_GEMM_SEED(gemm_lds64_seed_kernel<1>, BQ_L64_BYTES);
-            else
-                BQ_GEMM_SEED(gemm_lds64_seed_kernel<2>, BQ_L64_BYTES);
-#undef BQ_GEMM_SEED
-            HIPCHK(c, hipGetLastError());
-            return BQ_OK;
+    const bool f444 = g.qsj == 1 && (m % 64) == 0 && (n % 64) == 0;
+    const int t = gemm_lds_tile(c, m, n, k, lower, batch);
+    const int ldst = f444 ? t : 0;
+    const bool qt64 = !ldst && g.qsk == 1 && (g.qsj & 1) == 0 && (m % 64) == 0 && t != 0 &&
+                      tiles(64) >= c->cus / 2;
+    if (g.rows) {
+        const bool lds = (g.qsj == 1 || (g.qsk == 1 && (g.qsj & 1) == 0)) && (m % 64) == 0 && t != 0;
+        if (!lds && (m % 32) == 0 && (n % 32) == 0 && (k % 64) == 0 && k <= 2048 &&
+            (long)(m / 32) * (n / 32) <= 4L * c->cus) {
+            r.kernel = GemmRoute::SplitK;
+            r.grid = dim3(m / 32, n / 32);
+            return r;
         }
     }
-    if (ldst == 128) {
-        dim3 g = grid_for(128);
-        hipLaunchKernelGGL(gemm_lds_kernel, g, dim3(256), BQ_LDS_BYTES, c->cur, C, ldc, cstride, P,
-                           ldp, pstride, Q, qsk, qstride, m, n, k, mode,
-                           ccut > 0 ? ccut : 0x7fffffff);
-    } else if (ldst == 64) {
-        dim3 g = grid_for(64);
-        hipLaunchKernelGGL((gemm_lds64_kernel<false, 1>), g, dim3(256), BQ_L64_BYTES, c->cur, C, ldc,
-                           cstride, P, ldp, pstride, Q, qsk, qstride, m, n, k, mode,
-                           ccut > 0 ? ccut : 0x7fffffff);
-    } else if (qsk == 1 && (qsj & 1) == 0 && fuse_j0 < 0 && (m % 64) == 0 &&
-               gemm_lds_tile(c, m, n, k, lower, batch) != 0 && tiles(64) >= c->cus / 2) {
-        // Q given k-contiguous (the backward row sweep): the 64-tile kernel's transposed staging
-        dim3 g = grid_for(64);
-        hipLaunchKernelGGL((gemm_lds64_kernel<true, 1>), g, dim3(256), BQ_L64_BYTES, c->cur, C, ldc,
-                           cstride, P, ldp, pstride, Q, qsj, qstride, m, n, k, mode,
-                           ccut > 0 ? ccut : 0x7fffffff);
-    } else if (tiles(128) >= cu && n >= 128) {
-        BQ_GEMM_SUB(4, 4, 128);
-    } else if (tiles(64) >= cu / 2) {
-        if (k == 64)
-            hipLaunchKernelGGL((gemm_k64_kernel<2, 2>), grid_for(64), dim3(256), 0, c->cur, C, ldc,
-                               cstride, P, ldp, pstride, Q, qsj, qsk, qstride, m, n, mode, fuse_j0,
-                               dinv, dstride, info);
-        else
-            BQ_GEMM_SUB(2, 2, 64);
+    r.fused = g.fuse.j0 >= 0 && !ldst && !qt64;
+    r.seeded = g.seed && ldst && (g.seed->d == 1 || g.seed->d == 2);
+    r.assemble_first = g.seed && !r.seeded;
+    int wg = 32; // rows of the workgroup tile
+    if (ldst) {
+        r.kernel = ldst == 128 ? GemmRoute::Lds128 : GemmRoute::Lds64;
+        wg = ldst;
+    } else if (qt64) {
+        r.kernel = GemmRoute::Lds64QT;
+        wg = 64;
+    } else if (tiles(128) >= c->cus && n >= 128) {
+        r.kernel = GemmRoute::Sub128;
+        wg = 128;
+    } else if (tiles(64) >= c->cus / 2) {
+        r.kernel = k == 64 ? GemmRoute::K64x64 : GemmRoute::Sub64;
+        wg = 64;
     } else {
-        if (k == 64)
-            hipLaunchKernelGGL((gemm_k64_kernel<1, 1>), grid_for(32), dim3(256), 0, c->cur, C, ldc,
-                               cstride, P, ldp, pstride, Q, qsj, qsk, qstride, m, n, mode, fuse_j0,
-                               dinv, dstride, info);
-        else
-            BQ_GEMM_SUB(1, 1, 32);
+        r.kernel = k == 64 ? GemmRoute::K64x32 : GemmRoute::Sub32;
     }
-#undef BQ_GEMM_SUB
+    const bool sub = r.kernel == GemmRoute::Sub128 || r.kernel == GemmRoute::Sub64 ||
+                     r.kernel == GemmRoute::Sub32;
+    r.mfma = !sub ? 0 : f444 ? 4 : 16;
+    r.grid = grid_for(wg);
+    return r;
+}
+
+int launch_gemm(bq_ctx *c, int cls, const GemmJob &g, GemmRoute *ran)
+{
+    const int m = g.m, n = g.n, k = g.k, lower = g.lower, batch = g.batch;
+    GemmRoute mine, &r = ran ? *ran : mine;
+    r = GemmRoute{};
+    if (m <= 0 || n <= 0 || k <= 0)
+        return BQ_OK;
+    if ((m & 15) || (n & 15) || (k & 7))
+        return fail(c, BQ_ERR_BAD_ARG, "gemm: m,n must be multiples of 16 and k of 8");
+    if (g.rows && (lower || batch != 1 || g.seed || g.fuse.j0 >= 0))
+        return fail(c, BQ_ERR_BAD_ARG, "gemm: a sweep's product is one full matrix, unseeded, unfused");
+    r = gemm_route(c, g);
+    if (r.assemble_first) {
+        const GramSeed &sd = *g.seed;
+        const int ncol = g.ccut > 0 ? std::min(n, g.ccut) : n;
+        BQCHK(launch_assemble_region(c, sd, g.C - sd.r - (long)sd.c * g.ldc, g.ldc, g.cstride, m,
+                                     (ncol + 63) / 64 * 64, batch));
+    }
+    // algorithmic flops: full product 2mnk; lower trapezoid of a trailing block
+    // 2k(mn - n^2/2), i.e. m^2 k for the square update
+    const double flops = (lower ? 2.0 * k * ((double)m * n - 0.5 * (double)n * n)
+                                : 2.0 * (double)m * n * k) * batch;
+    Bracket br(c, cls == BQ_K_SYRK ? r.syrk_cls : cls, flops);
+    const int mode = (lower && m == n) ? 2 : lower, cut = g.ccut > 0 ? g.ccut : 0x7fffffff;
+    const int fj = r.fused ? g.fuse.j0 : -1;
+    // LDS-staged: Q's one free stride QS_ (+ the seed); register-streaming: the shape (k64: m, n)
+#define BQ_LDS(K_, BYTES_, QS_, ...)                                                               \
+    hipLaunchKernelGGL(K_, r.grid, dim3(256), BYTES_, c->cur, g.C, g.ldc, g.cstride, g.P, g.ldp,    \
+                       g.pstride, g.Q, QS_, g.qstride, m, n, k, mode, cut, ##__VA_ARGS__)
+#define BQ_REG(K_, ...)                                                                            \
+    hipLaunchKernelGGL(K_, r.grid, dim3(256), 0, c->cur, g.C, g.ldc, g.cstride, g.P, g.ldp,         \
+                       g.pstride, g.Q, g.qsj, g.qsk, g.qstride, __VA_ARGS__, mode, fj, g.fuse.dinv, \
+                       g.fuse.dstride, g.fuse.info)
+#define BQ_SUB(T_)                                                                                 \
+    if (r.mfma == 4)                                                                               \
+        BQ_REG((gemm_sub_kernel<T_, T_, 1>), m, n, k);                                             \
+    else                                                                                           \
+        BQ_REG((gemm_sub_kernel<T_, T_, 0>), m, n, k)
+    switch (r.kernel) {
+    case GemmRoute::Lds128:
+        if (!r.seeded)
+            BQ_LDS(gemm_lds_kernel, BQ_LDS_BYTES, g.qsk);
+        else if (g.seed->d == 1)
+            BQ_LDS(gemm_lds_seed_kernel<1>, BQ_LDS_BYTES, g.qsk, *g.seed);
+        else
+            BQ_LDS(gemm_lds_seed_kernel<2>, BQ_LDS_BYTES, g.qsk, *g.seed);
+        break;
+    case GemmRoute::Lds64:
+        if (!r.seeded)
+            BQ_LDS((gemm_lds64_kernel<false, 1>), BQ_L64_BYTES, g.qsk);
+        else if (g.seed->d == 1)
+            BQ_LDS(gemm_lds64_seed_kernel<1>, BQ_L64_BYTES, g.qsk, *g.seed);
+        else
+            BQ_LDS(gemm_lds64_seed_kernel<2>, BQ_L64_BYTES, g.qsk, *g.seed);
+        break;
+    case GemmRoute::Lds64QT: BQ_LDS((gemm_lds64_kernel<true, 1>), BQ_L64_BYTES, g.qsj); break;
+    case GemmRoute::Sub128: BQ_SUB(4); break;
+    case GemmRoute::Sub64: BQ_SUB(2); break;
+    case GemmRoute::Sub32: BQ_SUB(1); break;
+    case GemmRoute::K64x64: BQ_REG((gemm_k64_kernel<2, 2>), m, n); break;
+    case GemmRoute::K64x32: BQ_REG((gemm_k64_kernel<1, 1>), m, n); break;
+    case GemmRoute::SplitK:
+        hipLaunchKernelGGL(gemm_splitk_kernel, r.grid, dim3(256), 0, c->cur, g.C, g.ldc, g.P, g.ldp,
+                           g.Q, g.qsj, g.qsk, k);
+        break;
+    }
+#undef BQ_SUB
+#undef BQ_REG
+#undef BQ_LDS
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -241,7 +259,7 @@ int launch_gemm(bq_ctx *c, int cls, double *C, long ldc, long cstride, const dou
 //
 // Workgroup tile: 128 x 128 once the lower 128-tiles number at least kGrad128PerCu per CU, else
 // 64 x 64 (four times the workgroups).  BQ_GEMM_TILE=64|128 forces one (measurements).
-static int grad_tile(const bq_ctx *c, int npad)
+int grad_tile(const bq_ctx *c, int npad)
 {
     constexpr long kGrad128PerCu = 2;
     if (c->gemm_tile == 64 || c->gemm_tile == 128)
@@ -339,19 +357,13 @@ int launch_trsm_sweep(bq_ctx *c, double *X, long ldx, long xstride, int m, const
 int launch_gemm_rows(bq_ctx *c, int cls, double *C, long ldc, const double *P, long ldp,
                      const double *Q, long qsj, long qsk, int m, int n, int k)
 {
-    // small products (posterior variance at C2 size): split-k tiles, gemm_splitk_kernel --
-    // unless the 64 x 64 LDS-staged tiles already get half a chip of workgroups
-    const bool lds = (qsj == 1 || (qsk == 1 && (qsj & 1) == 0)) && (m % 64) == 0 &&
-                     gemm_lds_tile(c, m, n, k, 0, 1) != 0;
-    if (!lds && (m % 32) == 0 && (n % 32) == 0 && (k % 64) == 0 && k <= 2048 &&
-        (long)(m / 32) * (n / 32) <= 4L * c->cus) {
-        Bracket br(c, cls, 2.0 * (double)m * n * k);
-        hipLaunchKernelGGL(gemm_splitk_kernel, dim3(m / 32, n / 32), dim3(256), 0, c->cur, C, ldc,
-                           P, ldp, Q, qsj, qsk, k);
-        HIPCHK(c, hipGetLastError());
-        return BQ_OK;
-    }
-    return launch_gemm(c, cls, C, ldc, 0, P, ldp, 0, Q, qsj, qsk, 0, m, n, k, 0, 1);
+    GemmJob g;
+    g.C = C, g.ldc = ldc;
+    g.P = P, g.ldp = ldp;
+    g.Q = Q, g.qsj = qsj, g.qsk = qsk;
+    g.m = m, g.n = n, g.k = k;
+    g.rows = true;
+    return launch_gemm(c, cls, g);
 }
 
 // one step of the row sweep over a large resident factor in one launch (rows_fused_kernel):

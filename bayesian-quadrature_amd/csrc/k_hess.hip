@@ -19,13 +19,7 @@ size_t hess_ws_doubles(int npad, int d)
 
 // Workgroup tile of the products: the tall 256 x 64 tile where the gradient's product takes its
 // 128 x 128 tile (as many workgroups), else 64 x 64
-static bool hess_tall(const bq_ctx *c, int npad)
-{
-    if (c->gemm_tile == 64 || c->gemm_tile == 128)
-        return c->gemm_tile == 128;
-    const long gm = (npad + 127) / 128;
-    return gm * (gm + 1) / 2 >= 2L * c->cus;
-}
+static bool hess_tall(const bq_ctx *c, int npad) { return grad_tile(c, npad) == 128; }
 
 template <int D>
 static void hess_launch_prod(bq_ctx *c, bool tall, double *C, const double *A, const double *Q,

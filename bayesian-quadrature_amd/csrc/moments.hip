@@ -741,8 +741,12 @@ extern "C" int bq_esm_border(bq_ctx *c, bq_fit *gp_l, int64_t ns, const double *
     BQCHK(enqueue_forward_rows_blk(c, F.d(), mrows, mrows, gp_l->A.d(), gp_l->ldl, npad,
                                    gp_l->dw.d()));
     if (p > 0) {
-        BQCHK(launch_gemm(c, BQ_K_GEMM, G.d(), mrows, 0, F.d(), mrows, 0, F.d(), 1, mrows, 0, mrows,
-                          T, p, 0, 1));
+        GemmJob fft;
+        fft.C = G.d(), fft.ldc = mrows;
+        fft.P = F.d(), fft.ldp = mrows;
+        fft.Q = F.d(), fft.qsj = 1, fft.qsk = mrows;
+        fft.m = mrows, fft.n = T, fft.k = p;
+        BQCHK(launch_gemm(c, BQ_K_GEMM, fft));
         BQCHK(launch_rowdot(c, F.d(), (long)mrows, mrows, mrows, p, nullptr, 0.0, nullptr, sq.d()));
     }
     // (of G only columns rb and rl -- the products with the b and l rows -- are read)

@@ -127,6 +127,20 @@ SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch, size_t w
     return r;
 }
 
+// The trailing update of block (r_row, r_col) by the panel that starts at column K0:
+// A[r_row.., r_col..] (m x n) -= A[r_row.., K0..] A[r_col.., K0..]^T over k columns
+static GemmJob trailing_job(double *A, long lda, long astride, int r_row, int r_col, int K0, int m,
+                            int n, int k, int lower, int batch)
+{
+    GemmJob g;
+    g.C = A + r_row + (long)r_col * lda, g.ldc = lda, g.cstride = astride;
+    g.P = A + r_row + (long)K0 * lda, g.ldp = lda, g.pstride = astride;
+    g.Q = A + r_col + (long)K0 * lda, g.qsj = 1, g.qsk = lda, g.qstride = astride;
+    g.m = m, g.n = n, g.k = k;
+    g.lower = lower, g.batch = batch;
+    return g;
+}
+
 // Columns [j0, j0 + w) of a panel, recursively: the left half, ONE update of the right half's
 // columns with the whole left half, the right half.  Same flops as the left-looking slab
 // order (each 64-column slab updated with everything before it, n = 64 per launch), but two
@@ -134,7 +148,7 @@ SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch, size_t w
 // enough for the LDS-staged kernel -- instead of two n = 64 launches that re-stream the panel
 // (a batch's panel does not fit in L2: the n = 64 updates ran at 12 TFLOP/s; C5 shard
 // 6.8 -> see DESIGN).  A 64-column slab: its diagonal factor (unless the launch that last
-// updated it carried it: diag_done) and the solve of the rows below.
+// updated it carried it, GemmRoute::fused: diag_done) and the solve of the rows below.
 static int enqueue_panel_rec(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot, int j0,
                       int w, double *dinv, int *info, bool diag_done)
 {
@@ -148,11 +162,11 @@ static int enqueue_panel_rec(bq_ctx *c, double *A, long lda, long astride, int b
     const int wl = ((w / 64 + 1) / 2) * 64, wr = w - wl;
     BQCHK(enqueue_panel_rec(c, A, lda, astride, batch, ntot, j0, wl, dinv, info, diag_done));
     const int r0 = j0 + wl;
-    const double *P = A + r0 + (long)j0 * lda;
-    const int fj = gemm_uses_lds(c, ntot - r0, wr, wl, 1, batch) ? -1 : r0;
-    BQCHK(launch_gemm(c, BQ_K_GEMM, A + r0 + (long)r0 * lda, lda, astride, P, lda, astride, P, 1,
-                      lda, astride, ntot - r0, wr, wl, 1, batch, fj, dinv, BQ_DINV_STRIDE, info));
-    return enqueue_panel_rec(c, A, lda, astride, batch, ntot, r0, wr, dinv, info, fj >= 0);
+    GemmJob g = trailing_job(A, lda, astride, r0, r0, j0, ntot - r0, wr, wl, 1, batch);
+    g.fuse = {r0, dinv, BQ_DINV_STRIDE, info};
+    GemmRoute ran;
+    BQCHK(launch_gemm(c, BQ_K_GEMM, g, &ran));
+    return enqueue_panel_rec(c, A, lda, astride, batch, ntot, r0, wr, dinv, info, ran.fused);
 }
 
 // the 64-column slabs of one outer block [K0, K0+KB): left-looking update, diagonal
@@ -236,14 +250,6 @@ static int enqueue_slab_sweep(bq_ctx *c, double *A, long lda, long astride, int 
     return BQ_OK;
 }
 
-// (tile choice while two streams share the chip: gemm_lds_tile)
-struct Sharing {
-    bq_ctx *c;
-    int prev;
-    Sharing(bq_ctx *c_, int how) : c(c_), prev(c_->sharing) { c->sharing = how; }
-    ~Sharing() { c->sharing = prev; }
-};
-
 // Eliminate the first ncols columns (multiple of 64) of the ntot x ntot lower
 // matrix (ntot multiple of 64), batched, with outer block NB.  dinv: BQ_DINV_STRIDE doubles per
 // problem.  ws: the slab sweep's scratch (SweepRoute::Blocked of one or two matrices, else null):
@@ -294,7 +300,6 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
             // the rest of the sweep runs sequentially on the main stream.
             if (ntot - r0 < c->la_min)
                 break;
-            const double *P = A + r0 + (long)K0 * lda;
             const int nw = (r0 < ncols) ? std::min(NB, ncols - r0) : 0; // width of the next panel
             if (nw > 0) {
                 // aux stream: bring the next panel's columns up to date (they were last
@@ -304,14 +309,13 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
                 c->cur = c->aux;
                 // (a wide panel's update is worth the LDS-staged kernel, which carries no
                 // fused diagonal factor: enqueue_panel then factors the block itself)
-                const int fj =
-                    !gemm_uses_lds(c, ntot - r0, nw, KB, 1, batch) ? r0 : -1;
-                st = launch_gemm(c, BQ_K_SYRK, A + r0 + (long)r0 * lda, lda, astride, P, lda,
-                                 astride, P, 1, lda, astride, ntot - r0, nw, KB, 1, batch, fj, dinv,
-                                 BQ_DINV_STRIDE, info);
+                GemmJob g = trailing_job(A, lda, astride, r0, r0, K0, ntot - r0, nw, KB, 1, batch);
+                g.fuse = {r0, dinv, BQ_DINV_STRIDE, info};
+                GemmRoute ran;
+                st = launch_gemm(c, BQ_K_SYRK, g, &ran);
                 if (st == BQ_OK)
                     st = enqueue_panel(c, A, lda, astride, batch, ntot, r0, nw, dinv, info,
-                                       fj >= 0, ws);
+                                       ran.fused, ws);
                 c->cur = c->stream;
                 if (st != BQ_OK)
                     break;
@@ -319,18 +323,17 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
                 // main stream: everything right of the next panel, concurrently
                 const int r1 = r0 + nw;
                 if (r1 < ntot) {
-                    const double *P1 = A + r1 + (long)K0 * lda;
-                    st = launch_gemm(c, BQ_K_SYRK, A + r1 + (long)r1 * lda, lda, astride, P1, lda,
-                                     astride, P1, 1, lda, astride, ntot - r1, ntot - r1, KB, 1,
-                                     batch, -1, nullptr, 0, nullptr,
-                                     skip_border ? ncols - r1 : 0);
+                    GemmJob b = trailing_job(A, lda, astride, r1, r1, K0, ntot - r1, ntot - r1, KB,
+                                             1, batch);
+                    b.ccut = skip_border ? ncols - r1 : 0;
+                    st = launch_gemm(c, BQ_K_SYRK, b);
                     HIPCHK(c, hipEventRecord(c->ev_next, c->stream));
                     have_b = true;
                 }
             } else {
                 // no further panel: the remaining trailing block is pure Schur complement
-                st = launch_gemm(c, BQ_K_SYRK, A + r0 + (long)r0 * lda, lda, astride, P, lda,
-                                 astride, P, 1, lda, astride, ntot - r0, ntot - r0, KB, 1, batch);
+                st = launch_gemm(c, BQ_K_SYRK, trailing_job(A, lda, astride, r0, r0, K0, ntot - r0,
+                                                            ntot - r0, KB, 1, batch));
             }
             panel_done = false;
         }
@@ -353,16 +356,14 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
         // the one-launch steps are its shortest chain: hand the rest to the slab sweep.
         const bool to_slab = ws && NB > 64 && r0 < ncols && ntot - r0 < kSlabMax;
         if (r0 < ntot) {
-            const double *P = A + r0 + (long)K0 * lda;
+            GemmJob g = trailing_job(A, lda, astride, r0, r0, K0, ntot - r0, ntot - r0, KB, 1, batch);
+            g.ccut = skip_border ? ncols - r0 : 0;
             // the trailing update also factors the next diagonal block if there is one
-            const int fj = (r0 < ncols && !to_slab &&
-                            !gemm_uses_lds(c, ntot - r0, ntot - r0, KB, 1, batch))
-                               ? r0
-                               : -1;
-            BQCHK(launch_gemm(c, BQ_K_SYRK, A + r0 + (long)r0 * lda, lda, astride, P, lda, astride,
-                              P, 1, lda, astride, ntot - r0, ntot - r0, KB, 1, batch, fj, dinv,
-                              BQ_DINV_STRIDE, info, skip_border ? ncols - r0 : 0));
-            diag_done = fj >= 0;
+            if (r0 < ncols && !to_slab)
+                g.fuse = {r0, dinv, BQ_DINV_STRIDE, info};
+            GemmRoute ran;
+            BQCHK(launch_gemm(c, BQ_K_SYRK, g, &ran));
+            diag_done = ran.fused;
         }
         if (to_slab)
             return enqueue_slab_sweep(c, A + r0 + (long)r0 * lda, lda, astride, batch, ntot - r0,
@@ -403,17 +404,15 @@ static int enqueue_trsm_rec(bq_ctx *c, double *A, long lda, long astride, int ba
     const int wl = ((w / 64 + 1) / 2) * 64, wr = w - wl;
     BQCHK(enqueue_trsm_rec(c, A, lda, astride, batch, rx, m, K0, j0, wl, rec, rstride, solved));
     const long cl = K0 + j0, cr = cl + wl;
-    double *C = A + rx + cr * lda;
-    const double *P = A + rx + cl * lda;
-    const double *Q = A + cr + cl * lda; // L11[j0 + wl .., j0 ..): wr x wl
     const bool fuse = gemm_trsm_ok(c, m, wr, wl);
     if (fuse)
-        BQCHK(launch_gemm_trsm(c, C, lda, astride, P, lda, astride, Q, lda, astride, m, wr, wl,
-                               A + cr + cr * lda, lda, astride,
-                               rec + (long)((j0 + wl) / 64) * BQ_DINV_HALF, rstride, batch));
+        // (Q = L11[j0 + wl .., j0 ..): wr x wl)
+        BQCHK(launch_gemm_trsm(c, A + rx + cr * lda, lda, astride, A + rx + cl * lda, lda, astride,
+                               A + cr + cl * lda, lda, astride, m, wr, wl, A + cr + cr * lda, lda,
+                               astride, rec + (long)((j0 + wl) / 64) * BQ_DINV_HALF, rstride, batch));
     else
-        BQCHK(launch_gemm(c, BQ_K_GEMM, C, lda, astride, P, lda, astride, Q, 1, lda, astride, m, wr,
-                          wl, 0, batch));
+        BQCHK(launch_gemm(c, BQ_K_GEMM,
+                          trailing_job(A, lda, astride, rx, (int)cr, (int)cl, m, wr, wl, 0, batch)));
     return enqueue_trsm_rec(c, A, lda, astride, batch, rx, m, K0, j0 + wl, wr, rec, rstride, fuse);
 }
 
@@ -457,7 +456,7 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
                                   ws, SweepArgs(), K0, rstride);
     };
     BQCHK(diag(0, NB, recs[0]));
-    // while a diagonal factor runs beside an update, gemm_lds_tile keeps the rule of a product
+    // while a diagonal factor runs beside an update, gemm_route keeps the rule of a product
     // alone (C5 shard 5.73 ms against 6.05 with the look-ahead's sharing mode 1)
     Sharing scope(c, la ? 0 : c->sharing);
     // The caller assembled only the first NB columns (SweepRoute::seed_cols) and left the rest as a
@@ -477,7 +476,6 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
         if (m2 <= 0)
             break;
         const double *rec = recs[par];
-        const double *P = A + r0 + (long)K0 * lda;
         const int nw = r0 < ncols ? std::min(NB, ncols - r0) : 0;
         if (nw == 0) {
             BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r0, m2, K0, KB, rec, rstride,
@@ -485,8 +483,8 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
             // what is left is the Schur complement of the border: nobody reads it when the
             // results come off the border rows
             if (!skip_border)
-                BQCHK(launch_gemm(c, BQ_K_SYRK, A + r0 + (long)r0 * lda, lda, astride, P, lda,
-                                  astride, P, 1, lda, astride, m2, m2, KB, 1, batch));
+                BQCHK(launch_gemm(c, BQ_K_SYRK,
+                                  trailing_job(A, lda, astride, r0, r0, K0, m2, m2, KB, 1, batch)));
             break;
         }
         const int r1 = r0 + nw;
@@ -512,9 +510,9 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
         const bool sd0 = seeded && K0 == 0;
         if (st == BQ_OK) {
             const GramSeed sd = seed_at(r0, r0);
-            st = launch_gemm(c, BQ_K_SYRK, A + r0 + (long)r0 * lda, lda, astride, P, lda, astride, P,
-                             1, lda, astride, nw, nw, KB, 1, batch, -1, nullptr, 0, nullptr, 0,
-                             sd0 ? &sd : nullptr);
+            GemmJob g = trailing_job(A, lda, astride, r0, r0, K0, nw, nw, KB, 1, batch);
+            g.seed = sd0 ? &sd : nullptr;
+            st = launch_gemm(c, BQ_K_SYRK, g);
         }
         if (st == BQ_OK)
             st = diag(r0, nw, recs[par ^ 1]);
@@ -525,7 +523,6 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
         }
         BQCHK(st);
         if (r1 < ntot) {
-            const double *P1 = A + r1 + (long)K0 * lda;
             if (early) {
                 BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r1, ntot - r1, K0, KB, rec,
                                           rstride, one_launch));
@@ -542,14 +539,15 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
             // update alone gives back.)
             const bool sq = !(skip_border && r1 >= ncols);
             const GramSeed sdc = seed_at(r1, r0), sds = seed_at(r1, r1);
-            BQCHK(launch_gemm(c, BQ_K_SYRK, A + r1 + (long)r0 * lda, lda, astride, P1, lda, astride,
-                              P, 1, lda, astride, ntot - r1, nw, KB, 0, batch, -1, nullptr, 0,
-                              nullptr, 0, sd0 ? &sdc : nullptr));
-            if (sq)
-                BQCHK(launch_gemm(c, BQ_K_SYRK, A + r1 + (long)r1 * lda, lda, astride, P1, lda,
-                                  astride, P1, 1, lda, astride, ntot - r1, ntot - r1, KB, 1, batch,
-                                  -1, nullptr, 0, nullptr, skip_border ? ncols - r1 : 0,
-                                  sd0 ? &sds : nullptr));
+            GemmJob col = trailing_job(A, lda, astride, r1, r0, K0, ntot - r1, nw, KB, 0, batch);
+            col.seed = sd0 ? &sdc : nullptr;
+            BQCHK(launch_gemm(c, BQ_K_SYRK, col));
+            if (sq) {
+                GemmJob g = trailing_job(A, lda, astride, r1, r1, K0, ntot - r1, ntot - r1, KB, 1, batch);
+                g.ccut = skip_border ? ncols - r1 : 0;
+                g.seed = sd0 ? &sds : nullptr;
+                BQCHK(launch_gemm(c, BQ_K_SYRK, g));
+            }
         }
         if (la)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_panel, 0));

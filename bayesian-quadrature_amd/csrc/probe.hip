@@ -112,6 +112,20 @@ extern "C" int bq_probe_hbm_read8(bq_ctx *c, size_t bytes, int64_t reps, double 
     return BQ_OK;
 }
 
+// the probes' product on packed batch elements: C ldc x n, P ldp x k, Q ldq x k -- or, qt, Q given
+// k-contiguous, ldq x n
+static GemmJob probe_job(double *C, long ldc, const double *P, long ldp, const double *Q, long ldq,
+                         int m, int n, int k, int lower, int batch, int qt)
+{
+    GemmJob g;
+    g.C = C, g.ldc = ldc, g.cstride = ldc * n;
+    g.P = P, g.ldp = ldp, g.pstride = ldp * k;
+    g.Q = Q, g.qsj = qt ? ldq : 1, g.qsk = qt ? 1 : ldq, g.qstride = ldq * (qt ? n : k);
+    g.m = m, g.n = n, g.k = k;
+    g.lower = lower, g.batch = batch;
+    return g;
+}
+
 // C (m x n) -= P (m x k) Q (n x k)^T on scratch operands through launch_gemm (the engine's own
 // kernel selection): average ms over `reps` back-to-back launches.  qt: Q given k-contiguous.
 extern "C" int bq_probe_gemm(bq_ctx *c, int64_t m, int64_t n, int64_t k, int lower, int64_t batch,
@@ -131,18 +145,87 @@ extern "C" int bq_probe_gemm(bq_ctx *c, int64_t m, int64_t n, int64_t k, int low
     hipLaunchKernelGGL(probe_fill_kernel, dim3(2048), dim3(256), 0, c->stream, Q.d(),
                        Q.bytes / sizeof(double), 77u);
     HIPCHK(c, hipGetLastError());
-    auto run = [&]() {
-        return launch_gemm(c, BQ_K_GEMM, C.d(), ldc, ldc * n, P.d(), ldp, ldp * k, Q.d(),
-                           qt ? ldq : 1, qt ? 1 : ldq, (long)n * k, (int)m, (int)n, (int)k, lower,
-                           (int)batch);
-    };
-    BQCHK(run());
+    const GemmJob g = probe_job(C.d(), ldc, P.d(), ldp, Q.d(), ldq, (int)m, (int)n, (int)k, lower,
+                                (int)batch, qt);
+    BQCHK(launch_gemm(c, BQ_K_GEMM, g));
     float ms = 0;
     BQCHK(bq_timer_start(c));
     for (int64_t i = 0; i < reps; ++i)
-        BQCHK(run());
+        BQCHK(launch_gemm(c, BQ_K_GEMM, g));
     BQCHK(bq_timer_stop_ms(c, &ms));
     *ms_out = ms / (double)reps;
+    return BQ_OK;
+}
+
+// ONE product on the caller's own operands, and the route it took (GemmRoute; bqhip_probe.h).
+// Without operands nothing is launched: route[] is gemm_route's answer for the shape.
+extern "C" int bq_probe_gemm_product(bq_ctx *c, double *C, int64_t ldc, const double *P, int64_t ldp,
+                                     const double *Q, int64_t ldq, int64_t m, int64_t n, int64_t k,
+                                     int lower, int64_t batch, int qt, int64_t ccut, int sharing,
+                                     int want_fuse, int64_t j0, int seed_d, int rows, double *dinv,
+                                     int32_t *info, int32_t *route)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (!route)
+        return fail(c, BQ_ERR_BAD_ARG, "gemm_product: null route");
+    if (m < 16 || (m & 15) || n < 16 || (n & 15) || k < 8 || (k & 7) || m > 65536 || n > 65536 ||
+        k > 65536 || batch < 1 || batch > 65535 || ccut < 0 || ccut > 65536)
+        return fail(c, BQ_ERR_BAD_ARG, "gemm_product: m, n multiples of 16 and k of 8");
+    if (sharing < 0 || sharing > 2 || seed_d < 0 || seed_d > 3)
+        return fail(c, BQ_ERR_BAD_ARG, "gemm_product: sharing in 0 .. 2, seed_d in 0 .. 3");
+    if (want_fuse && (m < 64 || n < 64 || j0 < 0 || j0 > (1 << 30)))
+        return fail(c, BQ_ERR_BAD_ARG, "gemm_product: a fused factor needs a leading 64 x 64 block");
+    if (rows && (lower || batch != 1 || seed_d || want_fuse))
+        return fail(c, BQ_ERR_BAD_ARG, "gemm_product: a sweep's product is one full matrix");
+    const bool run = C || P || Q;
+    if (run && (!C || !P || !Q || ldc < m || ldp < m || ldq < (qt ? k : n) || seed_d > 0 ||
+                (want_fuse && (!dinv || !info))))
+        return fail(c, BQ_ERR_BAD_ARG,
+                    "gemm_product: all three operands with their leading dimensions, no seed");
+    HIPCHK(c, hipSetDevice(c->device));
+    Sharing scope(c, sharing);
+    GramSeed sd{};
+    sd.d = seed_d;
+    GemmRoute ran{};
+    DevBuf Cd, Pd, Qd, dv, inf;
+    if (run) {
+        HIPCHK(c, Cd.alloc(sizeof(double) * (size_t)ldc * n * batch));
+        HIPCHK(c, Pd.alloc(sizeof(double) * (size_t)ldp * k * batch));
+        HIPCHK(c, Qd.alloc(sizeof(double) * (size_t)ldq * (qt ? n : k) * batch));
+        HIPCHK(c, dv.alloc(sizeof(double) * BQ_DINV_STRIDE * (size_t)batch));
+        HIPCHK(c, inf.alloc(sizeof(int) * (size_t)batch));
+        HIPCHK(c, hipMemcpyAsync(Cd.p, C, Cd.bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(Pd.p, P, Pd.bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(Qd.p, Q, Qd.bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(dv.p, 0, dv.bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(inf.p, 0, inf.bytes, c->stream));
+    }
+    GemmJob g = probe_job(Cd.d(), (long)ldc, Pd.d(), (long)ldp, Qd.d(), (long)ldq, (int)m, (int)n,
+                          (int)k, lower, (int)batch, qt);
+    g.ccut = (int)ccut;
+    g.rows = rows != 0;
+    if (seed_d)
+        g.seed = &sd;
+    if (want_fuse)
+        g.fuse = {(int)j0, dv.d(), BQ_DINV_STRIDE, inf.i()};
+    if (run)
+        BQCHK(launch_gemm(c, BQ_K_GEMM, g, &ran));
+    else
+        ran = gemm_route(c, g);
+    const int32_t r[8] = {(int32_t)ran.kernel, ran.mfma, ran.fused, ran.seeded, ran.assemble_first,
+                          (int32_t)ran.grid.x, (int32_t)ran.grid.y, (int32_t)ran.grid.z};
+    std::memcpy(route, r, sizeof r);
+    if (!run)
+        return BQ_OK;
+    HIPCHK(c, hipMemcpyAsync(C, Cd.p, Cd.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (ran.fused) {
+        // (the reciprocal pivots: the first 64 doubles of every record)
+        HIPCHK(c, hipMemcpy2DAsync(dinv, sizeof(double) * 64, dv.p, sizeof(double) * BQ_DINV_STRIDE,
+                                   sizeof(double) * 64, batch, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(info, inf.p, inf.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return BQ_OK;
 }
 

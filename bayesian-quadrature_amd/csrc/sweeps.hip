@@ -55,9 +55,14 @@ int compute_wide_inverses(bq_ctx *c, const double *L, long ldl, int npad, const 
             BQCHK(launch_trsm_blk(c, X + (long)jb * B, B, xs, bs, L11, ldl, ls,
                                   dw + (long)((J0 + jb) / 64) * BQ_DINV_HALF, ds, batch));
             const int rest = bs - jb - 64;
-            if (rest > 0)
-                BQCHK(launch_gemm(c, BQ_K_GEMM, X + (long)(jb + 64) * B, B, xs, X + (long)jb * B, B,
-                                  xs, L11 + 64, 1, ldl, ls, bs, rest, 64, 0, batch));
+            if (rest > 0) {
+                GemmJob g;
+                g.C = X + (long)(jb + 64) * B, g.ldc = B, g.cstride = xs;
+                g.P = X + (long)jb * B, g.ldp = B, g.pstride = xs;
+                g.Q = L11 + 64, g.qsj = 1, g.qsk = ldl, g.qstride = ls;
+                g.m = bs, g.n = rest, g.k = 64, g.batch = batch;
+                BQCHK(launch_gemm(c, BQ_K_GEMM, g));
+            }
         }
     }
     // NT = the blocks' transposes, behind NR
@@ -80,13 +85,22 @@ int compute_wide_inverses(bq_ctx *c, const double *L, long ldl, int npad, const 
         HIPCHK(c, hipMemsetAsync(uu, 0, sizeof(double) * wide_doubles(npad), c->stream));
         const long bb = (long)B * B, ls = (long)B * (1 + ldl);
         // full blocks J = B .. (nfull - 1) B, then the partial last one
-        if (nfull > 1)
-            BQCHK(launch_gemm(c, BQ_K_GEMM, tmp + bb, B, bb, nt + bb, B, bb, L + B, ldl, 1, ls, B, B,
-                              B, 0, nfull - 1));
+        if (nfull > 1) {
+            GemmJob g;
+            g.C = tmp + bb, g.ldc = B, g.cstride = bb;
+            g.P = nt + bb, g.ldp = B, g.pstride = bb;
+            g.Q = L + B, g.qsj = ldl, g.qsk = 1, g.qstride = ls;
+            g.m = B, g.n = B, g.k = B, g.batch = nfull - 1;
+            BQCHK(launch_gemm(c, BQ_K_GEMM, g));
+        }
         if (rem) {
             const long J = (long)nfull * B;
-            BQCHK(launch_gemm(c, BQ_K_GEMM, tmp + nfull * bb, B, 0, nt + J * B, B, 0,
-                              L + J + (J - B) * ldl, ldl, 1, 0, rem, B, rem, 0, 1));
+            GemmJob g;
+            g.C = tmp + nfull * bb, g.ldc = B;
+            g.P = nt + J * B, g.ldp = B;
+            g.Q = L + J + (J - B) * ldl, g.qsj = ldl, g.qsk = 1;
+            g.m = rem, g.n = B, g.k = rem;
+            BQCHK(launch_gemm(c, BQ_K_GEMM, g));
         }
         for (int part = 0; part < 2; ++part) {
             const int batch = part == 0 ? nfull - 1 : (rem ? 1 : 0), bs = part == 0 ? B : rem;
@@ -96,13 +110,22 @@ int compute_wide_inverses(bq_ctx *c, const double *L, long ldl, int npad, const 
             BQCHK(launch_transpose_blocks(c, tmp + off, tt + off, B, bb, bs / 64, B / 64, batch));
         }
         // U_J for the blocks with a full neighbour below, then the one above the partial block
-        if (nfull > 1)
-            BQCHK(launch_gemm(c, BQ_K_GEMM, uu, B, bb, L + B, ldl, ls, nr, 1, B, bb, B, B, B, 0,
-                              nfull - 1));
+        if (nfull > 1) {
+            GemmJob g;
+            g.C = uu, g.ldc = B, g.cstride = bb;
+            g.P = L + B, g.ldp = ldl, g.pstride = ls;
+            g.Q = nr, g.qsj = 1, g.qsk = B, g.qstride = bb;
+            g.m = B, g.n = B, g.k = B, g.batch = nfull - 1;
+            BQCHK(launch_gemm(c, BQ_K_GEMM, g));
+        }
         if (rem) {
             const long J = (long)(nfull - 1) * B;
-            BQCHK(launch_gemm(c, BQ_K_GEMM, uu + J * B, B, 0, L + J + B + J * ldl, ldl, 0,
-                              nr + J * B, 1, B, 0, rem, B, B, 0, 1));
+            GemmJob g;
+            g.C = uu + J * B, g.ldc = B;
+            g.P = L + J + B + J * ldl, g.ldp = ldl;
+            g.Q = nr + J * B, g.qsj = 1, g.qsk = B;
+            g.m = rem, g.n = B, g.k = B;
+            BQCHK(launch_gemm(c, BQ_K_GEMM, g));
         }
     }
     return BQ_OK;
@@ -156,9 +179,14 @@ int enqueue_forward_rows_blk(bq_ctx *c, double *X, long ldx, int mrows, const do
         BQCHK(launch_trsm_blk(c, X + (long)jb * ldx, ldx, 0, mrows, L11, ldl, 0,
                               dw + (long)(jb / 64) * BQ_DINV_HALF, 0, 1));
         const int rest = npad - jb - 64;
-        if (rest > 0)
-            BQCHK(launch_gemm(c, BQ_K_GEMM, X + (long)(jb + 64) * ldx, ldx, 0, X + (long)jb * ldx,
-                              ldx, 0, L11 + 64, 1, ldl, 0, mrows, rest, 64, 0, 1));
+        if (rest > 0) {
+            GemmJob g;
+            g.C = X + (long)(jb + 64) * ldx, g.ldc = ldx;
+            g.P = X + (long)jb * ldx, g.ldp = ldx;
+            g.Q = L11 + 64, g.qsj = 1, g.qsk = ldl;
+            g.m = mrows, g.n = rest, g.k = 64;
+            BQCHK(launch_gemm(c, BQ_K_GEMM, g));
+        }
     }
     return BQ_OK;
 }

@@ -459,6 +459,64 @@ class Engine(object):
                                       C.cast(C.byref(v), _dp)))
         return float(v.value)
 
+    GEMM_KERNELS = ("Lds128", "Lds64", "Lds64QT", "Sub128", "Sub64", "Sub32", "K64x64", "K64x32",
+                    "SplitK")
+
+    def probe_gemm_product(self, m, n, k, C_=None, P=None, Q=None, lower=0, batch=1, qt=False, ccut=0,
+                           sharing=0, want_fuse=False, j0=0, seed_d=0, rows=False, ldq=0):
+        """ONE product C (m x n) -= P (m x k) Q (n x k)^T per batch element on the caller's operands
+        (bq_probe_gemm_product), and the route the launch took.  C_, P, Q: Fortran-ordered float64
+        arrays whose first axis is the leading dimension and whose columns are the batch elements'
+        side by side -- (ldc, n batch), (ldp, k batch), (ldq, k batch), or with qt (Q k-contiguous)
+        (ldq, n batch) holding Q^T; C_ is updated in place.  Without operands nothing is launched and
+        the route is the engine's answer for the shape (seed_d > 0 only then; ldq: the leading
+        dimension Q would have).
+        Returns {"kernel", "mfma", "fused", "seeded", "assemble_first", "grid"} and, when the launch
+        carried the diagonal factor want_fuse asks for, "dinv" (batch x 64 reciprocal pivots) and
+        "info" (per element: 0, or j0 + the 1-based failing column)."""
+        m, n, k, batch, ccut, j0, seed_d = (int(v) for v in (m, n, k, batch, ccut, j0, seed_d))
+        if m < 16 or m % 16 or n < 16 or n % 16 or k < 8 or k % 8:
+            raise ValueError("m and n must be multiples of 16, k of 8")
+        if batch < 1 or ccut < 0 or j0 < 0:
+            raise ValueError("batch >= 1, ccut >= 0, j0 >= 0")
+        if sharing not in (0, 1, 2):
+            raise ValueError("sharing must be 0, 1 or 2")
+        if seed_d not in (0, 1, 2, 3):
+            raise ValueError("seed_d must be 0 .. 3")
+        if want_fuse and (m < 64 or n < 64):
+            raise ValueError("a fused diagonal factor needs a leading 64 x 64 block")
+        if rows and (lower or batch != 1 or seed_d or want_fuse):
+            raise ValueError("a sweep's product is one full matrix, unseeded, unfused")
+        ops = (C_, P, Q)
+        run = any(a is not None for a in ops)
+        if run:
+            if any(a is None for a in ops):
+                raise ValueError("C_, P and Q come together")
+            if seed_d:
+                raise ValueError("a seeded product is only routed (no operands)")
+            for name, a, rows_min, cols in (("C_", C_, m, n * batch), ("P", P, m, k * batch),
+                                            ("Q", Q, k if qt else n, (n if qt else k) * batch)):
+                if a.dtype != np.float64 or a.ndim != 2 or not a.flags.f_contiguous:
+                    raise ValueError("%s must be a Fortran-ordered float64 matrix" % name)
+                if a.shape[0] < rows_min or a.shape[1] != cols:
+                    raise ValueError("%s must be (ld >= %d, %d)" % (name, rows_min, cols))
+        e = self.probe_engine()
+        route = np.full(8, -1, dtype=np.int32)
+        dinv = np.zeros((batch, 64))
+        info = np.full(batch, -1, dtype=np.int32)
+        e._check(e._lib.bq_probe_gemm_product(
+            e._ctx, L.dptr(C_) if run else None, C_.shape[0] if run else 0,
+            L.dptr(P) if run else None, P.shape[0] if run else 0,
+            L.dptr(Q) if run else None, Q.shape[0] if run else int(ldq), m, n, k, int(lower), batch,
+            1 if qt else 0, ccut, int(sharing), 1 if want_fuse else 0, j0, seed_d, 1 if rows else 0,
+            L.dptr(dinv), info.ctypes.data_as(L._i32p), route.ctypes.data_as(L._i32p)))
+        out = {"kernel": self.GEMM_KERNELS[route[0]], "mfma": int(route[1]), "fused": bool(route[2]),
+               "seeded": bool(route[3]), "assemble_first": bool(route[4]),
+               "grid": tuple(int(v) for v in route[5:8])}
+        if run and out["fused"]:
+            out["dinv"], out["info"] = dinv, info
+        return out
+
     def probe_panel_solve(self, Lfac, X, mode=0, reps=0):
         """X L^-T for a batch of lower-triangular kb x kb factors L (batch, kb, kb) and row blocks
         X (batch, m, kb) through the batched factorisation's panel-solve launches."""

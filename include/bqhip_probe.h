@@ -36,6 +36,24 @@ int bq_probe_xcd_hop(bq_ctx *ctx, int mode, int64_t iters, int64_t kib, double *
  * back-to-back launches -- the tuning probe behind tools/gemm_probe.py */
 int bq_probe_gemm(bq_ctx *ctx, int64_t m, int64_t n, int64_t k, int lower, int64_t batch, int qt,
                   int64_t reps, double *ms);
+/* ONE product C (m x n) -= P (m x k) Q (n x k)^T on the caller's operands, and the route it took.
+ * Packed batch elements, column-major: C ldc x n, P ldp x k, Q ldq x k -- or, qt, Q given
+ * k-contiguous, Q(j, kk) at Q[j ldq + kk], ldq x n.  lower: only the lower trapezoid is needed;
+ * ccut > 0: columns >= ccut need no update; sharing 0 .. 2: how the chip is shared (0 alone, 1 the
+ * two streams of a look-ahead, 2 the two halves of a batch); want_fuse: ask for the diagonal
+ * factor of C's leading 64 x 64 block in the same launch (failures counted from column j0);
+ * seed_d 1 .. 3: a product whose C was left out of the assembly, in seed_d dimensions; rows: a
+ * sweep's product (split-k tiles allowed).  C goes up and comes back whole.  route[8], from the
+ * launch itself: kernel (0 Lds128, 1 Lds64, 2 Lds64QT, 3 Sub128, 4 Sub64, 5 Sub32, 6 K64x64,
+ * 7 K64x32, 8 SplitK), MFMA form of a Sub kernel (4: 4x4x4, 16: 16x16x4, else 0), fused, seeded,
+ * assemble_first, grid x / y / z.  When fused: dinv (64 reciprocal pivots per batch element) and
+ * info (1-based failing column + j0, or 0, per element).  With C = P = Q = NULL nothing is
+ * launched and route[] is the answer for the shape (the only form that takes seed_d > 0).
+ * Status 2 for sizes that are not multiples of 16 (k: 8) or anything else out of range. */
+int bq_probe_gemm_product(bq_ctx *ctx, double *C, int64_t ldc, const double *P, int64_t ldp,
+                          const double *Q, int64_t ldq, int64_t m, int64_t n, int64_t k, int lower,
+                          int64_t batch, int qt, int64_t ccut, int sharing, int want_fuse, int64_t j0,
+                          int seed_d, int rows, double *dinv, int32_t *info, int32_t *route);
 /* `reps` read-only passes over `bytes` with 8-byte-per-lane loads, 512 contiguous bytes per
  * wave (the access pattern of the single-vector sweeps): a known byte count for calibrating
  * the profiler's FETCH_SIZE counter on that pattern; read_gbs may be NULL */
