@@ -67,6 +67,7 @@ SIGNATURES = {
     "bq_gp_set_y": (C.c_int, [_vp, _vp, _dp]),
     "bq_gp_refit_predict": (C.c_int, [_vp, _vp, _dbl, _dp, _dbl, _dp, _i64, _dp, _dp]),
     "bq_gp_append": (C.c_int, [_vp, _vp, _dp, _dp, _i64]),
+    "bq_gp_remove": (C.c_int, [_vp, _vp, _i64p, _i64]),
     "bq_fit_destroy": (None, [_vp, _vp]),
     "bq_gp_logml": (C.c_int, [_vp, _vp, _dp]),
     "bq_gp_logml_grad": (C.c_int, [_vp, _vp, _dp]),

@@ -521,6 +521,158 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
     return BQ_OK;
 }
 
+// Remove k observations from a resident fit under its current hyper-parameters: O(k n^2), no Gram,
+// no refactorisation (remove.h has the arithmetic).  Decided once, here:
+//   trailing   the removed are exactly the last k: no arithmetic on the factor -- in place when the
+//              layout stays (identity back on the new padding), else the compaction alone;
+//   update     everything else: one compaction into buffers of the new layout, then one sweep per 64
+//              removed indices (highest first) from the block column of the sweep's first index.
+// Every buffer is allocated before the first launch and the fit's own buffers are only read until
+// the new ones are swapped in: a failed call leaves the handle exactly as it was.
+extern "C" int bq_gp_remove(bq_ctx *c, bq_fit *f, const int64_t *idx, int64_t k64)
+{
+    BQCHK(check_fit(c, f));
+    if (!idx || k64 < 1 || k64 >= f->n)
+        return fail(c, BQ_ERR_BAD_ARG, "remove: 1 <= k < n indices");
+    const int d = f->d, n = f->n, k = (int)k64, n2 = n - k;
+    std::vector<int> rem, keep;
+    try {
+        rem.resize(k);
+        keep.resize(n2);
+    } catch (const std::bad_alloc &) {
+        return fail(c, BQ_ERR_NOMEM, "out of host memory");
+    }
+    for (int j = 0; j < k; ++j) {
+        if (idx[j] < 0 || idx[j] >= n)
+            return fail(c, BQ_ERR_BAD_ARG, "remove: index %lld out of range [0, %d)",
+                        (long long)idx[j], n);
+        rem[j] = (int)idx[j];
+    }
+    std::sort(rem.begin(), rem.end());
+    for (int j = 1; j < k; ++j)
+        if (rem[j] == rem[j - 1])
+            return fail(c, BQ_ERR_BAD_ARG, "remove: index %d given twice", rem[j]);
+    for (int i = 0, j = 0, o = 0; i < n; ++i) {
+        if (j < k && rem[j] == i)
+            ++j;
+        else
+            keep[o++] = i;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Layout L2 = make_layout(n2, 0, true);
+    const long ldl2 = pick_ld(L2.ntot);
+    const bool trailing = rem[0] == n2;
+    const bool inplace = trailing && L2.npad == f->npad && f->L.M == 0;
+    const int kp = trailing ? 0 : (int)roundup(k, 64);
+
+    // ---- buffers of the new layout, and the side buffers
+    DevBuf nA, npts, ny, ndinv, ndw, nalpha, npanel;
+    if (!inplace) {
+        hipError_t e = hipSuccess;
+        auto A = [&](DevBuf &b, size_t bytes) {
+            if (e == hipSuccess)
+                e = b.alloc(bytes);
+        };
+        A(nA, sizeof(double) * (size_t)ldl2 * L2.ntot);
+        A(npts, sizeof(double) * (size_t)d * L2.ntot);
+        A(ny, sizeof(double) * (size_t)L2.npad);
+        A(ndinv, sizeof(double) * ((size_t)L2.npad + BQ_DINV_STRIDE));
+        A(npanel, sizeof(double) * sweep_route(c, L2.ntot, L2.ntot, 1).ws_doubles);
+        A(ndw, sizeof(double) * BQ_DINV_HALF * (size_t)(L2.npad / 64));
+        A(nalpha, sizeof(double) * (size_t)L2.npad);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                        "remove: the layout of %d points could not be allocated: %s", n2,
+                        hipGetErrorString(e));
+        }
+    }
+    Scratch sc(c);
+    const size_t oout = sc.take(8), oV = sc.take(inplace ? 0 : (size_t)L2.ntot * kp),
+                 oM = sc.take(kp ? BQ_REMOVE_M_DOUBLES : 0),
+                 okeep = sc.take(inplace ? 0 : ((size_t)n2 + 1) / 2),
+                 orem = sc.take(kp ? ((size_t)k + 1) / 2 : 0);
+    BQCHK(sc.commit());
+    double *out = sc.at(oout);
+
+    if (inplace) {
+        BQCHK(launch_remove_trail(c, f->A.d(), f->ldl, f->L.yrow, f->pts.d(), f->y.d(), d, n2, n,
+                                  f->npad));
+        BQCHK(launch_remove_finish(c, f->A.d(), f->ldl, f->L.yrow, n2, f->npad, f->dinv.d(), out));
+    } else {
+        int *dkeep = reinterpret_cast<int *>(sc.at(okeep)), *drem = reinterpret_cast<int *>(sc.at(orem));
+        HIPCHK(c, hipMemcpyAsync(dkeep, keep.data(), sizeof(int) * n2, hipMemcpyHostToDevice,
+                                 c->stream));
+        if (kp)
+            HIPCHK(c, hipMemcpyAsync(drem, rem.data(), sizeof(int) * k, hipMemcpyHostToDevice,
+                                     c->stream));
+        RemoveJob job{};
+        job.A = f->A.d(), job.ldl = f->ldl, job.yrow = f->L.yrow;
+        job.pts = f->pts.d(), job.y = f->y.d();
+        job.keep = dkeep, job.rem = drem;
+        job.A2 = nA.d(), job.ldl2 = ldl2, job.pts2 = npts.d(), job.y2 = ny.d();
+        job.V = sc.at(oV);
+        job.d = d, job.n2 = n2, job.npad2 = L2.npad, job.ntot2 = L2.ntot, job.k = k, job.kp = kp;
+        BQCHK(launch_remove_compact(c, job));
+        // sweep s takes the removed indices 64 s .. 64 s + 63 (ascending): rem[64 s] - 64 s
+        // survivors lie ahead of its first one, and V's columns are zero above that row
+        for (int s = kp / 64 - 1; s >= 0; --s) {
+            const int first = rem[64 * s] - 64 * s;
+            if (first >= n2)
+                continue; // (every survivor lies ahead of this sweep's indices: its V is zero)
+            for (int J = first / 64; J < L2.npad / 64; ++J)
+                BQCHK(launch_remove_step(c, nA.d(), ldl2, job.V + (size_t)64 * s * L2.ntot, L2.ntot,
+                                         J, L2.ntot / 64, sc.at(oM)));
+        }
+        BQCHK(launch_remove_finish(c, nA.d(), ldl2, L2.yrow, n2, L2.npad, ndinv.d(), out));
+    }
+    double hout[6];
+    HIPCHK(c, hipMemcpyAsync(hout, out, sizeof hout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+
+    // ---- bookkeeping: a fit of n - k points in every respect
+    if (!inplace) {
+        auto take = [](DevBuf &dst, DevBuf &src) {
+            std::swap(dst.p, src.p);
+            std::swap(dst.bytes, src.bytes);
+            std::swap(dst.guard, src.guard);
+        };
+        take(f->A, nA), take(f->pts, npts), take(f->y, ny), take(f->dinv, ndinv);
+        take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
+        // everything sized by the old npad goes; the captured sweeps hold the old pointers
+        for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart,
+                          &f->hB})
+            b->release();
+        if (f->hvec)
+            (void)hipHostFree(f->hvec);
+        f->hvec = nullptr;
+        for (int i = 0; i < 3; ++i) {
+            if (f->vgexec[i])
+                (void)hipGraphExecDestroy(f->vgexec[i]);
+            if (f->vgraph[i])
+                (void)hipGraphDestroy(f->vgraph[i]);
+            f->vgexec[i] = nullptr;
+            f->vgraph[i] = nullptr;
+            f->vg_failed[i] = false;
+        }
+        f->L = L2;
+        f->npad = L2.npad;
+        f->ldl = ldl2;
+    }
+    f->n = n2;
+    f->L.n = n2;
+    f->have_alpha = false;
+    f->have_zc = false;
+    f->have_y = false;
+    f->have_hess = false;
+    f->have_wide = false;
+    f->have_dw = false;
+    f->logml = hout[2];
+    f->logdet = hout[3];
+    f->qf = hout[4];
+    return BQ_OK;
+}
+
 extern "C" void bq_fit_destroy(bq_ctx *c, bq_fit *f)
 {
     if (!f)

@@ -10,7 +10,7 @@
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
 //   k_reduce.hip reduce.h trsv.h append.h        read-outs, single-vector sweeps, utilities, the
-//                kernels                        finishing kernels of an append
+//                remove.h kernels               finishing kernels of an append, shrinking a fit
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -175,6 +175,7 @@ struct bq_ctx {
     GaussParams gbuf_host{};
     bool gbuf_valid = false;
     DevBuf dinv64; // potf2 reciprocal-diagonal scratch
+    bool remove_lds_set = false; // remove_diag_kernel's dynamic LDS limit is raised (launch_remove_step)
 };
 
 namespace bqh {
@@ -487,6 +488,15 @@ int launch_append_rhs(bq_ctx *c, const double *yn, const double *vz, int k, doub
 int launch_append_commit(bq_ctx *c, const AppendJob &a);
 int launch_append_grow(bq_ctx *c, double *A, long lda, int r0, int ntot, int yrow,
                        const double *Aold, long ldold, int yold, int ncopy);
+// shrinking a resident fit by k observations (remove.h): the pass into the new layout, the
+// in-place form of a trailing removal, one block column of the update, the scalars
+int launch_remove_compact(bq_ctx *c, const RemoveJob &r);
+int launch_remove_trail(bq_ctx *c, double *A, long ldl, int yrow, double *pts, double *y, int d,
+                        int n2, int n, int npad);
+int launch_remove_step(bq_ctx *c, double *A, long lda, double *V, long ldv, int J, int nblocks,
+                       double *Ms);
+int launch_remove_finish(bq_ctx *c, const double *A, long lda, int yrow, int n, int npad,
+                         double *dinv, double *out);
 
 // ---- potrf.hip ------------------------------------------------------------------------
 // scope of bq_ctx::sharing: how the chip is shared while the launches queued inside it run

@@ -1,10 +1,11 @@
-// k_reduce.hip -- read-outs, single-vector sweeps and small utilities (reduce.h, trsv.h) and
-// their launchers.
+// k_reduce.hip -- read-outs, single-vector sweeps and small utilities (reduce.h, trsv.h), the
+// kernels that grow and shrink a resident fit (append.h, remove.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "trsv.h"
 #include "trsvflow.h"
 #include "append.h"
+#include "remove.h"
 
 namespace bqh {
 
@@ -167,6 +168,63 @@ int launch_append_grow(bq_ctx *c, double *A, long lda, int r0, int ntot, int yro
         return BQ_OK;
     hipLaunchKernelGGL(append_grow_kernel, dim3((ntot - r0 + 255) / 256, ntot), dim3(256), 0,
                        c->stream, A, lda, r0, ntot, yrow, Aold, ldold, yold, ncopy);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// ---- shrinking a resident fit (remove.h; fit.hip, bq_gp_remove) ----
+int launch_remove_compact(bq_ctx *c, const RemoveJob &r)
+{
+    Bracket br(c, BQ_K_REDUCE, 8.0 * r.ntot2 * (0.5 * r.npad2 + r.kp));
+    const dim3 grid(r.ntot2 / 64, r.npad2 / 64 + 1 + r.kp / 64);
+    hipLaunchKernelGGL(remove_compact_kernel, grid, dim3(256), 0, c->stream, r);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_remove_trail(bq_ctx *c, double *A, long ldl, int yrow, double *pts, double *y, int d,
+                        int n2, int n, int npad)
+{
+    Bracket br(c, BQ_K_REDUCE, 8.0 * (n - n2) * npad);
+    hipLaunchKernelGGL(remove_trail_kernel, dim3((npad + 255) / 256), dim3(256), 0, c->stream, A,
+                       ldl, yrow, pts, y, d, n2, n, npad);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// block column J of one sweep: the diagonal launch, then the row blocks below it (nblocks = every
+// 64-row block of the system, the border block included)
+int launch_remove_step(bq_ctx *c, double *A, long lda, double *V, long ldv, int J, int nblocks,
+                       double *Ms)
+{
+    constexpr size_t lds = sizeof(double) * BQ_REMOVE_LDS_DOUBLES;
+    if (J < 0 || J + 1 >= nblocks)
+        return fail(c, BQ_ERR_BAD_ARG, "remove: block column %d of %d", J, nblocks);
+    if (!c->remove_lds_set) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(remove_diag_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        c->remove_lds_set = true;
+    }
+    {
+        Bracket br(c, BQ_K_POTF2, 2.0 * 64 * 64 * 64);
+        hipLaunchKernelGGL(remove_diag_kernel, dim3(1), dim3(256), lds, c->stream, A, lda, V, ldv, J,
+                           Ms);
+        HIPCHK(c, hipGetLastError());
+    }
+    const int below = nblocks - J - 1;
+    Bracket br(c, BQ_K_GEMM, 2.0 * 64 * below * 128 * 128);
+    hipLaunchKernelGGL(remove_rows_kernel, dim3(below), dim3(256), 0, c->stream, A, lda, V, ldv, J,
+                       Ms);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_remove_finish(bq_ctx *c, const double *A, long lda, int yrow, int n, int npad,
+                         double *dinv, double *out)
+{
+    Bracket br(c, BQ_K_REDUCE, 16.0 * npad);
+    hipLaunchKernelGGL(remove_finish_kernel, dim3(1), dim3(256), 0, c->stream, A, lda, yrow, n, npad,
+                       dinv, out);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

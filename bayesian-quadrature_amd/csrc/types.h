@@ -99,6 +99,25 @@ struct AppendJob {
     int d, n, k, kp, yrow;
 };
 
+// Removing k observations from a resident fit (remove.h): what remove_compact_kernel reads of the
+// old fit and writes into buffers of the new layout.
+#define BQ_REMOVE_M_DOUBLES (128 * 128) // the 128 x 128 transform of one block column (scratch)
+struct RemoveJob {
+    // the old fit
+    const double *A;    // bordered factor, z in row yrow
+    long ldl;
+    int yrow;
+    const double *pts, *y;
+    // ascending old indices: the n2 survivors, the k removed
+    const int *keep, *rem;
+    // buffers of the layout of n2 points
+    double *A2;         // ntot2 x ntot2
+    long ldl2;
+    double *pts2, *y2;  // d x ntot2, npad2
+    double *V;          // ntot2 x kp (ld ntot2): L[keep, rem], z[rem] in row npad2
+    int d, n2, npad2, ntot2, k, kp;
+};
+
 // Read-out of a bordered system folded into the one-launch sweep (slab.h): the diagonal factors
 // add their share of log|K| to scal[4b + 1] as they go, and the LAST step's tiles -- the Schur
 // complement of the border -- store what finalize_kernel would read from it (no launch of its own).

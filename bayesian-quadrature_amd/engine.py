@@ -672,6 +672,21 @@ class Fit(object):
         e._check(e._lib.bq_gp_append(e._ctx, self._handle(), L.dptr(x_new), L.dptr(y_new), k))
         self.n += k
 
+    def remove(self, idx):
+        """Remove the observations idx (distinct indices in [0, n), any order, any integer
+        sequence) under the current hyper-parameters (bq_gp_remove): O(k n^2) on the resident
+        factor from the first removed index on, no refactorisation; the survivors keep their
+        order.  ValueError (no index, every point, out of range, a duplicate, a stale or closed
+        fit) leaves the fit as it was."""
+        idx = np.asarray(idx)
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+            raise ValueError("idx must be a non-empty one-dimensional sequence of integers")
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        e = self._eng
+        e._check(e._lib.bq_gp_remove(e._ctx, self._handle(), idx.ctypes.data_as(L._i64p),
+                                     idx.size))
+        self.n -= idx.size
+
     def refit_predict(self, h, w, s, xo):
         """New hyper-parameters and the posterior mean / marginal variance at xo in one sweep
         (bq_gp_refit_predict: the hyper-parameter loop's body)."""

@@ -197,6 +197,45 @@ class GP(object):
         self._x = new_x
         self._y = new_y
 
+    def remove(self, idx):
+        """Drop observations: observably the same as assigning ``np.delete(x, idx)`` and
+        ``np.delete(y, idx)``, but a device fit whose parameters are current shrinks in place
+        (engine.Fit.remove, O(k n^2) on the resident factor) instead of being dropped and rebuilt
+        from nothing -- a sliding window, a retired sample, an outlier.  Indices in [-n, n);
+        a ValueError (out of range, a duplicate, every point) leaves the GP as it was."""
+        idx = np.atleast_1d(np.asarray(idx))
+        if idx.ndim != 1:
+            raise ValueError("idx must be one-dimensional")
+        if idx.size == 0:
+            return
+        if idx.dtype.kind not in "iu":
+            raise ValueError("idx must hold integers")
+        n = self._x.size
+        idx = idx.astype(np.int64)
+        if ((idx < -n) | (idx >= n)).any():
+            raise ValueError("index out of range for %d observations" % n)
+        idx = np.where(idx < 0, idx + n, idx)
+        if np.unique(idx).size != idx.size:
+            raise ValueError("an index is given twice")
+        if idx.size >= n:
+            raise ValueError("cannot remove every observation")
+        new_x = np.delete(self._x, idx)
+        new_y = np.delete(self._y, idx)
+        fit = getattr(self, "_fit", None)
+        params = (self.K.h, self.K.w, self._s)
+        if fit is not None and self._fit_params == params and hasattr(fit, "remove"):
+            try:
+                fit.remove(idx)
+            except (ValueError, RuntimeError, MemoryError,  # the engine's error types
+                    np.linalg.LinAlgError):
+                self._invalidate()
+            else:
+                self._memoized = {}
+        else:
+            self._invalidate()
+        self._x = new_x
+        self._y = new_y
+
     @property
     def s(self):
         return self._s

@@ -175,6 +175,16 @@ int bq_gp_refit_predict(bq_ctx *ctx, bq_fit *fit, double h, const double *w, dou
  * left exactly as it was (n, factor, z, log-ML, alpha: same bits).
  * BQ_ERR_BAD_ARG: stale fit ("refit required", as every consumer), null / k < 1 / non-finite. */
 int bq_gp_append(bq_ctx *ctx, bq_fit *fit, const double *x_new, const double *y_new, int64_t k);
+/* Remove the k observations idx[0 .. k) (distinct indices in [0, n), any order) from a resident fit
+ * under its current hyper-parameters; the survivors keep their relative order.  Afterwards the
+ * handle is a fit of n - k points in every respect.  O(k n^2) from the block column of the first
+ * removed index on: no Gram, no refactorisation; removing the last k observations costs no
+ * arithmetic on the factor at all.  A positive-semidefinite matrix is added to the compacted
+ * factor's product, so there is no BQ_ERR_NOT_PD outcome.
+ * BQ_ERR_BAD_ARG: stale fit ("refit required", as every consumer), null / k < 1 / k >= n / an index
+ * out of range or given twice.  BQ_ERR_NOMEM / BQ_ERR_HIP: only from allocation, and before
+ * anything is written: a failed call leaves the fit exactly as it was. */
+int bq_gp_remove(bq_ctx *ctx, bq_fit *fit, const int64_t *idx, int64_t k);
 void bq_fit_destroy(bq_ctx *ctx, bq_fit *fit);
 int bq_gp_logml(bq_ctx *ctx, bq_fit *fit, double *out);
 /* gradient of the fit's log marginal likelihood with respect to its hyper-parameters:
@@ -189,7 +199,7 @@ int bq_gp_logml_grad(bq_ctx *ctx, bq_fit *fit, double *grad);
  * null handle or pointer; BQ_ERR_NOMEM when the workspace cannot be allocated, with nothing
  * half-made left behind).  The first call builds what the gradient keeps (L^-T) if it is not
  * there, and d npad^2 doubles of device memory more, kept with the fit; the result is kept until
- * the next (re)fit, bq_gp_set_y or bq_gp_append.  The fit itself is not disturbed. */
+ * the next (re)fit, bq_gp_set_y, bq_gp_append or bq_gp_remove.  The fit itself is not disturbed. */
 int bq_gp_logml_hess(bq_ctx *ctx, bq_fit *fit, double *hess);
 /* which: 0 = L (n x n, strict upper zeroed), 1 = alpha = Kxx^-1 y (n),
  * 2 = z = L^-1 y (n), 3 = Kxx (n x n, recomputed) */
