@@ -31,6 +31,9 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     f->have_dw = false;
     f->have_y = false;
     f->have_hess = false;
+    f->have_prod = false;
+    f->have_loo = false;
+    f->have_loo_grad = false;
     // pinned staging: [0, 136) results, then the kernel parameters, then border points
     if (!f->hfit)
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
@@ -265,6 +268,9 @@ extern "C" int bq_gp_set_y(bq_ctx *c, bq_fit *f, const double *y)
     f->have_zc = false;
     f->have_y = false;
     f->have_hess = false;
+    f->have_prod = false;
+    f->have_loo = false;
+    f->have_loo_grad = false;
     HIPCHK(c, hipMemcpyAsync(f->y.p, y, sizeof(double) * f->n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // y is the caller's buffer
     return BQ_OK;
@@ -489,7 +495,7 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
         take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
         // everything sized by the old npad goes; the captured sweeps hold the old pointers
         for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart,
-                          &f->hB})
+                          &f->hB, &f->loo})
             b->release();
         if (f->hvec)
             (void)hipHostFree(f->hvec);
@@ -513,6 +519,9 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
     f->have_zc = false;
     f->have_y = false;
     f->have_hess = false;
+    f->have_prod = false;
+    f->have_loo = false;
+    f->have_loo_grad = false;
     f->have_wide = false;
     f->have_dw = false;
     f->logml = hm[2];
@@ -641,7 +650,7 @@ extern "C" int bq_gp_remove(bq_ctx *c, bq_fit *f, const int64_t *idx, int64_t k6
         take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
         // everything sized by the old npad goes; the captured sweeps hold the old pointers
         for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart,
-                          &f->hB})
+                          &f->hB, &f->loo})
             b->release();
         if (f->hvec)
             (void)hipHostFree(f->hvec);
@@ -665,6 +674,9 @@ extern "C" int bq_gp_remove(bq_ctx *c, bq_fit *f, const int64_t *idx, int64_t k6
     f->have_zc = false;
     f->have_y = false;
     f->have_hess = false;
+    f->have_prod = false;
+    f->have_loo = false;
+    f->have_loo_grad = false;
     f->have_wide = false;
     f->have_dw = false;
     f->logml = hout[2];
@@ -721,6 +733,9 @@ static int fit_y(bq_ctx *c, bq_fit *f)
     BQCHK(enqueue_inverse_rows(c, f->gX.d(), f->gY.d(), f->A.d(), f->ldl, npad, w));
     f->have_y = true;
     f->have_hess = false; // (Kxx^-1 lived in the sweep's workspace)
+    f->have_prod = false;
+    f->have_loo = false;
+    f->have_loo_grad = false;
     return BQ_OK;
 }
 
@@ -758,6 +773,35 @@ extern "C" int bq_gp_logml_grad(bq_ctx *c, bq_fit *f, double *grad)
     return BQ_OK;
 }
 
+// the Hessian's workspace beside Kxx^-1 (hess_ws_doubles), kept with the fit
+static int fit_hess_ws(bq_ctx *c, bq_fit *f)
+{
+    const size_t bytes = sizeof(double) * hess_ws_doubles(f->npad, f->d);
+    if (f->hB.bytes < bytes) {
+        f->hB.release();
+        hipError_t e = f->hB.alloc(bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                        "Hessian workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+    }
+    return BQ_OK;
+}
+
+static HessJob fit_hess_job(const bq_fit *f)
+{
+    HessJob hj;
+    hj.pts = f->pts.d();
+    hj.alpha = f->alpha.d();
+    hj.g = f->g;
+    for (int k = 0; k < BQ_MAXD; ++k)
+        hj.iw[k] = k < f->d ? 1.0 / f->w[k] : 0.0;
+    hj.n = f->n;
+    hj.npad = f->npad;
+    return hj;
+}
+
 // d^2 log p / d theta^2 in the gradient's parameter order (hess.h has the formula): Kxx^-1 = Y Y^T
 // into the sweep's idle workspace, one MFMA product Kxx^-1 dK/dw_k per length scale with the
 // derivative generated from the points, tile sums and the quadratic terms on the device; the
@@ -768,31 +812,16 @@ extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
     if (!hess)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     HIPCHK(c, hipSetDevice(c->device));
-    const int d = f->d, npad = f->npad, np = d + 2;
+    const int d = f->d, np = d + 2;
     if (!f->have_hess) {
         BQCHK(fit_alpha(c, f));
         BQCHK(fit_y(c, f));
-        const size_t bytes = sizeof(double) * hess_ws_doubles(npad, d);
-        if (f->hB.bytes < bytes) {
-            f->hB.release();
-            hipError_t e = f->hB.alloc(bytes);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                            "Hessian workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
-            }
-        }
-        HessJob hj;
-        hj.pts = f->pts.d();
-        hj.alpha = f->alpha.d();
-        hj.g = f->g;
-        for (int k = 0; k < BQ_MAXD; ++k)
-            hj.iw[k] = k < d ? 1.0 / f->w[k] : 0.0;
-        hj.n = f->n;
-        hj.npad = npad;
+        BQCHK(fit_hess_ws(c, f));
+        const HessJob hj = fit_hess_job(f);
         const double *sums = nullptr;
         BQCHK(launch_logml_hess(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h, f->s,
-                                &sums));
+                                f->have_prod, &sums));
+        f->have_prod = true;
         const int ng = hess_ng(d), nt = hess_nt(d), nq = hess_nq(d);
         double hs[hess_ng(BQ_MAXD) + hess_nt(BQ_MAXD) + hess_nq(BQ_MAXD)];
         HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof(double) * (ng + nt + nq), hipMemcpyDeviceToHost,
@@ -824,6 +853,99 @@ extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
     }
     for (int i = 0; i < np * np; ++i)
         hess[i] = f->hess[i];
+    return BQ_OK;
+}
+
+// the leave-one-out workspace (loo_ws_doubles), kept with the fit
+static int fit_loo_ws(bq_ctx *c, bq_fit *f)
+{
+    const size_t bytes = sizeof(double) * loo_ws_doubles(f->npad, f->d);
+    if (f->loo.bytes < bytes) {
+        f->loo.release();
+        hipError_t e = f->loo.alloc(bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                        "leave-one-out workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
+        }
+    }
+    return BQ_OK;
+}
+
+// mu | var | lp on the device (npad apart behind k, q and the t_k) and L_loo in the handle
+static int fit_loo(bq_ctx *c, bq_fit *f)
+{
+    if (f->have_loo)
+        return BQ_OK;
+    BQCHK(fit_loo_ws(c, f));
+    BQCHK(fit_alpha(c, f));
+    BQCHK(fit_y(c, f));
+    const double *vecs = nullptr, *total = nullptr;
+    BQCHK(launch_loo(c, f->d, f->gY.d(), f->alpha.d(), f->y.d(), f->n, f->npad, f->loo.d(), &vecs,
+                     &total));
+    HIPCHK(c, hipMemcpyAsync(&f->loo_total, total, sizeof(double), hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->have_loo = true;
+    return BQ_OK;
+}
+
+// Leave-one-out cross-validation (loo.h has the formulas): the predictive mean, variance and log
+// density of every observation from the n - 1 others, and their sum, from diag Kxx^-1 -- the row
+// sums of squares of Y = L^-T -- and alpha.  Kept until the fit changes.
+extern "C" int bq_gp_loo(bq_ctx *c, bq_fit *f, double *mean, double *var, double *logpred,
+                         double *total)
+{
+    BQCHK(check_fit(c, f));
+    if (!mean && !var && !logpred && !total)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    BQCHK(fit_loo(c, f));
+    const double *vecs = f->loo.d() + (size_t)(f->d + 2) * f->npad;
+    double *outs[3] = {mean, var, logpred};
+    for (int v = 0; v < 3; ++v)
+        if (outs[v])
+            HIPCHK(c, hipMemcpyAsync(outs[v], vecs + (size_t)v * f->npad, sizeof(double) * f->n,
+                                     hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (total)
+        *total = f->loo_total;
+    return BQ_OK;
+}
+
+// dL_loo / dtheta in the gradient's parameter order: the Hessian's products stage (Kxx^-1, the d
+// products Kxx^-1 dK/dw_k, the vectors Kxx^-1 D_p a) if neither it nor a Hessian has run since the
+// fit last changed, then one read of those matrices for the row sums and one workgroup for the
+// d + 2 entries.  Both workspaces are allocated before anything is launched.
+extern "C" int bq_gp_loo_grad(bq_ctx *c, bq_fit *f, double *total, double *grad)
+{
+    BQCHK(check_fit(c, f));
+    if (!grad)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d;
+    if (!f->have_loo_grad) {
+        BQCHK(fit_hess_ws(c, f));
+        BQCHK(fit_loo_ws(c, f));
+        BQCHK(fit_loo(c, f));
+        if (!f->have_prod) {
+            const HessJob hj = fit_hess_job(f);
+            BQCHK(launch_hess_products(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h,
+                                       f->s));
+            f->have_prod = true;
+        }
+        const double *gd = nullptr;
+        BQCHK(launch_loo_grad(c, d, f->gX.d(), f->hB.d(), f->alpha.d(), f->n, f->npad, f->h, f->s,
+                              f->g.s2, f->loo.d(), &gd));
+        HIPCHK(c, hipMemcpyAsync(f->loo_grad, gd, sizeof(double) * (d + 2), hipMemcpyDeviceToHost,
+                                 c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        f->have_loo_grad = true;
+    }
+    for (int p = 0; p < d + 2; ++p)
+        grad[p] = f->loo_grad[p];
+    if (total)
+        *total = f->loo_total;
     return BQ_OK;
 }
 

@@ -371,7 +371,16 @@ int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob
 // the log-ML Hessian's sums (hess.h) into the workspace; *sums: where they are on the device
 size_t hess_ws_doubles(int npad, int d);
 int launch_logml_hess(bq_ctx *c, int d, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                      const double *y, double h, double s, const double **sums);
+                      const double *y, double h, double s, bool have_prod, const double **sums);
+// its products stage alone (Ki, B_k, D_p a, Ki D_p a); launch_logml_hess with have_prod runs the rest
+int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *ws,
+                         const HessJob &hj, const double *y, double h, double s);
+// leave-one-out (loo.h) into its own workspace; *vecs: mu | var | lp, npad apart
+size_t loo_ws_doubles(int npad, int d);
+int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const double *y, int n,
+               int npad, double *ws, const double **vecs, const double **total);
+int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const double *alpha,
+                    int n, int npad, double h, double s, double s2, double *ws, const double **grad);
 
 // ---- k_gemm.hip (continued) -----------------------------------------------------------
 // One product C(m x n) -= P(m x k) Q(n x k)^T per batch element, as operands and a shape.
@@ -675,6 +684,15 @@ struct bq_fit {
     DevBuf hB;
     bool have_hess = false;
     double hess[(BQ_MAXD + 2) * (BQ_MAXD + 2)] = {0};
+    bool have_prod = false; // gX and hB hold the Hessian's products stage (Kxx^-1, the d products, the
+                            // vectors D_p a and Kxx^-1 D_p a): the Hessian and the LOO gradient
+                            // both read it, whichever comes first runs it
+    // leave-one-out (bq_gp_loo, bq_gp_loo_grad): diag Kxx^-1, the row sums, mean / variance / log
+    // density per point and the partial sums (loo_ws_doubles), allocated on the first call; the
+    // results until the next (re)fit, new targets, append or remove
+    DevBuf loo;
+    bool have_loo = false, have_loo_grad = false;
+    double loo_total = 0, loo_grad[BQ_MAXD + 2] = {0};
     bool have_zc = false; // wz holds z = L^-1 y contiguously (gathered from the factor's y row on
                           // the first posterior after a (re)fit: the row reductions then read one
                           // line per 8 entries instead of one per entry)

@@ -1,6 +1,8 @@
-// k_hess.hip -- the log-ML Hessian's kernels (hess.h) and their launcher.
+// k_hess.hip -- the log-ML Hessian's kernels (hess.h), the leave-one-out kernels that read its
+// products (loo.h), and their launchers.
 #include "host.h"
 #include "hess.h"
+#include "loo.h"
 
 namespace bqh {
 
@@ -34,14 +36,13 @@ static void hess_launch_prod(bq_ctx *c, bool tall, double *C, const double *A, c
                            C, A, Q, hj, kdim);
 }
 
+// Ki = Y Y^T and the d products B_k = Ki D_k
 template <int D>
-static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                    const double *y, double h, double s)
+static int hess_run_prods(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj)
 {
-    const int npad = hj.npad, n = hj.n;
+    const int npad = hj.npad;
     const bool tall = hess_tall(c, npad);
-    double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
-    double *part = ws + hess_off_part(npad, D), *sums = ws + hess_off_sums(npad, D);
+    double *B = ws;
     const double n3 = (double)npad * npad * npad;
     {
         Bracket br(c, BQ_K_GEMM, n3 * 2.0 / 3.0);
@@ -53,6 +54,44 @@ static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const He
         hess_launch_prod<D>(c, tall, B + (size_t)k * npad * npad, Ki, nullptr, hj, k);
         HIPCHK(c, hipGetLastError());
     }
+    return BQ_OK;
+}
+
+// V = D_p a and Z = Ki V
+template <int D>
+static void hess_launch_vecs(bq_ctx *c, const double *Ki, double *ws, const HessJob &hj,
+                             const double *y, double h, double s)
+{
+    const int npad = hj.npad;
+    double *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
+    hipLaunchKernelGGL(hess_dka_kernel<D>, dim3((unsigned)npad / 16), dim3(256), 0, c->stream, hj, y,
+                       2.0 / h, 2.0 * s, V);
+    hipLaunchKernelGGL(hess_kiv_kernel, dim3((unsigned)npad / 4), dim3(256), 0, c->stream, Ki, hj.n,
+                       npad, D + 2, V, Z);
+}
+
+// The products stage alone (what bq_gp_loo_grad needs of the Hessian): Ki, B_k, V, Z
+template <int D>
+static int hess_run_products(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj,
+                             const double *y, double h, double s)
+{
+    BQCHK(hess_run_prods<D>(c, Y, Ki, ws, hj));
+    Bracket br(c, BQ_K_REDUCE);
+    hess_launch_vecs<D>(c, Ki, ws, hj, y, h, s);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// have_prod: Ki, B_k, V and Z are there (the products stage has run on this fit): only the sums
+template <int D>
+static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj,
+                    const double *y, double h, double s, bool have_prod)
+{
+    const int npad = hj.npad, n = hj.n;
+    double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
+    double *part = ws + hess_off_part(npad, D), *sums = ws + hess_off_sums(npad, D);
+    if (!have_prod)
+        BQCHK(hess_run_prods<D>(c, Y, Ki, ws, hj));
     Bracket br(c, BQ_K_REDUCE);
     const unsigned g64 = (unsigned)npad / 64;
     const int nwg = (int)(g64 * g64);
@@ -63,10 +102,8 @@ static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const He
                        part);
     hipLaunchKernelGGL(hess_finalize_kernel, dim3(hess_nt(D)), dim3(256), 0, c->stream, part, nwg,
                        sums + hess_ng(D));
-    hipLaunchKernelGGL(hess_dka_kernel<D>, dim3((unsigned)npad / 16), dim3(256), 0, c->stream, hj, y,
-                       2.0 / h, 2.0 * s, V);
-    hipLaunchKernelGGL(hess_kiv_kernel, dim3((unsigned)npad / 4), dim3(256), 0, c->stream, Ki, n,
-                       npad, D + 2, V, Z);
+    if (!have_prod)
+        hess_launch_vecs<D>(c, Ki, ws, hj, y, h, s);
     hipLaunchKernelGGL(hess_quad_kernel, dim3(1), dim3(256), 0, c->stream, V, Z, n, npad, D + 2,
                        sums + hess_ng(D) + hess_nt(D));
     HIPCHK(c, hipGetLastError());
@@ -75,22 +112,113 @@ static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const He
 
 // The sums of one Hessian (types.h: hess_ng + hess_nt + hess_nq of them, at *sums inside ws) from
 // Y = L^-T (npad x npad, zero below its diagonal) and the fit's alpha.  Ki: npad^2 doubles, left
-// holding Kxx^-1; ws: hess_ws_doubles(npad, d).
+// holding Kxx^-1; ws: hess_ws_doubles(npad, d).  have_prod: launch_hess_products has run on these
+// buffers since the fit last changed, and its launches are left out.
 int launch_logml_hess(bq_ctx *c, int d, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                      const double *y, double h, double s, const double **sums)
+                      const double *y, double h, double s, bool have_prod, const double **sums)
 {
     if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
         return fail(c, BQ_ERR_BAD_ARG, "logml_hess: d in [1, %d], npad a multiple of 64", BQ_MAXD);
     *sums = ws + hess_off_sums(hj.npad, d);
     switch (d) {
-    case 1: return hess_run<1>(c, Y, Ki, ws, hj, y, h, s);
-    case 2: return hess_run<2>(c, Y, Ki, ws, hj, y, h, s);
-    case 3: return hess_run<3>(c, Y, Ki, ws, hj, y, h, s);
-    case 4: return hess_run<4>(c, Y, Ki, ws, hj, y, h, s);
-    case 5: return hess_run<5>(c, Y, Ki, ws, hj, y, h, s);
-    case 6: return hess_run<6>(c, Y, Ki, ws, hj, y, h, s);
-    case 7: return hess_run<7>(c, Y, Ki, ws, hj, y, h, s);
-    default: return hess_run<8>(c, Y, Ki, ws, hj, y, h, s);
+    case 1: return hess_run<1>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    case 2: return hess_run<2>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    case 3: return hess_run<3>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    case 4: return hess_run<4>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    case 5: return hess_run<5>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    case 6: return hess_run<6>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    case 7: return hess_run<7>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    default: return hess_run<8>(c, Y, Ki, ws, hj, y, h, s, have_prod);
+    }
+}
+
+// The Hessian's products stage on its own: Ki = Y Y^T, B_k = Ki D_k, V = D_p a, Z = Ki V -- the
+// launches of launch_logml_hess that its sums read, with the same results.
+int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *ws,
+                         const HessJob &hj, const double *y, double h, double s)
+{
+    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
+        return fail(c, BQ_ERR_BAD_ARG, "hess_products: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    switch (d) {
+    case 1: return hess_run_products<1>(c, Y, Ki, ws, hj, y, h, s);
+    case 2: return hess_run_products<2>(c, Y, Ki, ws, hj, y, h, s);
+    case 3: return hess_run_products<3>(c, Y, Ki, ws, hj, y, h, s);
+    case 4: return hess_run_products<4>(c, Y, Ki, ws, hj, y, h, s);
+    case 5: return hess_run_products<5>(c, Y, Ki, ws, hj, y, h, s);
+    case 6: return hess_run_products<6>(c, Y, Ki, ws, hj, y, h, s);
+    case 7: return hess_run_products<7>(c, Y, Ki, ws, hj, y, h, s);
+    default: return hess_run_products<8>(c, Y, Ki, ws, hj, y, h, s);
+    }
+}
+
+// ---- leave-one-out (loo.h) ---------------------------------------------------------------
+// device workspace of one fit's LOO: [k | q | t_1 .. t_d | mu | var | lp | partials | total, grad]
+static int loo_chunks(int npad) { return (npad + BQ_LOO_CW - 1) / BQ_LOO_CW; }
+static size_t loo_off_part(int npad, int d) { return (size_t)(d + 5) * npad; }
+static size_t loo_off_out(int npad, int d)
+{
+    return loo_off_part(npad, d) + (size_t)(1 + d) * loo_chunks(npad) * npad;
+}
+size_t loo_ws_doubles(int npad, int d) { return loo_off_out(npad, d) + (size_t)(d + 3); }
+
+// mu, var, lp (n each, at *vecs, npad apart) and L_loo (at *total) from Y = L^-T, alpha and y
+int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const double *y, int n,
+               int npad, double *ws, const double **vecs, const double **total)
+{
+    if (d < 1 || d > BQ_MAXD || (npad % 64))
+        return fail(c, BQ_ERR_BAD_ARG, "loo: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    double *kd = ws, *mu = ws + (size_t)(d + 2) * npad;
+    double *part = ws + loo_off_part(npad, d), *out = ws + loo_off_out(npad, d);
+    const int nch = loo_chunks(npad);
+    Bracket br(c, BQ_K_REDUCE);
+    hipLaunchKernelGGL(loo_diag_kernel, dim3((unsigned)npad / 64, (unsigned)nch), dim3(256), 0,
+                       c->stream, Y, n, npad, part);
+    hipLaunchKernelGGL(loo_fold_kernel, dim3((unsigned)(npad + 255) / 256, 1), dim3(256), 0,
+                       c->stream, part, nch, npad, kd);
+    hipLaunchKernelGGL(loo_point_kernel, dim3(1), dim3(256), 0, c->stream, y, alpha, kd, n, mu,
+                       mu + npad, mu + 2 * (size_t)npad, out);
+    HIPCHK(c, hipGetLastError());
+    *vecs = mu;
+    *total = out;
+    return BQ_OK;
+}
+
+template <int D>
+static int loo_grad_run(bq_ctx *c, const double *Ki, const double *hws, const double *alpha, int n,
+                        int npad, double h, double s, double s2, double *ws)
+{
+    const double *B = hws, *Z = hws + hess_off_v(npad, D) + (size_t)(D + 2) * npad;
+    double *kd = ws, *q = ws + npad;
+    double *part = ws + loo_off_part(npad, D), *out = ws + loo_off_out(npad, D);
+    const int nch = loo_chunks(npad);
+    Bracket br(c, BQ_K_REDUCE);
+    hipLaunchKernelGGL(loo_rows_kernel<D>, dim3((unsigned)npad / 64, (unsigned)nch), dim3(256), 0,
+                       c->stream, Ki, B, n, npad, part);
+    hipLaunchKernelGGL(loo_fold_kernel, dim3((unsigned)(npad + 255) / 256, 1 + D), dim3(256), 0,
+                       c->stream, part, nch, npad, q);
+    hipLaunchKernelGGL(loo_grad_kernel<D>, dim3(1), dim3(256), 0, c->stream, alpha, kd, q,
+                       q + npad, Z, n, npad, 2.0 / h, s, s2, out + 1);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// The d + 2 entries of dL_loo / dtheta (at *grad) from what launch_loo left in ws (k) and the
+// Hessian's products stage left in Ki and hws (B_k, Z).
+int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const double *alpha,
+                    int n, int npad, double h, double s, double s2, double *ws, const double **grad)
+{
+    if (d < 1 || d > BQ_MAXD || (npad % 64))
+        return fail(c, BQ_ERR_BAD_ARG, "loo_grad: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    *grad = ws + loo_off_out(npad, d) + 1;
+    switch (d) {
+    case 1: return loo_grad_run<1>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    case 2: return loo_grad_run<2>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    case 3: return loo_grad_run<3>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    case 4: return loo_grad_run<4>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    case 5: return loo_grad_run<5>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    case 6: return loo_grad_run<6>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    case 7: return loo_grad_run<7>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
+    default: return loo_grad_run<8>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
     }
 }
 

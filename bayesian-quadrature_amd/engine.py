@@ -724,6 +724,27 @@ class Fit(object):
         e._check(e._lib.bq_gp_logml_hess(e._ctx, self._handle(), L.dptr(H)))
         return H
 
+    def loo(self):
+        """Leave-one-out cross-validation (bq_gp_loo): (mean, var, logpred, total) -- the
+        predictive mean, variance (of the noisy observation) and log density of every y_i from
+        the other n - 1 observations, (n,) each, and the sum of logpred."""
+        mean, var, lp = np.empty(self.n), np.empty(self.n), np.empty(self.n)
+        total = C.c_double()
+        e = self._eng
+        e._check(e._lib.bq_gp_loo(e._ctx, self._handle(), L.dptr(mean), L.dptr(var), L.dptr(lp),
+                                  C.cast(C.byref(total), _dp)))
+        return mean, var, lp, float(total.value)
+
+    def loo_grad(self):
+        """(total, grad): the leave-one-out log predictive density and its gradient, (d + 2,) in
+        the order of ``logml_grad`` (bq_gp_loo_grad)."""
+        g = np.empty(self.d + 2)
+        total = C.c_double()
+        e = self._eng
+        e._check(e._lib.bq_gp_loo_grad(e._ctx, self._handle(), C.cast(C.byref(total), _dp),
+                                       L.dptr(g)))
+        return float(total.value), g
+
     def _get(self, which, shape):
         out = np.empty(shape, order="F")
         e = self._eng

@@ -313,6 +313,28 @@ class GP(object):
         ``dloglh_dtheta``."""
         return self._memo("d2loglh_dtheta2", lambda: self._device_fit().logml_hess())
 
+    def loo(self):
+        """Leave-one-out cross-validation at the current parameters: (mean, var, logpred), the
+        predictive mean, variance (of the noisy observation: s^2 included) and log density of
+        every y_i from the other n - 1 observations (bq_gp_loo: closed form on the device fit,
+        nothing refitted); memoised like ``log_lh``.  ``argmin`` of logpred is the observation
+        the model predicts worst -- a candidate for ``remove``."""
+        return self._memo("loo_points", lambda: self._loo()[:3])
+
+    def _loo(self):
+        return self._memo("loo", lambda: self._device_fit().loo())
+
+    @property
+    def log_loo(self):
+        """The leave-one-out log predictive density, the sum of ``loo()[2]``; memoised."""
+        return self._loo()[3]
+
+    @property
+    def dlogloo_dtheta(self):
+        """Gradient of ``log_loo`` in the order of ``params``, [d/dh, d/dw, d/ds], from the
+        device fit (bq_gp_loo_grad); memoised like ``dloglh_dtheta``."""
+        return self._memo("dlogloo_dtheta", lambda: self._device_fit().loo_grad()[1])
+
     def hyper_cov(self, params):
         """Laplace covariance of the named subset of ("h", "w", "s") at the current parameters:
         the inverse of minus the Hessian of ``log_lh`` restricted to them, in their own units
@@ -331,9 +353,11 @@ class GP(object):
         C = np.linalg.inv(A)
         return 0.5 * (C + C.T)
 
-    def fit_MLII(self, params, method="L-BFGS-B", ntry=10):
+    def fit_MLII(self, params, method="L-BFGS-B", ntry=10, objective="log_lh"):
         """Maximise ``log_lh`` over the named subset of ("h", "w", "s") with the exact gradient
-        (util.find_good_parameters with ``logpdf_grad``).
+        (util.find_good_parameters with ``logpdf_grad``).  ``objective="loo"`` maximises the
+        leave-one-out log predictive density ``log_loo`` with ``dlogloo_dtheta`` instead; any
+        other objective is a ValueError.
 
         Positivity by reparametrisation: the search runs over log h, log w and log s, so every
         point it evaluates has h, w, s > 0 and none lies on the edge s = 0, where Kxx of close
@@ -341,6 +365,9 @@ class GP(object):
         An s that starts at exactly 0 has no logarithm: it is searched as it is, under the
         L-BFGS-B bound s >= 0.  Leaves the GP at the optimum and returns the optimiser's summary
         (x in the parameters' own units); RuntimeError when no optimum is found."""
+        if objective not in ("log_lh", "loo"):
+            raise ValueError("objective: 'log_lh' or 'loo'")
+        loo = objective == "loo"
         names = ("h", "w", "s")
         params = list(params)
         if not params or any(p not in names for p in params) or len(set(params)) != len(params):
@@ -361,7 +388,7 @@ class GP(object):
         def logpdf(u):
             try:
                 set_all(theta(u))
-                return self.log_lh
+                return self.log_loo if loo else self.log_lh
             except (ValueError, np.linalg.LinAlgError):
                 return -np.inf
 
@@ -370,7 +397,8 @@ class GP(object):
             if not np.isfinite(f):
                 return f, np.zeros(len(params))
             t = theta(u)
-            return f, self.dloglh_dtheta[idx] * np.where(logp, t, 1.0)
+            g = self.dlogloo_dtheta if loo else self.dloglh_dtheta
+            return f, g[idx] * np.where(logp, t, 1.0)
 
         u = util.find_good_parameters(logpdf, u0, method, ntry=ntry, logpdf_grad=logpdf_grad,
                                       bounds=bounds if method == "L-BFGS-B" else None)
@@ -380,7 +408,8 @@ class GP(object):
         x = theta(u)
         set_all(x)
         opt = util.LAST_OPT
-        return optim.OptimizeResult(x=x, fun=-self.log_lh, success=opt.get("success", False),
+        fun = -(self.log_loo if loo else self.log_lh)
+        return optim.OptimizeResult(x=x, fun=fun, success=opt.get("success", False),
                                     nfev=opt.get("nfev", -1), nit=opt.get("nit", -1),
                                     attempts=opt.get("attempts", -1))
 

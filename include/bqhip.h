@@ -201,6 +201,23 @@ int bq_gp_logml_grad(bq_ctx *ctx, bq_fit *fit, double *grad);
  * there, and d npad^2 doubles of device memory more, kept with the fit; the result is kept until
  * the next (re)fit, bq_gp_set_y, bq_gp_append or bq_gp_remove.  The fit itself is not disturbed. */
 int bq_gp_logml_hess(bq_ctx *ctx, bq_fit *fit, double *hess);
+/* Leave-one-out cross-validation of the fit (Rasmussen & Williams 5.4.2): mean[i] and var[i] are
+ * the predictive mean and variance of the noisy observation y_i (s^2 included) from the other
+ * n - 1 observations, logpred[i] its log density at y_i, *total the sum of the logpred.  mean,
+ * var, logpred: n doubles each on the host or NULL; total: one double or NULL; not all four NULL.
+ * Closed form from diag Kxx^-1 and Kxx^-1 y: O(n^2) once L^-T is there (the gradient keeps it;
+ * the first call builds it if not), nothing refitted.  Same status rules as bq_gp_logml_hess.
+ * The same bits on every call and whichever of the gradient, the Hessian or bq_gp_loo_grad ran
+ * before; kept until the next (re)fit, bq_gp_set_y, bq_gp_append or bq_gp_remove. */
+int bq_gp_loo(bq_ctx *ctx, bq_fit *fit, double *mean, double *var, double *logpred,
+              double *total);
+/* Gradient of that total with respect to the hyper-parameters, in the order of bq_gp_logml_grad:
+ * grad has d + 2 entries on the host (required); total: the value, or NULL.  Reads what the
+ * Hessian keeps (Kxx^-1 and one n x n x n product per length scale: built here if no Hessian has
+ * been taken since the fit last changed, and then not built again by bq_gp_logml_hess); beyond
+ * that O((d + 1) n^2).  Device memory: the Hessian's, and (d + 5) npad doubles and partial sums
+ * more, all allocated before anything runs: BQ_ERR_NOMEM leaves the fit as it was. */
+int bq_gp_loo_grad(bq_ctx *ctx, bq_fit *fit, double *total, double *grad);
 /* which: 0 = L (n x n, strict upper zeroed), 1 = alpha = Kxx^-1 y (n),
  * 2 = z = L^-1 y (n), 3 = Kxx (n x n, recomputed) */
 int bq_gp_get(bq_ctx *ctx, bq_fit *fit, int which, double *out_host);
