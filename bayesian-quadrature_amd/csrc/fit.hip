@@ -13,6 +13,39 @@ namespace bqh {
 constexpr size_t HF_PAR = 8 + 128, HF_PTS = HF_PAR + (sizeof(GaussParams) + 7) / 8;
 constexpr size_t HF_NPTS = 64 * BQ_MAXD;
 
+// the pinned staging of a fit, allocated on its first use
+static int fit_stage(bq_ctx *c, bq_fit *f)
+{
+    if (!f->hfit)
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
+                                sizeof(double) * (HF_PTS + HF_NPTS)));
+    return BQ_OK;
+}
+
+// new hyper-parameters, and a layout with M border points behind the fit's own
+static void fit_set_params(bq_fit *f, double h, const double *w, double s, int M)
+{
+    f->h = h;
+    f->s = s;
+    for (int k = 0; k < f->d; ++k)
+        f->w[k] = w[k];
+    f->g = make_params(f->d, h, w, s);
+    f->L = make_layout(f->n, M, true); // same ntot: border points share the y row's block
+}
+
+// buf holds at least `bytes` (kept between calls), or the call fails: "<what> (<bytes> bytes): ..."
+static int fit_grow(bq_ctx *c, DevBuf &buf, size_t bytes, const char *what)
+{
+    if (buf.bytes >= bytes)
+        return BQ_OK;
+    const hipError_t e = buf.alloc(bytes);
+    if (e == hipSuccess)
+        return BQ_OK;
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP, "%s (%zu bytes): %s", what,
+                bytes, hipGetErrorString(e));
+}
+
 // pm / pv: device buffers for the posterior mean / variance of the layout's M border points
 // (bq_gp_refit_predict), or null
 // npts_words: that many doubles of border points wait in the staging buffer (hfit + HF_PTS) for
@@ -25,19 +58,8 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     double *scal = f->misc.d() + 2;
     f->valid = false;
     f->stale = false;
-    f->have_alpha = false;
-    f->have_zc = false;
-    f->have_wide = false;
-    f->have_dw = false;
-    f->have_y = false;
-    f->have_hess = false;
-    f->have_prod = false;
-    f->have_loo = false;
-    f->have_loo_grad = false;
-    // pinned staging: [0, 136) results, then the kernel parameters, then border points
-    if (!f->hfit)
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
-                                sizeof(double) * (HF_PTS + HF_NPTS)));
+    f->drop(bq_fit::FACTOR_CHANGED);
+    BQCHK(fit_stage(c, f));
     std::memcpy(f->hfit + HF_PAR, &f->g, sizeof f->g);
     // The call's small transfers -- kernel parameters (and border points) in, the record out -- go
     // through one kernel each on the mapped staging buffer: a copy-engine operation costs the
@@ -76,7 +98,6 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     int hinfo = 0;
     std::memcpy(&hinfo, hm, sizeof hinfo);
     const double *hs = hm + 2;
-    f->have_alpha = false;
     if (hinfo != 0)
         return fail(c, BQ_ERR_NOT_PD, "matrix is not positive definite");
     f->logml = hs[0];
@@ -106,9 +127,9 @@ int check_fit(bq_ctx *c, const bq_fit *f)
 // wants), built on their first use after a (re)fit
 int fit_dw(bq_ctx *c, bq_fit *f)
 {
-    if (!f->have_dw) {
+    if (!(f->have & bq_fit::DW)) {
         BQCHK(launch_diag_winv(c, f->A.d(), f->ldl, f->npad, f->dw.d()));
-        f->have_dw = true;
+        f->have |= bq_fit::DW;
     }
     return BQ_OK;
 }
@@ -117,12 +138,12 @@ int fit_dw(bq_ctx *c, bq_fit *f)
 // hyper-parameter loop that only reads log-ML never pays for them
 int fit_wide(bq_ctx *c, bq_fit *f, WideInv &w)
 {
-    if (!f->have_wide) {
+    if (!(f->have & bq_fit::WIDE)) {
         BQCHK(fit_dw(c, f));
         if (f->wide.bytes < sizeof(double) * wide_alloc_doubles(f->npad))
             HIPCHK(c, f->wide.alloc(sizeof(double) * wide_alloc_doubles(f->npad)));
         BQCHK(compute_wide_inverses(c, f->A.d(), f->ldl, f->npad, f->dw.d(), f->wide.d()));
-        f->have_wide = true;
+        f->have |= bq_fit::WIDE;
     }
     w = wide_views(f->wide.d(), f->npad);
     return BQ_OK;
@@ -144,7 +165,7 @@ int fit_vec(bq_ctx *c, bq_fit *f)
 
 int fit_alpha(bq_ctx *c, bq_fit *f)
 {
-    if (f->have_alpha)
+    if (f->have & bq_fit::ALPHA)
         return BQ_OK;
     // alpha = L^-T z, z = A[yrow, 0:npad] (the forward-solved y of the bordered system)
     WideInv w;
@@ -161,7 +182,7 @@ int fit_alpha(bq_ctx *c, bq_fit *f)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return BQ_OK;
     }));
-    f->have_alpha = true;
+    f->have |= bq_fit::ALPHA;
     return BQ_OK;
 }
 
@@ -185,34 +206,20 @@ extern "C" int bq_gp_fit(bq_ctx *c, const double *x, const double *y, int64_t d,
         return fail(c, BQ_ERR_NOMEM, "out of host memory");
     f->d = (int)d;
     f->n = (int)n;
-    f->L = make_layout((int)n, 0, true);
-    f->npad = f->L.npad;
-    f->ldl = pick_ld(f->L.ntot);
-    f->h = h;
-    f->s = s;
-    for (int k = 0; k < d; ++k)
-        f->w[k] = w[k];
-    f->g = make_params((int)d, h, w, s);
-    hipError_t e = hipSuccess;
-    auto A = [&](DevBuf &b, size_t bytes) {
+    fit_set_params(f, h, w, s, 0);
+    int st = f->alloc(c, (int)d, (int)n, "fit allocation failed");
+    if (st == BQ_OK) {
+        hipError_t e = f->gp.alloc(sizeof(GaussParams));
         if (e == hipSuccess)
-            e = b.alloc(bytes);
-    };
-    A(f->A, sizeof(double) * (size_t)f->ldl * f->L.ntot);
-    A(f->pts, sizeof(double) * (size_t)d * f->L.ntot);
-    A(f->y, sizeof(double) * (size_t)f->npad);
-    A(f->gp, sizeof(GaussParams));
-    A(f->dinv, sizeof(double) * ((size_t)f->npad + BQ_DINV_STRIDE));
-    A(f->panel, sizeof(double) * sweep_route(c, f->L.ntot, f->L.ntot, 1).ws_doubles);
-    A(f->dw, sizeof(double) * BQ_DINV_HALF * (size_t)(f->npad / 64));
-    A(f->misc, sizeof(double) * (8 + 128));
-    A(f->alpha, sizeof(double) * (size_t)f->npad);
-    if (e != hipSuccess) {
-        delete f;
-        return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                    "fit allocation failed: %s", hipGetErrorString(e));
+            e = f->misc.alloc(sizeof(double) * (8 + 128));
+        if (e != hipSuccess)
+            st = fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
+                      "fit allocation failed: %s", hipGetErrorString(e));
     }
-    int st = BQ_OK;
+    if (st != BQ_OK) {
+        delete f;
+        return st;
+    }
     auto H = [&](hipError_t err) {
         if (st == BQ_OK && err != hipSuccess)
             st = fail(c, BQ_ERR_HIP, "fit upload failed: %s", hipGetErrorString(err));
@@ -240,12 +247,7 @@ extern "C" int bq_gp_refit(bq_ctx *c, bq_fit *f, double h, const double *w, doub
         return fail(c, BQ_ERR_BAD_ARG, "null fit handle");
     BQCHK(check_w(c, f->d, h, w, s));
     HIPCHK(c, hipSetDevice(c->device));
-    f->h = h;
-    f->s = s;
-    for (int k = 0; k < f->d; ++k)
-        f->w[k] = w[k];
-    f->g = make_params(f->d, h, w, s);
-    f->L = make_layout(f->n, 0, true);
+    fit_set_params(f, h, w, s, 0);
     return fit_factor(c, f);
 }
 
@@ -264,13 +266,7 @@ extern "C" int bq_gp_set_y(bq_ctx *c, bq_fit *f, const double *y)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     HIPCHK(c, hipSetDevice(c->device));
     f->stale = true; // the factor is intact, z / alpha / log-ML belong to the old targets
-    f->have_alpha = false;
-    f->have_zc = false;
-    f->have_y = false;
-    f->have_hess = false;
-    f->have_prod = false;
-    f->have_loo = false;
-    f->have_loo_grad = false;
+    f->drop(bq_fit::TARGETS_CHANGED);
     HIPCHK(c, hipMemcpyAsync(f->y.p, y, sizeof(double) * f->n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // y is the caller's buffer
     return BQ_OK;
@@ -299,18 +295,9 @@ extern "C" int bq_gp_refit_predict(bq_ctx *c, bq_fit *f, double h, const double 
     }
     BQCHK(check_w(c, f->d, h, w, s));
     HIPCHK(c, hipSetDevice(c->device));
-    f->h = h;
-    f->s = s;
-    for (int k = 0; k < f->d; ++k)
-        f->w[k] = w[k];
-    f->g = make_params(f->d, h, w, s);
-    f->L = make_layout(f->n, (int)M, true); // same ntot: the points share the y row's block
-    {
-        if (!f->hfit)
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hfit),
-                                    sizeof(double) * (HF_PTS + HF_NPTS)));
-        std::memcpy(f->hfit + HF_PTS, xo, sizeof(double) * f->d * M);
-    }
+    fit_set_params(f, h, w, s, (int)M);
+    BQCHK(fit_stage(c, f));
+    std::memcpy(f->hfit + HF_PTS, xo, sizeof(double) * f->d * M);
     double hv[128];
     BQCHK(fit_factor(c, f, f->misc.d() + 8, f->misc.d() + 8 + 64, hv, (size_t)f->d * (size_t)M));
     for (int64_t i = 0; i < M; ++i) {
@@ -347,31 +334,10 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
 
     // ---- a layout that holds n + k points, in buffers of its own until the append has succeeded
     const bool grow = n + k > npad;
-    Layout L2 = f->L;
-    long ldl2 = f->ldl;
-    DevBuf nA, npts, ny, ndinv, ndw, nalpha, npanel;
-    if (grow) {
-        L2 = make_layout(n + k, 0, true);
-        ldl2 = pick_ld(L2.ntot);
-        hipError_t e = hipSuccess;
-        auto A = [&](DevBuf &b, size_t bytes) {
-            if (e == hipSuccess)
-                e = b.alloc(bytes);
-        };
-        A(nA, sizeof(double) * (size_t)ldl2 * L2.ntot);
-        A(npts, sizeof(double) * (size_t)d * L2.ntot);
-        A(ny, sizeof(double) * (size_t)L2.npad);
-        A(ndinv, sizeof(double) * ((size_t)L2.npad + BQ_DINV_STRIDE));
-        A(npanel, sizeof(double) * sweep_route(c, L2.ntot, L2.ntot, 1).ws_doubles);
-        A(ndw, sizeof(double) * BQ_DINV_HALF * (size_t)(L2.npad / 64));
-        A(nalpha, sizeof(double) * (size_t)L2.npad);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                        "append: growing the fit to %d points failed: %s", n + k,
-                        hipGetErrorString(e));
-        }
-    }
+    FitCore grown;
+    if (grow)
+        BQCHK(grown.alloc(c, d, n + k, "append: growing the fit to %d points failed", n + k));
+    FitCore &to = grow ? grown : *f; // where the commit writes
 
     // ---- side buffers
     Scratch sc(c);
@@ -443,19 +409,19 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
 
     // ---- the grown layout: the old factor and its z, the identity on the new padding
     if (grow) {
-        HIPCHK(c, hipMemcpy2DAsync(nA.p, sizeof(double) * ldl2, f->A.p, sizeof(double) * f->ldl,
-                                   sizeof(double) * npad, npad, hipMemcpyDeviceToDevice,
-                                   c->stream));
-        BQCHK(launch_append_grow(c, nA.d(), ldl2, npad, L2.ntot, L2.yrow, f->A.d(), f->ldl,
+        HIPCHK(c, hipMemcpy2DAsync(to.A.p, sizeof(double) * to.ldl, f->A.p,
+                                   sizeof(double) * f->ldl, sizeof(double) * npad, npad,
+                                   hipMemcpyDeviceToDevice, c->stream));
+        BQCHK(launch_append_grow(c, to.A.d(), to.ldl, npad, to.L.ntot, to.L.yrow, f->A.d(), f->ldl,
                                  f->L.yrow, npad));
-        HIPCHK(c, hipMemsetAsync(npts.p, 0, npts.bytes, c->stream));
-        HIPCHK(c, hipMemsetAsync(ny.p, 0, ny.bytes, c->stream));
-        HIPCHK(c, hipMemsetAsync(ndinv.p, 0, ndinv.bytes, c->stream));
-        HIPCHK(c, hipMemcpyAsync(npts.p, f->pts.p, sizeof(double) * (size_t)d * n,
+        HIPCHK(c, hipMemsetAsync(to.pts.p, 0, to.pts.bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(to.y.p, 0, to.y.bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(to.dinv.p, 0, to.dinv.bytes, c->stream));
+        HIPCHK(c, hipMemcpyAsync(to.pts.p, f->pts.p, sizeof(double) * (size_t)d * n,
                                  hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(ny.p, f->y.p, sizeof(double) * n, hipMemcpyDeviceToDevice,
+        HIPCHK(c, hipMemcpyAsync(to.y.p, f->y.p, sizeof(double) * n, hipMemcpyDeviceToDevice,
                                  c->stream));
-        HIPCHK(c, hipMemcpyAsync(ndinv.p, f->dinv.p, sizeof(double) * npad,
+        HIPCHK(c, hipMemcpyAsync(to.dinv.p, f->dinv.p, sizeof(double) * npad,
                                  hipMemcpyDeviceToDevice, c->stream));
     }
 
@@ -463,14 +429,11 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
     AppendJob job{};
     job.V = V, job.S = S, job.zn = X, job.zstride = zstride, job.xn = xn, job.yn = yn;
     job.info = info;
-    job.A = grow ? nA.d() : f->A.d();
-    job.ldl = ldl2;
-    job.pts = grow ? npts.d() : f->pts.d();
-    job.y = grow ? ny.d() : f->y.d();
-    job.dinv = grow ? ndinv.d() : f->dinv.d();
+    job.A = to.A.d(), job.ldl = to.ldl, job.pts = to.pts.d(), job.y = to.y.d();
+    job.dinv = to.dinv.d();
     job.out = out;
     job.logdet = f->logdet, job.qf = f->qf;
-    job.d = d, job.n = n, job.k = k, job.kp = kp, job.yrow = L2.yrow;
+    job.d = d, job.n = n, job.k = k, job.kp = kp, job.yrow = to.L.yrow;
     BQCHK(launch_append_commit(c, job));
     double *hm = f->hfit;
     if (hmap)
@@ -485,45 +448,11 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
                     "append: the Schur complement of the new points is not positive definite");
 
     // ---- bookkeeping: a fit of n + k points in every respect
-    if (grow) {
-        auto take = [](DevBuf &dst, DevBuf &src) {
-            std::swap(dst.p, src.p);
-            std::swap(dst.bytes, src.bytes);
-            std::swap(dst.guard, src.guard);
-        };
-        take(f->A, nA), take(f->pts, npts), take(f->y, ny), take(f->dinv, ndinv);
-        take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
-        // everything sized by the old npad goes; the captured sweeps hold the old pointers
-        for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart,
-                          &f->hB, &f->loo})
-            b->release();
-        if (f->hvec)
-            (void)hipHostFree(f->hvec);
-        f->hvec = nullptr;
-        for (int i = 0; i < 3; ++i) {
-            if (f->vgexec[i])
-                (void)hipGraphExecDestroy(f->vgexec[i]);
-            if (f->vgraph[i])
-                (void)hipGraphDestroy(f->vgraph[i]);
-            f->vgexec[i] = nullptr;
-            f->vgraph[i] = nullptr;
-            f->vg_failed[i] = false;
-        }
-        f->L = L2;
-        f->npad = L2.npad;
-        f->ldl = ldl2;
-    }
+    if (grow)
+        fit_adopt(f, grown);
     f->n = n + k;
     f->L.n = n + k;
-    f->have_alpha = false;
-    f->have_zc = false;
-    f->have_y = false;
-    f->have_hess = false;
-    f->have_prod = false;
-    f->have_loo = false;
-    f->have_loo_grad = false;
-    f->have_wide = false;
-    f->have_dw = false;
+    f->drop(bq_fit::FACTOR_CHANGED);
     f->logml = hm[2];
     f->logdet = hm[3];
     f->qf = hm[4];
@@ -569,33 +498,14 @@ extern "C" int bq_gp_remove(bq_ctx *c, bq_fit *f, const int64_t *idx, int64_t k6
     }
     HIPCHK(c, hipSetDevice(c->device));
     const Layout L2 = make_layout(n2, 0, true);
-    const long ldl2 = pick_ld(L2.ntot);
     const bool trailing = rem[0] == n2;
     const bool inplace = trailing && L2.npad == f->npad && f->L.M == 0;
     const int kp = trailing ? 0 : (int)roundup(k, 64);
 
     // ---- buffers of the new layout, and the side buffers
-    DevBuf nA, npts, ny, ndinv, ndw, nalpha, npanel;
-    if (!inplace) {
-        hipError_t e = hipSuccess;
-        auto A = [&](DevBuf &b, size_t bytes) {
-            if (e == hipSuccess)
-                e = b.alloc(bytes);
-        };
-        A(nA, sizeof(double) * (size_t)ldl2 * L2.ntot);
-        A(npts, sizeof(double) * (size_t)d * L2.ntot);
-        A(ny, sizeof(double) * (size_t)L2.npad);
-        A(ndinv, sizeof(double) * ((size_t)L2.npad + BQ_DINV_STRIDE));
-        A(npanel, sizeof(double) * sweep_route(c, L2.ntot, L2.ntot, 1).ws_doubles);
-        A(ndw, sizeof(double) * BQ_DINV_HALF * (size_t)(L2.npad / 64));
-        A(nalpha, sizeof(double) * (size_t)L2.npad);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                        "remove: the layout of %d points could not be allocated: %s", n2,
-                        hipGetErrorString(e));
-        }
-    }
+    FitCore next; // (its layout is L2)
+    if (!inplace)
+        BQCHK(next.alloc(c, d, n2, "remove: the layout of %d points could not be allocated", n2));
     Scratch sc(c);
     const size_t oout = sc.take(8), oV = sc.take(inplace ? 0 : (size_t)L2.ntot * kp),
                  oM = sc.take(kp ? BQ_REMOVE_M_DOUBLES : 0),
@@ -619,7 +529,7 @@ extern "C" int bq_gp_remove(bq_ctx *c, bq_fit *f, const int64_t *idx, int64_t k6
         job.A = f->A.d(), job.ldl = f->ldl, job.yrow = f->L.yrow;
         job.pts = f->pts.d(), job.y = f->y.d();
         job.keep = dkeep, job.rem = drem;
-        job.A2 = nA.d(), job.ldl2 = ldl2, job.pts2 = npts.d(), job.y2 = ny.d();
+        job.A2 = next.A.d(), job.ldl2 = next.ldl, job.pts2 = next.pts.d(), job.y2 = next.y.d();
         job.V = sc.at(oV);
         job.d = d, job.n2 = n2, job.npad2 = L2.npad, job.ntot2 = L2.ntot, job.k = k, job.kp = kp;
         BQCHK(launch_remove_compact(c, job));
@@ -630,55 +540,22 @@ extern "C" int bq_gp_remove(bq_ctx *c, bq_fit *f, const int64_t *idx, int64_t k6
             if (first >= n2)
                 continue; // (every survivor lies ahead of this sweep's indices: its V is zero)
             for (int J = first / 64; J < L2.npad / 64; ++J)
-                BQCHK(launch_remove_step(c, nA.d(), ldl2, job.V + (size_t)64 * s * L2.ntot, L2.ntot,
-                                         J, L2.ntot / 64, sc.at(oM)));
+                BQCHK(launch_remove_step(c, next.A.d(), next.ldl, job.V + (size_t)64 * s * L2.ntot,
+                                         L2.ntot, J, L2.ntot / 64, sc.at(oM)));
         }
-        BQCHK(launch_remove_finish(c, nA.d(), ldl2, L2.yrow, n2, L2.npad, ndinv.d(), out));
+        BQCHK(launch_remove_finish(c, next.A.d(), next.ldl, L2.yrow, n2, L2.npad, next.dinv.d(),
+                                   out));
     }
     double hout[6];
     HIPCHK(c, hipMemcpyAsync(hout, out, sizeof hout, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
 
     // ---- bookkeeping: a fit of n - k points in every respect
-    if (!inplace) {
-        auto take = [](DevBuf &dst, DevBuf &src) {
-            std::swap(dst.p, src.p);
-            std::swap(dst.bytes, src.bytes);
-            std::swap(dst.guard, src.guard);
-        };
-        take(f->A, nA), take(f->pts, npts), take(f->y, ny), take(f->dinv, ndinv);
-        take(f->dw, ndw), take(f->alpha, nalpha), take(f->panel, npanel);
-        // everything sized by the old npad goes; the captured sweeps hold the old pointers
-        for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart,
-                          &f->hB, &f->loo})
-            b->release();
-        if (f->hvec)
-            (void)hipHostFree(f->hvec);
-        f->hvec = nullptr;
-        for (int i = 0; i < 3; ++i) {
-            if (f->vgexec[i])
-                (void)hipGraphExecDestroy(f->vgexec[i]);
-            if (f->vgraph[i])
-                (void)hipGraphDestroy(f->vgraph[i]);
-            f->vgexec[i] = nullptr;
-            f->vgraph[i] = nullptr;
-            f->vg_failed[i] = false;
-        }
-        f->L = L2;
-        f->npad = L2.npad;
-        f->ldl = ldl2;
-    }
+    if (!inplace)
+        fit_adopt(f, next);
     f->n = n2;
     f->L.n = n2;
-    f->have_alpha = false;
-    f->have_zc = false;
-    f->have_y = false;
-    f->have_hess = false;
-    f->have_prod = false;
-    f->have_loo = false;
-    f->have_loo_grad = false;
-    f->have_wide = false;
-    f->have_dw = false;
+    f->drop(bq_fit::FACTOR_CHANGED);
     f->logml = hout[2];
     f->logdet = hout[3];
     f->qf = hout[4];
@@ -708,7 +585,7 @@ extern "C" int bq_gp_logml(bq_ctx *c, bq_fit *f, double *out)
 // Y = L^-T in gY (the gradient's and the Hessian's operand), built on its first use after a (re)fit
 static int fit_y(bq_ctx *c, bq_fit *f)
 {
-    if (f->have_y)
+    if (f->have & bq_fit::Y)
         return BQ_OK;
     const int npad = f->npad;
     WideInv w;
@@ -731,11 +608,7 @@ static int fit_y(bq_ctx *c, bq_fit *f)
         }
     }
     BQCHK(enqueue_inverse_rows(c, f->gX.d(), f->gY.d(), f->A.d(), f->ldl, npad, w));
-    f->have_y = true;
-    f->have_hess = false; // (Kxx^-1 lived in the sweep's workspace)
-    f->have_prod = false;
-    f->have_loo = false;
-    f->have_loo_grad = false;
+    f->have |= bq_fit::Y;
     return BQ_OK;
 }
 
@@ -776,17 +649,7 @@ extern "C" int bq_gp_logml_grad(bq_ctx *c, bq_fit *f, double *grad)
 // the Hessian's workspace beside Kxx^-1 (hess_ws_doubles), kept with the fit
 static int fit_hess_ws(bq_ctx *c, bq_fit *f)
 {
-    const size_t bytes = sizeof(double) * hess_ws_doubles(f->npad, f->d);
-    if (f->hB.bytes < bytes) {
-        f->hB.release();
-        hipError_t e = f->hB.alloc(bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                        "Hessian workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
-        }
-    }
-    return BQ_OK;
+    return fit_grow(c, f->hB, sizeof(double) * hess_ws_doubles(f->npad, f->d), "Hessian workspace");
 }
 
 static HessJob fit_hess_job(const bq_fit *f)
@@ -813,15 +676,15 @@ extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     HIPCHK(c, hipSetDevice(c->device));
     const int d = f->d, np = d + 2;
-    if (!f->have_hess) {
+    if (!(f->have & bq_fit::HESS)) {
         BQCHK(fit_alpha(c, f));
         BQCHK(fit_y(c, f));
         BQCHK(fit_hess_ws(c, f));
         const HessJob hj = fit_hess_job(f);
         const double *sums = nullptr;
         BQCHK(launch_logml_hess(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h, f->s,
-                                f->have_prod, &sums));
-        f->have_prod = true;
+                                (f->have & bq_fit::PROD) != 0, &sums));
+        f->have |= bq_fit::PROD;
         const int ng = hess_ng(d), nt = hess_nt(d), nq = hess_nq(d);
         double hs[hess_ng(BQ_MAXD) + hess_nt(BQ_MAXD) + hess_nq(BQ_MAXD)];
         HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof(double) * (ng + nt + nq), hipMemcpyDeviceToHost,
@@ -849,7 +712,7 @@ extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
                 H[p * np + q] -= Q[o];
                 H[q * np + p] = H[p * np + q];
             }
-        f->have_hess = true;
+        f->have |= bq_fit::HESS;
     }
     for (int i = 0; i < np * np; ++i)
         hess[i] = f->hess[i];
@@ -859,23 +722,14 @@ extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
 // the leave-one-out workspace (loo_ws_doubles), kept with the fit
 static int fit_loo_ws(bq_ctx *c, bq_fit *f)
 {
-    const size_t bytes = sizeof(double) * loo_ws_doubles(f->npad, f->d);
-    if (f->loo.bytes < bytes) {
-        f->loo.release();
-        hipError_t e = f->loo.alloc(bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP,
-                        "leave-one-out workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
-        }
-    }
-    return BQ_OK;
+    return fit_grow(c, f->loo, sizeof(double) * loo_ws_doubles(f->npad, f->d),
+                    "leave-one-out workspace");
 }
 
 // mu | var | lp on the device (npad apart behind k, q and the t_k) and L_loo in the handle
 static int fit_loo(bq_ctx *c, bq_fit *f)
 {
-    if (f->have_loo)
+    if (f->have & bq_fit::LOO)
         return BQ_OK;
     BQCHK(fit_loo_ws(c, f));
     BQCHK(fit_alpha(c, f));
@@ -886,7 +740,7 @@ static int fit_loo(bq_ctx *c, bq_fit *f)
     HIPCHK(c, hipMemcpyAsync(&f->loo_total, total, sizeof(double), hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    f->have_loo = true;
+    f->have |= bq_fit::LOO;
     return BQ_OK;
 }
 
@@ -924,15 +778,15 @@ extern "C" int bq_gp_loo_grad(bq_ctx *c, bq_fit *f, double *total, double *grad)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     HIPCHK(c, hipSetDevice(c->device));
     const int d = f->d;
-    if (!f->have_loo_grad) {
+    if (!(f->have & bq_fit::LOO_GRAD)) {
         BQCHK(fit_hess_ws(c, f));
         BQCHK(fit_loo_ws(c, f));
         BQCHK(fit_loo(c, f));
-        if (!f->have_prod) {
+        if (!(f->have & bq_fit::PROD)) {
             const HessJob hj = fit_hess_job(f);
             BQCHK(launch_hess_products(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h,
                                        f->s));
-            f->have_prod = true;
+            f->have |= bq_fit::PROD;
         }
         const double *gd = nullptr;
         BQCHK(launch_loo_grad(c, d, f->gX.d(), f->hB.d(), f->alpha.d(), f->n, f->npad, f->h, f->s,
@@ -940,7 +794,7 @@ extern "C" int bq_gp_loo_grad(bq_ctx *c, bq_fit *f, double *total, double *grad)
         HIPCHK(c, hipMemcpyAsync(f->loo_grad, gd, sizeof(double) * (d + 2), hipMemcpyDeviceToHost,
                                  c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        f->have_loo_grad = true;
+        f->have |= bq_fit::LOO_GRAD;
     }
     for (int p = 0; p < d + 2; ++p)
         grad[p] = f->loo_grad[p];
@@ -1063,10 +917,10 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
         }
         BQCHK(enqueue_forward_rows(c, V0.d(), V.d(), Mp, Mp, f->A.d(), f->ldl, npad, wi));
         // z lives in row yrow of the factor with stride ldl: gathered once per (re)fit
-        if (!f->have_zc) {
+        if (!(f->have & bq_fit::ZC)) {
             HIPCHK(c, grow(f->wz, sizeof(double) * (size_t)npad));
             BQCHK(launch_gather_row(c, f->wz.d(), f->A.d() + f->L.yrow, f->ldl, npad));
-            f->have_zc = true;
+            f->have |= bq_fit::ZC;
         }
         double *omean = direct ? hmap + (size_t)d * M : out.d();
         BQCHK(launch_rowdot(c, V.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(), g.c, omean, omean + Mp,

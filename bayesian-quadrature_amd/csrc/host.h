@@ -101,6 +101,12 @@ struct DevBuf {
             bad += h[i] != 0xA5;
         return bad;
     }
+    void swap(DevBuf &o)
+    {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        std::swap(guard, o.guard);
+    }
     double *d() const { return static_cast<double *>(p); }
     int *i() const { return static_cast<int *>(p); }
 };
@@ -652,50 +658,116 @@ struct bq_plan {
     }
 };
 
-struct bq_fit {
-    int d = 0, n = 0, npad = 0;
+// The layout of a fit's system and the seven buffers sized by it: allocated together, all or none,
+// and swapped together when a fit moves to another layout (fit_adopt).
+struct FitCore {
+    int npad = 0;
     long ldl = 0;
     Layout L{}; // layout of the fit system (M = 0, y row)
-    double h = 0, s = 0, w[BQ_MAXD] = {0};
-    GaussParams g{};
     DevBuf A;     // ntot x ntot bordered factor: L in [0,npad)^2, z in row yrow
     DevBuf pts;   // d x ntot
     DevBuf y;     // npad
-    DevBuf gp;    // GaussParams
     DevBuf dinv;  // npad reciprocal diagonal (+ BQ_DINV_STRIDE scratch for the factorisation)
     DevBuf panel; // scratch panel columns of the one-launch slab sweep
     DevBuf dw;    // diag_winv_kernel records of the resident factor (MFMA solves in the sweeps)
-    DevBuf wide;  // -W^T of the B-wide diagonal blocks (row sweeps), valid if have_wide
-    bool have_wide = false;
-    bool have_dw = false; // dw is built on its first use: a loop that reads log-ML never pays
-    DevBuf wV, wV2, wx, wout, wz; // prediction workspaces, grown on demand and kept
+    DevBuf alpha; // npad
+    // The layout of n points in d dimensions and its buffers.  A failure leaves nothing allocated,
+    // no layout, and the caller's words (printf-style) as the error: "<what>: <the HIP error>"
+    __attribute__((format(printf, 5, 6))) int alloc(bq_ctx *c, int d, int n, const char *what, ...)
+    {
+        L = bqh::make_layout(n, 0, true);
+        npad = L.npad;
+        ldl = bqh::pick_ld(L.ntot);
+        const size_t np = (size_t)npad, nt = (size_t)L.ntot;
+        hipError_t e = hipSuccess;
+        auto get = [&](DevBuf &b, size_t doubles) {
+            if (e == hipSuccess)
+                e = b.alloc(sizeof(double) * doubles);
+        };
+        get(A, (size_t)ldl * nt), get(pts, (size_t)d * nt), get(y, np);
+        get(dinv, np + BQ_DINV_STRIDE);
+        get(panel, bqh::sweep_route(c, L.ntot, L.ntot, 1).ws_doubles);
+        get(dw, BQ_DINV_HALF * (np / 64)), get(alpha, np);
+        if (e == hipSuccess)
+            return BQ_OK;
+        (void)hipGetLastError();
+        FitCore none;
+        swap(none); // (what was allocated goes with it)
+        char msg[160];
+        va_list ap;
+        va_start(ap, what);
+        vsnprintf(msg, sizeof msg, what, ap);
+        va_end(ap);
+        return bqh::fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP, "%s: %s", msg,
+                         hipGetErrorString(e));
+    }
+    void swap(FitCore &o)
+    {
+        std::swap(npad, o.npad), std::swap(ldl, o.ldl), std::swap(L, o.L);
+        A.swap(o.A), pts.swap(o.pts), y.swap(o.y), dinv.swap(o.dinv);
+        panel.swap(o.panel), dw.swap(o.dw), alpha.swap(o.alpha);
+    }
+};
+
+struct bq_fit : FitCore {
+    int d = 0, n = 0;
+    double h = 0, s = 0, w[BQ_MAXD] = {0};
+    GaussParams g{};
+    DevBuf gp;    // GaussParams
     DevBuf misc;  // info (int) + scal[4], then 2 x 64 doubles: the posterior of the border points
                   // of bq_gp_refit_predict (one read-back for all of it)
-    DevBuf alpha; // npad, valid if have_alpha
-    bool have_alpha = false;
-    // the log-ML gradient (bq_gp_logml_grad): Y = L^-T (npad x npad, zero below its diagonal) and
-    // the sweep's partial sums (npad x npad), allocated on the first gradient; the product's
-    // partials and the d + 2 results
+    // ---- derived state: what the handle holds beyond the factor, z and the scalars -------------
+    // One bit of `have` per result, set by the one function that computes it and cleared by the
+    // two events below.  This table is the only statement of either (DESIGN 4e repeats it):
+    //   bit       what is there                                     from        set by
+    //   DW        dw: 16 x 16 inverses of the factor's diagonal     the factor  fit_dw
+    //   WIDE      wide: -W^T of the B-wide diagonal blocks          DW          fit_wide
+    //   ZC        wz: z = L^-1 y contiguous (the factor's y row     z           bq_gp_predict
+    //             has stride ldl: the row reductions then read
+    //             one line per 8 entries, not one per entry)
+    //   ALPHA     alpha = L^-T z                                    WIDE, z     fit_alpha
+    //   Y         gY: Y = L^-T, zero below its diagonal (gX: the    WIDE        fit_y
+    //             sweep's workspace)
+    //   PROD      gX, hB: the Hessian's products stage (Kxx^-1,     Y, ALPHA    bq_gp_logml_hess or
+    //             the d products, the vectors D_p a and                         bq_gp_loo_grad,
+    //             Kxx^-1 D_p a), which both of them read                        whichever is first
+    //   HESS      hess                                              PROD        bq_gp_logml_hess
+    //   LOO       loo: mu | var | lp; loo_total                     Y, ALPHA    fit_loo
+    //   LOO_GRAD  loo_grad                                          PROD, LOO   bq_gp_loo_grad
+    // (z is the targets through the factor.)  A bit is never set while a bit it is computed from is
+    // clear: every producer runs the producers of what it reads first, and both events clear a bit
+    // together with everything computed from it.
+    enum : unsigned {
+        DW = 1u << 0,
+        WIDE = 1u << 1,
+        ZC = 1u << 2,
+        ALPHA = 1u << 3,
+        Y = 1u << 4,
+        PROD = 1u << 5,
+        HESS = 1u << 6,
+        LOO = 1u << 7,
+        LOO_GRAD = 1u << 8,
+        // the events: a (re)factorisation, an append, a removal ...
+        FACTOR_CHANGED = DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD,
+        // ... and bq_gp_set_y (the factor's own inverses stay)
+        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD,
+    };
+    unsigned have = 0;
+    void drop(unsigned event) { have &= ~event; }
+    DevBuf wide;                  // wide_alloc_doubles(npad), allocated on the first sweep
+    DevBuf wV, wV2, wx, wout, wz; // prediction workspaces, grown on demand and kept
+    // the log-ML gradient (bq_gp_logml_grad): Y and the sweep's partial sums (npad x npad each),
+    // allocated on the first gradient; the product's partials and the d + 2 results
     DevBuf gY, gX, gpart;
-    bool have_y = false;
     // the log-ML Hessian (bq_gp_logml_hess): Kxx^-1 takes gX once the sweep is done with it; the d
     // products Kxx^-1 dK/dw_k, the vectors and the partial sums (hess_ws_doubles) in hB, allocated
-    // on the first Hessian; the result until the next (re)fit, new targets or append
+    // on the first Hessian
     DevBuf hB;
-    bool have_hess = false;
     double hess[(BQ_MAXD + 2) * (BQ_MAXD + 2)] = {0};
-    bool have_prod = false; // gX and hB hold the Hessian's products stage (Kxx^-1, the d products, the
-                            // vectors D_p a and Kxx^-1 D_p a): the Hessian and the LOO gradient
-                            // both read it, whichever comes first runs it
     // leave-one-out (bq_gp_loo, bq_gp_loo_grad): diag Kxx^-1, the row sums, mean / variance / log
-    // density per point and the partial sums (loo_ws_doubles), allocated on the first call; the
-    // results until the next (re)fit, new targets, append or remove
+    // density per point and the partial sums (loo_ws_doubles), allocated on the first call
     DevBuf loo;
-    bool have_loo = false, have_loo_grad = false;
     double loo_total = 0, loo_grad[BQ_MAXD + 2] = {0};
-    bool have_zc = false; // wz holds z = L^-1 y contiguously (gathered from the factor's y row on
-                          // the first posterior after a (re)fit: the row reductions then read one
-                          // line per 8 entries instead of one per entry)
     // the single-vector sweeps (trsv.h): x | y, 2 npad doubles, and their captured launch
     // chains -- [0] solve (forward + backward), [1] backward into alpha, [2] forward; the
     // pointers survive a refit, so the graphs do too
@@ -711,6 +783,19 @@ struct bq_fit {
     hipGraphExec_t vgexec[3] = {nullptr, nullptr, nullptr};
     bool vg_failed[3] = {false, false, false};
     int vg_flow[3] = {0, 0, 0}; // c->trsv_flow when the slot's graph was captured
+    // the captured sweeps go: the next use of a slot captures again
+    void drop_graphs()
+    {
+        for (int i = 0; i < 3; ++i) {
+            if (vgexec[i])
+                (void)hipGraphExecDestroy(vgexec[i]);
+            if (vgraph[i])
+                (void)hipGraphDestroy(vgraph[i]);
+            vgexec[i] = nullptr;
+            vgraph[i] = nullptr;
+            vg_failed[i] = false;
+        }
+    }
     ~bq_fit()
     {
         if (hvec)
@@ -719,12 +804,7 @@ struct bq_fit {
             (void)hipHostFree(hio);
         if (hfit)
             (void)hipHostFree(hfit);
-        for (int i = 0; i < 3; ++i) {
-            if (vgexec[i])
-                (void)hipGraphExecDestroy(vgexec[i]);
-            if (vgraph[i])
-                (void)hipGraphDestroy(vgraph[i]);
-        }
+        drop_graphs();
     }
     // false from the start of a (re)factorisation until it has succeeded: a refit that hits a
     // non-positive pivot leaves L, dinv, dw and the scalars overwritten with garbage
@@ -733,6 +813,23 @@ struct bq_fit {
     bool stale = false;
     double logml = 0, logdet = 0, qf = 0;
 };
+
+namespace bqh {
+// A fit takes over the core of another layout (a growing append, a removal that is not in place;
+// the stream is idle).  Every workspace sized by the old padding goes, and so do the captured
+// sweeps, which hold the old pointers; the old core leaves in `core`, for the caller to free.
+inline void fit_adopt(bq_fit *f, FitCore &core)
+{
+    f->swap(core);
+    for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart, &f->hB,
+                      &f->loo})
+        b->release();
+    if (f->hvec)
+        (void)hipHostFree(f->hvec);
+    f->hvec = nullptr;
+    f->drop_graphs();
+}
+} // namespace bqh
 
 namespace bqh {
 // fit.hip: shared with moments.hip
