@@ -307,39 +307,25 @@ struct Potf2FSteps<16, NW, PAD, EARLY> {
     }
 };
 
-// lds: BQ_POTF2F_LDS_DOUBLES doubles.  src (leading dimension lsrc): where the block is read
-// from when it is not in place; when src lies in the slots' LDS (the slab step's Ts), pass
-// src_in_slots so that nobody publishes before every wave has its columns.
-// NW = 8: the workgroup has EIGHT waves (512 threads), two per SIMD, two panels each: the waves
-// that only update have half the columns to bring up to date per panel (32 FMAs + 20 LDS reads
-// instead of 64 + 36), which is what paces the early panels.
+#define BQ_STAMP(k)                                                                                \
+    if (stamps && threadIdx.x == 0)                                                                \
+    stamps[k] = (long long)__builtin_amdgcn_s_memtime()
+
+// The factor of a block that is already in the waves' registers (st: this wave's columns, row
+// `lane`, as potf2f_body loads them).  Nothing of the block is read from `lds` or from memory;
+// a caller that staged it in the slots' LDS has passed a barrier behind the last wave's load.
 template <int NW = 4>
-__device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, int j0,
-                                            double *__restrict__ dinv_b,
-                                            int *__restrict__ info_b, double *lds,
-                                            const double *src = nullptr, long lsrc = 0,
-                                            bool src_in_slots = false,
-                                            long long *stamps = nullptr,
-                                            double *logdet = nullptr, int nreal = 64)
+__device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__ Ab, long lda,
+                                           int j0, double *__restrict__ dinv_b,
+                                           int *__restrict__ info_b, double *lds,
+                                           long long *stamps = nullptr, double *logdet = nullptr,
+                                           int nreal = 64)
 {
     constexpr int NG = 16 / NW;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#define BQ_STAMP(k)                                                                                \
-    if (stamps && threadIdx.x == 0)                                                                \
-    stamps[k] = (long long)__builtin_amdgcn_s_memtime()
-    BQ_STAMP(0);
     double *slots = lds;
     double *blk = lds + BQ_POTF2F_SLOTS;
-    Potf2FT<NW> st;
-#pragma unroll
-    for (int q = 0; q < NG; ++q)
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            st.a[q][s] = src ? src[lane + (long)(4 * (NW * q + w) + s) * lsrc]
-                             : Ab[lane + (long)(4 * (NW * q + w) + s) * lda];
-    if (src_in_slots)
-        __syncthreads(); // the ring overwrites the block: every wave has its columns first
     BQ_STAMP(1);
     if (w == 0)
         potf2f_factor<0, NW>(st, slots, lane);
@@ -505,8 +491,39 @@ __device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, i
         BQ_POTF2F_LOGDET
 #undef BQ_POTF2F_LOGDET
     BQ_STAMP(4);
-#undef BQ_STAMP
 }
+
+// lds: BQ_POTF2F_LDS_DOUBLES doubles.  src (leading dimension lsrc): where the block is read
+// from when it is not in place; when src lies in the slots' LDS (the four-wave slab step's Ts),
+// pass src_in_slots so that nobody publishes before every wave has its columns.
+// NW = 8: the workgroup has EIGHT waves (512 threads), two per SIMD, two panels each: the waves
+// that only update have half the columns to bring up to date per panel (32 FMAs + 20 LDS reads
+// instead of 64 + 36), which is what paces the early panels.
+template <int NW = 4>
+__device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, int j0,
+                                            double *__restrict__ dinv_b,
+                                            int *__restrict__ info_b, double *lds,
+                                            const double *src = nullptr, long lsrc = 0,
+                                            bool src_in_slots = false,
+                                            long long *stamps = nullptr,
+                                            double *logdet = nullptr, int nreal = 64)
+{
+    constexpr int NG = 16 / NW;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    BQ_STAMP(0);
+    Potf2FT<NW> st;
+#pragma unroll
+    for (int q = 0; q < NG; ++q)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            st.a[q][s] = src ? src[lane + (long)(4 * (NW * q + w) + s) * lsrc]
+                             : Ab[lane + (long)(4 * (NW * q + w) + s) * lda];
+    if (src_in_slots)
+        __syncthreads(); // the ring overwrites the block: every wave has its columns first
+    potf2f_run<NW>(st, Ab, lda, j0, dinv_b, info_b, lds, stamps, logdet, nreal);
+}
+#undef BQ_STAMP
 
 // ---------------------------------------------------------------------------
 // The diagonal factor as every fused kernel calls it.  lds: BQ_POTF2_LDS_DOUBLES doubles; src

@@ -97,6 +97,40 @@ __device__ __forceinline__ void slab_frags(const double *Fs, int l15, int l4, do
 #define DIAG_RB(w, s) ((w) == 0 ? ((s) > 0 ? 1 : 0) : ((w) == 1 ? 2 : 3))
 #define DIAG_CB(w, s) ((w) == 0 ? ((s) == 2 ? 1 : 0) : (((w) == 3 ? 2 : 0) + ((w) >= 2 && (s) == 2 ? 1 : (s))))
 
+// Workgroup 0 of an eight-wave step hands the updated diagonal block to the factor as its ten
+// lower 16 x 16 blocks, packed: block (rb, cb), cb <= rb, at 256 (rb (rb + 1) / 2 + cb), element
+// (i, k) at i + 16 k -- BQ_SLAB_FW doubles, exactly the fragment region, which is dead once every
+// wave holds its fragments.  This wave's columns, row `lane`; a lane above a column's own block
+// row takes 0.0, which the factor never reads.
+__device__ __forceinline__ void slab_load_blocks8(Potf2FT<8> &st, const double *Bs, int w, int lane)
+{
+    const int rb = lane >> 4, i = lane & 15;
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int c = 4 * (8 * q + w) + s; // (potf2.h: panel 8 q + w is this wave's group q)
+            const int cb = c >> 4, rc = rb > cb ? rb : cb;
+            const double v = Bs[256 * ((rc * (rc + 1)) / 2 + cb) + i + 16 * (c & 15)];
+            st.a[q][s] = rb >= cb ? v : 0.0;
+        }
+}
+
+// ... and factors it: behind ONE barrier after the blocks were written.  Nobody reads the Q rows
+// any more, so the first panel may be published into their place at once.
+__device__ __forceinline__ void slab_corner_factor8(double *Ab, long lda, int j0, double *dinv_b,
+                                                    int *info_b, double *plds, long long *stamps,
+                                                    double *logdet)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (stamps && threadIdx.x == 0)
+        stamps[0] = (long long)__builtin_amdgcn_s_memtime();
+    Potf2FT<8> st;
+    slab_load_blocks8(st, plds + 4096, w, lane);
+    potf2f_run<8>(st, Ab, lda, j0, dinv_b, info_b, plds, stamps, logdet);
+}
+
 // STAMP: a profiling instantiation (tools/c2_timeline.py) whose workgroup 0 records s_memtime
 // at its phase boundaries; the shipped launches use STAMP = false and carry no stamp code.
 // NW = 8 (launch_slab_step has the rule): 512 threads; in an off-diagonal tile waves 4-7 solve the
@@ -128,9 +162,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     // of the 64-tile product frees on a CU (36 KiB + the 16 KiB four of them leave over), or it
     // starves behind a trailing update running on the other stream.  First 4096 doubles: the Q
     // rows of the tile, [k][row] (A-fragment reads are contiguous over rows); afterwards, in
-    // workgroup 0, the updated diagonal block on its way to the factor and the factor's panel
-    // slots.  Behind them: the fragments of L_jj and W (BQ_SLAB_FW doubles), later the factor's
-    // diagonal sub-blocks.
+    // workgroup 0, the factor's panel slots (four waves: first the updated diagonal block on its
+    // way to the factor).  Behind them: the fragments of L_jj and W (BQ_SLAB_FW doubles); after
+    // the update, in workgroup 0 of eight waves, the updated diagonal block as ten packed blocks.
     __shared__ __attribute__((aligned(16))) double plds[4096 + BQ_SLAB_FW];
     double *const Qs = plds;
     double *const Ts = plds; // the block sits where the factor's panel slots will be
@@ -150,7 +184,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     const int l15 = lane & 15, l4 = lane >> 4;
     if (NW == 8 && wave >= 4) {
         // the barriers of the tile update below, in their order: fragments staged; Q rows
-        // written; and for workgroup 0 with a next factor: Q rows read; diagonal block in LDS
+        // written; and for workgroup 0 with a next factor: diagonal block in LDS
         if (bx != by) {
             // off-diagonal tile: the Q rows (row block by) are solved HERE, beside waves 0-3's
             // solve of the P rows -- the two are independent, and one after the other they were
@@ -176,9 +210,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
         __syncthreads();
         if (blockIdx.x == 0 && factor_next) {
             __syncthreads();
-            __syncthreads();
-            potf2_body<8>(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds, Ts, 64,
-                          (long long *)nullptr, out.scal ? out.scal + 4 * b + 1 : nullptr);
+            slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds,
+                                nullptr, out.scal ? out.scal + 4 * b + 1 : nullptr);
         }
         return;
     }
@@ -316,8 +349,27 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     // which workgroup 0 factors in place, and the Schur complement of the last step stay in A)
     if (blockIdx.x == 0 && factor_next) {
         // the next diagonal block never touches memory between its update and its factor
-        // (only the ten lower blocks: the factor never reads a lane above its column's own);
-        // it lands where the Q rows were: every wave must be through with them
+        // (only the ten lower blocks: the factor never reads a lane above its column's own)
+        if constexpr (NW == 8) {
+            // eight waves: the blocks go, packed, where the fragments were -- every wave has had
+            // its fragments since the barrier in front of the update -- and ONE barrier later
+            // the factor's waves pick their columns out of them (slab_load_blocks8)
+            double *Bs = plds + 4096;
+#pragma unroll
+            for (int sb = 0; sb < 3; ++sb)
+                if (sb < DIAG_NB(wave)) {
+                    const int rb = DIAG_RB(wave, sb), cb = DIAG_CB(wave, sb);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        Bs[256 * ((rb * (rb + 1)) / 2 + cb) + l15 + 16 * (l4 + 4 * r)] = -acc[sb][r];
+                }
+            __syncthreads();
+            slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds,
+                                (STAMP && blockIdx.z == 0) ? stamps + 5 : nullptr,
+                                out.scal ? out.scal + 4 * b + 1 : nullptr);
+            return;
+        }
+        // four waves: it lands where the Q rows were: every wave must be through with them
         __syncthreads();
 #pragma unroll
         for (int sb = 0; sb < 3; ++sb)
