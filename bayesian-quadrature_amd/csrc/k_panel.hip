@@ -199,7 +199,10 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
     const int T = (ntot - j0 - 64) / 64;
     Bracket br(c, BQ_K_SYRK_SMALL, work);
     const long wgs = (long)T * (T + 1) / 2 * batch;
-    const bool w8 = c->potf2_8w && fnext && wgs <= slab8_limit(c);
+    // (the last step -- no next factor, the Schur complement of the border -- too: its
+    // off-diagonal workgroups solve their two row blocks side by side; waves 4-7 leave after the
+    // Q rows' barrier and waves 0-3 store and emit as in the four-wave form)
+    const bool w8 = c->potf2_8w && wgs <= slab8_limit(c);
     if (stamps && w8)
         hipLaunchKernelGGL((slab_step_kernel<true, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512), 0,
                            c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,

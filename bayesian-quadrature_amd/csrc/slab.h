@@ -243,33 +243,39 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 wv[q] = din[64 + 256 * q + t];
-            if (NW == 4 && bx != by)
+            // No branch between the loads either: a load under `if` is a basic block of its own,
+            // and hipcc puts the waits of the OTHER arm's pending loads in front of it.  So the
+            // four-wave form loads the Q rows in a diagonal tile too (they are its P rows: the
+            // same lines), and the C tile's sixteen loads differ between the two kinds of tile
+            // only in wave-uniform offsets.
+            if (NW == 4)
                 slab_load16(Sin + Cb + 16 * wave + l15 + (long)l4 * lds, lds, tq);
             slab_load16(Sin + Rb + 16 * wave + l15 + (long)l4 * lds, lds, tp);
-            // C tile (negated: the MFMAs add Q P^T).  Off-diagonal tiles: rows 16 wave .. +15,
+            // C tile, RAW: the MFMAs add Q P^T to -C, but a negation here draws the load's wait
+            // in between the loads (the scheduler places the sign flip as early as it may) and
+            // the tile then costs one memory round trip per group of loads; it is negated in
+            // front of the update instead.  Off-diagonal tiles: rows 16 wave .. +15,
             // four 16-column blocks.  Diagonal tiles need only their ten lower 16 x 16 blocks
             // and deal them 3 / 3 / 2 / 2 to the waves (DIAG_RB / DIAG_CB): 48 MFMAs on the
             // longest wave instead of 64 -- for workgroup (0, 0) this update sits between the
-            // launch's start and the diagonal factor.
-            if (bx == by) {
-                acc[2] = double4_t{0.0, 0.0, 0.0, 0.0};
+            // launch's start and the diagonal factor.  Waves 2 and 3 load their second block
+            // again as a third (s = 2, as for the MFMAs: never stored), and every wave of a
+            // diagonal tile loads its third block again as a fourth, which nothing reads.
+            {
+                const bool dg = bx == by;
 #pragma unroll
-                for (int sb = 0; sb < 3; ++sb)
-                    if (sb < DIAG_NB(wave)) {
-                        const double *Cin = A + Rb + 16 * DIAG_RB(wave, sb) + l15 +
-                                            (long)(Cb + 16 * DIAG_CB(wave, sb) + l4) * lda;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            acc[sb][r] = -Cin[(long)(4 * r) * lda];
-                    }
-            } else {
-                const double *Cin = A + Rb + 16 * wave + l15 + (long)(Cb + l4) * lda;
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb)
+                for (int cb = 0; cb < 4; ++cb) {
+                    const int sb = cb < 2 ? cb : 2;
+                    const int ro = dg ? 16 * DIAG_RB(wave, sb) : 16 * wave;
+                    const int co = dg ? 16 * DIAG_CB(wave, sb) : 16 * cb;
+                    const double *Cin = A + Rb + ro + l15 + (long)(Cb + co + l4) * lda;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        acc[cb][r] = -Cin[(long)(16 * cb + 4 * r) * lda];
+                        acc[cb][r] = Cin[(long)(4 * r) * lda];
+                }
             }
+            // nothing that waits for a load may move up between the loads
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 6; ++q)
                 Fs[256 * q + t] = f[q];
@@ -302,6 +308,24 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
                 Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xp[c][r];
     }
     BQ_SSTAMP(2, xp[3][3])
+    // The tile was loaded raw (see the prologue) and is negated HERE: behind the solve, which has
+    // given it 3,000 cycles to arrive, and in front of the stores below -- the wait counts
+    // stores too, and behind them the tile's wait would drain them on workgroup 0's path.
+    // (acc[3] of a diagonal tile is never read.)
+    // (The pins keep the sign flips, and the wait with them, from sinking to the accumulators'
+    // first uses behind the barrier.)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+        if (cb < 3 || bx != by) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double v = -acc[cb][r];
+                asm volatile("" : "+v"(v));
+                acc[cb][r] = v;
+            }
+        }
+    __builtin_amdgcn_sched_barrier(0);
     // the solved rows are the factor: tile column 0 owns the write
     if (by == 0) {
         double *Lw = A + Rb + 16 * wave + l15 + (long)(j0 + l4) * lda;
