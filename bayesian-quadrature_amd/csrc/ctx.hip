@@ -128,6 +128,7 @@ static int ctx_init(bq_ctx *c, int device)
         {"BQ_FOLD_READOUT", &bq_ctx::fold_readout},
         {"BQ_POTF2_8W", &bq_ctx::potf2_8w},
         {"BQ_SLAB8_ROUNDS", &bq_ctx::slab8_rounds},
+        {"BQ_FIRST_REGS", &bq_ctx::first_regs},
         {"BQ_GEMM_KSPLIT", &bq_ctx::gemm_ksplit},
         {"BQ_GEMM_TILE", &bq_ctx::gemm_tile},
         {"BQ_GRAPH", &bq_ctx::use_graph},

@@ -208,9 +208,17 @@ __global__ __launch_bounds__(256) void gram_cross_pad_kernel(const double *__res
 // slab sweep -- go to the sweep's scratch column as well (slab.h).
 // ib, jb: the tile's first row / column (default: from the block index); ilim, jlim: rows /
 // columns from there on are not written (a region of the system, assemble_region_kernel)
-template <int D>
+// CBW: columns whose operands and entries a thread holds at a time, 0 = the most the dimension
+// leaves registers for -- the first launch of a small system's sweep, whose tiles are latency.
+// The stand-alone assemblies (assemble_kernel, assemble_region_kernel: batches, large systems) are
+// throughput: there sixteen columns at once cost 134 instead of 46 VGPRs, 3 instead of 8 waves per
+// SIMD, and a C5 shard 0.7 % -- they take BQ_ASM_TILE_CB columns.
+#ifndef BQ_ASM_TILE_CB
+#define BQ_ASM_TILE_CB 4
+#endif
+template <int D, int CBW = 0>
 __device__ __forceinline__ void assemble_tile(const double *__restrict__ pts,
-                                              const double *__restrict__ y, const GaussParams &g,
+                                              const double *__restrict__ y, const GaussParams &gm,
                                               double *__restrict__ A, long lda, const Layout &L,
                                               double *__restrict__ S0, long lds, int ib = -1,
                                               int jb = -1, int ilim = 0x7fffffff,
@@ -224,36 +232,89 @@ __device__ __forceinline__ void assemble_tile(const double *__restrict__ pts,
     if (jb > ib + 127) // whole tile strictly above the diagonal
         return;
     const int i = ib + (t & 63) * 2;
+    // (the wave's sixteen columns.  The compiler is NOT told that they are the same in every lane:
+    // as scalar loads the column points and the exp's constants outgrew the scalar registers, 44 to
+    // 290 of them spilled per kernel; as vector loads they cost registers the kernel has.)
     const int jbase = jb + (t >> 6) * 16;
-    if (i >= L.ntot || i >= ilim)
+    // ntot, jlim: multiples of 64 -- a wave's sixteen columns are written or not as one
+    if (i >= L.ntot || i >= ilim || jbase >= L.ntot || jbase >= jlim)
         return;
+    // A thread's time here was latency, not work: per column one load under a branch, the wait for
+    // it, two exps one after the other in basic blocks of their own, and stores that the next
+    // column's wait drained.  Now every load is requested before the first exp -- indices clamped
+    // to a point that exists (index 0) where row or column carries none, targets from a buffer that
+    // exists where the tile has no y row, so that no load sits under a branch -- and the entries
+    // are straight-line code (bordered_entry_flat): CB columns = 2 CB independent exp chains at a
+    // time, and no wait between the stores.
+    // (the parameters too: behind a reference into memory they were fetched where first used)
+    GaussParams g;
+    g.c = gm.c, g.s2 = gm.s2;
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+        g.nh[k] = gm.nh[k];
     bool pi[2];
     double xi[2][D];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int ii = i + r;
         pi[r] = (ii < L.n) || (ii >= L.npad && ii < L.npad + L.M);
+        const long ic = pi[r] ? ii : 0;
 #pragma unroll
         for (int k = 0; k < D; ++k)
-            xi[r][k] = pi[r] ? pts[k + (long)ii * D] : 0.0;
+            xi[r][k] = pts[k + ic * D];
     }
-    for (int jj = 0; jj < 16; ++jj) {
-        const int j = jbase + jj;
-        if (j >= L.ntot || j >= jlim)
-            break;
-        const bool pj = (j < L.n) || (j >= L.npad && j < L.npad + L.M);
-        double xj[D];
+    // (only the y row reads targets -- a tile has it or not; y may be null for a system without)
+    const bool yt = L.yrow >= ib && L.yrow < ib + 128;
+    const double *__restrict__ ysrc = yt ? y : pts;
+    const bool to_s0 = S0 && jb == 0 && i >= 64;
+    // CB columns' entries at a time (d = 2: sixteen at once spilled in the 512-thread form); LB
+    // columns' operands requested at a time: all sixteen where the dimension leaves the registers
+    // for it and the caller asks for the most (d <= 2), else a batch's own.
+    constexpr int CBMAX = D == 1 ? 16 : (D == 2 ? 8 : 4);
+    constexpr int CB = CBW > 0 && CBW < CBMAX ? CBW : CBMAX;
+    constexpr int LB = (CBW == 0 && D <= 2) ? 16 : CB;
 #pragma unroll
-        for (int k = 0; k < D; ++k)
-            xj[k] = pj ? pts[k + (long)j * D] : 0.0;
-        double v[2];
+    for (int l0 = 0; l0 < 16; l0 += LB) {
+        bool pj[LB];
+        double xj[LB][D], yj[LB];
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
-            v[r] = bordered_entry<D>(i + r, j, pi[r], pj, xi[r], xj, g, L, y);
-        double2_t vv = {v[0], v[1]};
-        *reinterpret_cast<double2_t *>(A + i + (long)j * lda) = vv; // ntot, lda even
-        if (S0 && jb == 0 && i >= 64)
-            *reinterpret_cast<double2_t *>(S0 + i + (long)j * lds) = vv;
+        for (int jj = 0; jj < LB; ++jj) {
+            const int j = jbase + l0 + jj;
+            pj[jj] = (j < L.n) || (j >= L.npad && j < L.npad + L.M);
+            const long jc = pj[jj] ? j : 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+                xj[jj][k] = pts[k + jc * D];
+            yj[jj] = ysrc[j < L.n ? j : 0];
+        }
+        // nothing that waits for a load may move up between the loads
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c0 = 0; c0 < LB; c0 += CB) {
+            const int j0 = l0 + c0;
+            double2_t vv[CB];
+#pragma unroll
+            for (int jj = 0; jj < CB; ++jj) {
+                const int j = jbase + j0 + jj;
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+                    vv[jj][r] = bordered_entry_flat<D>(i + r, j, pi[r], pj[c0 + jj], xi[r],
+                                                       xj[c0 + jj], g, L, yj[c0 + jj]);
+            }
+            // (the stores behind the batch's entries, the scratch column's under ONE branch: a
+            // branch per column cut the entries into basic blocks again)
+#pragma unroll
+            for (int jj = 0; jj < CB; ++jj) // ntot, lda even
+                *reinterpret_cast<double2_t *>(A + i + (long)(jbase + j0 + jj) * lda) = vv[jj];
+            if (to_s0) {
+#pragma unroll
+                for (int jj = 0; jj < CB; ++jj)
+                    *reinterpret_cast<double2_t *>(S0 + i + (long)(jbase + j0 + jj) * lds) = vv[jj];
+            }
+            // (one batch's exp chains at a time: all sixteen columns' in flight cost the registers)
+            if (CB < LB)
+                __builtin_amdgcn_sched_barrier(0);
+        }
     }
 }
 
@@ -266,7 +327,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(const double *__restrict_
                                                        long lda, long astride, Layout L)
 {
     const int b = blockIdx.z;
-    assemble_tile<D>(pts + (long)b * pstride, y + (long)b * ystride, gp[(long)b * gpstride],
+    assemble_tile<D, BQ_ASM_TILE_CB>(pts + (long)b * pstride, y + (long)b * ystride, gp[(long)b * gpstride],
                      A + (long)b * astride, lda, L, nullptr, 0);
 }
 
@@ -285,7 +346,7 @@ __global__ __launch_bounds__(256) void assemble_region_kernel(const double *__re
                                                               int c, int m, int n)
 {
     const int b = blockIdx.z;
-    assemble_tile<D>(pts + (long)b * pstride, y + (long)b * ystride, gp[(long)b * gpstride],
+    assemble_tile<D, BQ_ASM_TILE_CB>(pts + (long)b * pstride, y + (long)b * ystride, gp[(long)b * gpstride],
                      A + (long)b * astride, lda, L, nullptr, 0, r + (int)blockIdx.x * 128,
                      c + (int)blockIdx.y * 64, r + m, c + n);
 }

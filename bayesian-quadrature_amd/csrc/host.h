@@ -155,6 +155,8 @@ struct bq_ctx {
                          // (GramSeed; BQ_ASM_FUSE=0: the whole system is assembled first)
     int potf2_8w = 1;    // the one-launch steps' diagonal factor on eight waves where a step's workgroups
                          // have a CU each (BQ_POTF2_8W)
+    int first_regs = 1;  // the assembly's workgroup (0, 0) computes the leading block in the factor's
+                         // registers (assemble_first_kernel; BQ_FIRST_REGS=0: stored, drained, reloaded)
     int slab8_rounds = 1 << 20; // ... and a slab step's 512-thread form while the step has at most this many
                          // workgroups per CU (launch_slab_step: no limit shipped; BQ_SLAB8_ROUNDS, 0: one)
     int gemm_ksplit = 1; // eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT)
@@ -222,7 +224,8 @@ inline unsigned long long launch_config_key(const bq_ctx *c)
 {
     const int f[] = {c->nb_override, c->lookahead, c->la_min,   c->gemm_lds,  c->fold_readout,
                      c->potf2_8w,    c->gemm_ksplit, c->gemm_tile, c->diag_first, c->df_sweep,
-                     c->df_wg,       c->df_early,   c->df_wg_rows, c->slab8_rounds};
+                     c->df_wg,       c->df_early,   c->df_wg_rows, c->slab8_rounds,
+                     c->first_regs};
     unsigned long long h = 1469598103934665603ull;
     for (int v : f)
         h = (h ^ (unsigned long long)(unsigned)v) * 1099511628211ull;
@@ -335,7 +338,8 @@ struct FirstStep {
     long lds = 0, sstride = 0;
     double *dinv = nullptr;
     int *info = nullptr;
-    double *scal = nullptr; // SlabOut::scal: log|K| starts at zero here
+    double *scal = nullptr; // SlabOut::scal: log|K| starts here (the leading block's factor stores it)
+    long long *stamps = nullptr; // the profiling instantiation (bq_probe_first_launch), d = 1
 };
 // jcols > 0: only the first jcols columns (a multiple of 64) of every system
 int launch_assemble(bq_ctx *c, int d, const double *pts, long pstride, const double *y,

@@ -14,18 +14,47 @@ void launch_assemble_d(bq_ctx *c, const double *pts, long pstride, const double 
                        Layout L, int batch, const FirstStep &fs, int jcols)
 {
     dim3 grid((L.ntot + 127) / 128, ((jcols > 0 ? jcols : L.ntot) + 63) / 64, batch);
-    const long wgs = (long)grid.x * grid.y * grid.z;
-    if (fs.S0 && c->potf2_8w && wgs <= 2L * c->cus)
-        hipLaunchKernelGGL((assemble_first_kernel<D, 8>), grid, dim3(512), 0, c->cur, pts, pstride, y,
-                           ystride, gp, gpstride, A, lda, astride, L, fs.S0, fs.lds, fs.sstride,
-                           fs.dinv, (long)BQ_DINV_STRIDE, fs.info, fs.scal);
-    else if (fs.S0)
-        hipLaunchKernelGGL((assemble_first_kernel<D, 4>), grid, dim3(256), 0, c->cur, pts, pstride, y,
-                           ystride, gp, gpstride, A, lda, astride, L, fs.S0, fs.lds, fs.sstride,
-                           fs.dinv, (long)BQ_DINV_STRIDE, fs.info, fs.scal);
-    else
+    if (!fs.S0) {
         hipLaunchKernelGGL(assemble_kernel<D>, grid, dim3(256), 0, c->cur, pts, pstride, y, ystride,
                            gp, gpstride, A, lda, astride, L);
+        return;
+    }
+    const bool regs = c->first_regs != 0;
+    // (the leading block in registers: workgroup (0, 2) takes rows 64-127 of column block 0 off
+    // workgroup (0, 0) -- an idle tile from ntot = 192 on, one more workgroup per problem at
+    // ntot = 128: assemble_first_kernel)
+    if (regs && grid.y < 3)
+        grid.y = 3;
+    const long wgs = (long)grid.x * grid.y * grid.z;
+    const bool w8 = c->potf2_8w && wgs <= 2L * c->cus;
+#define BQ_ASM_FIRST(NW_, REGS_, STAMP_)                                                           \
+    hipLaunchKernelGGL((assemble_first_kernel<D, NW_, REGS_, STAMP_>), grid, dim3(64 * NW_), 0,    \
+                       c->cur, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, fs.S0,  \
+                       fs.lds, fs.sstride, fs.dinv, (long)BQ_DINV_STRIDE, fs.info, fs.scal,        \
+                       fs.stamps)
+    if constexpr (D == 1) {
+        // (the stamped instantiation: the probe's, one dimension)
+        if (fs.stamps) {
+            if (w8 && regs)
+                BQ_ASM_FIRST(8, true, true);
+            else if (w8)
+                BQ_ASM_FIRST(8, false, true);
+            else if (regs)
+                BQ_ASM_FIRST(4, true, true);
+            else
+                BQ_ASM_FIRST(4, false, true);
+            return;
+        }
+    }
+    if (w8 && regs)
+        BQ_ASM_FIRST(8, true, false);
+    else if (w8)
+        BQ_ASM_FIRST(8, false, false);
+    else if (regs)
+        BQ_ASM_FIRST(4, true, false);
+    else
+        BQ_ASM_FIRST(4, false, false);
+#undef BQ_ASM_FIRST
 }
 
 int launch_assemble(bq_ctx *c, int d, const double *pts, long pstride, const double *y,
@@ -34,6 +63,8 @@ int launch_assemble(bq_ctx *c, int d, const double *pts, long pstride, const dou
 {
     if (jcols < 0 || (jcols & 63) || jcols > L.ntot || (jcols > 0 && fs.S0))
         return fail(c, BQ_ERR_BAD_ARG, "assemble: column limit");
+    if (fs.stamps && (!fs.S0 || d != 1))
+        return fail(c, BQ_ERR_BAD_ARG, "assemble: the stamped first launch is one-dimensional");
     const double cols = jcols > 0 ? jcols : L.ntot;
     Bracket br(c, BQ_K_GRAM, 8.0 * cols * (L.ntot - 0.5 * cols + 0.5) * batch);
     switch (d) {

@@ -314,12 +314,16 @@ struct Potf2FSteps<16, NW, PAD, EARLY> {
 // The factor of a block that is already in the waves' registers (st: this wave's columns, row
 // `lane`, as potf2f_body loads them).  Nothing of the block is read from `lds` or from memory;
 // a caller that staged it in the slots' LDS has passed a barrier behind the last wave's load.
+// fresh: this factor is the first of its sweep (the assembly's leading block,
+// assemble_first_kernel): *logdet and the failure flag START here.  The factor reads neither, takes
+// both as zero and stores both whatever they come to -- nobody has to clear them in front of it,
+// and no wait or barrier has to order such a store against its reads.
 template <int NW = 4>
 __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__ Ab, long lda,
                                            int j0, double *__restrict__ dinv_b,
                                            int *__restrict__ info_b, double *lds,
                                            long long *stamps = nullptr, double *logdet = nullptr,
-                                           int nreal = 64)
+                                           int nreal = 64, bool fresh = false)
 {
     constexpr int NG = 16 / NW;
     const int lane = threadIdx.x & 63;
@@ -335,7 +339,7 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
     // other --: inside slab_step_kernel the second instantiation cost C2 0.4 us per step)
     if (nreal >= 64) {
         // (a full block: the epilogue straight out of the panels' slots)
-        const double ld0 = logdet ? *logdet : 0.0; // one writer per launch, launches in order
+        const double ld0 = (logdet && !fresh) ? *logdet : 0.0; // one writer per launch, launches in order
         Potf2FSteps<0, NW, false, true>::run(
             st, slots, w, lane,
             (stamps && stamps[5] != 0) ? stamps + 8 : nullptr, 64);
@@ -378,7 +382,9 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
             const double dg = slots[256 * (lane >> 2) + 64 * (lane & 3) + lane];
             dinv_b[lane] = potf2f_rcp(dg);
             const unsigned long long badm = __ballot(!(dg > 0.0) || !(dg < 1.7e308));
-            if (lane == 0 && badm != 0ull && info_b[0] == 0)
+            if (lane == 0 && fresh)
+                info_b[0] = badm != 0ull ? j0 + __builtin_ctzll(badm) + 1 : 0;
+            else if (lane == 0 && badm != 0ull && info_b[0] == 0)
                 info_b[0] = j0 + __builtin_ctzll(badm) + 1;
         }
         if (w == WL && logdet) {
@@ -429,7 +435,7 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
         double lg = log(blk[256 * (lane >> 4) + 17 * (lane & 15)]);                                \
         _Pragma("unroll") for (int off = 32; off > 0; off >>= 1) lg += __shfl_down(lg, off, 64);   \
         if (lane == 0)                                                                             \
-            *logdet += 2.0 * lg;                                                                   \
+            *logdet = (fresh ? 0.0 : *logdet) + 2.0 * lg;                                          \
     }
     if (NW > 4 && w >= 4) {
         if (logdet && w == 4)
@@ -448,7 +454,9 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
         if (w == 0) {
             dinv_b[lane] = rc;
             const unsigned long long badm = __ballot(!(dg > 0.0) || !(dg < 1.7e308));
-            if (lane == 0 && badm != 0ull && info_b[0] == 0)
+            if (lane == 0 && fresh)
+                info_b[0] = badm != 0ull ? j0 + __builtin_ctzll(badm) + 1 : 0;
+            else if (lane == 0 && badm != 0ull && info_b[0] == 0)
                 info_b[0] = j0 + __builtin_ctzll(badm) + 1;
         }
         // Wave w inverts block w: lane j (mod 16) runs the forward substitution of unit column

@@ -699,6 +699,87 @@ extern "C" int bq_probe_sweep(bq_ctx *c, int which, int64_t n, const double *L, 
     return BQ_OK;
 }
 
+// The first launch of a small system's sweep alone (launch_assemble with a FirstStep), on the
+// caller's points, targets and parameters, and everything it leaves in memory: the first block
+// column of A (ntot rows x 64 columns per problem, the leading block's upper triangle included),
+// the scratch column S0, the factor's record, the failure flags and scal.  Every buffer starts as
+// 0xA5 bytes, so what the launch does not write comes back as that.  ntot, dinv_len: what the
+// caller sized Acol / S0 and dinv for (checked).  stamps16 (d = 1 only; or
+// null): the stamped instantiation's s_memtime values of workgroup (0, 0) of problem 0 --
+// [0] entry, [1] leading block assembled, [2 .. 6] the factor's five (block held, first panel,
+// chain done, epilogue entered, end).
+extern "C" int bq_probe_first_launch(bq_ctx *c, int64_t batch, int64_t d, int64_t n, int64_t M,
+                                     const double *x, const double *y, const double *xo, double h,
+                                     const double *w, double s, int64_t ntot, int64_t dinv_len,
+                                     double *Acol, double *S0, double *dinv, int32_t *info,
+                                     double *scal, int64_t *stamps16)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    BQCHK(check_dims(c, d, n));
+    if (batch < 1 || batch > 65535 || M < 0 || M > 4096 || !x || !y || (!xo && M) || !w || !Acol ||
+        !S0 || !dinv || !info || !scal)
+        return fail(c, BQ_ERR_BAD_ARG, "first_launch: illegal value");
+    BQCHK(check_w(c, d, h, w, s));
+    const Layout L = make_layout((int)n, (int)M, true);
+    const long lda = pick_ld(L.ntot), astride = lda * (long)L.ntot;
+    // (the caller sized Acol, S0 and dinv: it says for what)
+    if (ntot != L.ntot || dinv_len != BQ_DINV_STRIDE)
+        return fail(c, BQ_ERR_BAD_ARG, "first_launch: buffers for ntot = %d and %d doubles of record, not %lld and %lld",
+                    L.ntot, (int)BQ_DINV_STRIDE, (long long)ntot, (long long)dinv_len);
+    if (!sweep_route(c, L.ntot, L.npad, (int)batch, ~(size_t)0 >> 1).first_in_assembly)
+        return fail(c, BQ_ERR_BAD_ARG, "first_launch: this shape's sweep has no first launch in the assembly");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf A, pts, yd, gp, dv, ws, inf, sc, st;
+    HIPCHK(c, A.alloc(sizeof(double) * (size_t)astride * batch));
+    HIPCHK(c, pts.alloc(sizeof(double) * (size_t)d * L.ntot * batch));
+    HIPCHK(c, yd.alloc(sizeof(double) * (size_t)L.npad * batch));
+    HIPCHK(c, gp.alloc(sizeof(GaussParams) * (size_t)batch));
+    HIPCHK(c, dv.alloc(sizeof(double) * BQ_DINV_STRIDE * (size_t)batch));
+    HIPCHK(c, ws.alloc(sizeof(double) * 64 * (size_t)L.ntot * batch));
+    HIPCHK(c, inf.alloc(sizeof(int) * (size_t)batch));
+    HIPCHK(c, sc.alloc(sizeof(double) * 4 * (size_t)batch));
+    HIPCHK(c, st.alloc(sizeof(long long) * 16));
+    for (DevBuf *b : {&A, &dv, &ws, &inf, &sc})
+        HIPCHK(c, hipMemsetAsync(b->p, 0xA5, b->bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(pts.p, 0, pts.bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(yd.p, 0, yd.bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(st.p, 0, st.bytes, c->stream));
+    std::vector<GaussParams> hgp((size_t)batch, make_params((int)d, h, w, s));
+    HIPCHK(c, hipMemcpyAsync(gp.p, hgp.data(), gp.bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(pts.p, sizeof(double) * d * L.ntot, x, sizeof(double) * d * n,
+                               sizeof(double) * d * n, batch, hipMemcpyHostToDevice, c->stream));
+    if (M > 0)
+        HIPCHK(c, hipMemcpy2DAsync(pts.d() + (size_t)d * L.npad, sizeof(double) * d * L.ntot, xo,
+                                   sizeof(double) * d * M, sizeof(double) * d * M, batch,
+                                   hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(yd.p, sizeof(double) * L.npad, y, sizeof(double) * n,
+                               sizeof(double) * n, batch, hipMemcpyHostToDevice, c->stream));
+    FirstStep fs;
+    fs.S0 = ws.d();
+    fs.lds = L.ntot;
+    fs.sstride = 64L * L.ntot;
+    fs.dinv = dv.d();
+    fs.info = inf.i();
+    fs.scal = sc.d();
+    fs.stamps = stamps16 ? static_cast<long long *>(st.p) : nullptr;
+    BQCHK(launch_assemble(c, (int)d, pts.d(), (long)d * L.ntot, yd.d(), L.npad,
+                          static_cast<const GaussParams *>(gp.p), 1, A.d(), lda, astride, L,
+                          (int)batch, fs));
+    for (int64_t b = 0; b < batch; ++b)
+        HIPCHK(c, hipMemcpy2DAsync(Acol + (size_t)b * 64 * L.ntot, sizeof(double) * L.ntot,
+                                   A.d() + (size_t)b * astride, sizeof(double) * lda,
+                                   sizeof(double) * L.ntot, 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S0, ws.p, ws.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dinv, dv.p, dv.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(info, inf.p, inf.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(scal, sc.p, sc.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (stamps16)
+        HIPCHK(c, hipMemcpyAsync(stamps16, st.p, st.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+
 // One eager (not graph-replayed) pass of a plan with the profiling instantiation of the slab
 // step: stamps[160 * step + k] = s_memtime of workgroup 0 at (0) entry, (1) factor fragments
 // loaded, (2) panel rows solved, (3) tile loaded + Q in LDS, (4) tile updated, (5..9) the

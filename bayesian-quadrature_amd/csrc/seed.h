@@ -7,11 +7,17 @@
 // Entry (ii, j) of the bordered system from the two points (xi, xj; pi, pj: whether row / column
 // carry a point at all): THE arithmetic of the assembly -- the seeded products (gram_seed_neg)
 // call the same function, so a tile computed there has the bits of one stored here.
-template <int D>
-__device__ __forceinline__ double bordered_entry(int ii, int j, bool pi, bool pj,
-                                                 const double (&xi)[D], const double (&xj)[D],
-                                                 const GaussParams &g, const Layout &L,
-                                                 const double *__restrict__ y)
+// (bordered_entry_y: y as anything with y[j] -- the pointer, or YHeld for a caller that holds
+// y[j] already)
+struct YHeld {
+    double v;
+    __device__ __forceinline__ double operator[](int) const { return v; }
+};
+
+template <int D, class Y>
+__device__ __forceinline__ double bordered_entry_y(int ii, int j, bool pi, bool pj,
+                                                   const double (&xi)[D], const double (&xj)[D],
+                                                   const GaussParams &g, const Layout &L, Y y)
 {
     if (pi && pj) {
         double val = g.c * exp_gauss(gauss_q<D>(xi, xj, g));
@@ -22,6 +28,32 @@ __device__ __forceinline__ double bordered_entry(int ii, int j, bool pi, bool pj
     if (ii == L.yrow)
         return (j < L.n) ? y[j] : 0.0;
     return (ii == j) ? 1.0 : 0.0;
+}
+
+template <int D>
+__device__ __forceinline__ double bordered_entry(int ii, int j, bool pi, bool pj,
+                                                 const double (&xi)[D], const double (&xj)[D],
+                                                 const GaussParams &g, const Layout &L,
+                                                 const double *__restrict__ y)
+{
+    return bordered_entry_y<D, const double *__restrict__>(ii, j, pi, pj, xi, xj, g, L, y);
+}
+
+// The same entry as straight-line code, for the assembly: a thread there produces many entries,
+// and the branches above make every exp a basic block of its own -- one dependent chain after the
+// other, each behind the wait for its own loads.  Here the kernel value is computed whether or not
+// row and column carry a point (xi, xj: ANY valid point where they do not -- the caller loads with
+// clamped indices, under no branch) and the entry is selected afterwards.  Both arms are
+// bordered_entry's own.  yj: y[j] where j < L.n (anything elsewhere).
+template <int D>
+__device__ __forceinline__ double bordered_entry_flat(int ii, int j, bool pi, bool pj,
+                                                      const double (&xi)[D], const double (&xj)[D],
+                                                      const GaussParams &g, const Layout &L,
+                                                      double yj)
+{
+    const double kv = bordered_entry_y<D, YHeld>(ii, j, true, true, xi, xj, g, L, YHeld{yj});
+    const double ov = bordered_entry_y<D, YHeld>(ii, j, false, false, xi, xj, g, L, YHeld{yj});
+    return (pi && pj) ? kv : ov;
 }
 
 // The accumulators of a (16 TM) x (16 TN) wave tile in the rotated-quad layout (gemm.h, Tile444)

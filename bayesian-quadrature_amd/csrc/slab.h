@@ -473,24 +473,134 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
 
 // The assembly of the bordered system with the first launch of the slab sweep folded in: the
 // tiles of column block 0 also fill the sweep's scratch column, and the workgroup of tile
-// (0, 0) clears the failure flag and factors the leading 64 x 64 block once its own stores are
-// out -- one launch, one memset and 12 us less per pass of a small problem.
+// (0, 0) factors the leading 64 x 64 block and with it starts the failure flag and log|K| (its
+// factor stores them; the stored form, !REGS, clears them in front of it) -- one launch, one memset
+// and 12 us less per pass of a small problem.
 // NW = 8 (one problem or a few: the grid has a CU per workgroup): 512 threads, waves 4-7 only
-// join the diagonal factor of tile (0, 0) (potf2f_body<8>).
-template <int D, int NW = 4>
+// join workgroup (0, 0) (potf2f_body<8>).
+
+// The leading 64 x 64 block computed where the factor wants it: wave w's columns 4 (NW q + w) + s
+// of row `lane`, each entry by the assembly's own function (same arithmetic, same bits).  Rows and
+// columns below 64 <= npad carry a point or are identity padding, never the y row.  All of a
+// group's column points are requested before its first exp (all groups' where the dimension leaves
+// the registers for it; wv: the wave's number as a vector value, so that they are vector loads --
+// gram.h, assemble_tile), and the exps are independent.
+// The strict upper triangle -- the assembly has always written it, the factor never does -- is
+// stored from the registers: plain stores, nothing waits for them here.
+template <int D, int NW>
+__device__ __forceinline__ void first_block_regs(Potf2FT<NW> &st, const double *__restrict__ pts,
+                                                 const GaussParams &gm, double *__restrict__ A,
+                                                 long lda, const Layout &L, int wv, int lane)
+{
+    constexpr int NG = 16 / NW;
+    constexpr int GQ = 4 * NG * D <= 32 ? NG : 1; // groups whose points are held at a time
+    Layout L0 = L;
+    L0.yrow = -1;
+    GaussParams g;
+    g.c = gm.c, g.s2 = gm.s2;
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+        g.nh[k] = gm.nh[k];
+    const bool pi = lane < L.n;
+    double xi[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+        xi[k] = pts[k + (long)(pi ? lane : 0) * D];
+#pragma unroll
+    for (int q0 = 0; q0 < NG; q0 += GQ) {
+        double xj[GQ][4][D];
+#pragma unroll
+        for (int q = 0; q < GQ; ++q)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int c = 4 * (NW * (q0 + q) + wv) + s;
+#pragma unroll
+                for (int k = 0; k < D; ++k)
+                    xj[q][s][k] = pts[k + (long)(c < L.n ? c : 0) * D];
+            }
+        // nothing that waits for a load may move up between the loads
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < GQ; ++q)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int c = 4 * (NW * (q0 + q) + wv) + s;
+                st.a[q0 + q][s] =
+                    bordered_entry_flat<D>(lane, c, pi, c < L.n, xi, xj[q][s], g, L0, 0.0);
+            }
+    }
+    // (every entry is computed before the first store: the stores sit under a branch each, and the
+    // exps, sunk to their stores, were one basic block -- one dependent chain -- after the other)
+#pragma unroll
+    for (int q = 0; q < NG; ++q)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            PIN(st.a[q][s]);
+#pragma unroll
+    for (int q = 0; q < NG; ++q)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int c = 4 * (NW * q + wv) + s;
+            if (lane < c)
+                A[lane + (long)c * lda] = st.a[q][s];
+        }
+}
+
+// REGS (BQ_FIRST_REGS, the shipped form): workgroup (0, 0) assembles nothing but the leading block,
+// in registers, and factors it from there (first_block_regs) -- the unfactored lower triangle never
+// reaches memory: no store of it, no drain, no barrier, no reload.  Rows 64-127 of column block 0,
+// the other half of its tile, are the work of workgroup (0, 2): tile (0, 2) lies strictly above
+// the diagonal and has nothing else to do; at ntot = 128, where the grid has no such tile, the
+// launcher adds the row (one workgroup per problem: gridDim.x = 1 there).
+// !REGS: workgroup (0, 0) stores its tile, waits for the stores and loads the block back.
+// STAMP: the probe's instantiation (bq_probe_first_launch): workgroup (0, 0) of problem 0 records
+// s_memtime at [0] entry, [1] block assembled, [2 ..] the factor's own five (potf2.h, BQ_STAMP).
+template <int D, int NW = 4, bool REGS = true, bool STAMP = false>
 __global__ __launch_bounds__(64 * NW) void assemble_first_kernel(
     const double *__restrict__ pts, long pstride, const double *__restrict__ y, long ystride,
     const GaussParams *__restrict__ gp, int gpstride, double *__restrict__ A, long lda,
     long astride, Layout L, double *__restrict__ S0, long lds, long sstride,
-    double *__restrict__ dinv, long dstride, int *__restrict__ info, double *__restrict__ scal)
+    double *__restrict__ dinv, long dstride, int *__restrict__ info, double *__restrict__ scal,
+    long long *stamps)
 {
     __shared__ __attribute__((aligned(16))) double plds[BQ_POTF2_LDS_DOUBLES];
     const int b = blockIdx.z;
+    const bool corner = blockIdx.x == 0 && blockIdx.y == 0;
+    long long *const st0 = (STAMP && corner && b == 0) ? stamps : nullptr;
+    if (st0 && threadIdx.x == 0)
+        st0[0] = (long long)__builtin_amdgcn_s_memtime();
     A += (long)b * astride;
+    if constexpr (REGS) {
+        if (blockIdx.x == 0 && blockIdx.y == 2) {
+            if (NW == 4 || threadIdx.x < 256)
+                assemble_tile<D>(pts + (long)b * pstride, y + (long)b * ystride,
+                                 gp[(long)b * gpstride], A, lda, L, S0 + (long)b * sstride, lds, 64,
+                                 0, 128);
+            return;
+        }
+        if (corner) {
+            // info[b] = 0 and scal[4 b + 1] = 0 are not stored here: the factor is told that the
+            // failure flag and log|K| start with it (potf2f_run, `fresh`) -- it reads neither and
+            // stores both, a failure or none.  One writer per word, nothing to order.
+            __builtin_amdgcn_s_setprio(3);
+            const int lane = threadIdx.x & 63;
+            Potf2FT<NW> st;
+            first_block_regs<D, NW>(st, pts + (long)b * pstride, gp[(long)b * gpstride], A, lda, L,
+                                    (int)(threadIdx.x >> 6), lane);
+            if (st0) {
+                asm volatile("" ::"v"(st.a[0][0]));
+                if (threadIdx.x == 0)
+                    st0[1] = st0[2] = (long long)__builtin_amdgcn_s_memtime();
+            }
+            potf2f_run<NW>(st, A, lda, 0, dinv + (long)b * dstride, info + b, plds,
+                           st0 ? st0 + 2 : nullptr, scal ? scal + 4 * b + 1 : nullptr, L.n, true);
+            return;
+        }
+    }
     if (NW == 4 || threadIdx.x < 256)
         assemble_tile<D>(pts + (long)b * pstride, y + (long)b * ystride, gp[(long)b * gpstride],
                          A, lda, L, S0 + (long)b * sstride, lds);
-    if (blockIdx.x == 0 && blockIdx.y == 0) {
+    if (!REGS && corner) {
         if (threadIdx.x == 0) {
             info[b] = 0;
             if (scal)
@@ -498,9 +608,11 @@ __global__ __launch_bounds__(64 * NW) void assemble_first_kernel(
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads(); // the block's 64 x 64 entries (rows 0..63 of this tile) are in memory
+        if (st0 && threadIdx.x == 0)
+            st0[1] = (long long)__builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_setprio(3);
-        potf2_body<NW>(A, lda, 0, dinv + (long)b * dstride, info + b, plds, nullptr, 0, nullptr,
-                       scal ? scal + 4 * b + 1 : nullptr, L.n);
+        potf2_body<NW>(A, lda, 0, dinv + (long)b * dstride, info + b, plds, nullptr, 0,
+                       st0 ? st0 + 2 : nullptr, scal ? scal + 4 * b + 1 : nullptr, L.n);
     }
 }
 

@@ -558,6 +558,41 @@ class Engine(object):
             route.ctypes.data_as(L._i32p)))
         return info, (self.SWEEP_KINDS[route[0]], int(route[1]), bool(route[2]))
 
+    def probe_first_launch(self, x, y, xo, h, w, s, stamps=False):
+        """The first launch of a small system's sweep alone (bq_probe_first_launch): x (B, d, n),
+        y (B, n), xo (B, d, M) as a plan takes them.  Returns a dict of what the launch left in
+        memory -- "A" (B, ntot, 64), the first block column of every system; "S0" (B, ntot, 64);
+        "dinv" (B, record); "info" (B,); "scal" (B, 4) -- over buffers preset to 0xA5 bytes, and
+        with stamps (d = 1) "stamps": 16 shader-clock values of workgroup (0, 0)."""
+        e = self.probe_engine()
+        x = np.asarray(x, dtype=np.float64)
+        B, d, n = x.shape
+        xo = np.zeros((B, d, 0)) if xo is None else np.asarray(xo, dtype=np.float64)
+        M = xo.shape[2]
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != (B, n) or xo.shape != (B, d, M):
+            raise ValueError("y must be (B, n) and xo (B, d, M)")
+        # point-major per problem, as the plans take their inputs
+        xf = np.ascontiguousarray(np.transpose(x, (0, 2, 1)))
+        xof = np.ascontiguousarray(np.transpose(xo, (0, 2, 1)))
+        wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), (d,)))
+        ntot = -(-(-(-n // 64) * 64 + M + 1) // 64) * 64
+        rec = 2 * (64 + 4 * 256)  # (ntot and rec go along: the library checks both against its own)
+        out = {"A": np.empty((B, 64, ntot)), "S0": np.empty((B, 64, ntot)),
+               "dinv": np.empty((B, rec)), "info": np.empty(B, dtype=np.int32),
+               "scal": np.empty((B, 4))}
+        st = np.zeros(16, dtype=np.int64) if stamps else None
+        e._check(e._lib.bq_probe_first_launch(
+            e._ctx, B, d, n, M, L.dptr(xf), L.dptr(y), L.dptr(xof) if M else None, float(h),
+            L.dptr(wv), float(s), ntot, rec, L.dptr(out["A"]), L.dptr(out["S0"]), L.dptr(out["dinv"]),
+            out["info"].ctypes.data_as(L._i32p), L.dptr(out["scal"]),
+            st.ctypes.data_as(C.POINTER(C.c_int64)) if stamps else None))
+        out["A"] = np.transpose(out["A"], (0, 2, 1))
+        out["S0"] = np.transpose(out["S0"], (0, 2, 1))
+        if stamps:
+            out["stamps"] = st
+        return out
+
     SWEEPS = ("forward_rows", "backward_rows", "forward_rows_blk", "inverse_rows", "forward_vec",
               "backward_vec", "forward_vec_flow", "backward_vec_flow")
     ROWS_KINDS = ("step", "fused", "gemm_rows", "blk", "vec_block", "vec_flow")

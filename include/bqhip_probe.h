@@ -74,6 +74,21 @@ int bq_probe_launch(bq_ctx *ctx, int64_t n, double *us_per_launch);
  * instantiation of the one-launch slab step: 160 s_memtime stamps of workgroup 0 per step
  * (10 phase boundaries, then the diagonal factor's per-wave barrier stamps). */
 int bq_probe_c2_timeline(bq_ctx *ctx, bq_plan *plan, int64_t *stamps, int64_t nsteps);
+/* The first launch of a small system's sweep alone -- the assembly with the leading block's factor
+ * folded in (csrc/slab.h, assemble_first_kernel; BQ_FIRST_REGS selects its form) -- on `batch`
+ * problems of n points in d dimensions with M prediction points (x: batch x n x d, y: batch x n,
+ * xo: batch x M x d; one h, w[d], s for all), and what it leaves in memory, every buffer preset to
+ * 0xA5 bytes: Acol, the first 64 columns of every system (batch x 64 x ntot, column-major, ld
+ * ntot: the leading block's strict upper triangle, its factor, the unsolved rows below); S0, the
+ * sweep's scratch column (batch x 64 x ntot); dinv (batch x BQ_DINV_STRIDE doubles); info (batch);
+ * scal (batch x 4).  ntot = roundup(roundup(n, 64) + M + 1, 64) and dinv_len = the record's doubles as
+ * the caller sized its buffers for them: anything else is BQ_ERR_BAD_ARG.  stamps16 (null, or d = 1): 16
+ * s_memtime values of workgroup (0, 0) of problem 0 -- entry, block assembled, then the factor's
+ * five phase boundaries.  (tests/test_first_launch.py) */
+int bq_probe_first_launch(bq_ctx *ctx, int64_t batch, int64_t d, int64_t n, int64_t M,
+                          const double *x, const double *y, const double *xo, double h,
+                          const double *w, double s, int64_t ntot, int64_t dinv_len, double *Acol,
+                          double *S0, double *dinv, int32_t *info, double *scal, int64_t *stamps16);
 /* The 64 x 64 diagonal factor alone (the launch that heads every panel step): A is a
  * 64 x 64 host matrix, factored `reps` times from a resident copy (from_lds != 0: handed
  * over through LDS as the one-launch steps do).  Last launch's factor, its

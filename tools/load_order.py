@@ -9,7 +9,8 @@ issued here" is a wish until the ISA says so.
 For every kernel named (template arguments: bool and int literals) this walks the ISA of
 `make asm` (build/asm/k_*.s) from the kernel's entry to its first s_barrier IN TEXT ORDER and
 prints the loads, the vmcnt waits and the branches in between, run-length coded, then the number
-of vector-memory loads that follow a vmcnt wait.  Text order, not a walk of the flow graph: a load
+of vector-memory loads that follow a vmcnt wait (stores are listed too, and a wait that stands
+behind one is marked: vmcnt counts stores as well).  Text order, not a walk of the flow graph: a load
 counts if ANY wait stands above it, whichever path a wave takes, so 0 means every path is clean.
 Exit status 1 if the count is not 0 for any kernel named (or a kernel is not found).  Host-only."""
 import argparse
@@ -56,6 +57,7 @@ def find_kernel(files, prefix):
 
 
 LOAD = re.compile(r"^\s+((?:global|flat|buffer|scratch)_load_\w+)")
+STORE = re.compile(r"^\s+((?:global|flat|buffer|scratch)_store_\w+)")
 WAIT = re.compile(r"^\s+s_waitcnt\b.*\bvmcnt\((\d+)\)")
 BRANCH = re.compile(r"^\s+(s_c?branch\w*)\s+(\S+)")
 CMP = re.compile(r"^\s+(s_cmpk?_\w+\s+.*)$")
@@ -64,7 +66,7 @@ CMP = re.compile(r"^\s+(s_cmpk?_\w+\s+.*)$")
 def walk(body):
     """events up to the first s_barrier: (kind, text); and the number of loads behind a wait"""
     ev, waited, behind, last_cmp = [], False, 0, None
-    found = False
+    found = stored = False
     for line in body:
         line = line.split(";")[0].rstrip()
         if re.match(r"^\s+s_barrier\b", line):
@@ -78,9 +80,14 @@ def walk(body):
             ev.append(("load" + (" BEHIND A WAIT" if waited else ""), m.group(1)))
             behind += waited
             continue
+        m = STORE.match(line)
+        if m:  # (vmcnt counts stores too: a wait behind one may stand for its acknowledgement)
+            ev.append(("store", m.group(1)))
+            stored = True
+            continue
         m = WAIT.match(line)
         if m:
-            ev.append(("wait", "vmcnt(%s)" % m.group(1)))
+            ev.append(("wait" + (" behind a store" if stored else ""), "vmcnt(%s)" % m.group(1)))
             waited = True
             continue
         m = BRANCH.match(line)
