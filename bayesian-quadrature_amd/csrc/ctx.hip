@@ -108,34 +108,8 @@ static int ctx_init(bq_ctx *c, int device)
         *c->flow_abort = 0;
     }
     // environment switches: each selects a path that a GPU test compares the shipped one against
-    // (README lists them with their tests)
-    static const struct {
-        const char *name;
-        int bq_ctx::*field;
-    } switches[] = {
-        {"BQ_TRSV_FLOW", &bq_ctx::trsv_flow},
-        {"BQ_LOOKAHEAD", &bq_ctx::lookahead},
-        {"BQ_DIAG_FIRST", &bq_ctx::diag_first},
-        {"BQ_ASM_FUSE", &bq_ctx::asm_fuse},
-        {"BQ_DF_SWEEP", &bq_ctx::df_sweep},
-        {"BQ_DF_WG", &bq_ctx::df_wg},
-        {"BQ_PAIR_BORDER", &bq_ctx::pair_border},
-        {"BQ_DF_WG_ROWS", &bq_ctx::df_wg_rows},
-        {"BQ_DF_EARLY", &bq_ctx::df_early},
-        {"BQ_SOLVE_KCOPY", &bq_ctx::solve_kcopy},
-        {"BQ_LA_MIN", &bq_ctx::la_min},
-        {"BQ_GEMM_LDS", &bq_ctx::gemm_lds},
-        {"BQ_FOLD_READOUT", &bq_ctx::fold_readout},
-        {"BQ_POTF2_8W", &bq_ctx::potf2_8w},
-        {"BQ_SLAB8_ROUNDS", &bq_ctx::slab8_rounds},
-        {"BQ_FIRST_REGS", &bq_ctx::first_regs},
-        {"BQ_GEMM_KSPLIT", &bq_ctx::gemm_ksplit},
-        {"BQ_GEMM_TILE", &bq_ctx::gemm_tile},
-        {"BQ_GRAPH", &bq_ctx::use_graph},
-    };
-    for (const auto &sw : switches)
-        if (const char *e = std::getenv(sw.name))
-            c->*sw.field = std::atoi(e);
+    // (launch_config.h is the list; README names them with their tests)
+    c->cfg = LaunchConfig::from_env();
     return BQ_OK;
 }
 
@@ -256,7 +230,7 @@ extern "C" int bq_set_block(bq_ctx *c, int nb)
 {
     if (!c || nb < 0 || (nb & 63))
         return c ? fail(c, BQ_ERR_BAD_ARG, "block must be a multiple of 64") : BQ_ERR_BAD_ARG;
-    c->nb_override = nb;
+    c->cfg.nb_override = nb;
     return BQ_OK;
 }
 
@@ -264,7 +238,7 @@ extern "C" int bq_set_lookahead(bq_ctx *c, int on)
 {
     if (!c)
         return BQ_ERR_BAD_ARG;
-    c->lookahead = on ? 1 : 0;
+    c->cfg.lookahead = on ? 1 : 0;
     return BQ_OK;
 }
 
@@ -273,11 +247,11 @@ extern "C" int bq_get_config(bq_ctx *c, int *nb, int *lookahead, int *min_rows)
     if (!c)
         return BQ_ERR_BAD_ARG;
     if (nb)
-        *nb = c->nb_override;
+        *nb = c->cfg.nb_override;
     if (lookahead)
-        *lookahead = c->lookahead;
+        *lookahead = c->cfg.lookahead;
     if (min_rows)
-        *min_rows = c->la_min;
+        *min_rows = c->cfg.la_min;
     return BQ_OK;
 }
 
@@ -289,8 +263,9 @@ extern "C" int bq_ctx_stats(bq_ctx *c, int64_t *out, int n)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     for (int i = 0; i < n; ++i)
         out[i] = 0;
-    if (n > 0)
-        out[0] = c->n_flow_fallback;
+    const int64_t v[] = {c->n_flow_fallback, c->graphs.captures, c->graphs.replays, c->graphs.drops};
+    for (int i = 0; i < n && i < 4; ++i)
+        out[i] = v[i];
     return BQ_OK;
 }
 
@@ -298,7 +273,7 @@ extern "C" int bq_set_lookahead_rows(bq_ctx *c, int min_rows)
 {
     if (!c || min_rows < 0)
         return c ? fail(c, BQ_ERR_BAD_ARG, "min_rows must be >= 0") : BQ_ERR_BAD_ARG;
-    c->la_min = min_rows;
+    c->cfg.la_min = min_rows;
     return BQ_OK;
 }
 

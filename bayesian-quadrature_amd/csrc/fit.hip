@@ -66,7 +66,7 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     // stream 8-9 us, a further kernel 2.9 (tools/stream_ops_bench.hip); a refit at the reference's
     // own sizes is 40 us in all.
     double *hmap = nullptr;
-    if (c->solve_kcopy)
+    if (c->cfg.solve_kcopy)
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hfit, 0));
     static_assert(sizeof(GaussParams) % 8 == 0, "GaussParams is copied in 8-byte words");
     if (hmap) {
@@ -354,7 +354,7 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
 
     // ---- the observations in: through the fit's mapped staging when they fit in it
     double *hmap = nullptr;
-    if (c->solve_kcopy && f->hfit)
+    if (c->cfg.solve_kcopy && f->hfit)
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hfit, 0));
     const size_t nx = (size_t)d * k;
     if (hmap && nx + k <= HF_NPTS) {
@@ -879,7 +879,7 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
     // (points in and results out through kernels on the mapped staging buffer: a copy-engine
     // operation costs the stream 8-9 us, a further kernel 2.9 -- tools/stream_ops_bench.hip)
     double *hmap = nullptr;
-    if (c->solve_kcopy)
+    if (c->cfg.solve_kcopy)
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hio, 0));
     // mean + variance without the covariance (BQ.l_var, _set_gp_log_l_params: bq.py:227-228,
     // 942-943) is six launches: the cross Gram reads the points out of the mapped staging buffer

@@ -1,7 +1,10 @@
 // host.h -- internal header of libbqhip.so's host side: the context, the handle types and
 // the launch / enqueue helpers the translation units share.  Nothing here is part of the C
 // ABI (include/bqhip.h is); the library is built with hidden visibility and exports only
-// the extern "C" entry points.
+// the extern "C" entry points.  The switches that select launches and the hipGraph a launch sequence
+// is captured into live in launch_config.h (LaunchConfig: one list; CapturedSeq: the only code that
+// captures, launches or destroys a graph); bq_ctx::cfg is the former, plans, pairs and fits hold the
+// latter.
 //
 // Translation units (Makefile; all but probe.hip make libbqhip.so, all of them together
 // libbqhip_probe.so, whose extra entry points include/bqhip_probe.h declares):
@@ -28,6 +31,7 @@
 #include "../../include/bqhip.h"
 #pragma GCC visibility pop
 
+#include "launch_config.h"
 #include "types.h"
 
 #include <algorithm>
@@ -124,49 +128,20 @@ struct bq_ctx {
     hipStream_t aux = nullptr;    // high-priority panel stream of the look-ahead Cholesky
     hipStream_t cur = nullptr;    // stream the launch helpers enqueue on (stream or aux)
     hipEvent_t ev_panel = nullptr, ev_next = nullptr, ev_fork = nullptr, ev_top = nullptr;
-    int lookahead = 1;
-    int diag_first = 1;  // batches: every outer block as diagonal factor, ONE panel solve, update
-                         // (enqueue_potrf_dfirst; BQ_DIAG_FIRST=0: the recursive panels)
-    int df_sweep = 1;    // the panel solve of an outer block in one launch (trsm_sweep_kernel; BQ_DF_SWEEP)
-    int df_wg = -1;      // a batch's diagonal factor by one workgroup per matrix (potrf_wg_kernel): -1 by
-                         // batch size (potrf.hip, dfirst_wg), 0 / 1 forced (BQ_DF_WG)
-    int trsv_flow = 1;   // single-vector sweeps as one launch each, hand-offs through memory
-                         // (trsvflow.h; BQ_TRSV_FLOW=0: one launch per block column)
+    LaunchConfig cfg;    // every field an environment switch or a setter writes (launch_config.h)
+    CaptureStats graphs; // what the captured sequences of this context did (bq_ctx_stats)
     int *flow_abort = nullptr; // mapped host word a timed-out hand-off raises
     long n_flow_fallback = 0;  // solves re-issued on the per-block sweeps after such a time-out
                                // (bq_ctx_stats)
-    int pair_border = 1; // bq_pair_esm as S factorisations + border rows (BQ_PAIR_BORDER=0: the S Ma
-                         // full bordered systems)
-    int df_wg_rows = 1000; // ... and, below that batch size, for the blocks with at least this many rows
-                         // below them: the factors an update hides (BQ_DF_WG_ROWS; 0: never)
-    int df_early = 1;    // the diagonal-first sweep forks before the panel solve: the next diagonal block's
-                         // rows are solved, updated and factored beside the rest of the solve (BQ_DF_EARLY)
-    int solve_kcopy = 1; // a one-vector solve's vector in / out and sentinel fill by kernels (BQ_SOLVE_KCOPY)
     double *hstage = nullptr; // mapped pinned staging of the small host-buffer calls (ctx_stage)
     size_t hstage_len = 0;
-    int la_min = 3072;   // look-ahead only while the bulk update has at least this many rows (BQ_LA_MIN)
     DevBuf panel_ws;     // scratch panel columns of the eager linalg entry points
     DevBuf scratch;      // per-call temporaries of the acquisition / moment entry points, kept
                          // between calls (hipFree synchronises the device); bq_ctx_trim frees it
-    int gemm_lds = 1;    // LDS-staged 128x128 trailing update (BQ_GEMM_LDS)
-    int fold_readout = 1; // one-launch sweeps carry their read-out (SlabOut; BQ_FOLD_READOUT)
-    int asm_fuse = 1;    // a batched plan assembles only the first outer block's columns; the rest of
-                         // the system is computed inside the first products that touch it
-                         // (GramSeed; BQ_ASM_FUSE=0: the whole system is assembled first)
-    int potf2_8w = 1;    // the one-launch steps' diagonal factor on eight waves where a step's workgroups
-                         // have a CU each (BQ_POTF2_8W)
-    int first_regs = 1;  // the assembly's workgroup (0, 0) computes the leading block in the factor's
-                         // registers (assemble_first_kernel; BQ_FIRST_REGS=0: stored, drained, reloaded)
-    int slab8_rounds = 1 << 20; // ... and a slab step's 512-thread form while the step has at most this many
-                         // workgroups per CU (launch_slab_step: no limit shipped; BQ_SLAB8_ROUNDS, 0: one)
-    int gemm_ksplit = 1; // eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT)
-    int gemm_tile = 0;   // 64 / 128: force the LDS kernel's workgroup tile (BQ_GEMM_TILE; measurements)
     int sharing = 0;     // how the chip is shared while the launches being queued run (gemm_route):
                          // 0 alone, 1 the two streams of a look-ahead, 2 the two halves of a batch
-    int use_graph = 1;   // replay plans from a captured hipGraph (BQ_GRAPH=0 disables)
     bool own_stream = false;
     int cus = 256;
-    int nb_override = 0;
     bq_plan *plan_cache = nullptr; // workspace of the last batched call, kept for the next one
     char err[512] = {0};
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -216,21 +191,6 @@ inline int fail(bq_ctx *c, int code, const char *fmt, ...)
     } while (0)
 
 inline long roundup(long v, long q) { return (v + q - 1) / q * q; }
-
-// Every context field that decides which launches a sweep is made of, hashed: a captured
-// hipGraph (plans, the pair's objective) is replayed only while this is what it was captured
-// under -- whichever setter, environment switch or probe changed a field.
-inline unsigned long long launch_config_key(const bq_ctx *c)
-{
-    const int f[] = {c->nb_override, c->lookahead, c->la_min,   c->gemm_lds,  c->fold_readout,
-                     c->potf2_8w,    c->gemm_ksplit, c->gemm_tile, c->diag_first, c->df_sweep,
-                     c->df_wg,       c->df_early,   c->df_wg_rows, c->slab8_rounds,
-                     c->first_regs};
-    unsigned long long h = 1469598103934665603ull;
-    for (int v : f)
-        h = (h ^ (unsigned long long)(unsigned)v) * 1099511628211ull;
-    return h;
-}
 
 // leading dimension for an ntot x ntot column-major matrix: even, and nudged
 // off large powers of two so that the 4 columns of an MFMA fragment do not
@@ -525,6 +485,14 @@ struct Sharing {
     Sharing(bq_ctx *c_, int how) : c(c_), prev(c_->sharing) { c->sharing = how; }
     ~Sharing() { c->sharing = prev; }
 };
+// scope of bq_ctx::cur: the launch helpers enqueue on `s` (the second stream of a look-ahead; the
+// stream in force where a sweep forks only conditionally) until the scope ends, on every exit path
+struct OnStream {
+    bq_ctx *c;
+    hipStream_t prev;
+    OnStream(bq_ctx *c_, hipStream_t s) : c(c_), prev(c_->cur) { c->cur = s; }
+    ~OnStream() { c->cur = prev; }
+};
 int auto_nb(const bq_ctx *c, int ntot, int batch);
 // How the first ncols columns of `batch` matrices of ntot rows are eliminated, decided in ONE place
 // (sweep_route): every enqueue asks again with the workspace on hand (a setter may have changed the
@@ -645,10 +613,7 @@ struct bq_plan {
     bool has_inputs = false;
     // the launch sequence of a plan is static: it is captured once into a hipGraph
     // and replayed (cuts the host launch cost of the ~50 short kernels of a step)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    int graph_state = 0; // 0 = not tried, 1 = ready, -1 = unavailable (eager launches)
-    unsigned long long graph_key = 0; // launch_config_key the graph was captured under
+    CapturedSeq seq;
     double *hres = nullptr; // pinned staging of bq_plan_results: [scal 4 nb | info nb | mean | var]
     double *hin = nullptr;  // pinned staging of a small plan's inputs (bq_plan_set_inputs)
     size_t hin_len = 0;
@@ -783,23 +748,7 @@ struct bq_fit : FitCore {
     size_t hio_len = 0;
     double *hfit = nullptr; // pinned staging of a (re)fit: [results 8 + 128 | GaussParams | 63 d
                             // border points] -- the hyper-parameter loop's body is three small copies
-    hipGraph_t vgraph[3] = {nullptr, nullptr, nullptr};
-    hipGraphExec_t vgexec[3] = {nullptr, nullptr, nullptr};
-    bool vg_failed[3] = {false, false, false};
-    int vg_flow[3] = {0, 0, 0}; // c->trsv_flow when the slot's graph was captured
-    // the captured sweeps go: the next use of a slot captures again
-    void drop_graphs()
-    {
-        for (int i = 0; i < 3; ++i) {
-            if (vgexec[i])
-                (void)hipGraphExecDestroy(vgexec[i]);
-            if (vgraph[i])
-                (void)hipGraphDestroy(vgraph[i]);
-            vgexec[i] = nullptr;
-            vgraph[i] = nullptr;
-            vg_failed[i] = false;
-        }
-    }
+    CapturedSeq vseq[3];
     ~bq_fit()
     {
         if (hvec)
@@ -808,8 +757,7 @@ struct bq_fit : FitCore {
             (void)hipHostFree(hio);
         if (hfit)
             (void)hipHostFree(hfit);
-        drop_graphs();
-    }
+    } // (the captured sweeps go with vseq)
     // false from the start of a (re)factorisation until it has succeeded: a refit that hits a
     // non-positive pivot leaves L, dinv, dw and the scalars overwritten with garbage
     bool valid = false;
@@ -831,7 +779,8 @@ inline void fit_adopt(bq_fit *f, FitCore &core)
     if (f->hvec)
         (void)hipHostFree(f->hvec);
     f->hvec = nullptr;
-    f->drop_graphs();
+    for (CapturedSeq &v : f->vseq)
+        v.drop();
 }
 } // namespace bqh
 
@@ -842,47 +791,16 @@ int fit_dw(bq_ctx *c, bq_fit *f);
 int fit_wide(bq_ctx *c, bq_fit *f, WideInv &w);
 int fit_vec(bq_ctx *c, bq_fit *f);
 int fit_alpha(bq_ctx *c, bq_fit *f);
-// Replays a chain of sweep launches over a fit's own buffers from a captured hipGraph (a
-// sweep is 2 npad / B launches of 2-8 us each: enqueued one by one the host is the
-// bottleneck); eager when graphs are off, under the launch profiler, or if capture fails.
+// Replays a chain of sweep launches over a fit's own buffers from the slot's captured hipGraph (a
+// sweep is 2 npad / B launches of 2-8 us each: enqueued one by one the host is the bottleneck).
 template <class F>
 int fit_replay(bq_ctx *c, bq_fit *f, int slot, F &&enqueue)
 {
     // (a one-launch sweep is two memsets and a kernel: enqueued directly it costs the host less
     // than a graph launch does)
-    if (!c->use_graph || c->prof || !c->own_stream || c->cur != c->stream ||
-        trsv_flow_ok(c, f->npad, wide_block(f->npad)))
+    if (trsv_flow_ok(c, f->npad, wide_block(f->npad)))
         return enqueue();
-    // a graph captured with the one-launch sweeps inside is not what a fall-back retry (or a
-    // caller that switched them off) asks for: such a call is enqueued eagerly
-    if (f->vgexec[slot] && f->vg_flow[slot] != c->trsv_flow)
-        return enqueue();
-    if (!f->vgexec[slot] && !f->vg_failed[slot]) {
-        f->vg_failed[slot] = true;
-        f->vg_flow[slot] = c->trsv_flow;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-            const int st = enqueue();
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(c->stream, &g);
-            if (st == BQ_OK && e == hipSuccess && g &&
-                hipGraphInstantiate(&f->vgexec[slot], g, nullptr, nullptr, 0) == hipSuccess) {
-                f->vgraph[slot] = g;
-                f->vg_failed[slot] = false;
-            } else {
-                if (g)
-                    (void)hipGraphDestroy(g);
-                f->vgexec[slot] = nullptr;
-                (void)hipGetLastError();
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (f->vgexec[slot]) {
-        HIPCHK(c, hipGraphLaunch(f->vgexec[slot], c->stream));
-        return BQ_OK;
-    }
-    return enqueue();
+    return f->vseq[slot].run(c, enqueue);
 }
 // A one-launch sweep whose hand-off timed out (trsvflow.h: a shared device, a lost slot) has raised
 // the context's abort word and every spinner has left: the results of `attempt` are garbage.
@@ -897,13 +815,13 @@ int with_flow_fallback(bq_ctx *c, F &&attempt)
     if (st != BQ_OK || !flow_timed_out(c))
         return st;
     ++c->n_flow_fallback;
-    const int saved = c->trsv_flow;
-    c->trsv_flow = 0;
+    const int saved = c->cfg.trsv_flow;
+    c->cfg.trsv_flow = 0;
     st = attempt();
-    c->trsv_flow = saved;
+    c->cfg.trsv_flow = saved;
     // the retry must not have gone through a one-launch sweep again (a captured graph that still
-    // holds one: fit_replay keys its graphs on trsv_flow) -- if the word is up again the results
-    // are garbage and the call says so
+    // holds one: a slot captured under another trsv_flow is dropped, CapturedSeq) -- if the word
+    // is up again the results are garbage and the call says so
     if (st == BQ_OK && flow_timed_out(c))
         return fail(c, BQ_ERR_HIP, "a sweep's hand-off timed out again on the per-block kernels");
     return st;

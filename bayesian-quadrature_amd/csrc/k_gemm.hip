@@ -73,7 +73,7 @@ int gemm_init(bq_ctx *c)
 // BQ_GEMM_TILE=64|128 (read when a context is created) forces a tile where its kernel can run.
 static int gemm_lds_tile(const bq_ctx *c, int m, int n, int k, int lower, int batch)
 {
-    if (!c->gemm_lds || (m % 64) || (n % 64) || (k % 32))
+    if (!c->cfg.gemm_lds || (m % 64) || (n % 64) || (k % 32))
         return 0;
     const bool tri = lower && m == n;
     auto tiles = [&](int t) {
@@ -83,7 +83,7 @@ static int gemm_lds_tile(const bq_ctx *c, int m, int n, int k, int lower, int ba
     };
     const long a = tiles(128), a64 = tiles(64);
     const bool can64 = k >= 64, can128 = n >= 128;
-    const int forced = c->gemm_tile;
+    const int forced = c->cfg.gemm_tile;
     if (forced == 64 && can64)
         return 64;
     if (forced == 128 && can128)
@@ -262,8 +262,8 @@ int launch_gemm(bq_ctx *c, int cls, const GemmJob &g, GemmRoute *ran)
 int grad_tile(const bq_ctx *c, int npad)
 {
     constexpr long kGrad128PerCu = 2;
-    if (c->gemm_tile == 64 || c->gemm_tile == 128)
-        return c->gemm_tile;
+    if (c->cfg.gemm_tile == 64 || c->cfg.gemm_tile == 128)
+        return c->cfg.gemm_tile;
     const long gm = (npad + 127) / 128;
     return gm * (gm + 1) / 2 >= kGrad128PerCu * c->cus ? 128 : 64;
 }
@@ -379,7 +379,7 @@ int launch_rows_fused(bq_ctx *c, int mrows, const RowsJob &a, double *C, long ld
     // tiles walk their k range in half the steps (the last step of an N = 4096 sweep, job tiles
     // only: 24 -> 16 us; a posterior variance at N = 1024: 0.067 -> 0.060 ms); the LDS tiles are
     // MFMA-bound either way
-    const bool ks2 = c->gemm_ksplit && nd + nu <= 2 * c->cus && ((a.k1 + a.k2) % 128) == 0 &&
+    const bool ks2 = c->cfg.gemm_ksplit && nd + nu <= 2 * c->cus && ((a.k1 + a.k2) % 128) == 0 &&
                      (nu == 0 || k >= 32);
 #define BQ_ROWS_FUSED(QT_, KS_)                                                                    \
     hipLaunchKernelGGL((rows_fused_kernel<QT_, KS_>), dim3(nd + nu), dim3(256 * KS_),              \
@@ -401,7 +401,7 @@ int launch_rows_fused(bq_ctx *c, int mrows, const RowsJob &a, double *C, long ld
 int launch_rows_step(bq_ctx *c, int mrows, const RowsJob &a, const RowsJob &b, double work)
 {
     Bracket br(c, BQ_K_GEMM, work);
-    const bool nw8 = c->gemm_ksplit && ((a.k1 + a.k2) % 128) == 0 &&
+    const bool nw8 = c->cfg.gemm_ksplit && ((a.k1 + a.k2) % 128) == 0 &&
                      (b.ny == 0 || ((b.k1 + b.k2) % 128) == 0) &&
                      (long)(mrows / 32) * (a.ny + b.ny) <= 2L * c->cus;
     if (nw8)

@@ -19,14 +19,14 @@ void launch_assemble_d(bq_ctx *c, const double *pts, long pstride, const double 
                            gp, gpstride, A, lda, astride, L);
         return;
     }
-    const bool regs = c->first_regs != 0;
+    const bool regs = c->cfg.first_regs != 0;
     // (the leading block in registers: workgroup (0, 2) takes rows 64-127 of column block 0 off
     // workgroup (0, 0) -- an idle tile from ntot = 192 on, one more workgroup per problem at
     // ntot = 128: assemble_first_kernel)
     if (regs && grid.y < 3)
         grid.y = 3;
     const long wgs = (long)grid.x * grid.y * grid.z;
-    const bool w8 = c->potf2_8w && wgs <= 2L * c->cus;
+    const bool w8 = c->cfg.potf2_8w && wgs <= 2L * c->cus;
 #define BQ_ASM_FIRST(NW_, REGS_, STAMP_)                                                           \
     hipLaunchKernelGGL((assemble_first_kernel<D, NW_, REGS_, STAMP_>), grid, dim3(64 * NW_), 0,    \
                        c->cur, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, fs.S0,  \
@@ -119,7 +119,7 @@ int launch_potf2(bq_ctx *c, double *A, long lda, long astride, int j0, double *d
 {
     Bracket br(c, BQ_K_POTF2, 64.0 * 64 * 64 / 3.0 * batch);
     // (eight waves where every matrix of the batch has a CU: potf2f_body<8>)
-    if (c->potf2_8w && batch <= c->cus)
+    if (c->cfg.potf2_8w && batch <= c->cus)
         hipLaunchKernelGGL(potf2_kernel<8>, dim3(1, 1, batch), dim3(512), 0, c->cur, A, lda, astride,
                            j0, dinv, dstride, info);
     else
@@ -177,7 +177,7 @@ int launch_panel_step(bq_ctx *c, double *A, long lda, long astride, int batch, i
     // NB / 64 x 21 us: from m = 4,000 rows down (64 row blocks) the chain out-lasts the update
     // it sits beside, finds free CUs for most of its steps, and takes the eight waves again.
     const bool beside_bulk = c->sharing != 0 && (long)nrb * batch > 64;
-    if (c->potf2_8w && !beside_bulk && (long)nrb * batch <= c->cus)
+    if (c->cfg.potf2_8w && !beside_bulk && (long)nrb * batch <= c->cus)
         hipLaunchKernelGGL(panel_step_kernel<8>, dim3(nrb, 1, batch), dim3(512), 0, c->cur, A, lda,
                            astride, Sin, Sout, lds, sstride, K0, j0, dinv_in, dinv_out,
                            (long)BQ_DINV_STRIDE, has_next, first, SL, info);
@@ -217,7 +217,7 @@ int launch_slab_first(bq_ctx *c, double *A, long lda, long astride, int batch, d
 // level from 1,700; the 3 - 4 us a step gains with every 256 workgroups are the same in both.
 static long slab8_limit(const bq_ctx *c)
 {
-    return (long)(c->slab8_rounds > 1 ? c->slab8_rounds : 1) * c->cus;
+    return (long)(c->cfg.slab8_rounds > 1 ? c->cfg.slab8_rounds : 1) * c->cus;
 }
 
 // one 64-column step of a small system in one launch (slab_step_kernel); out: the read-out the
@@ -233,7 +233,7 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
     // (the last step -- no next factor, the Schur complement of the border -- too: its
     // off-diagonal workgroups solve their two row blocks side by side; waves 4-7 leave after the
     // Q rows' barrier and waves 0-3 store and emit as in the four-wave form)
-    const bool w8 = c->potf2_8w && wgs <= slab8_limit(c);
+    const bool w8 = c->cfg.potf2_8w && wgs <= slab8_limit(c);
     if (stamps && w8)
         hipLaunchKernelGGL((slab_step_kernel<true, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512), 0,
                            c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,

@@ -272,7 +272,7 @@ bool trsv_flow_ok(const bq_ctx *c, int npad, int B, bool prefilled)
     // unless the caller fills the slots on its way in, bq_gp_solve: then from 1024 rows, half the
     // threshold: n = 1000 0.061 -> 0.053 ms, 1536 0.077 -> 0.074)
     constexpr int kFlowMin = 2048;
-    return c->trsv_flow && c->flow_abort && B <= 512 && (B & 63) == 0 && (npad & 63) == 0 &&
+    return c->cfg.trsv_flow && c->flow_abort && B <= 512 && (B & 63) == 0 && (npad & 63) == 0 &&
            npad >= (prefilled ? kFlowMin / 2 : kFlowMin) && (npad + B - 1) / B >= 2;
 }
 

@@ -52,7 +52,7 @@ extern "C" int bq_cho_factor(bq_ctx *c, const double *C, double *L, int64_t n, i
     if (n > 65536)
         return fail(c, BQ_ERR_BAD_ARG, "n too large");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->solve_kcopy && n <= 64) {
+    if (c->cfg.solve_kcopy && n <= 64) {
         // one 64 x 64 block: the diagonal factor's kernel straight on the mapped staging buffer
         // ([flag | the block with its identity padding]), one launch, one synchronisation
         double *hs = nullptr, *ds = nullptr;
@@ -88,7 +88,7 @@ extern "C" int bq_cho_factor(bq_ctx *c, const double *C, double *L, int64_t n, i
     long lda;
     // a small matrix (the reference's own sizes): in and out through the mapped staging buffer,
     // one kernel each way and ONE synchronisation
-    const bool small = c->solve_kcopy && (size_t)n * n + 1 <= (32u << 10);
+    const bool small = c->cfg.solve_kcopy && (size_t)n * n + 1 <= (32u << 10);
     double *hs = nullptr, *ds = nullptr;
     HIPCHK(c, ws.alloc(BQ_DINV_STRIDE * sizeof(double) + 64));
     double *dinv = ws.d();
@@ -158,7 +158,7 @@ extern "C" int bq_cho_solve(bq_ctx *c, const double *L, const double *B, double 
     if (n == 0 || nrhs == 0)
         return BQ_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->solve_kcopy && n <= 64 && nrhs <= 64) {
+    if (c->cfg.solve_kcopy && n <= 64 && nrhs <= 64) {
         // the reference's own sizes: one launch on the mapped staging buffer [X | L | B]
         double *hs = nullptr, *ds = nullptr;
         const size_t nx = (size_t)n * nrhs;
@@ -175,7 +175,7 @@ extern "C" int bq_cho_solve(bq_ctx *c, const double *L, const double *B, double 
     long ldl;
     // one vector against a small factor (the reference's own sizes): factor and vector in, solution
     // out through the mapped staging buffer -- [x n | L n^2 | b n] -- by kernels
-    const bool small = c->solve_kcopy && nrhs == 1 && (size_t)n * n + 2 * (size_t)n <= (32u << 10);
+    const bool small = c->cfg.solve_kcopy && nrhs == 1 && (size_t)n * n + 2 * (size_t)n <= (32u << 10);
     double *hs = nullptr, *ds = nullptr;
     if (small) {
         BQCHK(ctx_stage(c, (size_t)n * n + 2 * (size_t)n, &hs, &ds));
@@ -245,7 +245,7 @@ extern "C" int bq_logdet(bq_ctx *c, const double *L, int64_t n, double *out)
     std::vector<double> diag((size_t)n);
     for (int64_t i = 0; i < n; ++i)
         diag[(size_t)i] = L[i + i * n];
-    if (c->solve_kcopy && n + 1 <= (32 << 10)) {
+    if (c->cfg.solve_kcopy && n + 1 <= (32 << 10)) {
         // (the diagonal and the result through the mapped staging buffer: one launch, no
         // allocation, no copy operation)
         double *hs = nullptr, *ds = nullptr;

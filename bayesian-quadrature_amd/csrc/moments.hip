@@ -395,7 +395,7 @@ extern "C" int bq_gp_solve(bq_ctx *c, bq_fit *f, const double *B, int64_t nrhs, 
             // through the fit's pinned staging vector (zero padded): truly asynchronous copies
             std::memcpy(f->hvec, B, sizeof(double) * n);
             std::memset(f->hvec + n, 0, sizeof(double) * (npad - n));
-            if (c->solve_kcopy && trsv_flow_ok(c, npad, wv.B, true)) {
+            if (c->cfg.solve_kcopy && trsv_flow_ok(c, npad, wv.B, true)) {
                 // [x | y | ws_f | x_out | ws_b]: the vector comes in and goes out through kernels
                 // on the mapped pinned vector, and one of them sets both sweeps' hand-off slots
                 double *hdev = nullptr;
@@ -412,7 +412,7 @@ extern "C" int bq_gp_solve(bq_ctx *c, bq_fit *f, const double *B, int64_t nrhs, 
                 return BQ_OK;
             }
             double *hmap = nullptr;
-            if (c->solve_kcopy)
+            if (c->cfg.solve_kcopy)
                 HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hvec, 0));
             if (hmap)
                 BQCHK(launch_flow_in(c, hmap, n, x, npad, nullptr, 0));

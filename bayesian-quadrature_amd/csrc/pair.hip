@@ -28,10 +28,7 @@ struct bq_pair {
     bool merged = false;
     // the whole device side of a bq_pair_llh pass -- parameters up from pinned staging, both
     // plans' launches, targets, the record per set, the record down -- as ONE graph launch
-    hipGraph_t lgraph = nullptr;
-    hipGraphExec_t lgexec = nullptr;
-    int lgraph_state = 0; // 0 = not tried, 1 = ready, -1 = unavailable (eager launches)
-    unsigned long long lgraph_key = 0;
+    CapturedSeq lseq;
     DevBuf l_s, x_sc, x_a, y2, flag;
     // stage 2 of bq_pair_esm, kept between calls (choose_next calls it once per step with the
     // same shapes; allocating and releasing its tens of GB per call costs more than the pass)
@@ -50,10 +47,6 @@ struct bq_pair {
     DevBuf dres;
     ~bq_pair()
     {
-        if (lgexec)
-            (void)hipGraphExecDestroy(lgexec);
-        if (lgraph)
-            (void)hipGraphDestroy(lgraph);
         if (hpar)
             (void)hipHostFree(hpar);
         if (hres)
@@ -225,7 +218,7 @@ static int pair_llh_enqueue(bq_ctx *c, bq_pair *pr)
     // copy-engine operation costs the stream -- or the captured graph -- 8-9 us, a kernel 2.9)
     GaussParams *hpar_d = nullptr;
     double *hres_d = nullptr;
-    if (c->solve_kcopy) {
+    if (c->cfg.solve_kcopy) {
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hpar_d), pr->hpar, 0));
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hres_d), pr->hres, 0));
     }
@@ -302,38 +295,7 @@ extern "C" int bq_pair_llh(bq_ctx *c, bq_pair *pr, const double *p_tl, const dou
     }
     // one graph launch per pass where graphs are in use (the pass of a small system is a dozen
     // stream operations of a few microseconds each)
-    const unsigned long long key = launch_config_key(c);
-    if (pr->lgraph_state == 1 && pr->lgraph_key != key) {
-        (void)hipGraphExecDestroy(pr->lgexec);
-        (void)hipGraphDestroy(pr->lgraph);
-        pr->lgexec = nullptr;
-        pr->lgraph = nullptr;
-        pr->lgraph_state = 0;
-    }
-    if (!c->prof && c->use_graph && c->own_stream && pr->lgraph_state == 0) {
-        pr->lgraph_key = key;
-        pr->lgraph_state = -1;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-            const int st = pair_llh_enqueue(c, pr);
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(c->stream, &g);
-            if (st == BQ_OK && e == hipSuccess && g &&
-                hipGraphInstantiate(&pr->lgexec, g, nullptr, nullptr, 0) == hipSuccess) {
-                pr->lgraph = g;
-                pr->lgraph_state = 1;
-            } else {
-                if (g)
-                    (void)hipGraphDestroy(g);
-                (void)hipGetLastError(); // clear; fall back to eager launches
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (!c->prof && c->use_graph && c->own_stream && pr->lgraph_state == 1)
-        HIPCHK(c, hipGraphLaunch(pr->lgexec, c->stream));
-    else
-        BQCHK(pair_llh_enqueue(c, pr));
+    BQCHK(pr->lseq.run(c, [&]() -> int { return pair_llh_enqueue(c, pr); }));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int b = 0; b < S; ++b) {
         const double *r = pr->hres + (size_t)b * (5 + nc);
@@ -514,7 +476,7 @@ extern "C" int bq_pair_esm(bq_ctx *c, bq_pair *pr, const double *p_tl, const dou
     }
     // the cut of the border route: the jitter sits on candidate points, rows >= ns >= pcut
     const int pcut = (ns / 64) * 64;
-    const bool border = c->pair_border && pcut >= 64;
+    const bool border = c->cfg.pair_border && pcut >= 64;
     if (!border && pr->chunk == 0) {
         // the S Ma full systems: a workspace of at most 8 GB (it stays with the pair between
         // calls -- choose_next calls once per step with the same shapes -- and a BQ object keeps

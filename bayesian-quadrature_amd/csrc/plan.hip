@@ -54,8 +54,6 @@ extern "C" int bq_plan_create(bq_ctx *c, int64_t nprob, int64_t d, int64_t n, in
     return BQ_OK;
 }
 
-static void plan_drop_graph(bq_plan *p);
-
 extern "C" void bq_plan_destroy(bq_ctx *c, bq_plan *p)
 {
     if (!p)
@@ -64,7 +62,6 @@ extern "C" void bq_plan_destroy(bq_ctx *c, bq_plan *p)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
     }
-    plan_drop_graph(p);
     delete p;
 }
 
@@ -171,7 +168,7 @@ extern "C" int bq_plan_set_inputs(bq_ctx *c, bq_plan *p, const double *x, const 
     static_assert(sizeof(GaussParams) % 8 == 0, "GaussParams is copied in 8-byte words");
     constexpr size_t GW = sizeof(GaussParams) / 8;
     const size_t words = (size_t)p->nprob * (GW + (size_t)d * n + (size_t)d * M + (size_t)n);
-    if (c->solve_kcopy && words * 8 <= (256u << 10)) {
+    if (c->cfg.solve_kcopy && words * 8 <= (256u << 10)) {
         if (p->in_flight)
             HIPCHK(c, hipStreamSynchronize(c->stream));
         p->in_flight = false;
@@ -249,16 +246,6 @@ int plan_enqueue(bq_ctx *c, bq_plan *p, long long *stamps, int stamped_steps)
 
 } // namespace bqh
 
-static void plan_drop_graph(bq_plan *p)
-{
-    if (p->gexec)
-        (void)hipGraphExecDestroy(p->gexec);
-    if (p->graph)
-        (void)hipGraphDestroy(p->graph);
-    p->gexec = nullptr;
-    p->graph = nullptr;
-}
-
 extern "C" int bq_plan_run(bq_ctx *c, bq_plan *p)
 {
     if (!c)
@@ -268,38 +255,7 @@ extern "C" int bq_plan_run(bq_ctx *c, bq_plan *p)
     if (!p->has_inputs)
         return fail(c, BQ_ERR_BAD_ARG, "plan has no inputs");
     HIPCHK(c, hipSetDevice(c->device)); // (a context may be driven from any one thread)
-    if (c->prof || !c->use_graph || !c->own_stream)
-        return plan_enqueue(c, p);
-    // settings that change the launch sequence invalidate the captured graph
-    if (p->graph_state == 1 && p->graph_key != launch_config_key(c)) {
-        plan_drop_graph(p);
-        p->graph_state = 0;
-    }
-    if (p->graph_state == 0) {
-        p->graph_key = launch_config_key(c);
-        p->graph_state = -1;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-            const int st = plan_enqueue(c, p);
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(c->stream, &g);
-            if (st == BQ_OK && e == hipSuccess && g &&
-                hipGraphInstantiate(&p->gexec, g, nullptr, nullptr, 0) == hipSuccess) {
-                p->graph = g;
-                p->graph_state = 1;
-            } else {
-                if (g)
-                    (void)hipGraphDestroy(g);
-                (void)hipGetLastError(); // clear; fall back to eager launches
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (p->graph_state == 1) {
-        HIPCHK(c, hipGraphLaunch(p->gexec, c->stream));
-        return BQ_OK;
-    }
-    return plan_enqueue(c, p);
+    return p->seq.run(c, [&]() -> int { return plan_enqueue(c, p); });
 }
 
 extern "C" int bq_plan_results(bq_ctx *c, bq_plan *p, double *mean, double *var, double *logml,
@@ -318,7 +274,7 @@ extern "C" int bq_plan_results(bq_ctx *c, bq_plan *p, double *mean, double *var,
                                 sizeof(double) * (o_var + (size_t)M * nb + 1)));
     double *scal = p->hres;
     int *info = reinterpret_cast<int *>(p->hres + o_info);
-    if (c->solve_kcopy && (o_var + (size_t)M * nb) * 8 <= (256u << 10)) {
+    if (c->cfg.solve_kcopy && (o_var + (size_t)M * nb) * 8 <= (256u << 10)) {
         // (a small plan's record in one kernel on the mapped staging instead of up to four copies)
         double *hmap = nullptr;
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), p->hres, 0));

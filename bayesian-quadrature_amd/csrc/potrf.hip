@@ -10,7 +10,7 @@ namespace bqh {
 // -- the workgroups then cover the chip, and unlike the one-launch steps they solve nothing
 // twice --, the one-launch steps below (64 matrices would leave three quarters of the CUs without
 // a factor to work on: 366 us alone against 236).  BQ_DF_WG = 0 / 1 forces either.
-static bool dfirst_wg(const bq_ctx *c, int batch) { return c->df_wg < 0 ? batch >= 96 : c->df_wg != 0; }
+static bool dfirst_wg(const bq_ctx *c, int batch) { return c->cfg.df_wg < 0 ? batch >= 96 : c->cfg.df_wg != 0; }
 
 // One or two matrices below kSlabNbMax rows run the one-launch steps throughout (auto_nb); the last
 // kSlabMax rows of a larger one are handed to them (enqueue_potrf_group)
@@ -19,8 +19,8 @@ constexpr int kSlabMax = 4800;
 
 int auto_nb(const bq_ctx *c, int ntot, int batch)
 {
-    if (c->nb_override > 0)
-        return c->nb_override;
+    if (c->cfg.nb_override > 0)
+        return c->cfg.nb_override;
     // the trailing update re-reads and re-writes the whole remaining matrix once per
     // outer block: when the batch's matrices do not fit the caches the outer block
     // must be wide (256: 46 GB instead of 183 GB of traffic at N=16384), when they do
@@ -65,7 +65,7 @@ int auto_nb(const bq_ctx *c, int ntot, int batch)
     // 5.71 / 5.90 on the one-launch steps; with a workgroup per matrix 256 x C2 4.45 / 4.32 / 4.50 /
     // 4.52, the C3 grid 188 / 178 / 190 / 180)
     if (ntot >= 1024 && mb >= 500.0)
-        return (c->diag_first && dfirst_wg(c, batch)) ? 384 : 448;
+        return (c->cfg.diag_first && dfirst_wg(c, batch)) ? 384 : 448;
     if (ntot >= 512)
         return 128;
     return 64;
@@ -90,7 +90,7 @@ SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch, size_t w
     // and skips the border x border block in its trailing updates; the one-launch steps of small
     // systems update everything and read the Schur complement.
     r.border_rows = r.nb >= 128;
-    if (c->diag_first && batch >= 3 && ncols >= 128 && r.nb >= 128) {
+    if (c->cfg.diag_first && batch >= 3 && ncols >= 128 && r.nb >= 128) {
         // (two sets of records: with the early fork the next block's diagonal factor writes its own
         // while the rest of this block's panel solve still reads this block's)
         const int nb = std::min(r.nb, ncols);
@@ -99,7 +99,7 @@ SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch, size_t w
             r.kind = SweepRoute::DiagFirst;
             r.ws_doubles = need;
             // (with one outer block there is no product that could seed what lies right of it)
-            r.seed_cols = c->asm_fuse && nb < ncols ? nb : 0;
+            r.seed_cols = c->cfg.asm_fuse && nb < ncols ? nb : 0;
             return r;
         }
     }
@@ -114,8 +114,8 @@ SweepRoute sweep_route(const bq_ctx *c, int ntot, int ncols, int batch, size_t w
     // as ONE sequential group: the product is power-bound (docs/LABBOOK.md section 4), beside it the
     // panel chain only takes clock away (C3, 100 x N = 4096: 189.8 ms with the look-ahead,
     // 198 in two halves, 186.3 sequential; up to 32 matrices the look-ahead still gains 1-2 %)
-    const bool big = ncols > r.nb && ntot - std::min(r.nb, ncols) >= c->la_min;
-    if (c->lookahead && c->aux && c->cur == c->stream && batch >= 8 && r.nb >= 128 && !big) {
+    const bool big = ncols > r.nb && ntot - std::min(r.nb, ncols) >= c->cfg.la_min;
+    if (c->cfg.lookahead && c->aux && c->cur == c->stream && batch >= 8 && r.nb >= 128 && !big) {
         r.kind = SweepRoute::Halves;
         return r;
     }
@@ -267,25 +267,23 @@ static int enqueue_slab_sweep(bq_ctx *c, double *A, long lda, long astride, int 
 static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int batch, int ntot,
                         int ncols, double *dinv, int *info, double *ws, int NB, bool skip_border)
 {
-    const bool la = c->lookahead && c->aux && NB >= 128 && ncols > NB && batch <= BQ_LA_MAX_BATCH;
+    const bool la = c->cfg.lookahead && c->aux && NB >= 128 && ncols > NB && batch <= BQ_LA_MAX_BATCH;
     int K0 = 0;
     bool panel_done = false; // panel K0 was already factored by the look-ahead phase
-    int st = BQ_OK;
-    if (la && ntot - std::min(NB, ncols) >= c->la_min) {
+    if (la && ntot - std::min(NB, ncols) >= c->cfg.la_min) {
         // fork: the aux stream starts after everything already queued on the main stream
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
         // aux stream: panel 0
-        c->cur = c->aux;
-        st = enqueue_panel(c, A, lda, astride, batch, ntot, 0, std::min(NB, ncols), dinv, info,
-                           false, ws);
-        c->cur = c->stream;
-        if (st != BQ_OK)
-            return st;
+        {
+            OnStream aux(c, c->aux);
+            BQCHK(enqueue_panel(c, A, lda, astride, batch, ntot, 0, std::min(NB, ncols), dinv, info,
+                                false, ws));
+        }
         HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
         bool have_b = false; // a trailing update is in flight on the main stream
         Sharing la_scope(c, 1);
-        for (; K0 < ncols && st == BQ_OK; K0 += NB) {
+        for (; K0 < ncols; K0 += NB) {
             const int KB = std::min(NB, ncols - K0);
             const int r0 = K0 + KB;
             // main stream: wait for panel K0
@@ -298,7 +296,7 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
             // Once the bulk update is shorter than the panel chain it has to hide, the two
             // streams only slow each other down (N = 4096: 2.50 ms with, 2.26 ms without):
             // the rest of the sweep runs sequentially on the main stream.
-            if (ntot - r0 < c->la_min)
+            if (ntot - r0 < c->cfg.la_min)
                 break;
             const int nw = (r0 < ncols) ? std::min(NB, ncols - r0) : 0; // width of the next panel
             if (nw > 0) {
@@ -306,19 +304,17 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
                 // written by the previous trailing update on the main stream), factor it
                 if (have_b)
                     HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_next, 0));
-                c->cur = c->aux;
-                // (a wide panel's update is worth the LDS-staged kernel, which carries no
-                // fused diagonal factor: enqueue_panel then factors the block itself)
-                GemmJob g = trailing_job(A, lda, astride, r0, r0, K0, ntot - r0, nw, KB, 1, batch);
-                g.fuse = {r0, dinv, BQ_DINV_STRIDE, info};
-                GemmRoute ran;
-                st = launch_gemm(c, BQ_K_SYRK, g, &ran);
-                if (st == BQ_OK)
-                    st = enqueue_panel(c, A, lda, astride, batch, ntot, r0, nw, dinv, info,
-                                       ran.fused, ws);
-                c->cur = c->stream;
-                if (st != BQ_OK)
-                    break;
+                {
+                    OnStream aux(c, c->aux);
+                    // (a wide panel's update is worth the LDS-staged kernel, which carries no
+                    // fused diagonal factor: enqueue_panel then factors the block itself)
+                    GemmJob g = trailing_job(A, lda, astride, r0, r0, K0, ntot - r0, nw, KB, 1, batch);
+                    g.fuse = {r0, dinv, BQ_DINV_STRIDE, info};
+                    GemmRoute ran;
+                    BQCHK(launch_gemm(c, BQ_K_SYRK, g, &ran));
+                    BQCHK(enqueue_panel(c, A, lda, astride, batch, ntot, r0, nw, dinv, info,
+                                        ran.fused, ws));
+                }
                 HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
                 // main stream: everything right of the next panel, concurrently
                 const int r1 = r0 + nw;
@@ -326,20 +322,17 @@ static int enqueue_potrf_group(bq_ctx *c, double *A, long lda, long astride, int
                     GemmJob b = trailing_job(A, lda, astride, r1, r1, K0, ntot - r1, ntot - r1, KB,
                                              1, batch);
                     b.ccut = skip_border ? ncols - r1 : 0;
-                    st = launch_gemm(c, BQ_K_SYRK, b);
+                    BQCHK(launch_gemm(c, BQ_K_SYRK, b));
                     HIPCHK(c, hipEventRecord(c->ev_next, c->stream));
                     have_b = true;
                 }
             } else {
                 // no further panel: the remaining trailing block is pure Schur complement
-                st = launch_gemm(c, BQ_K_SYRK, trailing_job(A, lda, astride, r0, r0, K0, ntot - r0,
-                                                            ntot - r0, KB, 1, batch));
+                BQCHK(launch_gemm(c, BQ_K_SYRK, trailing_job(A, lda, astride, r0, r0, K0, ntot - r0,
+                                                             ntot - r0, KB, 1, batch)));
             }
             panel_done = false;
         }
-        c->cur = c->stream;
-        if (st != BQ_OK)
-            return st;
     }
     // sequential sweep: everything without look-ahead, otherwise the rest
     bool diag_done = false;
@@ -417,7 +410,7 @@ static int enqueue_trsm_rec(bq_ctx *c, double *A, long lda, long astride, int ba
 }
 
 // the panel solve of one outer block as enqueue_potrf_dfirst issues it (also bq_probe_panel_solve);
-// one_launch: trsm_sweep_kernel (c->df_sweep), else the recursive products and solves
+// one_launch: trsm_sweep_kernel (c->cfg.df_sweep), else the recursive products and solves
 int enqueue_panel_solve(bq_ctx *c, double *A, long lda, long astride, int batch, int r0, int m2,
                         int K0, int KB, const double *rec, long rstride, bool one_launch)
 {
@@ -431,17 +424,17 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
                                 int *info, double *ws, const SweepArgs &a)
 {
     const int batch = r.batch, ntot = r.ntot, ncols = r.ncols, NB = std::min(r.nb, ncols);
-    const bool skip_border = a.skip_border, one_launch = c->df_sweep;
+    const bool skip_border = a.skip_border, one_launch = c->cfg.df_sweep;
     double *recs[2] = {ws + panel_ws_doubles(NB, batch),
                        ws + panel_ws_doubles(NB, batch) + dfirst_rec_doubles(NB, batch)};
     const long rstride = (long)(NB / 64) * BQ_DINV_HALF;
-    const bool la = c->lookahead && c->aux && c->cur == c->stream;
+    const bool la = c->cfg.lookahead && c->aux && c->cur == c->stream;
     // df_early: the streams fork BEFORE the panel solve.  The next diagonal block's chain -- the
     // panel solve of ITS rows (the top nw of the panel), its update, its factor -- starts on the
     // second stream at once, beside the solve of the other rows; round 4 forked after the whole
     // panel solve, and in the late blocks the update was shorter than the chain it should hide
     // (C5 shard: 0.11-0.14 ms exposed after three of four blocks, tools/plan_timeline.py).
-    const bool early = la && c->df_early;
+    const bool early = la && c->cfg.df_early;
     // A factor that has a long update to hide behind (df_wg_rows rows or more below its block) goes
     // to the workgroup-per-matrix kernel whatever the batch: slower alone (366 against 236 us for
     // 64 blocks of 448), but its `batch` workgroups take far fewer slots from the update beside it
@@ -449,7 +442,7 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
     // factor and the late ones, which nothing hides, stay on the steps)
     auto diag = [&](int K0, int KB, double *rec) {
         if (dfirst_wg(c, batch) ||
-            (c->df_wg < 0 && c->df_wg_rows > 0 && K0 > 0 && ntot - K0 - KB >= c->df_wg_rows))
+            (c->cfg.df_wg < 0 && c->cfg.df_wg_rows > 0 && K0 > 0 && ntot - K0 - KB >= c->cfg.df_wg_rows))
             return launch_potrf_wg(c, A + K0 + (long)K0 * lda, lda, astride, KB, rec, rstride, info,
                                    K0, batch);
         return enqueue_slab_sweep(c, A + K0 + (long)K0 * lda, lda, astride, batch, KB, KB, rec, info,
@@ -496,32 +489,23 @@ static int enqueue_potrf_dfirst(bq_ctx *c, const SweepRoute &r, double *A, long 
         if (la) {
             HIPCHK(c, hipEventRecord(c->ev_next, c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_next, 0));
-            c->cur = c->aux;
-        }
-        int st = BQ_OK;
-        if (early) {
-            st = enqueue_panel_solve(c, A, lda, astride, batch, r0, nw, K0, KB, rec, rstride,
-                                     one_launch);
-            // (no early return while c->cur is the second stream: a failed record falls through
-            // to the block below that restores it -- ADVICE r05)
-            if (st == BQ_OK && hipEventRecord(c->ev_top, c->aux) != hipSuccess)
-                st = fail(c, BQ_ERR_HIP, "hipEventRecord(ev_top)");
         }
         const bool sd0 = seeded && K0 == 0;
-        if (st == BQ_OK) {
+        {
+            OnStream next(c, la ? c->aux : c->cur);
+            if (early) {
+                BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r0, nw, K0, KB, rec, rstride,
+                                          one_launch));
+                HIPCHK(c, hipEventRecord(c->ev_top, c->aux));
+            }
             const GramSeed sd = seed_at(r0, r0);
             GemmJob g = trailing_job(A, lda, astride, r0, r0, K0, nw, nw, KB, 1, batch);
             g.seed = sd0 ? &sd : nullptr;
-            st = launch_gemm(c, BQ_K_SYRK, g);
+            BQCHK(launch_gemm(c, BQ_K_SYRK, g));
+            BQCHK(diag(r0, nw, recs[par ^ 1]));
         }
-        if (st == BQ_OK)
-            st = diag(r0, nw, recs[par ^ 1]);
-        if (la) {
-            c->cur = c->stream;
-            if (st == BQ_OK)
-                HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
-        }
-        BQCHK(st);
+        if (la)
+            HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
         if (r1 < ntot) {
             if (early) {
                 BQCHK(enqueue_panel_solve(c, A, lda, astride, batch, r1, ntot - r1, K0, KB, rec,
@@ -589,13 +573,12 @@ int enqueue_potrf_partial(bq_ctx *c, const SweepRoute &r, double *A, long lda, l
     Sharing halves(c, 2);
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-    c->cur = c->aux;
-    int st = enqueue_potrf_group(c, A + (long)b0 * astride, lda, astride, b1, ntot, ncols,
-                                 dinv + (long)b0 * BQ_DINV_STRIDE, info + b0, nullptr, r.nb,
-                                 a.skip_border);
-    c->cur = c->stream;
-    if (st != BQ_OK)
-        return st;
+    {
+        OnStream aux(c, c->aux);
+        BQCHK(enqueue_potrf_group(c, A + (long)b0 * astride, lda, astride, b1, ntot, ncols,
+                                  dinv + (long)b0 * BQ_DINV_STRIDE, info + b0, nullptr, r.nb,
+                                  a.skip_border));
+    }
     HIPCHK(c, hipEventRecord(c->ev_panel, c->aux));
     BQCHK(enqueue_potrf_group(c, A, lda, astride, b0, ntot, ncols, dinv, info, nullptr, r.nb,
                               a.skip_border));
@@ -626,7 +609,7 @@ int enqueue_bordered(bq_ctx *c, const GramSeed &sys, int batch, double *A, long 
         fs.sstride = 64L * L.ntot;
         fs.dinv = dinv;
         fs.info = info;
-        fs.scal = c->fold_readout ? scal : nullptr;
+        fs.scal = c->cfg.fold_readout ? scal : nullptr;
         a.first_done = true;
     } else {
         HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int) * batch, c->stream));
@@ -639,7 +622,7 @@ int enqueue_bordered(bq_ctx *c, const GramSeed &sys, int batch, double *A, long 
         a.seed = sys;
     a.skip_border = rows && L.yrow >= 0 && r.border_rows;
     // a sweep of one-launch steps carries the read-out itself (SlabOut: no finalize launch)
-    const bool folded = r.first_in_assembly && L.yrow >= 0 && c->fold_readout;
+    const bool folded = r.first_in_assembly && L.yrow >= 0 && c->cfg.fold_readout;
     if (folded)
         a.out = SlabOut{scal, mean, var, mstride, L.n, L.npad, L.M, L.yrow};
     BQCHK(enqueue_potrf_partial(c, r, A, lda, astride, dinv, info, ws, a));

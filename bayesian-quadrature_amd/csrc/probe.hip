@@ -520,7 +520,7 @@ extern "C" int bq_probe_panel_solve(bq_ctx *c, int64_t m, int64_t kb, int64_t ba
                                    hipMemcpyHostToDevice, c->stream));
         BQCHK(launch_diag_winv(c, A.d() + b * astride, lda, (int)kb, rec.d() + b * rstride));
     }
-    const bool one_launch = mode == 0 ? c->df_sweep != 0 : mode == 2;
+    const bool one_launch = mode == 0 ? c->cfg.df_sweep != 0 : mode == 2;
     const int st = enqueue_panel_solve(c, A.d(), lda, astride, (int)batch, (int)kb, (int)m, 0,
                                        (int)kb, rec.d(), rstride, one_launch);
     if (st == BQ_OK && reps > 0 && ms_per_call) {

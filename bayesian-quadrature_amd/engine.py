@@ -124,10 +124,14 @@ class Engine(object):
 
     def stats(self):
         """Counters of the context: ``flow_fallbacks`` = single-vector solves re-issued on the
-        per-block sweeps after a hand-off of the one-launch sweeps timed out."""
+        per-block sweeps after a hand-off of the one-launch sweeps timed out; ``graph_captures`` =
+        launch sequences (a plan's pass, a pair's objective, a fit's vector sweeps) captured into
+        a hipGraph, ``graph_replays`` = launches of such graphs, ``graph_drops`` = graphs dropped
+        because a setter had changed the configuration they were captured under."""
         v = (C.c_int64 * 4)()
         self._check(self._lib.bq_ctx_stats(self._ctx, v, 4))
-        return {"flow_fallbacks": int(v[0])}
+        return {"flow_fallbacks": int(v[0]), "graph_captures": int(v[1]),
+                "graph_replays": int(v[2]), "graph_drops": int(v[3])}
 
     def trim(self):
         """Release the workspace the batched calls keep between calls."""

@@ -74,7 +74,11 @@ int bq_get_config(bq_ctx *ctx, int *nb, int *lookahead, int *min_rows);
 /* counters of the context since its creation, out[0 .. n): [0] single-vector solves that were
  * re-issued on the per-block sweeps after a hand-off of the one-launch sweeps timed out (the
  * call still returned BQ_OK with the right answer; non-zero on a healthy, unshared device means
- * something is wrong with it).  Entries beyond the ones defined are set to 0.  No reference
+ * something is wrong with it); [1] launch sequences captured into a hipGraph and instantiated
+ * (a plan's pass, a pair's objective, a fit's single-vector sweeps); [2] launches of such graphs;
+ * [3] graphs dropped because a setter had changed the configuration they were captured under
+ * (the sequence is captured again at its next use).  [1]-[3] stay 0 with BQ_GRAPH=0.  Entries
+ * beyond the ones defined are set to 0.  No reference
  * counterpart (linalg_c.pyx:96-136 is a LAPACK call) */
 int bq_ctx_stats(bq_ctx *ctx, int64_t *out, int n);
 /* bq_batch_fit_predict and bq_gp_logml_grid keep their device workspace (up to half of

@@ -17,10 +17,11 @@ LAPACK would carry on).
 """
 import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
+
+from engine_env import engine_env as _engine_env
 
 gpu = pytest.mark.gpu
 
@@ -165,27 +166,6 @@ def column_classes(nelim, nbs, extra=()):
         cols.add(nb + nb // 2)
     cols |= set(extra)
     return sorted(c for c in cols if 0 <= c < nelim)
-
-
-@contextlib.contextmanager
-def _engine_env(env, probes=False):
-    """A second Engine(0) created with the environment switches `env` set -- a context reads them
-    when it is created --, the environment restored at once; the engine is closed on exit."""
-    from bayesian_quadrature_amd import Engine
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = Engine(0, probes=probes)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    try:
-        yield eng
-    finally:
-        eng.close()
 
 
 # ---- the reference's own test (CPU) ---------------------------------------------------------------

@@ -17,7 +17,8 @@ import pytest
 
 from conftest import rand_spd
 from test_cholesky_contracts import EPS, fwd_err
-from test_slab_wave_groups import _bits, _engine_env, _matrix, _pack, _unpack
+from engine_env import engine_env
+from test_slab_wave_groups import _bits, _matrix, _pack, _unpack
 
 gpu = pytest.mark.gpu
 
@@ -27,7 +28,7 @@ CONTEXTS = (("default", {}), ("four_waves", {"BQ_POTF2_8W": "0"}))
 @pytest.fixture(scope="module")
 def engines(engine):
     with contextlib.ExitStack() as stack:
-        yield [(name, stack.enter_context(_engine_env(env))) for name, env in CONTEXTS]
+        yield [(name, stack.enter_context(engine_env(env, probes=True))) for name, env in CONTEXTS]
 
 
 # ---- the factor alone ---------------------------------------------------------------------------
@@ -265,7 +266,7 @@ def test_workgroup_per_matrix_eight_waves(engine):
     src = _pack(mats, ntot)
     outs = []
     for env in ({"BQ_DF_WG": "1"}, {"BQ_DF_WG": "1", "BQ_POTF2_8W": "0"}):
-        with _engine_env(env) as eng:
+        with engine_env(env, probes=True) as eng:
             buf = src.copy()
             info, route = eng.probe_potrf_batch(buf, batch, ntot, None, ntot, ntot * ntot)
             assert route[0] == "diag_first" and route[1] == 128 and not info.any(), (route, info)

@@ -15,7 +15,8 @@ import contextlib
 import numpy as np
 import pytest
 
-from test_slab_wave_groups import _bits, _engine_env
+from engine_env import engine_env
+from test_slab_wave_groups import _bits
 
 gpu = pytest.mark.gpu
 
@@ -29,7 +30,7 @@ PAIRS = (("regs", "stored"), ("regs4", "stored4"))
 @pytest.fixture(scope="module")
 def engines(engine):
     with contextlib.ExitStack() as stack:
-        yield {name: stack.enter_context(_engine_env(env)) for name, env in CONTEXTS}
+        yield {name: stack.enter_context(engine_env(env, probes=True)) for name, env in CONTEXTS}
 
 
 def _gram(x, h, w, s):
@@ -189,7 +190,7 @@ def test_tiles_beyond_the_first_block_column(engine, oracle, B, d, n, M):
     x, y, xo, h, w, s = _problem(B, d, n, M, B + n + d, checked=2)
     mean, var, logml, status = engine.batch_fit_predict(x, y, h, w, s, xo)
     assert (status == 0).all()
-    with _engine_env({"BQ_ASM_FUSE": "0"}) as e2:
+    with engine_env({"BQ_ASM_FUSE": "0"}, probes=True) as e2:
         m2, v2, l2, st2 = e2.batch_fit_predict(x, y, h, w, s, xo)
     assert np.array_equal(_bits(mean), _bits(m2)) and np.array_equal(_bits(var), _bits(v2))
     assert np.array_equal(_bits(logml), _bits(l2)) and np.array_equal(status, st2)

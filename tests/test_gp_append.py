@@ -3,37 +3,16 @@ BQ.add_observation) on the device: against the oracle's fresh fit of all n + k p
 fresh device fits bit for bit where the state must be the same, against mpmath where the new
 pivot cancels, and at the engine's own sizes."""
 import contextlib
-import os
 
 import numpy as np
 import pytest
 
-from bayesian_quadrature_amd import Engine
+from engine_env import engine_env as _engine_env
 from bayesian_quadrature_amd import workloads as wl
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10
-
-
-@contextlib.contextmanager
-def _engine_env(env):
-    """A second Engine(0) created with the environment switches `env` set (a context reads them
-    when it is created), closed on exit; no switches: the session's engine."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = Engine(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    try:
-        yield eng
-    finally:
-        eng.close()
 
 
 def relmax(a, b, scale=None):

@@ -2,39 +2,19 @@
 the same seeded inputs (SURVEY.md section 8d bars), plus size-independent
 properties at the full BASELINE sizes.  All calls go through libbqhip.so (the hardware probes
 through libbqhip_probe.so)."""
-import contextlib
 import os
 
 import numpy as np
 import pytest
 
 from conftest import rand_spd
+from engine_env import engine_env as _engine_env
 from bayesian_quadrature_amd import Engine
 from bayesian_quadrature_amd import workloads as wl
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10  # north_star: posterior mean/variance and log-ML within 1e-10 relative fp64
-
-
-@contextlib.contextmanager
-def _engine_env(env):
-    """A second Engine(0) created with the environment switches `env` set -- a context reads them
-    when it is created --, the environment restored at once; the engine is closed on exit."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = Engine(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    try:
-        yield eng
-    finally:
-        eng.close()
 
 
 def relmax(a, b, scale=None):

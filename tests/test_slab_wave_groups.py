@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import rand_spd
+from engine_env import engine_env
 from test_cholesky_contracts import EPS, fwd_err, ld_cholesky
 
 gpu = pytest.mark.gpu
@@ -26,32 +27,10 @@ CONTEXTS = (("default", {}), ("always", {"BQ_SLAB8_ROUNDS": "1000000"}),
             ("one_round", {"BQ_SLAB8_ROUNDS": "0"}), ("four_waves", {"BQ_POTF2_8W": "0"}))
 
 
-@contextlib.contextmanager
-def _engine_env(env):
-    """A second Engine(0) on the probe library, created with the environment switches `env` set
-    (a context reads them when it is created); the environment is restored at once and the
-    engine closed on exit."""
-    from bayesian_quadrature_amd import Engine
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        eng = Engine(0, probes=True)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    try:
-        yield eng
-    finally:
-        eng.close()
-
-
 @pytest.fixture(scope="module")
 def engines(engine):
     with contextlib.ExitStack() as stack:
-        yield [(name, stack.enter_context(_engine_env(env))) for name, env in CONTEXTS]
+        yield [(name, stack.enter_context(engine_env(env, probes=True))) for name, env in CONTEXTS]
 
 
 _REF = {}
@@ -219,5 +198,5 @@ def test_readme_names_the_test_of_the_rounds_switch():
     m = re.search(r"`BQ_SLAB8_ROUNDS[^`]*`[^;]*?-- `(test_\w+)`", text)
     assert m, "README has no BQ_SLAB8_ROUNDS line that names a test"
     assert callable(globals().get(m.group(1))), m.group(1)
-    with open(os.path.join(ROOT, "bayesian-quadrature_amd", "csrc", "ctx.hip")) as f:
+    with open(os.path.join(ROOT, "bayesian-quadrature_amd", "csrc", "launch_config.h")) as f:
         assert '"BQ_SLAB8_ROUNDS"' in f.read()

@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 
 from test_cholesky_contracts import EPS, fwd_err, ld_cholesky
-from test_slab_wave_groups import _bits, _engine_env, _matrix, _pack, _unpack
+from engine_env import engine_env
+from test_slab_wave_groups import _bits, _matrix, _pack, _unpack
 
 gpu = pytest.mark.gpu
 
@@ -26,7 +27,7 @@ CONTEXTS = (("default", {}), ("four_waves", {"BQ_POTF2_8W": "0"}))
 @pytest.fixture(scope="module")
 def engines(engine):
     with contextlib.ExitStack() as stack:
-        yield [(name, stack.enter_context(_engine_env(env))) for name, env in CONTEXTS]
+        yield [(name, stack.enter_context(engine_env(env, probes=True))) for name, env in CONTEXTS]
 
 
 def _factor_both(engines, src, batch, ntot, ld):

@@ -1,5 +1,5 @@
 // Host-side soundness of a fit's core buffers (csrc/host.h: FitCore::alloc's failure path,
-// fit_adopt, bq_fit::drop_graphs), for a machine WITHOUT a device: there every hipMalloc of the
+// fit_adopt, the drop() of a fit's three captured sweeps), for a machine WITHOUT a device: there every hipMalloc of the
 // real runtime fails, which is the all-or-nothing path.  The release calls (hipFree, hipHostFree,
 // hipGraphExecDestroy, hipGraphDestroy) are this program's own: they take a handle out of a set of
 // live ones, so a handle freed twice or never is seen.  Host code only, under the sanitizers:
@@ -105,9 +105,9 @@ int main()
             hold(*b, 128);
         f->hvec = handle<double *>(), f->hio = handle<double *>(), f->hfit = handle<double *>();
         for (int i = 0; i < 3; ++i) {
-            f->vgraph[i] = handle<hipGraph_t>();
-            f->vgexec[i] = handle<hipGraphExec_t>();
-            f->vg_failed[i] = true;
+            f->vseq[i].graph = handle<hipGraph_t>();
+            f->vseq[i].exec = handle<hipGraphExec_t>();
+            f->vseq[i].state = CapturedSeq::Unavailable;
         }
         f->have = bq_fit::FACTOR_CHANGED;
         const size_t before = live.size();
@@ -116,13 +116,19 @@ int main()
         EXPECT(live.size() == before - 10 - 1 - 6);
         EXPECT(!f->hvec && f->hio && f->hfit && f->gp.p && f->misc.p && f->wx.p && f->wout.p);
         for (int i = 0; i < 3; ++i)
-            EXPECT(!f->vgraph[i] && !f->vgexec[i] && !f->vg_failed[i]);
+            EXPECT(!f->vseq[i].graph && !f->vseq[i].exec && f->vseq[i].state == CapturedSeq::NotTried);
         // ... and the fit holds the new core, the caller the old one
         EXPECT(f->npad == 192 && f->ldl == 256 && f->L.n == 140 && f->A.bytes == 192);
         EXPECT(next.npad == 128 && next.ldl == 192 && next.L.n == 100 && next.alpha.bytes == 128);
         EXPECT(f->have == bq_fit::FACTOR_CHANGED); // (the caller drops the derived state)
         f->drop(bq_fit::TARGETS_CHANGED);
         EXPECT(f->have == (bq_fit::DW | bq_fit::WIDE));
+        // ~bq_fit lets the graph handles of a live fit go as well, once each
+        for (int i = 0; i < 3; ++i) {
+            f->vseq[i].graph = handle<hipGraph_t>();
+            f->vseq[i].exec = handle<hipGraphExec_t>();
+            f->vseq[i].state = CapturedSeq::Ready;
+        }
         delete f;
         EXPECT(live.size() == 7); // the old core, until it goes out of scope
     }
