@@ -200,21 +200,23 @@ int launch_slab_first(bq_ctx *c, double *A, long lda, long astride, int batch, d
     return BQ_OK;
 }
 
-// The most workgroups a step may have and still run in its 512-thread form, whose waves 4-7 idle
-// through a diagonal tile's update: slab8_rounds rounds of one workgroup per CU.  Shipped: no
-// limit -- us per step, 512 / 256 threads (tools/slab_step_time.py, medians of 7; LABBOOK,
-// "Wave groups of the one-launch steps"):
+// The most workgroups a step may have and still run in its 512-thread form: slab8_rounds rounds of
+// one workgroup per CU.  (Its waves 4-7 work in every tile: in an off-diagonal tile they solve the
+// Q rows, in a diagonal tile they update it behind the solve's column blocks -- slab.h, PIPE.)
+// Shipped: no limit -- us per step, 512 / 256 threads (tools/slab_step_time.py, medians of 7;
+// profiles/diagpipe_slab_step_time.txt; LABBOOK, "A diagonal tile's update under its solve"):
 //     workgroups      one matrix         5 x N = 1024      16 x N = 768
-//        ~50        16.5 / 17.2        17.1 / 18.0        18.0 / 18.7
-//        ~250       18.5 / 18.8        20.4 / 22.3        20.6 / 22.0
-//        ~280       21.8 / 22.6        22.6 / 23.8        25.9 / 28.0 (336)
-//        ~500       23.4 / 23.7        26.4 / 29.1        25.7 / 27.4
-//        ~600       26.6 / 27.7        28.2 / 30.4        30.2 / 31.6
-//        ~950       33.3 / 34.7             --            38.3 / 40.2
-//        ~2150      53.5 / 53.4             --                 --
-//        ~2550      52.6 / 52.5             --                 --
-// The 512-thread form is 0.3 - 1.4 us ahead up to 1,000 workgroups (more in a stacked batch) and
-// level from 1,700; the 3 - 4 us a step gains with every 256 workgroups are the same in both.
+//        ~50        15.0 / 17.0        15.6 / 19.8        16.5 / 18.7
+//        ~250       17.0 / 18.4        18.3 / 21.6        19.0 / 21.8
+//        ~280       20.5 / 22.2        21.2 / 22.7        24.8 / 27.4 (336)
+//        ~500       21.5 / 23.2        25.4 / 28.3        23.7 / 26.3
+//        ~600       25.7 / 26.8        26.6 / 29.1        27.5 / 29.8
+//        ~950       32.6 / 33.8             --            38.4 / 42.9
+//        ~2150      55.1 / 54.3             --                 --
+//        ~2550      53.1 / 53.3             --                 --
+// The 512-thread form is 0.8 - 2.0 us ahead up to 1,000 workgroups (more in a stacked batch) and
+// level from 1,700 (within +-0.8 us, either way); the 3 - 4 us a step gains with every 256
+// workgroups are the same in both.
 static long slab8_limit(const bq_ctx *c)
 {
     return (long)(c->cfg.slab8_rounds > 1 ? c->cfg.slab8_rounds : 1) * c->cus;
@@ -234,25 +236,27 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
     // off-diagonal workgroups solve their two row blocks side by side; waves 4-7 leave after the
     // Q rows' barrier and waves 0-3 store and emit as in the four-wave form)
     const bool w8 = c->cfg.potf2_8w && wgs <= slab8_limit(c);
-    if (stamps && w8)
-        hipLaunchKernelGGL((slab_step_kernel<true, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512), 0,
-                           c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
-                           dinv_out, dstride, fnext, last, info, col0, stamps, out);
+    // (512 threads: both row-block solves at once, the diagonal factor on eight waves, and --
+    // diag_pipe -- a diagonal tile's update on waves 4-7 behind the solve's column blocks)
+    const bool pipe = w8 && c->cfg.diag_pipe != 0;
+#define BQ_SLAB_STEP(STAMP_, NW_, PIPE_)                                                           \
+    hipLaunchKernelGGL((slab_step_kernel<STAMP_, NW_, PIPE_>), dim3(T * (T + 1) / 2, 1, batch),    \
+                       dim3(64 * NW_), 0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot,  \
+                       j0, dinv_in, dinv_out, dstride, fnext, last, info, col0,                    \
+                       STAMP_ ? stamps : (long long *)nullptr, out)
+    if (stamps && pipe)
+        BQ_SLAB_STEP(true, 8, true);
+    else if (stamps && w8)
+        BQ_SLAB_STEP(true, 8, false);
     else if (stamps)
-        hipLaunchKernelGGL((slab_step_kernel<true, 4>), dim3(T * (T + 1) / 2, 1, batch), dim3(256), 0,
-                           c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
-                           dinv_out, dstride, fnext, last, info, col0, stamps, out);
+        BQ_SLAB_STEP(true, 4, false);
+    else if (pipe)
+        BQ_SLAB_STEP(false, 8, true);
     else if (w8)
-        // 512 threads: both row-block solves at once, the diagonal factor on eight waves
-        hipLaunchKernelGGL((slab_step_kernel<false, 8>), dim3(T * (T + 1) / 2, 1, batch), dim3(512),
-                           0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
-                           dinv_out, dstride, fnext, last, info, col0,
-                           (long long *)nullptr, out);
+        BQ_SLAB_STEP(false, 8, false);
     else
-        hipLaunchKernelGGL((slab_step_kernel<false, 4>), dim3(T * (T + 1) / 2, 1, batch), dim3(256),
-                           0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in,
-                           dinv_out, dstride, fnext, last, info, col0,
-                           (long long *)nullptr, out);
+        BQ_SLAB_STEP(false, 4, false);
+#undef BQ_SLAB_STEP
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -60,6 +60,9 @@
     /* ... and a slab step's 512-thread form while the step has at most this many workgroups per    \
        CU (launch_slab_step: no limit shipped; BQ_SLAB8_ROUNDS, 0: one) */                          \
     X(slab8_rounds, "BQ_SLAB8_ROUNDS", 1 << 20)                                                     \
+    /* ... whose diagonal tiles are updated by waves 4-7, one k-block behind waves 0-3's solve      \
+       (slab_step_kernel; BQ_DIAG_PIPE=0: solve, barrier, update on waves 0-3) */                   \
+    X(diag_pipe, "BQ_DIAG_PIPE", 1)                                                                 \
     /* eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT) */                    \
     X(gemm_ksplit, "BQ_GEMM_KSPLIT", 1)                                                             \
     /* 64 / 128: force the LDS kernel's workgroup tile (BQ_GEMM_TILE; measurements) */              \

@@ -134,10 +134,34 @@ __device__ __forceinline__ void slab_corner_factor8(double *Ab, long lda, int j0
 // STAMP: a profiling instantiation (tools/c2_timeline.py) whose workgroup 0 records s_memtime
 // at its phase boundaries; the shipped launches use STAMP = false and carry no stamp code.
 // NW = 8 (launch_slab_step has the rule): 512 threads; in an off-diagonal tile waves 4-7 solve the
-// Q rows while waves 0-3 solve the P rows; in a diagonal tile they pass the update's barriers,
-// and in workgroup 0 they join the diagonal factor as its second wave per SIMD (potf2f_body<8>:
-// the chain 16.5 k -> 13.2 k cycles).
-template <bool STAMP, int NW = 4>
+// Q rows while waves 0-3 solve the P rows; in a diagonal tile they update the tile behind the
+// solve's column blocks (PIPE, below; !PIPE: they pass the update's barriers), and in workgroup 0
+// they join the diagonal factor as its second wave per SIMD (potf2f_body<8>: the chain 16.5 k ->
+// 13.2 k cycles).
+// PIPE (BQ_DIAG_PIPE, the shipped eight-wave form; NW = 8 only): in a DIAGONAL tile waves 4-7 do
+// not idle.  The tile's update is a sum over the four 16-column k-blocks of X, and k-block c needs
+// only x_c, which slab_solve16 delivers about 8 dependent MFMAs before x_{c+1}: waves 0-3 publish
+// every x_c in the Q rows behind a barrier of its own (B_c), and waves 4-7, which requested the
+// ten lower blocks of the C tile at entry, run k-block c of the update (12 MFMAs per wave) while
+// waves 0-3 solve x_{c+1}.  Behind the solve stand only the last k-block and the hand-off.  Same
+// MFMAs on the same operands in the same order per accumulator as PIPE = false, on other waves.
+// STAMP: [2] is wave 0 behind B_3, [3] stays 0, [4] is wave 4 behind its last MFMA, [16..18] /
+// [19..21] are wave 4's / wave 0's arrivals at B_1 .. B_3.
+//
+// Barriers per workgroup, in order -- every wave of a workgroup executes the same row:
+//                                                        waves 0-3            waves 4-7 (NW = 8)
+//   off-diagonal tile (any NW, PIPE)                     A Q                  A Q
+//   diagonal, NW = 4, workgroup 0 with factor_next       A Q T F [+ factor]   --
+//   diagonal, NW = 4, else (`last`, other tiles)         A Q                  --
+//   diagonal, NW = 8, !PIPE, workgroup 0, factor_next    A Q F [+ factor]     A Q F [+ factor]
+//   diagonal, NW = 8, !PIPE, else                        A Q                  A Q
+//   diagonal, NW = 8, PIPE, workgroup 0, factor_next     A B0 B1 B2 B3 F [+]  A B0 B1 B2 B3 F [+]
+//   diagonal, NW = 8, PIPE, else                         A B0 B1 B2 B3        A B0 B1 B2 B3
+// A: fragments staged; Q: solved rows in LDS; T: every wave through with the Q rows; B_c: x_c in
+// LDS; F: updated diagonal block in LDS; [+ factor]: the barriers of the diagonal factor
+// (potf2.h), all waves alike.  `last` has factor_next = 0; workgroup 0 is a diagonal tile; which
+// row a workgroup takes depends on blockIdx and kernel arguments only, never on the wave.
+template <bool STAMP, int NW = 4, bool PIPE = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(double *__restrict__ A, long lda,
                                                         long astride,
                                                         const double *__restrict__ Sin,
@@ -156,6 +180,37 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
         if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0)                                \
             stamps[k] = (long long)__builtin_amdgcn_s_memtime();                                   \
         __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+    // (the same for another thread of workgroup 0: wave 4's lane 0 is thread 256)
+#define BQ_SSTAMP_T(k, dep, tid)                                                                   \
+    if (STAMP) {                                                                                   \
+        asm volatile("" ::"v"(dep));                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+        if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == (tid))                            \
+            stamps[k] = (long long)__builtin_amdgcn_s_memtime();                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+    // The last step's tiles are the Schur complement S of the border: with the read-out folded
+    // in (SlabOut) the lane that holds S[c, c], S[yrow, c] or S[yrow, yrow] stores var_i, mean_i
+    // and -- log|K| is complete since the previous launch -- the log-ML (reduce.h,
+    // finalize_kernel, is the stand-alone form).  row / col: this sweep's numbering = the
+    // system's (col0 = 0 for every caller that sets `out`).
+#define BQ_SLAB_EMIT(ROW_, COL_, S_)                                                               \
+    {                                                                                              \
+        const int row_ = (ROW_), col_ = (COL_);                                                    \
+        const double s_ = (S_);                                                                    \
+        if (row_ == col_ && row_ >= out.npad && row_ < out.npad + out.M && out.var)                \
+            out.var[(long)b * out.mstride + (row_ - out.npad)] = s_;                               \
+        if (row_ == out.yrow) {                                                                    \
+            if (col_ >= out.npad && col_ < out.npad + out.M && out.mean)                           \
+                out.mean[(long)b * out.mstride + (col_ - out.npad)] = -s_;                         \
+            if (col_ == out.yrow) {                                                                \
+                const double qf_ = -s_, ld_ = out.scal[4 * b + 1];                                 \
+                out.scal[4 * b + 2] = qf_;                                                         \
+                out.scal[4 * b + 0] =                                                              \
+                    -0.5 * qf_ - 0.5 * ld_ - 0.5 * (double)out.n * 1.8378770664093453;             \
+            }                                                                                      \
+        }                                                                                          \
     }
     BQ_SSTAMP(0, 0)
     // One region, 52 KiB -- a workgroup of this kernel must fit into what ONE retiring workgroup
@@ -182,6 +237,204 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     const int r0 = j0 + 64;
     const int Rb = r0 + 64 * bx, Cb = r0 + 64 * by;
     const int l15 = lane & 15, l4 = lane >> 4;
+    if constexpr (NW == 8 && PIPE) {
+        // A diagonal tile of the pipelined form is a path of its own from here to its return
+        // (the barrier table in front of the kernel): nothing of it is shared with the
+        // off-diagonal tiles below, whose code and registers stay the one-phase form's.
+        if (bx == by) {
+            if (wave >= 4) {
+                // diagonal tile: the update is THIS group's (the barrier table in front of the kernel).
+                // The ten lower blocks, dealt 3 / 3 / 2 / 2 by DIAG_RB / DIAG_CB of wave - 4 and
+                // requested RAW before the first barrier; the two-block waves load and update their
+                // second block again as a third, which nothing stores (an MFMA ignores EXEC).
+                const int wu = wave - 4;
+                const int rb0 = DIAG_RB(wu, 0), rb1 = DIAG_RB(wu, 1), rb2 = DIAG_RB(wu, 2);
+                const int cb0 = DIAG_CB(wu, 0), cb1 = DIAG_CB(wu, 1), cb2 = DIAG_CB(wu, 2);
+                double4_t acc[3];
+    #pragma unroll
+                for (int sb = 0; sb < 3; ++sb) {
+                    const double *Cin = A + Rb + 16 * DIAG_RB(wu, sb) + l15 +
+                                        (long)(Cb + 16 * DIAG_CB(wu, sb) + l4) * lda;
+    #pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        acc[sb][r] = Cin[(long)(4 * r) * lda];
+                }
+                __syncthreads(); // A
+                // negated behind the first barrier: nothing needs the tile before x_0 is published
+                __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+                for (int sb = 0; sb < 3; ++sb)
+    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double v = -acc[sb][r];
+                        asm volatile("" : "+v"(v));
+                        acc[sb][r] = v;
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+                // k-block c behind the barrier that publishes x_c: block (rb, cb) += X_cb X_rb^T in
+                // D^T form, the MFMAs of every accumulator in the order c, r of the one-phase update;
+                // all 24 LDS operands of the k-block are requested before its first MFMA
+    #pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c > 0)
+                        BQ_SSTAMP_T(15 + c, acc[0][0], 256) // wave 4 arrives at B_c
+                    // (pinned: left alone, the scheduler sinks eleven of a k-block's MFMAs behind
+                    // the next barrier, and two k-blocks instead of one stand behind the solve)
+                    __builtin_amdgcn_sched_barrier(0);
+                    __syncthreads(); // B_c
+                    __builtin_amdgcn_sched_barrier(0);
+                    double qa[4][3], qb[4][3];
+    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
+                        qa[r][0] = qrow[16 * cb0], qb[r][0] = qrow[16 * rb0];
+                        qa[r][1] = qrow[16 * cb1], qb[r][1] = qrow[16 * rb1];
+                        qa[r][2] = qrow[16 * cb2], qb[r][2] = qrow[16 * rb2];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][0], qb[r][0], acc[0], 0, 0, 0);
+                        acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][1], qb[r][1], acc[1], 0, 0, 0);
+                        acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][2], qb[r][2], acc[2], 0, 0, 0);
+                    }
+                }
+                BQ_SSTAMP_T(4, acc[1][3] + acc[0][0], 256)
+                if (blockIdx.x == 0 && factor_next) {
+                    // the packed blocks go where the fragments were: waves 0-3 took their last
+                    // fragments in front of B_3
+                    double *Bs = plds + 4096;
+    #pragma unroll
+                    for (int sb = 0; sb < 3; ++sb)
+                        if (sb < DIAG_NB(wu)) {
+                            const int rb = DIAG_RB(wu, sb), cb = DIAG_CB(wu, sb);
+    #pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                Bs[256 * ((rb * (rb + 1)) / 2 + cb) + l15 + 16 * (l4 + 4 * r)] = -acc[sb][r];
+                        }
+                    __syncthreads(); // F
+                    slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds,
+                                        nullptr, out.scal ? out.scal + 4 * b + 1 : nullptr);
+                    return;
+                }
+                const bool emit = last && out.scal != nullptr;
+    #pragma unroll
+                for (int sb = 0; sb < 3; ++sb)
+                    if (sb < DIAG_NB(wu)) {
+                        double *Cd = A + Rb + 16 * DIAG_RB(wu, sb) + l15 +
+                                     (long)(Cb + 16 * DIAG_CB(wu, sb) + l4) * lda;
+    #pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            Cd[(long)(4 * r) * lda] = -acc[sb][r];
+                        if (emit) {
+    #pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                BQ_SLAB_EMIT(Rb + 16 * DIAG_RB(wu, sb) + l15,
+                                             Cb + 16 * DIAG_CB(wu, sb) + l4 + 4 * r, -acc[sb][r])
+                        }
+                    }
+                return;
+            }
+            // Waves 0-3: the fragments of L_jj and W staged once per workgroup and the panel
+            // rows, as in the prologue below -- but no C tile: that is waves 4-7's.  A COPY of that
+            // prologue (a shared one cost 254 VGPRs and spills: LABBOOK) and of slab_solve16's
+            // body: the two must stay in step -- the same Fs / Ws layout, which slab_frags reads
+            // and slab_load_blocks8 overwrites, and the same MFMA order per accumulator.
+            double la[4][3][4], wneg[4][4], tp[4][4];
+            double *Fs = plds + 4096;
+            {
+                double *Ws = plds + 4096 + 6 * 256;
+                const int t = threadIdx.x, ti = t & 15, tk = t >> 4;
+                const double *L11 = A + j0 + (long)j0 * lda + ti + (long)tk * lda;
+                double f[6], wv[4];
+#pragma unroll
+                for (int c = 1; c < 4; ++c)
+#pragma unroll
+                    for (int bb = 0; bb < c; ++bb)
+                        f[(c * (c - 1)) / 2 + bb] = L11[16 * c + (long)(16 * bb) * lda];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    wv[q] = din[64 + 256 * q + t];
+                slab_load16(Sin + Rb + 16 * wave + l15 + (long)l4 * lds, lds, tp);
+                // nothing that waits for a load may move up between the loads
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+                    Fs[256 * q + t] = f[q];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    Ws[256 * q + t] = -wv[q];
+            }
+            __syncthreads(); // A
+            {
+                // Every column block x_c is published in the Q rows the moment it exists, a
+                // barrier behind it (B_c).  slab_solve16's MFMAs in its order; the
+                // fragments of column block c + 2 are requested in front of B_c, so that no
+                // LDS round trip stands between a barrier and the chain (the last ones in
+                // front of B_1: waves 4-7 overwrite the fragment region behind B_3).
+                const double *Ws = Fs + 6 * 256;
+                double4_t x[4];
+#define BQ_PIPE_FRAGS(C_)                                                                          \
+    do {                                                                                           \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) wneg[C_][r] =                                \
+            Ws[256 * (C_) + 64 * r + l15 + 16 * l4];                                               \
+        _Pragma("unroll") for (int bb = 0; bb < (C_); ++bb) _Pragma("unroll") for (int r = 0;      \
+                                                                                   r < 4; ++r)     \
+            la[C_][bb][r] = Fs[256 * (((C_) * ((C_) - 1)) / 2 + bb) + l15 + 16 * (l4 + 4 * r)];    \
+    } while (0)
+                BQ_PIPE_FRAGS(0);
+                BQ_PIPE_FRAGS(1);
+                BQ_SSTAMP(1, wneg[0][3] + wneg[1][3])
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    double4_t a = {-tp[c][0], -tp[c][1], -tp[c][2], -tp[c][3]};
+#pragma unroll
+                    for (int bb = 0; bb < c; ++bb)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            a = __builtin_amdgcn_mfma_f64_16x16x4f64(la[c][bb][r], x[bb][r], a, 0, 0, 0);
+                    double4_t xc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        xc = __builtin_amdgcn_mfma_f64_16x16x4f64(wneg[c][r], a[r], xc, 0, 0, 0);
+                    x[c] = xc;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xc[r];
+                    if (c == 0) {
+                        BQ_PIPE_FRAGS(2);
+                    }
+                    if (c == 1) {
+                        BQ_PIPE_FRAGS(3);
+                    }
+                    if (c > 0)
+                        BQ_SSTAMP(18 + c, xc[3]) // wave 0 arrives at B_c
+                    // (not pinned: hipcc moves the MFMAs of x_{c+1} up in front of B_c and only
+                    // its ds_write behind it; pinned to 4 / 8 / 12 / 16 MFMAs per interval the
+                    // update waits less and the headline is the same: LABBOOK)
+                    __syncthreads(); // B_c
+                }
+#undef BQ_PIPE_FRAGS
+                BQ_SSTAMP(2, x[3][3])
+                // the solved rows are the factor: tile column 0 owns the write
+                if (by == 0) {
+                    double *Lw = A + Rb + 16 * wave + l15 + (long)(j0 + l4) * lda;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            Lw[(long)(16 * c + 4 * r) * lda] = x[c][r];
+                }
+                if (blockIdx.x == 0 && factor_next) {
+                    __syncthreads(); // F
+                    slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b,
+                                        plds, (STAMP && blockIdx.z == 0) ? stamps + 5 : nullptr,
+                                        out.scal ? out.scal + 4 * b + 1 : nullptr);
+                }
+                return;
+            }
+        }
+    }
     if (NW == 8 && wave >= 4) {
         // the barriers of the tile update below, in their order: fragments staged; Q rows
         // written; and for workgroup 0 with a next factor: diagonal block in LDS
@@ -283,7 +536,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
             for (int q = 0; q < 4; ++q)
                 Ws[256 * q + t] = -wv[q];
         }
-        __syncthreads();
+        __syncthreads(); // A
         slab_frags(Fs, l15, l4, la, wneg);
     }
     BQ_SSTAMP(1, la[3][2][3] + wneg[3][3])
@@ -371,7 +624,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     BQ_SSTAMP(4, acc[1][3] + acc[0][0])
     // tile column 0 is the next panel: it goes to the scratch column (the diagonal tile,
     // which workgroup 0 factors in place, and the Schur complement of the last step stay in A)
-    if (blockIdx.x == 0 && factor_next) {
+    // (the pipelined form never comes here with a diagonal tile, and workgroup 0 is one)
+    if (!(NW == 8 && PIPE) && blockIdx.x == 0 && factor_next) {
         // the next diagonal block never touches memory between its update and its factor
         // (only the ten lower blocks: the factor never reads a lane above its column's own)
         if constexpr (NW == 8) {
@@ -414,28 +668,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     double *Cout = to_s ? Sout + Rb + 16 * wave + l15 + (long)l4 * lds
                         : A + Rb + 16 * wave + l15 + (long)(Cb + l4) * lda;
     const long ldo = to_s ? lds : lda;
-    // The last step's tiles are the Schur complement S of the border: with the read-out folded
-    // in (SlabOut) the lane that holds S[c, c], S[yrow, c] or S[yrow, yrow] stores var_i, mean_i
-    // and -- log|K| is complete since the previous launch -- the log-ML (reduce.h,
-    // finalize_kernel, is the stand-alone form).  row / col: this sweep's numbering = the
-    // system's (col0 = 0 for every caller that sets `out`).
-#define BQ_SLAB_EMIT(ROW_, COL_, S_)                                                               \
-    {                                                                                              \
-        const int row_ = (ROW_), col_ = (COL_);                                                    \
-        const double s_ = (S_);                                                                    \
-        if (row_ == col_ && row_ >= out.npad && row_ < out.npad + out.M && out.var)                \
-            out.var[(long)b * out.mstride + (row_ - out.npad)] = s_;                               \
-        if (row_ == out.yrow) {                                                                    \
-            if (col_ >= out.npad && col_ < out.npad + out.M && out.mean)                           \
-                out.mean[(long)b * out.mstride + (col_ - out.npad)] = -s_;                         \
-            if (col_ == out.yrow) {                                                                \
-                const double qf_ = -s_, ld_ = out.scal[4 * b + 1];                                 \
-                out.scal[4 * b + 2] = qf_;                                                         \
-                out.scal[4 * b + 0] =                                                              \
-                    -0.5 * qf_ - 0.5 * ld_ - 0.5 * (double)out.n * 1.8378770664093453;             \
-            }                                                                                      \
-        }                                                                                          \
-    }
+    // (the last step's tiles are the Schur complement of the border: BQ_SLAB_EMIT, above)
     const bool emit = last && out.scal != nullptr;
     if (bx == by) {
 #pragma unroll
@@ -468,6 +701,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
         }
     }
 #undef BQ_SLAB_EMIT
+#undef BQ_SSTAMP_T
 #undef BQ_SSTAMP
 }
 

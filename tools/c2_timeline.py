@@ -12,6 +12,11 @@ from bayesian_quadrature_amd import workloads as wl  # noqa: E402
 
 NAMES = ["entry", "frags_loaded", "rows_solved", "tile_loaded", "tile_updated", "potf2_entry",
          "potf2_loaded", "potf2_chain", "potf2_blocks", "potf2_end"]
+# The pipelined diagonal tile (BQ_DIAG_PIPE, the default): rows_solved is wave 0 behind B_3, the
+# barrier that publishes the last column block; tile_updated is wave 4's lane 0 behind its last
+# MFMA; there is no tile_loaded (slot 3 stays 0).  Slots 16-18 / 19-21: wave 4's / wave 0's
+# arrivals at B_1 .. B_3.
+PIPE_COLS = [0, 1, 2, 4, 5, 6, 7, 8, 9]
 
 if __name__ == "__main__":
     e = Engine(0, probes=True)
@@ -24,16 +29,31 @@ if __name__ == "__main__":
     nsteps = 16
     st = (C.c_int64 * (160 * nsteps))()
     e._check(e._lib.bq_probe_c2_timeline(e._ctx, plan._h, st, nsteps))
-    t = np.array(list(st), dtype=np.int64).reshape(nsteps, 160)[:, :10]
+    raw = np.array(list(st), dtype=np.int64).reshape(nsteps, 160)
+    pipe = bool((raw[1:15, 16:22] != 0).all())
+    cols = PIPE_COLS if pipe else list(range(10))
+    names = [NAMES[k] for k in cols]
+    t = raw[:, cols]
     d = np.diff(t, axis=1)                       # phase lengths per step
-    gap = t[1:, 0] - t[:-1, 9]                   # end of a step's factor -> next step's entry
-    out = {"library": L.PROBE_LIB_PATH, "unit": "s_memtime ticks",
-           "phases_mean_steps_1_14": {NAMES[i + 1]: float(d[1:15, i].mean()) for i in range(9)},
-           "phases_step_5": {NAMES[i + 1]: int(d[5, i]) for i in range(9)},
-           "step_total_mean": float((t[1:15, 9] - t[1:15, 0]).mean()),
+    gap = t[1:, 0] - t[:-1, -1]                  # end of a step's factor -> next step's entry
+    out = {"library": L.PROBE_LIB_PATH, "unit": "s_memtime ticks", "diag_pipe": pipe,
+           "phases_mean_steps_1_14": {names[i + 1]: float(d[1:15, i].mean())
+                                      for i in range(len(cols) - 1)},
+           "phases_step_5": {names[i + 1]: int(d[5, i]) for i in range(len(cols) - 1)},
+           "step_total_mean": float((t[1:15, -1] - t[1:15, 0]).mean()),
+           "solve_end_to_potf2_entry_mean": float((raw[1:15, 5] - raw[1:15, 2]).mean()),
            "gap_end_to_next_entry_mean": float(gap[:14].mean()),
            "gap_all": gap.tolist(),
-           "pass_total": int(t[15, 4] - t[0, 0])}
+           "pass_total": int(raw[15, 4] - raw[0, 0])}
+    if pipe:
+        # wave 0's arrival minus wave 4's at B_1 .. B_3: positive = the update waited for the solve
+        lead = raw[1:15, 19:22] - raw[1:15, 16:19]
+        out["wave0_minus_wave4_arrival_B1_B3_mean"] = lead.mean(axis=0).tolist()
+        out["wave0_minus_wave4_arrival_B1_B3_min"] = lead.min(axis=0).tolist()
+        out["solve_intervals_B1_B2_B3_mean"] = [
+            float((raw[1:15, 19] - raw[1:15, 1]).mean()),
+            float((raw[1:15, 20] - raw[1:15, 19]).mean()),
+            float((raw[1:15, 21] - raw[1:15, 20]).mean())]
     print(json.dumps(out, indent=1))
     plan.close()
     e.close()

@@ -12,7 +12,19 @@ prints the loads, the vmcnt waits and the branches in between, run-length coded,
 of vector-memory loads that follow a vmcnt wait (stores are listed too, and a wait that stands
 behind one is marked: vmcnt counts stores as well).  Text order, not a walk of the flow graph: a load
 counts if ANY wait stands above it, whichever path a wave takes, so 0 means every path is clean.
-Exit status 1 if the count is not 0 for any kernel named (or a kernel is not found).  Host-only."""
+
+The text-order walk sees only the prologue that hipcc happens to lay out first (in the pipelined
+steps, slab_step_kernel<., 8, true>, the off-diagonal tiles'; the diagonal tiles' two prologues lie
+further down).  So the flow graph is walked as well: every path from the kernel's entry to the
+first s_barrier ON THAT PATH (or its first store, or its end), both ways at every branch, with
+the number of loads pending on the path; a vmcnt(N) wait counts only where more than N are pending (hipcc
+puts a vmcnt(0) at the top of a block that has a predecessor with loads in flight, which costs a
+wave arriving with nothing pending nothing), and the loads behind such a wait are counted once
+each, whichever path finds them.
+
+
+Exit status 1 if the text-order count is not 0 for any kernel named (or a kernel is not found);
+with --paths also if the path count is not 0.  Host-only."""
 import argparse
 import glob
 import os
@@ -102,10 +114,56 @@ def walk(body):
     return ev, behind, found
 
 
+def walk_paths(body):
+    """(loads in front of some path's first s_barrier, of them behind a wait that had to wait,
+    prologues = distinct first barriers reached)"""
+    lines = [l.split(";")[0].rstrip() for l in body]
+    label = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"^(\.LBB\w+):", l)
+        if m:
+            label[m.group(1)] = i
+    loads, behind, barriers, seen = set(), set(), set(), set()
+    todo = [(0, 0, False)]
+    while todo:
+        i, pending, waited = todo.pop()
+        while i < len(lines):
+            if (i, pending, waited) in seen:
+                break
+            seen.add((i, pending, waited))
+            l = lines[i]
+            if re.match(r"^\s+s_barrier\b", l):
+                barriers.add(i)
+                break
+            if re.match(r"^\s+s_endpgm\b", l):
+                break
+            if LOAD.match(l):
+                loads.add(i)
+                if waited:
+                    behind.add(i)
+                pending += 1
+            elif STORE.match(l):
+                break  # (behind a path's first store nothing is a prologue: the read-out's loads)
+            else:
+                m = WAIT.match(l)
+                if m and pending > int(m.group(1)):
+                    pending, waited = int(m.group(1)), True
+                m = BRANCH.match(l)
+                if m and m.group(2) in label:
+                    if m.group(1) == "s_branch":
+                        i = label[m.group(2)]
+                        continue
+                    todo.append((label[m.group(2)], pending, waited))
+            i += 1
+    return len(loads), len(behind), len(barriers)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--asm", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                                   "build", "asm"))
+    ap.add_argument("--paths", action="store_true",
+                    help="the exit status counts the walk of every path as well")
     ap.add_argument("kernels", nargs="+")
     a = ap.parse_args()
     files = sorted(glob.glob(os.path.join(a.asm, "*-hip-amdgcn-amd-amdhsa-gfx950.s")))
@@ -144,7 +202,10 @@ def main():
         nload = sum(1 for k, _ in ev if k.startswith("load"))
         print("   loads in front of the first s_barrier: %d, of them behind a vmcnt wait: %d"
               % (nload, behind))
-        bad += behind != 0
+        nl, nb, npro = walk_paths(body)
+        print("   every path to its first s_barrier or store (%d prologues): %d loads, of them behind a "
+              "vmcnt wait that had loads to wait for: %d" % (npro, nl, nb))
+        bad += behind != 0 or (a.paths and nb != 0)
     return 1 if bad else 0
 
 
