@@ -4,6 +4,7 @@
 #include "common.h"
 #include "potf2.h"
 #include "seed.h"
+#include "solve16.h"
 
 
 // one wave tile of C -= P Q^T (see gemm_sub_kernel); C, P, Q already point at the batch element
@@ -198,6 +199,22 @@ template <int TM, int TN> struct Tile444 {
                 for (int s = 0; s < 4; ++s)
                     *at(tm, tn, s) = -acc[tm][tn][s];
             }
+    }
+    // The finished tile (-acc) un-rotated into a column-major 64 x 64 LDS tile Ts, this wave's
+    // part at (wr, wc): the hand-off in front of a solve in 16-rows-per-wave form (solve16.h).
+    static __device__ __forceinline__ void store_neg_lds(const double (&acc)[TM][TN][4], double *Ts,
+                                                         int wr, int wc)
+    {
+        const int lane = threadIdx.x & 63;
+        const int l15 = lane & 15, l4 = lane >> 4, blk = (lane >> 2) & 3;
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    Ts[wr + 16 * tm + l15 + 64 * (wc + 16 * tn + l4 + 4 * ((blk - s) & 3))] =
+                        -acc[tm][tn][s];
     }
 };
 
@@ -988,43 +1005,12 @@ __device__ __forceinline__ void gemm_lds64_body(unsigned char *smem, double *__r
         // (lower == 0 and whole tiles here: every wave is active)
         double *Ts = reinterpret_cast<double *>(smem); // the updated tile, column-major 64 x 64
         __syncthreads();                               // the staging buffers are free
-        {
-            const int blk = (lane >> 2) & 3;
-#pragma unroll
-            for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        Ts[wr + 16 * tm + l15 + 64 * (wc + 16 * tn + l4 + 4 * ((blk - s) & 3))] =
-                            -acc[tm][tn][s];
-        }
+        Tile444<2, 2>::store_neg_lds(acc, Ts, wr, wc);
         __syncthreads();
-        // rows 16 wave .. + 15 of the tile: X_c = (T_c - sum_{b<c} X_b L_cb^T) W_cc^T (trsm.h)
-        const double *L11 = Lss + l15 + (long)l4 * ldl;
-        const double *W = wrec + 64 + l15 + 16 * l4;
-        const double *Tw = Ts + 16 * wave + l15 + 64 * l4;
-        double *Xr = C + R0 + 16 * wave + l15 + (long)(C0 + l4) * ldc;
-        double4_t x[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double4_t a4 = {-Tw[64 * (16 * c)], -Tw[64 * (16 * c + 4)], -Tw[64 * (16 * c + 8)],
-                            -Tw[64 * (16 * c + 12)]};
-#pragma unroll
-            for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        L11[16 * c + (long)(16 * bb + 4 * r) * ldl], x[bb][r], a4, 0, 0, 0);
-            double4_t xc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                xc = __builtin_amdgcn_mfma_f64_16x16x4f64(-W[256 * c + 64 * r], a4[r], xc, 0, 0, 0);
-            x[c] = xc;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Xr[(long)(16 * c + 4 * r) * ldc] = xc[r];
-        }
+        // rows 16 wave .. + 15 of the tile, every x_c stored as it comes; fragments streamed
+        const Solve16Stream f(Lss, ldl, wrec);
+        solve16_tile(Ts + 16 * wave + l15 + 64 * l4, f,
+                     C + R0 + 16 * wave + l15 + (long)(C0 + l4) * ldc, ldc);
         return;
     }
     if (!active)

@@ -9,9 +9,11 @@
 // Translation units (Makefile; all but probe.hip make libbqhip.so, all of them together
 // libbqhip_probe.so, whose extra entry points include/bqhip_probe.h declares):
 //   k_gram.hip   gram.h kernels                 launch_gram_sym / _cross
-//   k_gemm.hip   gemm.h kernels                 launch_gemm, launch_gemm_rows, launch_rows_step
+//   k_gemm.hip   gemm.h trsmsweep.h kernels     launch_gemm, launch_gemm_rows, launch_rows_step
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
+//                solve16.h                      (both units: the 16-row solve from block inverses,
+//                                               its fragment loaders and LDS staging)
 //   k_reduce.hip reduce.h trsv.h append.h        read-outs, single-vector sweeps, utilities, the
 //                remove.h kernels               finishing kernels of an append, shrinking a fit
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences

@@ -216,7 +216,12 @@ int launch_slab_first(bq_ctx *c, double *A, long lda, long astride, int batch, d
 //        ~2550      53.1 / 53.3             --                 --
 // The 512-thread form is 0.8 - 2.0 us ahead up to 1,000 workgroups (more in a stacked batch) and
 // level from 1,700 (within +-0.8 us, either way); the 3 - 4 us a step gains with every 256
-// workgroups are the same in both.
+// workgroups are the same in both.  (Measured again, parent against branch, when the kernel became
+// a dispatcher over named tile paths: 512-thread medians of one matrix -0.4 ... +0.5 us, mean +0.05 us;
+// of 5 x N = 1024 -0.2 ... +1.0 us with minima within +-0.3 us (a median of 7 carries outliers there,
+// in either build).  One matrix lies inside the +-0.8 us above and the 256-thread column moved as
+// much: the table stands -- profiles/solve16_slab_step_time.txt; LABBOOK, "One 16-row block-inverse
+// solve".)
 static long slab8_limit(const bq_ctx *c)
 {
     return (long)(c->cfg.slab8_rounds > 1 ? c->cfg.slab8_rounds : 1) * c->cus;

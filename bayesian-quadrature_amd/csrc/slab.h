@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "potf2.h"
+#include "solve16.h"
 
 // ---------------------------------------------------------------------------
 // Small systems (one 64-column slab per outer step: C2, the reference's own problem
@@ -32,76 +33,125 @@
 // grid: (T (T + 1) / 2, 1, batch), T = (ntot - j0 - 64) / 64; block 256.
 // ---------------------------------------------------------------------------
 
-// Solve 16 rows of the panel: returns X^T blocks x[c] (D / B-fragment form: x[c][r] of lane l
-// is X[row l & 15][16 c + (l >> 4) + 4 r]).  la / w: A fragments of L_jj's off-diagonal
-// blocks and of the (negated) block inverses, shared by every solve of the wave.
-__device__ __forceinline__ void slab_load16(const double *__restrict__ S, long lds,
-                                            double (&t)[4][4])
-{
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            t[c][r] = S[(long)(16 * c + 4 * r) * lds];
-}
-
-__device__ __forceinline__ void slab_solve16(const double (&t)[4][4], const double (&la)[4][3][4],
-                                             const double (&wneg)[4][4], double4_t (&x)[4])
-{
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        double4_t acc = {-t[c][0], -t[c][1], -t[c][2], -t[c][3]};
-#pragma unroll
-        for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(la[c][bb][r], x[bb][r], acc, 0, 0, 0);
-        double4_t xc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            xc = __builtin_amdgcn_mfma_f64_16x16x4f64(wneg[c][r], acc[r], xc, 0, 0, 0);
-        x[c] = xc;
-    }
-}
-
-// The A fragments of a step's solves out of the workgroup's LDS staging area: Fs holds the six
-// blocks (c, bb), c > bb, below L_jj's diagonal at 256 ((c (c - 1)) / 2 + bb), then the four
-// negated block inverses as they lie in global memory.
-__device__ __forceinline__ void slab_frags(const double *Fs, int l15, int l4, double (&la)[4][3][4],
-                                           double (&wneg)[4][4])
-{
-    const double *Ws = Fs + 6 * 256;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            wneg[c][r] = Ws[256 * c + 64 * r + l15 + 16 * l4];
-#pragma unroll
-    for (int c = 1; c < 4; ++c)
-#pragma unroll
-        for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                la[c][bb][r] = Fs[256 * ((c * (c - 1)) / 2 + bb) + l15 + 16 * (l4 + 4 * r)];
-}
-
 // The ten lower 16 x 16 blocks (rb, cb) of a diagonal tile dealt to the four waves:
 //   wave 0: (0,0) (1,0) (1,1)   wave 1: (2,0) (2,1) (2,2)   wave 2: (3,0) (3,1)   wave 3: (3,2) (3,3)
 // Every wave issues THREE MFMAs per k-step: waves 2 and 3 repeat their second block into an
 // accumulator that is never stored.  (A third MFMA under `if (wave < 2)` was miscompiled into
 // a wrong block (3, 1): an MFMA ignores EXEC, so it must never sit under anything but a scalar
 // branch, and the redundant one costs nothing -- the other two waves issue three anyway.)
-// doubles of LDS behind the tile for the fragments of L_jj (6 blocks) and W (4 blocks)
-#define BQ_SLAB_FW (10 * 256)
-#define DIAG_NB(w) ((w) < 2 ? 3 : 2)
-#define DIAG_RB(w, s) ((w) == 0 ? ((s) > 0 ? 1 : 0) : ((w) == 1 ? 2 : 3))
-#define DIAG_CB(w, s) ((w) == 0 ? ((s) == 2 ? 1 : 0) : (((w) == 3 ? 2 : 0) + ((w) >= 2 && (s) == 2 ? 1 : (s))))
+__device__ __forceinline__ constexpr int slab_diag_nb(int w) { return w < 2 ? 3 : 2; }
+__device__ __forceinline__ constexpr int slab_diag_rb(int w, int s)
+{
+    return w == 0 ? (s > 0 ? 1 : 0) : (w == 1 ? 2 : 3);
+}
+__device__ __forceinline__ constexpr int slab_diag_cb(int w, int s)
+{
+    return w == 0 ? (s == 2 ? 1 : 0) : ((w == 3 ? 2 : 0) + (w >= 2 && s == 2 ? 1 : s));
+}
+
+// What a workgroup of slab_step_kernel knows about itself, handed by value to the tile paths
+// below: the batch-offset pointers, the tile, the wave number, the kernel's flags.  (Lane numbers:
+// mfma_l15 / mfma_l4, solve16.h.)
+struct SlabWg {
+    double *A;
+    const double *Sin;
+    double *Sout;
+    const double *din;
+    double *dout;
+    long lda, lds;
+    int j0, r0, Rb, Cb, bx, by, wave, b, factor_next, last, col0;
+    int *info;
+    long long *stamps;
+    // The kernel's own argument, by reference: by value its fields sit in SGPRs across the whole
+    // kernel.  WHOEVER READS out's fields in a loop copies it first (`const SlabOut o = g.out`, as
+    // slab_store_diag does): through the reference every entry re-reads them behind its stores.
+    const SlabOut &out;
+};
+
+// A wave's solved 16 rows (rows 16 w .. + 15 of the tile's 64) into the Q rows, [k][row]: column
+// block c as it comes, or all four
+__device__ __forceinline__ void slab_publish_block(double *Qs, int c, int w, int l15, int l4,
+                                                   const double4_t &xc)
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        Qs[(16 * c + l4 + 4 * r) * 64 + 16 * w + l15] = xc[r];
+}
+
+__device__ __forceinline__ void slab_publish(double *Qs, int w, int l15, int l4,
+                                             const double4_t (&x)[4])
+{
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        slab_publish_block(Qs, c, w, l15, l4, x[c]);
+}
+
+// The last step's tiles are the Schur complement S of the border: with the read-out folded
+// in (SlabOut) the lane that holds S[c, c], S[yrow, c] or S[yrow, yrow] stores var_i, mean_i
+// and -- log|K| is complete since the previous launch -- the log-ML (reduce.h,
+// finalize_kernel, is the stand-alone form).  row / col: this sweep's numbering = the
+// system's (col0 = 0 for every caller that sets `out`).
+__device__ __forceinline__ void slab_emit(const SlabOut &out, int b, int row, int col, double s)
+{
+    if (row == col && row >= out.npad && row < out.npad + out.M && out.var)
+        out.var[(long)b * out.mstride + (row - out.npad)] = s;
+    if (row == out.yrow) {
+        if (col >= out.npad && col < out.npad + out.M && out.mean)
+            out.mean[(long)b * out.mstride + (col - out.npad)] = -s;
+        if (col == out.yrow) {
+            const double qf = -s, ld = out.scal[4 * b + 1];
+            out.scal[4 * b + 2] = qf;
+            out.scal[4 * b + 0] = -0.5 * qf - 0.5 * ld - 0.5 * (double)out.n * 1.8378770664093453;
+        }
+    }
+}
+
+// Wave w's blocks of an updated diagonal tile (-acc: the accumulators hold the negated tile)
+// back to A, and the read-out of the last step
+template <int NA>
+__device__ __forceinline__ void slab_store_diag(const SlabWg &g, int w, const double4_t (&acc)[NA])
+{
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+    const bool emit = g.last && g.out.scal != nullptr;
+#pragma unroll
+    for (int sb = 0; sb < 3; ++sb)
+        if (sb < slab_diag_nb(w)) {
+            double *Cd = g.A + g.Rb + 16 * slab_diag_rb(w, sb) + l15 +
+                         (long)(g.Cb + 16 * slab_diag_cb(w, sb) + l4) * g.lda;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                Cd[(long)(4 * r) * g.lda] = -acc[sb][r];
+            if (emit) {
+                const SlabOut o = g.out; // (by value: every field is read once, not per entry)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    slab_emit(o, g.b, g.Rb + 16 * slab_diag_rb(w, sb) + l15,
+                              g.Cb + 16 * slab_diag_cb(w, sb) + l4 + 4 * r, -acc[sb][r]);
+            }
+        }
+}
 
 // Workgroup 0 of an eight-wave step hands the updated diagonal block to the factor as its ten
 // lower 16 x 16 blocks, packed: block (rb, cb), cb <= rb, at 256 (rb (rb + 1) / 2 + cb), element
 // (i, k) at i + 16 k -- BQ_SLAB_FW doubles, exactly the fragment region, which is dead once every
-// wave holds its fragments.  This wave's columns, row `lane`; a lane above a column's own block
-// row takes 0.0, which the factor never reads.
+// wave holds its fragments.  Wave w's blocks go in ...
+template <int NA>
+__device__ __forceinline__ void slab_pack_blocks8(double *Bs, int w,
+                                                  const double4_t (&acc)[NA])
+{
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+#pragma unroll
+    for (int sb = 0; sb < 3; ++sb)
+        if (sb < slab_diag_nb(w)) {
+            const int rb = slab_diag_rb(w, sb), cb = slab_diag_cb(w, sb);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                Bs[256 * ((rb * (rb + 1)) / 2 + cb) + l15 + 16 * (l4 + 4 * r)] = -acc[sb][r];
+        }
+}
+
+// ... and every wave of the factor picks its columns out of them, row `lane`; a lane above a
+// column's own block row takes 0.0, which the factor never reads.
 __device__ __forceinline__ void slab_load_blocks8(Potf2FT<8> &st, const double *Bs, int w, int lane)
 {
     const int rb = lane >> 4, i = lane & 15;
@@ -131,8 +181,390 @@ __device__ __forceinline__ void slab_corner_factor8(double *Ab, long lda, int j0
     potf2f_run<8>(st, Ab, lda, j0, dinv_b, info_b, plds, stamps, logdet);
 }
 
+// (the step's call of it: the diagonal block at r0 of this problem; stamps: the factor's own)
+__device__ __forceinline__ void slab_factor_next8(const SlabWg &g, double *plds, long long *stamps)
+{
+    slab_corner_factor8(g.A + g.r0 + (long)g.r0 * g.lda, g.lda, g.col0 + g.r0, g.dout, g.info + g.b,
+                        plds, stamps, g.out.scal ? g.out.scal + 4 * g.b + 1 : nullptr);
+}
+
 // STAMP: a profiling instantiation (tools/c2_timeline.py) whose workgroup 0 records s_memtime
 // at its phase boundaries; the shipped launches use STAMP = false and carry no stamp code.
+// tid: the thread of workgroup 0 that records (wave 4's lane 0 is thread 256).
+#define BQ_SSTAMP(stamps_, k, dep, tid)                                                            \
+    if (STAMP) {                                                                                   \
+        asm volatile("" ::"v"(dep));                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+        if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == (tid))                            \
+            (stamps_)[k] = (long long)__builtin_amdgcn_s_memtime();                                \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+
+// --- the tile paths of slab_step_kernel, one per row group of the barrier table in front of it ---
+
+// Table rows "diagonal, NW = 8, PIPE", waves 4-7: A B0 B1 B2 B3 [F + factor].
+// diagonal tile: the update is THIS group's.  The ten lower blocks, dealt 3 / 3 / 2 / 2 by
+// slab_diag_rb / slab_diag_cb of wave - 4 and requested RAW before the first barrier; the
+// two-block waves load and update their second block again as a third, which nothing stores (an
+// MFMA ignores EXEC).
+template <bool STAMP>
+__device__ __forceinline__ void slab_pipe_update(const SlabWg g, double *plds)
+{
+    double *const Qs = plds;
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+    __builtin_assume(g.wave >= 4); // (the dispatch's condition, lost behind the call)
+    const int wu = g.wave - 4;
+    const int rb0 = slab_diag_rb(wu, 0), rb1 = slab_diag_rb(wu, 1), rb2 = slab_diag_rb(wu, 2);
+    const int cb0 = slab_diag_cb(wu, 0), cb1 = slab_diag_cb(wu, 1), cb2 = slab_diag_cb(wu, 2);
+    double4_t acc[3];
+#pragma unroll
+    for (int sb = 0; sb < 3; ++sb) {
+        const double *Cin = g.A + g.Rb + 16 * slab_diag_rb(wu, sb) + l15 +
+                            (long)(g.Cb + 16 * slab_diag_cb(wu, sb) + l4) * g.lda;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            acc[sb][r] = Cin[(long)(4 * r) * g.lda];
+    }
+    __syncthreads(); // A
+    // negated behind the first barrier: nothing needs the tile before x_0 is published
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int sb = 0; sb < 3; ++sb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double v = -acc[sb][r];
+            asm volatile("" : "+v"(v));
+            acc[sb][r] = v;
+        }
+    __builtin_amdgcn_sched_barrier(0);
+    // k-block c behind the barrier that publishes x_c: block (rb, cb) += X_cb X_rb^T in
+    // D^T form, the MFMAs of every accumulator in the order c, r of the one-phase update;
+    // all 24 LDS operands of the k-block are requested before its first MFMA
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (c > 0)
+            BQ_SSTAMP(g.stamps, 15 + c, acc[0][0], 256) // wave 4 arrives at B_c
+        // (pinned: left alone, the scheduler sinks eleven of a k-block's MFMAs behind
+        // the next barrier, and two k-blocks instead of one stand behind the solve)
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads(); // B_c
+        __builtin_amdgcn_sched_barrier(0);
+        double qa[4][3], qb[4][3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
+            qa[r][0] = qrow[16 * cb0], qb[r][0] = qrow[16 * rb0];
+            qa[r][1] = qrow[16 * cb1], qb[r][1] = qrow[16 * rb1];
+            qa[r][2] = qrow[16 * cb2], qb[r][2] = qrow[16 * rb2];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][0], qb[r][0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][1], qb[r][1], acc[1], 0, 0, 0);
+            acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][2], qb[r][2], acc[2], 0, 0, 0);
+        }
+    }
+    BQ_SSTAMP(g.stamps, 4, acc[1][3] + acc[0][0], 256)
+    if (blockIdx.x == 0 && g.factor_next) {
+        // the packed blocks go where the fragments were: waves 0-3 took their last
+        // fragments in front of B_3
+        slab_pack_blocks8(plds + 4096, wu, acc);
+        __syncthreads(); // F
+        slab_factor_next8(g, plds, nullptr);
+        return;
+    }
+    slab_store_diag(g, wu, acc);
+}
+
+// Column block C of the pipelined solve: x_C published in the Q rows the moment it exists, a
+// barrier behind it (B_C); the fragments of column block C + 2 are requested in front of B_C,
+// so that no LDS round trip stands between a barrier and the chain (the last ones in front of
+// B_1: waves 4-7 overwrite the fragment region behind B_3).
+template <bool STAMP, int C>
+__device__ __forceinline__ void slab_pipe_block(const SlabWg &g, double *plds, const double (&tc)[4],
+                                                Solve16Regs<> &f, double4_t (&x)[4])
+{
+    solve16_block<C>(tc, f, x);
+    slab_publish_block(plds, C, g.wave, mfma_l15(), mfma_l4(), x[C]);
+    if constexpr (C < 2)
+        f.template load_lds_block<C + 2>(plds + 4096);
+    if (C > 0)
+        BQ_SSTAMP(g.stamps, 18 + C, x[C][3], 0) // wave 0 arrives at B_c
+    // (not pinned: hipcc moves the MFMAs of x_{c+1} up in front of B_c and only
+    // its ds_write behind it; pinned to 4 / 8 / 12 / 16 MFMAs per interval the
+    // update waits less and the headline is the same: LABBOOK)
+    __syncthreads(); // B_c
+}
+
+// Table rows "diagonal, NW = 8, PIPE", waves 0-3: A B0 B1 B2 B3 [F + factor].
+// The fragments of L_jj and W staged once per workgroup and the panel rows, as in the one-phase
+// prologue -- but no C tile: that is waves 4-7's.  A path of its own from its first load to its
+// return (ONE prologue with a branch behind barrier A cost 254 VGPRs and spills: LABBOOK); it
+// shares the staging, the fragments and the solve with the one-phase body through solve16.h.
+template <bool STAMP>
+__device__ __forceinline__ void slab_pipe_solve(const SlabWg g, double *plds)
+{
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+    double tp[4][4];
+    double *Fs = plds + 4096;
+    {
+        double f6[6], wv[4];
+        solve16_stage_request(g.A + g.j0 + (long)g.j0 * g.lda, g.lda, g.din, f6, wv);
+        solve16_load(g.Sin + g.Rb + 16 * g.wave + l15 + (long)l4 * g.lds, g.lds, tp);
+        // nothing that waits for a load may move up between the loads
+        __builtin_amdgcn_sched_barrier(0);
+        solve16_stage_store(Fs, f6, wv);
+    }
+    __syncthreads(); // A
+    Solve16Regs<> f;
+    double4_t x[4];
+    f.load_lds_block<0>(Fs);
+    f.load_lds_block<1>(Fs);
+    BQ_SSTAMP(g.stamps, 1, f.wf[0][3] + f.wf[1][3], 0)
+    slab_pipe_block<STAMP, 0>(g, plds, tp[0], f, x);
+    slab_pipe_block<STAMP, 1>(g, plds, tp[1], f, x);
+    slab_pipe_block<STAMP, 2>(g, plds, tp[2], f, x);
+    slab_pipe_block<STAMP, 3>(g, plds, tp[3], f, x);
+    BQ_SSTAMP(g.stamps, 2, x[3][3], 0)
+    // the solved rows are the factor: tile column 0 owns the write
+    if (g.by == 0)
+        solve16_store(g.A + g.Rb + 16 * g.wave + l15 + (long)(g.j0 + l4) * g.lda, g.lda, x);
+    if (blockIdx.x == 0 && g.factor_next) {
+        __syncthreads(); // F
+        slab_factor_next8(g, plds, (STAMP && blockIdx.z == 0) ? g.stamps + 5 : nullptr);
+    }
+}
+
+// Table rows "off-diagonal tile", waves 4-7: A Q; and "diagonal, NW = 8, !PIPE", waves 4-7:
+// A Q [F + factor] -- the barriers of the one-phase body below, in their order: fragments
+// staged; Q rows written; and for workgroup 0 with a next factor: diagonal block in LDS.
+__device__ __forceinline__ void slab_upper_waves(const SlabWg g, double *plds)
+{
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+    if (g.bx != g.by) {
+        // off-diagonal tile: the Q rows (row block by) are solved HERE, beside waves 0-3's
+        // solve of the P rows -- the two are independent, and one after the other they were
+        // 2 x 3,300 cycles of every such workgroup.  Same MFMAs on the same operands in the
+        // same order as the four-wave form does them on waves 0-3.
+        __builtin_assume(g.wave >= 4); // (the dispatch's condition, lost behind the call)
+        const int wq = g.wave - 4;
+        double tq[4][4];
+        solve16_load(g.Sin + g.Cb + 16 * wq + l15 + (long)l4 * g.lds, g.lds, tq);
+        __syncthreads();
+        Solve16Regs<> f;
+        f.load_lds(plds + 4096);
+        double4_t xq[4];
+        solve16(tq, f, xq);
+        slab_publish(plds, wq, l15, l4, xq);
+        __syncthreads();
+        return; // (workgroup 0 is a diagonal tile)
+    }
+    __syncthreads();
+    __syncthreads();
+    if (blockIdx.x == 0 && g.factor_next) {
+        __syncthreads();
+        slab_factor_next8(g, plds, nullptr);
+    }
+}
+
+// The update of a one-phase diagonal tile, both operands from LDS (Q = P here): block (rb, cb)
+// += X_cb X_rb^T in D^T form.  D[n][i] = sum_k Q[n][k] P[i][k], C -= D^T.
+__device__ __forceinline__ void slab_update_diag(const double *Qs, int wave,
+                                                 double4_t (&acc)[4])
+{
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+    const int rb0 = slab_diag_rb(wave, 0), rb1 = slab_diag_rb(wave, 1), rb2 = slab_diag_rb(wave, 2);
+    const int cb0 = slab_diag_cb(wave, 0), cb1 = slab_diag_cb(wave, 1), cb2 = slab_diag_cb(wave, 2);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb0], qrow[16 * rb0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb1], qrow[16 * rb1], acc[1], 0, 0, 0);
+            acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb2], qrow[16 * rb2], acc[2], 0, 0, 0);
+        }
+}
+
+// ... and of an off-diagonal one: A operand = Q fragment from LDS, B operand = P as it stands
+__device__ __forceinline__ void slab_update_offdiag(const double *Qs,
+                                                    const double4_t (&xp)[4], double4_t (&acc)[4])
+{
+    const int l15 = mfma_l15(), l4 = mfma_l4();
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double pf = xp[c][r];
+            const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb)
+                acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb], pf, acc[cb], 0, 0, 0);
+        }
+}
+
+// Table rows "off-diagonal tile", waves 0-3: A Q; "diagonal, NW = 4": A Q [T F + factor];
+// "diagonal, NW = 8, !PIPE", waves 0-3: A Q [F + factor] -- the one-phase body (four waves, or
+// waves 0-3 of eight).
+template <bool STAMP, int NW, bool PIPE>
+__device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
+{
+    double *const Qs = plds;
+    double *const Ts = plds; // the block sits where the factor's panel slots will be
+    double *const Fs = plds + 4096;
+    const int bx = g.bx, by = g.by, wave = g.wave, l15 = mfma_l15(), l4 = mfma_l4();
+    // Every global load of the step is issued here, before the first MFMA: the fragments of
+    // L_jj (blocks below its diagonal) and of the negated block inverses, the unsolved panel
+    // rows of both row blocks and the C tile.  (Loaded where they are first used, the tile
+    // waited behind the factor's stores, which may alias it, and the launch paid three
+    // memory round trips one after the other.)
+    Solve16Regs<> f;
+    double tp[4][4], tq[4][4];
+    double4_t acc[4];
+    {
+        // The fragments of L_jj and W are the same for all four waves: the workgroup fetches
+        // the six 16 x 16 blocks below L_jj's diagonal and the four block inverses ONCE into
+        // LDS (10 doubles per thread; the region is the diagonal factor's, free until the
+        // tile update is over) instead of 64 doubles per lane from L2 -- a CU takes in about
+        // 40 B per cycle and the fragment loads were half of the launch's 190 KB.
+        double f6[6], wv[4];
+        solve16_stage_request(g.A + g.j0 + (long)g.j0 * g.lda, g.lda, g.din, f6, wv);
+        // No branch between the loads either: a load under `if` is a basic block of its own,
+        // and hipcc puts the waits of the OTHER arm's pending loads in front of it.  So the
+        // four-wave form loads the Q rows in a diagonal tile too (they are its P rows: the
+        // same lines), and the C tile's sixteen loads differ between the two kinds of tile
+        // only in wave-uniform offsets.
+        if (NW == 4)
+            solve16_load(g.Sin + g.Cb + 16 * wave + l15 + (long)l4 * g.lds, g.lds, tq);
+        solve16_load(g.Sin + g.Rb + 16 * wave + l15 + (long)l4 * g.lds, g.lds, tp);
+        // C tile, RAW: the MFMAs add Q P^T to -C, but a negation here draws the load's wait
+        // in between the loads (the scheduler places the sign flip as early as it may) and
+        // the tile then costs one memory round trip per group of loads; it is negated in
+        // front of the update instead.  Off-diagonal tiles: rows 16 wave .. +15,
+        // four 16-column blocks.  Diagonal tiles need only their ten lower 16 x 16 blocks
+        // and deal them 3 / 3 / 2 / 2 to the waves (slab_diag_rb / slab_diag_cb): 48 MFMAs on
+        // the longest wave instead of 64 -- for workgroup (0, 0) this update sits between the
+        // launch's start and the diagonal factor.  Waves 2 and 3 load their second block
+        // again as a third (s = 2, as for the MFMAs: never stored), and every wave of a
+        // diagonal tile loads its third block again as a fourth, which nothing reads.
+        {
+            const bool dg = bx == by;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                const int sb = cb < 2 ? cb : 2;
+                const int ro = dg ? 16 * slab_diag_rb(wave, sb) : 16 * wave;
+                const int co = dg ? 16 * slab_diag_cb(wave, sb) : 16 * cb;
+                const double *Cin = g.A + g.Rb + ro + l15 + (long)(g.Cb + co + l4) * g.lda;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    acc[cb][r] = Cin[(long)(4 * r) * g.lda];
+            }
+        }
+        // nothing that waits for a load may move up between the loads
+        __builtin_amdgcn_sched_barrier(0);
+        solve16_stage_store(Fs, f6, wv);
+    }
+    __syncthreads(); // A
+    f.load_lds(Fs);
+    BQ_SSTAMP(g.stamps, 1, f.la[3][2][3] + f.wf[3][3], 0)
+    // Q rows (row block by) -> LDS (eight waves: by waves 4-7, slab_upper_waves); P rows (row
+    // block bx) stay in registers
+    double4_t xp[4];
+    if (NW == 4 && bx != by) {
+        double4_t xq[4];
+        solve16(tq, f, xq);
+        slab_publish(Qs, wave, l15, l4, xq);
+    }
+    solve16(tp, f, xp);
+    if (bx == by)
+        slab_publish(Qs, wave, l15, l4, xp);
+    BQ_SSTAMP(g.stamps, 2, xp[3][3], 0)
+    // The tile was loaded raw (see the prologue) and is negated HERE: behind the solve, which has
+    // given it 3,000 cycles to arrive, and in front of the stores below -- the wait counts
+    // stores too, and behind them the tile's wait would drain them on workgroup 0's path.
+    // (acc[3] of a diagonal tile is never read.)
+    // (The pins keep the sign flips, and the wait with them, from sinking to the accumulators'
+    // first uses behind the barrier.)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+        if (cb < 3 || bx != by) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double v = -acc[cb][r];
+                asm volatile("" : "+v"(v));
+                acc[cb][r] = v;
+            }
+        }
+    __builtin_amdgcn_sched_barrier(0);
+    // the solved rows are the factor: tile column 0 owns the write
+    if (by == 0)
+        solve16_store(g.A + g.Rb + 16 * wave + l15 + (long)(g.j0 + l4) * g.lda, g.lda, xp);
+    __syncthreads(); // Q
+    BQ_SSTAMP(g.stamps, 3, acc[1][3] + acc[0][0], 0)
+    if (bx == by)
+        slab_update_diag(Qs, wave, acc);
+    else
+        slab_update_offdiag(Qs, xp, acc);
+    BQ_SSTAMP(g.stamps, 4, acc[1][3] + acc[0][0], 0)
+    // tile column 0 is the next panel: it goes to the scratch column (the diagonal tile,
+    // which workgroup 0 factors in place, and the Schur complement of the last step stay in A)
+    // (the pipelined form never comes here with a diagonal tile, and workgroup 0 is one)
+    if (!(NW == 8 && PIPE) && blockIdx.x == 0 && g.factor_next) {
+        // the next diagonal block never touches memory between its update and its factor
+        // (only the ten lower blocks: the factor never reads a lane above its column's own)
+        if constexpr (NW == 8) {
+            // eight waves: the blocks go, packed, where the fragments were -- every wave has had
+            // its fragments since the barrier in front of the update -- and ONE barrier later
+            // the factor's waves pick their columns out of them (slab_load_blocks8)
+            slab_pack_blocks8(Fs, wave, acc);
+            __syncthreads(); // F
+            slab_factor_next8(g, plds, (STAMP && blockIdx.z == 0) ? g.stamps + 5 : nullptr);
+            return;
+        }
+        // four waves: it lands where the Q rows were: every wave must be through with them
+        __syncthreads(); // T
+#pragma unroll
+        for (int sb = 0; sb < 3; ++sb)
+            if (sb < slab_diag_nb(wave)) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    Ts[16 * slab_diag_rb(wave, sb) + l15 +
+                       64 * (16 * slab_diag_cb(wave, sb) + l4 + 4 * r)] = -acc[sb][r];
+            }
+        __syncthreads(); // F
+        // (col0: the global column of this sweep's first column, for the failure report)
+        potf2_body<NW>(g.A + g.r0 + (long)g.r0 * g.lda, g.lda, g.col0 + g.r0, g.dout, g.info + g.b,
+                       plds, Ts, 64, (STAMP && blockIdx.z == 0) ? g.stamps + 5 : nullptr,
+                       g.out.scal ? g.out.scal + 4 * g.b + 1 : nullptr);
+        return;
+    }
+    const bool to_s = by == 0 && bx > 0 && !g.last;
+    double *Cout = to_s ? g.Sout + g.Rb + 16 * wave + l15 + (long)l4 * g.lds
+                        : g.A + g.Rb + 16 * wave + l15 + (long)(g.Cb + l4) * g.lda;
+    const long ldo = to_s ? g.lds : g.lda;
+    if (bx == by) {
+        slab_store_diag(g, wave, acc);
+    } else {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                Cout[(long)(16 * cb + 4 * r) * ldo] = -acc[cb][r];
+        // (the last step's tiles are the Schur complement of the border: slab_emit)
+        if (g.last && g.out.scal != nullptr) {
+            const SlabOut o = g.out; // (by value: every field is read once, not per entry)
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    slab_emit(o, g.b, g.Rb + 16 * wave + l15, g.Cb + 16 * cb + l4 + 4 * r,
+                              -acc[cb][r]);
+        }
+    }
+}
+
 // NW = 8 (launch_slab_step has the rule): 512 threads; in an off-diagonal tile waves 4-7 solve the
 // Q rows while waves 0-3 solve the P rows; in a diagonal tile they update the tile behind the
 // solve's column blocks (PIPE, below; !PIPE: they pass the update's barriers), and in workgroup 0
@@ -140,7 +572,7 @@ __device__ __forceinline__ void slab_corner_factor8(double *Ab, long lda, int j0
 // 13.2 k cycles).
 // PIPE (BQ_DIAG_PIPE, the shipped eight-wave form; NW = 8 only): in a DIAGONAL tile waves 4-7 do
 // not idle.  The tile's update is a sum over the four 16-column k-blocks of X, and k-block c needs
-// only x_c, which slab_solve16 delivers about 8 dependent MFMAs before x_{c+1}: waves 0-3 publish
+// only x_c, which solve16 delivers about 8 dependent MFMAs before x_{c+1}: waves 0-3 publish
 // every x_c in the Q rows behind a barrier of its own (B_c), and waves 4-7, which requested the
 // ten lower blocks of the C tile at entry, run k-block c of the update (12 MFMAs per wave) while
 // waves 0-3 solve x_{c+1}.  Behind the solve stand only the last k-block and the hand-off.  Same
@@ -173,46 +605,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
                                                         int *__restrict__ info, int col0,
                                                         long long *stamps, SlabOut out)
 {
-#define BQ_SSTAMP(k, dep)                                                                          \
-    if (STAMP) {                                                                                   \
-        asm volatile("" ::"v"(dep));                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0)                                \
-            stamps[k] = (long long)__builtin_amdgcn_s_memtime();                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-    }
-    // (the same for another thread of workgroup 0: wave 4's lane 0 is thread 256)
-#define BQ_SSTAMP_T(k, dep, tid)                                                                   \
-    if (STAMP) {                                                                                   \
-        asm volatile("" ::"v"(dep));                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == (tid))                            \
-            stamps[k] = (long long)__builtin_amdgcn_s_memtime();                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-    }
-    // The last step's tiles are the Schur complement S of the border: with the read-out folded
-    // in (SlabOut) the lane that holds S[c, c], S[yrow, c] or S[yrow, yrow] stores var_i, mean_i
-    // and -- log|K| is complete since the previous launch -- the log-ML (reduce.h,
-    // finalize_kernel, is the stand-alone form).  row / col: this sweep's numbering = the
-    // system's (col0 = 0 for every caller that sets `out`).
-#define BQ_SLAB_EMIT(ROW_, COL_, S_)                                                               \
-    {                                                                                              \
-        const int row_ = (ROW_), col_ = (COL_);                                                    \
-        const double s_ = (S_);                                                                    \
-        if (row_ == col_ && row_ >= out.npad && row_ < out.npad + out.M && out.var)                \
-            out.var[(long)b * out.mstride + (row_ - out.npad)] = s_;                               \
-        if (row_ == out.yrow) {                                                                    \
-            if (col_ >= out.npad && col_ < out.npad + out.M && out.mean)                           \
-                out.mean[(long)b * out.mstride + (col_ - out.npad)] = -s_;                         \
-            if (col_ == out.yrow) {                                                                \
-                const double qf_ = -s_, ld_ = out.scal[4 * b + 1];                                 \
-                out.scal[4 * b + 2] = qf_;                                                         \
-                out.scal[4 * b + 0] =                                                              \
-                    -0.5 * qf_ - 0.5 * ld_ - 0.5 * (double)out.n * 1.8378770664093453;             \
-            }                                                                                      \
-        }                                                                                          \
-    }
-    BQ_SSTAMP(0, 0)
+    BQ_SSTAMP(stamps, 0, 0, 0)
     // One region, 52 KiB -- a workgroup of this kernel must fit into what ONE retiring workgroup
     // of the 64-tile product frees on a CU (36 KiB + the 16 KiB four of them leave over), or it
     // starves behind a trailing update running on the other stream.  First 4096 doubles: the Q
@@ -221,489 +614,36 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     // way to the factor).  Behind them: the fragments of L_jj and W (BQ_SLAB_FW doubles); after
     // the update, in workgroup 0 of eight waves, the updated diagonal block as ten packed blocks.
     __shared__ __attribute__((aligned(16))) double plds[4096 + BQ_SLAB_FW];
-    double *const Qs = plds;
-    double *const Ts = plds; // the block sits where the factor's panel slots will be
     __builtin_amdgcn_s_setprio(3);
     const int b = blockIdx.z;
-    const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int bx, by;
     tri_decode(blockIdx.x, bx, by);
-    A += (long)b * astride;
-    Sin += (long)b * sstride;
-    Sout += (long)b * sstride;
-    din += (long)b * dstride;
-    dout += (long)b * dstride;
     const int r0 = j0 + 64;
-    const int Rb = r0 + 64 * bx, Cb = r0 + 64 * by;
-    const int l15 = lane & 15, l4 = lane >> 4;
+    const SlabWg g = {A + (long)b * astride, Sin + (long)b * sstride, Sout + (long)b * sstride,
+                      din + (long)b * dstride, dout + (long)b * dstride, lda, lds, j0, r0,
+                      r0 + 64 * bx, r0 + 64 * by, bx, by, wave, b, factor_next, last, col0, info,
+                      stamps, out};
+    // A diagonal tile of the pipelined form is a path of its own from here to its return:
+    // nothing of it is shared with the off-diagonal tiles, whose code and registers stay the
+    // one-phase form's.
     if constexpr (NW == 8 && PIPE) {
-        // A diagonal tile of the pipelined form is a path of its own from here to its return
-        // (the barrier table in front of the kernel): nothing of it is shared with the
-        // off-diagonal tiles below, whose code and registers stay the one-phase form's.
-        if (bx == by) {
-            if (wave >= 4) {
-                // diagonal tile: the update is THIS group's (the barrier table in front of the kernel).
-                // The ten lower blocks, dealt 3 / 3 / 2 / 2 by DIAG_RB / DIAG_CB of wave - 4 and
-                // requested RAW before the first barrier; the two-block waves load and update their
-                // second block again as a third, which nothing stores (an MFMA ignores EXEC).
-                const int wu = wave - 4;
-                const int rb0 = DIAG_RB(wu, 0), rb1 = DIAG_RB(wu, 1), rb2 = DIAG_RB(wu, 2);
-                const int cb0 = DIAG_CB(wu, 0), cb1 = DIAG_CB(wu, 1), cb2 = DIAG_CB(wu, 2);
-                double4_t acc[3];
-    #pragma unroll
-                for (int sb = 0; sb < 3; ++sb) {
-                    const double *Cin = A + Rb + 16 * DIAG_RB(wu, sb) + l15 +
-                                        (long)(Cb + 16 * DIAG_CB(wu, sb) + l4) * lda;
-    #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        acc[sb][r] = Cin[(long)(4 * r) * lda];
-                }
-                __syncthreads(); // A
-                // negated behind the first barrier: nothing needs the tile before x_0 is published
-                __builtin_amdgcn_sched_barrier(0);
-    #pragma unroll
-                for (int sb = 0; sb < 3; ++sb)
-    #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        double v = -acc[sb][r];
-                        asm volatile("" : "+v"(v));
-                        acc[sb][r] = v;
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-                // k-block c behind the barrier that publishes x_c: block (rb, cb) += X_cb X_rb^T in
-                // D^T form, the MFMAs of every accumulator in the order c, r of the one-phase update;
-                // all 24 LDS operands of the k-block are requested before its first MFMA
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (c > 0)
-                        BQ_SSTAMP_T(15 + c, acc[0][0], 256) // wave 4 arrives at B_c
-                    // (pinned: left alone, the scheduler sinks eleven of a k-block's MFMAs behind
-                    // the next barrier, and two k-blocks instead of one stand behind the solve)
-                    __builtin_amdgcn_sched_barrier(0);
-                    __syncthreads(); // B_c
-                    __builtin_amdgcn_sched_barrier(0);
-                    double qa[4][3], qb[4][3];
-    #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
-                        qa[r][0] = qrow[16 * cb0], qb[r][0] = qrow[16 * rb0];
-                        qa[r][1] = qrow[16 * cb1], qb[r][1] = qrow[16 * rb1];
-                        qa[r][2] = qrow[16 * cb2], qb[r][2] = qrow[16 * rb2];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-    #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][0], qb[r][0], acc[0], 0, 0, 0);
-                        acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][1], qb[r][1], acc[1], 0, 0, 0);
-                        acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[r][2], qb[r][2], acc[2], 0, 0, 0);
-                    }
-                }
-                BQ_SSTAMP_T(4, acc[1][3] + acc[0][0], 256)
-                if (blockIdx.x == 0 && factor_next) {
-                    // the packed blocks go where the fragments were: waves 0-3 took their last
-                    // fragments in front of B_3
-                    double *Bs = plds + 4096;
-    #pragma unroll
-                    for (int sb = 0; sb < 3; ++sb)
-                        if (sb < DIAG_NB(wu)) {
-                            const int rb = DIAG_RB(wu, sb), cb = DIAG_CB(wu, sb);
-    #pragma unroll
-                            for (int r = 0; r < 4; ++r)
-                                Bs[256 * ((rb * (rb + 1)) / 2 + cb) + l15 + 16 * (l4 + 4 * r)] = -acc[sb][r];
-                        }
-                    __syncthreads(); // F
-                    slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds,
-                                        nullptr, out.scal ? out.scal + 4 * b + 1 : nullptr);
-                    return;
-                }
-                const bool emit = last && out.scal != nullptr;
-    #pragma unroll
-                for (int sb = 0; sb < 3; ++sb)
-                    if (sb < DIAG_NB(wu)) {
-                        double *Cd = A + Rb + 16 * DIAG_RB(wu, sb) + l15 +
-                                     (long)(Cb + 16 * DIAG_CB(wu, sb) + l4) * lda;
-    #pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            Cd[(long)(4 * r) * lda] = -acc[sb][r];
-                        if (emit) {
-    #pragma unroll
-                            for (int r = 0; r < 4; ++r)
-                                BQ_SLAB_EMIT(Rb + 16 * DIAG_RB(wu, sb) + l15,
-                                             Cb + 16 * DIAG_CB(wu, sb) + l4 + 4 * r, -acc[sb][r])
-                        }
-                    }
+        if (g.bx == g.by) {
+            if (g.wave >= 4) {
+                slab_pipe_update<STAMP>(g, plds);
                 return;
             }
-            // Waves 0-3: the fragments of L_jj and W staged once per workgroup and the panel
-            // rows, as in the prologue below -- but no C tile: that is waves 4-7's.  A COPY of that
-            // prologue (a shared one cost 254 VGPRs and spills: LABBOOK) and of slab_solve16's
-            // body: the two must stay in step -- the same Fs / Ws layout, which slab_frags reads
-            // and slab_load_blocks8 overwrites, and the same MFMA order per accumulator.
-            double la[4][3][4], wneg[4][4], tp[4][4];
-            double *Fs = plds + 4096;
-            {
-                double *Ws = plds + 4096 + 6 * 256;
-                const int t = threadIdx.x, ti = t & 15, tk = t >> 4;
-                const double *L11 = A + j0 + (long)j0 * lda + ti + (long)tk * lda;
-                double f[6], wv[4];
-#pragma unroll
-                for (int c = 1; c < 4; ++c)
-#pragma unroll
-                    for (int bb = 0; bb < c; ++bb)
-                        f[(c * (c - 1)) / 2 + bb] = L11[16 * c + (long)(16 * bb) * lda];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    wv[q] = din[64 + 256 * q + t];
-                slab_load16(Sin + Rb + 16 * wave + l15 + (long)l4 * lds, lds, tp);
-                // nothing that waits for a load may move up between the loads
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-                    Fs[256 * q + t] = f[q];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    Ws[256 * q + t] = -wv[q];
-            }
-            __syncthreads(); // A
-            {
-                // Every column block x_c is published in the Q rows the moment it exists, a
-                // barrier behind it (B_c).  slab_solve16's MFMAs in its order; the
-                // fragments of column block c + 2 are requested in front of B_c, so that no
-                // LDS round trip stands between a barrier and the chain (the last ones in
-                // front of B_1: waves 4-7 overwrite the fragment region behind B_3).
-                const double *Ws = Fs + 6 * 256;
-                double4_t x[4];
-#define BQ_PIPE_FRAGS(C_)                                                                          \
-    do {                                                                                           \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) wneg[C_][r] =                                \
-            Ws[256 * (C_) + 64 * r + l15 + 16 * l4];                                               \
-        _Pragma("unroll") for (int bb = 0; bb < (C_); ++bb) _Pragma("unroll") for (int r = 0;      \
-                                                                                   r < 4; ++r)     \
-            la[C_][bb][r] = Fs[256 * (((C_) * ((C_) - 1)) / 2 + bb) + l15 + 16 * (l4 + 4 * r)];    \
-    } while (0)
-                BQ_PIPE_FRAGS(0);
-                BQ_PIPE_FRAGS(1);
-                BQ_SSTAMP(1, wneg[0][3] + wneg[1][3])
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    double4_t a = {-tp[c][0], -tp[c][1], -tp[c][2], -tp[c][3]};
-#pragma unroll
-                    for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            a = __builtin_amdgcn_mfma_f64_16x16x4f64(la[c][bb][r], x[bb][r], a, 0, 0, 0);
-                    double4_t xc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        xc = __builtin_amdgcn_mfma_f64_16x16x4f64(wneg[c][r], a[r], xc, 0, 0, 0);
-                    x[c] = xc;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xc[r];
-                    if (c == 0) {
-                        BQ_PIPE_FRAGS(2);
-                    }
-                    if (c == 1) {
-                        BQ_PIPE_FRAGS(3);
-                    }
-                    if (c > 0)
-                        BQ_SSTAMP(18 + c, xc[3]) // wave 0 arrives at B_c
-                    // (not pinned: hipcc moves the MFMAs of x_{c+1} up in front of B_c and only
-                    // its ds_write behind it; pinned to 4 / 8 / 12 / 16 MFMAs per interval the
-                    // update waits less and the headline is the same: LABBOOK)
-                    __syncthreads(); // B_c
-                }
-#undef BQ_PIPE_FRAGS
-                BQ_SSTAMP(2, x[3][3])
-                // the solved rows are the factor: tile column 0 owns the write
-                if (by == 0) {
-                    double *Lw = A + Rb + 16 * wave + l15 + (long)(j0 + l4) * lda;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            Lw[(long)(16 * c + 4 * r) * lda] = x[c][r];
-                }
-                if (blockIdx.x == 0 && factor_next) {
-                    __syncthreads(); // F
-                    slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b,
-                                        plds, (STAMP && blockIdx.z == 0) ? stamps + 5 : nullptr,
-                                        out.scal ? out.scal + 4 * b + 1 : nullptr);
-                }
-                return;
-            }
-        }
-    }
-    if (NW == 8 && wave >= 4) {
-        // the barriers of the tile update below, in their order: fragments staged; Q rows
-        // written; and for workgroup 0 with a next factor: diagonal block in LDS
-        if (bx != by) {
-            // off-diagonal tile: the Q rows (row block by) are solved HERE, beside waves 0-3's
-            // solve of the P rows -- the two are independent, and one after the other they were
-            // 2 x 3,300 cycles of every such workgroup.  Same MFMAs on the same operands in the
-            // same order as the four-wave form does them on waves 0-3.
-            const int wq = wave - 4;
-            double tq[4][4];
-            slab_load16(Sin + Cb + 16 * wq + l15 + (long)l4 * lds, lds, tq);
-            __syncthreads();
-            double la[4][3][4], wneg[4][4];
-            slab_frags(plds + 4096, l15, l4, la, wneg);
-            double4_t xq[4];
-            slab_solve16(tq, la, wneg, xq);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wq + l15] = xq[c][r];
-            __syncthreads();
-            return; // (workgroup 0 is a diagonal tile)
-        }
-        __syncthreads();
-        __syncthreads();
-        if (blockIdx.x == 0 && factor_next) {
-            __syncthreads();
-            slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds,
-                                nullptr, out.scal ? out.scal + 4 * b + 1 : nullptr);
-        }
-        return;
-    }
-
-    // Every global load of the step is issued here, before the first MFMA: the fragments of
-    // L_jj (blocks below its diagonal) and of the negated block inverses, the unsolved panel
-    // rows of both row blocks and the C tile.  (Loaded where they are first used, the tile
-    // waited behind the factor's stores, which may alias it, and the launch paid three
-    // memory round trips one after the other.)
-    double la[4][3][4], wneg[4][4], tp[4][4], tq[4][4];
-    double4_t acc[4];
-    {
-        // The fragments of L_jj and W are the same for all four waves: the workgroup fetches
-        // the six 16 x 16 blocks below L_jj's diagonal and the four block inverses ONCE into
-        // LDS (10 doubles per thread; the region is the diagonal factor's, free until the
-        // tile update is over) instead of 64 doubles per lane from L2 -- a CU takes in about
-        // 40 B per cycle and the fragment loads were half of the launch's 190 KB.
-        double *Fs = plds + 4096;          // block (c, bb), c > bb, at 256 ((c (c - 1)) / 2 + bb)
-        double *Ws = plds + 4096 + 6 * 256; // W blocks as in global memory
-        {
-            const int t = threadIdx.x, ti = t & 15, tk = t >> 4;
-            const double *L11 = A + j0 + (long)j0 * lda + ti + (long)tk * lda;
-            double f[6], wv[4];
-#pragma unroll
-            for (int c = 1; c < 4; ++c)
-#pragma unroll
-                for (int bb = 0; bb < c; ++bb)
-                    f[(c * (c - 1)) / 2 + bb] = L11[16 * c + (long)(16 * bb) * lda];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                wv[q] = din[64 + 256 * q + t];
-            // No branch between the loads either: a load under `if` is a basic block of its own,
-            // and hipcc puts the waits of the OTHER arm's pending loads in front of it.  So the
-            // four-wave form loads the Q rows in a diagonal tile too (they are its P rows: the
-            // same lines), and the C tile's sixteen loads differ between the two kinds of tile
-            // only in wave-uniform offsets.
-            if (NW == 4)
-                slab_load16(Sin + Cb + 16 * wave + l15 + (long)l4 * lds, lds, tq);
-            slab_load16(Sin + Rb + 16 * wave + l15 + (long)l4 * lds, lds, tp);
-            // C tile, RAW: the MFMAs add Q P^T to -C, but a negation here draws the load's wait
-            // in between the loads (the scheduler places the sign flip as early as it may) and
-            // the tile then costs one memory round trip per group of loads; it is negated in
-            // front of the update instead.  Off-diagonal tiles: rows 16 wave .. +15,
-            // four 16-column blocks.  Diagonal tiles need only their ten lower 16 x 16 blocks
-            // and deal them 3 / 3 / 2 / 2 to the waves (DIAG_RB / DIAG_CB): 48 MFMAs on the
-            // longest wave instead of 64 -- for workgroup (0, 0) this update sits between the
-            // launch's start and the diagonal factor.  Waves 2 and 3 load their second block
-            // again as a third (s = 2, as for the MFMAs: never stored), and every wave of a
-            // diagonal tile loads its third block again as a fourth, which nothing reads.
-            {
-                const bool dg = bx == by;
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) {
-                    const int sb = cb < 2 ? cb : 2;
-                    const int ro = dg ? 16 * DIAG_RB(wave, sb) : 16 * wave;
-                    const int co = dg ? 16 * DIAG_CB(wave, sb) : 16 * cb;
-                    const double *Cin = A + Rb + ro + l15 + (long)(Cb + co + l4) * lda;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        acc[cb][r] = Cin[(long)(4 * r) * lda];
-                }
-            }
-            // nothing that waits for a load may move up between the loads
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-                Fs[256 * q + t] = f[q];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                Ws[256 * q + t] = -wv[q];
-        }
-        __syncthreads(); // A
-        slab_frags(Fs, l15, l4, la, wneg);
-    }
-    BQ_SSTAMP(1, la[3][2][3] + wneg[3][3])
-    // Q rows (row block by) -> LDS (eight waves: by waves 4-7, above); P rows (row block bx)
-    // stay in registers
-    double4_t xp[4];
-    if (NW == 4 && bx != by) {
-        double4_t xq[4];
-        slab_solve16(tq, la, wneg, xq);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xq[c][r];
-    }
-    slab_solve16(tp, la, wneg, xp);
-    if (bx == by) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xp[c][r];
-    }
-    BQ_SSTAMP(2, xp[3][3])
-    // The tile was loaded raw (see the prologue) and is negated HERE: behind the solve, which has
-    // given it 3,000 cycles to arrive, and in front of the stores below -- the wait counts
-    // stores too, and behind them the tile's wait would drain them on workgroup 0's path.
-    // (acc[3] of a diagonal tile is never read.)
-    // (The pins keep the sign flips, and the wait with them, from sinking to the accumulators'
-    // first uses behind the barrier.)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-        if (cb < 3 || bx != by) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double v = -acc[cb][r];
-                asm volatile("" : "+v"(v));
-                acc[cb][r] = v;
-            }
-        }
-    __builtin_amdgcn_sched_barrier(0);
-    // the solved rows are the factor: tile column 0 owns the write
-    if (by == 0) {
-        double *Lw = A + Rb + 16 * wave + l15 + (long)(j0 + l4) * lda;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Lw[(long)(16 * c + 4 * r) * lda] = xp[c][r];
-    }
-    // D[n][i] = sum_k Q[n][k] P[i][k] (A operand = Q fragment from LDS, B operand = P as it
-    // stands), C -= D^T
-    __syncthreads();
-    BQ_SSTAMP(3, acc[1][3] + acc[0][0])
-    if (bx == by) {
-        // both operands from LDS (Q = P here): block (rb, cb) += X_cb X_rb^T in D^T form
-        const int rb0 = DIAG_RB(wave, 0), rb1 = DIAG_RB(wave, 1), rb2 = DIAG_RB(wave, 2);
-        const int cb0 = DIAG_CB(wave, 0), cb1 = DIAG_CB(wave, 1), cb2 = DIAG_CB(wave, 2);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
-                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb0], qrow[16 * rb0], acc[0],
-                                                              0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb1], qrow[16 * rb1], acc[1],
-                                                              0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb2], qrow[16 * rb2],
-                                                              acc[2], 0, 0, 0);
-            }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double pf = xp[c][r];
-                const double *qrow = Qs + (16 * c + l4 + 4 * r) * 64 + l15;
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb)
-                    acc[cb] =
-                        __builtin_amdgcn_mfma_f64_16x16x4f64(qrow[16 * cb], pf, acc[cb], 0, 0, 0);
-            }
-    }
-    BQ_SSTAMP(4, acc[1][3] + acc[0][0])
-    // tile column 0 is the next panel: it goes to the scratch column (the diagonal tile,
-    // which workgroup 0 factors in place, and the Schur complement of the last step stay in A)
-    // (the pipelined form never comes here with a diagonal tile, and workgroup 0 is one)
-    if (!(NW == 8 && PIPE) && blockIdx.x == 0 && factor_next) {
-        // the next diagonal block never touches memory between its update and its factor
-        // (only the ten lower blocks: the factor never reads a lane above its column's own)
-        if constexpr (NW == 8) {
-            // eight waves: the blocks go, packed, where the fragments were -- every wave has had
-            // its fragments since the barrier in front of the update -- and ONE barrier later
-            // the factor's waves pick their columns out of them (slab_load_blocks8)
-            double *Bs = plds + 4096;
-#pragma unroll
-            for (int sb = 0; sb < 3; ++sb)
-                if (sb < DIAG_NB(wave)) {
-                    const int rb = DIAG_RB(wave, sb), cb = DIAG_CB(wave, sb);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        Bs[256 * ((rb * (rb + 1)) / 2 + cb) + l15 + 16 * (l4 + 4 * r)] = -acc[sb][r];
-                }
-            __syncthreads();
-            slab_corner_factor8(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds,
-                                (STAMP && blockIdx.z == 0) ? stamps + 5 : nullptr,
-                                out.scal ? out.scal + 4 * b + 1 : nullptr);
+            slab_pipe_solve<STAMP>(g, plds);
             return;
         }
-        // four waves: it lands where the Q rows were: every wave must be through with them
-        __syncthreads();
-#pragma unroll
-        for (int sb = 0; sb < 3; ++sb)
-            if (sb < DIAG_NB(wave)) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    Ts[16 * DIAG_RB(wave, sb) + l15 +
-                       64 * (16 * DIAG_CB(wave, sb) + l4 + 4 * r)] = -acc[sb][r];
-            }
-        __syncthreads();
-        // (col0: the global column of this sweep's first column, for the failure report)
-        potf2_body<NW>(A + r0 + (long)r0 * lda, lda, col0 + r0, dout, info + b, plds, Ts, 64,
-                       (STAMP && blockIdx.z == 0) ? stamps + 5 : nullptr,
-                       out.scal ? out.scal + 4 * b + 1 : nullptr);
+    }
+    if (NW == 8 && g.wave >= 4) {
+        slab_upper_waves(g, plds);
         return;
     }
-    const bool to_s = by == 0 && bx > 0 && !last;
-    double *Cout = to_s ? Sout + Rb + 16 * wave + l15 + (long)l4 * lds
-                        : A + Rb + 16 * wave + l15 + (long)(Cb + l4) * lda;
-    const long ldo = to_s ? lds : lda;
-    // (the last step's tiles are the Schur complement of the border: BQ_SLAB_EMIT, above)
-    const bool emit = last && out.scal != nullptr;
-    if (bx == by) {
-#pragma unroll
-        for (int sb = 0; sb < 3; ++sb)
-            if (sb < DIAG_NB(wave)) {
-                double *Cd = A + Rb + 16 * DIAG_RB(wave, sb) + l15 +
-                             (long)(Cb + 16 * DIAG_CB(wave, sb) + l4) * lda;
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    Cd[(long)(4 * r) * lda] = -acc[sb][r];
-                if (emit) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        BQ_SLAB_EMIT(Rb + 16 * DIAG_RB(wave, sb) + l15,
-                                     Cb + 16 * DIAG_CB(wave, sb) + l4 + 4 * r, -acc[sb][r])
-                }
-            }
-    } else {
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Cout[(long)(16 * cb + 4 * r) * ldo] = -acc[cb][r];
-        if (emit) {
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    BQ_SLAB_EMIT(Rb + 16 * wave + l15, Cb + 16 * cb + l4 + 4 * r, -acc[cb][r])
-        }
-    }
-#undef BQ_SLAB_EMIT
-#undef BQ_SSTAMP_T
-#undef BQ_SSTAMP
+    slab_one_phase<STAMP, NW, PIPE>(g, plds);
 }
+#undef BQ_SSTAMP
 
 // The assembly of the bordered system with the first launch of the slab sweep folded in: the
 // tiles of column block 0 also fill the sweep's scratch column, and the workgroup of tile
@@ -950,35 +890,16 @@ __global__ __launch_bounds__(64 * NW) void panel_step_kernel(double *__restrict_
         return;
     }
 
-    double la[4][3][4], wneg[4][4];
-    {
-        const double *L11 = A + j0 + (long)j0 * lda + l15 + (long)l4 * lda;
-        const double *W = din + 64 + l15 + 16 * l4;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                wneg[c][r] = -W[256 * c + 64 * r];
-#pragma unroll
-        for (int c = 1; c < 4; ++c)
-#pragma unroll
-            for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    la[c][bb][r] = L11[16 * c + (long)(16 * bb + 4 * r) * lda];
-    }
+    Solve16Regs<> f;
+    f.load_global(A + j0 + (long)j0 * lda, lda, din, l15, l4);
     double4_t xp[4];
     if (has_next && blockIdx.x != 0 && (NW == 4 || wave >= 4)) {
         const int wq = wave & 3;
         double4_t xq[4];
         double tq[4][4];
-        slab_load16(Sp + r0 + 16 * wq + l15 + (long)l4 * ldsp, ldsp, tq);
-        slab_solve16(tq, la, wneg, xq);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wq + l15] = xq[c][r];
+        solve16_load(Sp + r0 + 16 * wq + l15 + (long)l4 * ldsp, ldsp, tq);
+        solve16(tq, f, xq);
+        slab_publish(Qs, wq, l15, l4, xq);
         if (NW == 8) {
             __syncthreads(); // (the one in front of the slab-s product below)
             return;
@@ -986,30 +907,20 @@ __global__ __launch_bounds__(64 * NW) void panel_step_kernel(double *__restrict_
     }
     {
         double tp[4][4];
-        slab_load16(Sp + Rb + 16 * wave + l15 + (long)l4 * ldsp, ldsp, tp);
-        slab_solve16(tp, la, wneg, xp);
+        solve16_load(Sp + Rb + 16 * wave + l15 + (long)l4 * ldsp, ldsp, tp);
+        solve16(tp, f, xp);
     }
     {
         // (a lone workgroup has no readers to protect, and no next step to move the block)
         const bool side = first && has_next && blockIdx.x == 0 && gridDim.x > 1;
         double *Lw = side ? SL + 16 * wave + l15 + 64 * l4
                           : A + Rb + 16 * wave + l15 + (long)(j0 + l4) * lda;
-        const long ldw = side ? 64 : lda;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Lw[(long)(16 * c + 4 * r) * ldw] = xp[c][r];
+        solve16_store(Lw, side ? 64 : lda, xp);
     }
     if (!has_next)
         return;
-    if (blockIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Qs[(16 * c + l4 + 4 * r) * 64 + 16 * wave + l15] = xp[c][r];
-    }
+    if (blockIdx.x == 0)
+        slab_publish(Qs, wave, l15, l4, xp);
     // my rows of slab s + 1 (columns r0 .. r0 + 63), still as the last trailing update left them
     const double *Cin = A + Rb + 16 * wave + l15 + (long)(r0 + l4) * lda;
     double4_t acc[4];
@@ -1092,7 +1003,7 @@ __global__ __launch_bounds__(64 * NW) void panel_step_kernel(double *__restrict_
 // workgroups displace the update's.  Here the factor of a matrix occupies one workgroup (eight
 // waves) from its first column to its last:
 //     per 64-column slab: the 64 x 64 factor (potf2f_body<8>, leaves its record behind);
-//     the rows below, 16 per wave-task, on the matrix cores (slab_solve16);
+//     the rows below, 16 per wave-task, on the matrix cores (solve16);
 //     the trailing tiles of the block, 32 x 32 per wave-task, k = 64 (all fragments requested
 //     up front), lower triangle only;
 // phases separated by workgroup barriers -- the block (1.6 MB at kb = 448) lives in L2, the same
@@ -1178,32 +1089,15 @@ __global__ __launch_bounds__(512) void potrf_wg_kernel(double *__restrict__ A, l
             break;
         const int r0 = 64 * (s + 1);
         {
-            double la[4][3][4], wneg[4][4];
-            const double *L11 = Ass + l15 + (long)l4 * lda;
-            const double *W = rs + 64 + l15 + 16 * l4;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    wneg[c][r] = -W[256 * c + 64 * r];
-#pragma unroll
-            for (int c = 1; c < 4; ++c)
-#pragma unroll
-                for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        la[c][bb][r] = L11[16 * c + (long)(16 * bb + 4 * r) * lda];
+            Solve16Regs<> f;
+            f.load_global(Ass, lda, rs, l15, l4);
             for (int task = wave; task < 4 * nr; task += 8) {
                 double *Xr = A + r0 + 16 * task + l15 + (long)(64 * s + l4) * lda;
                 double t[4][4];
                 double4_t x[4];
-                slab_load16(Xr, lda, t);
-                slab_solve16(t, la, wneg, x);
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        Xr[(long)(16 * c + 4 * r) * lda] = x[c][r];
+                solve16_load(Xr, lda, t);
+                solve16(t, f, x);
+                solve16_store(Xr, lda, x);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

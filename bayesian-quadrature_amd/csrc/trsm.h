@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "potf2.h"
+#include "solve16.h"
 
 // ---------------------------------------------------------------------------
 // Panel solve on the matrix cores: X (m x 64) <- X L11^-T in four 16-column block steps,
@@ -12,6 +13,7 @@
 // v_mfma_f64_16x16x4_f64, register r of the D tile IS the B fragment of k-step r, so
 // X_b^T (a D tile) feeds T_c^T -= L_cb X_b^T and X_c^T = W_cc T_c^T directly; L_cb and W_cc
 // are A fragments read from global memory (lane l: row l & 15, k = (l >> 4) + 4 r).
+// solve16.h has the solve itself; here a wave stores every x_c as it comes.
 // 40 MFMAs per wave.  m is a multiple of 16.  The inverse of a 16 x 16 diagonal block of
 // a Cholesky factor is as well conditioned as the block (MAGMA's trtri-based trsm does
 // the same with 128-wide blocks); the parity bars of tests/test_gpu_parity.py hold.
@@ -31,46 +33,20 @@ __global__ __launch_bounds__(256) void trsm_blk_kernel(double *__restrict__ X, l
         return;
     const int l15 = lane & 15, l4 = lane >> 4;
     double *Xr = X + (long)b * xstride + row0 + l15 + (long)l4 * ldx;
-    const double *L11 = Lm + (long)b * lstride + l15 + (long)l4 * ldl;
-    const double *W = dinv + (long)b * dstride + 64 + l15 + 16 * l4;
     // t[c][r] = X[row0 + l15][16 c + l4 + 4 r]: B fragments of the transposed row block
-    double t[4][4], w[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            t[c][r] = Xr[(long)(16 * c + 4 * r) * ldx];
-            w[c][r] = W[256 * c + 64 * r]; // W_c[l15][l4 + 4 r]
-        }
-    // la[c][b][r] = L11[16 c + l15][16 b + l4 + 4 r], c > b
-    double la[4][3][4];
-#pragma unroll
-    for (int c = 1; c < 4; ++c)
-#pragma unroll
-        for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                la[c][bb][r] = L11[16 * c + (long)(16 * bb + 4 * r) * ldl];
+    double t[4][4];
+    solve16_load(Xr, ldx, t);
+    Solve16Regs<true> f; // W negated at its use, as this kernel always did
+    f.load_global(Lm + (long)b * lstride, ldl, dinv + (long)b * dstride, l15, l4);
     double4_t x[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        // acc = sum_b L_cb X_b^T - T_c^T
-        double4_t acc = {-t[c][0], -t[c][1], -t[c][2], -t[c][3]};
-#pragma unroll
-        for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(la[c][bb][r], x[bb][r], acc, 0, 0, 0);
-        // X_c^T = -W_cc acc
-        double4_t xc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            xc = __builtin_amdgcn_mfma_f64_16x16x4f64(-w[c][r], acc[r], xc, 0, 0, 0);
-        x[c] = xc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            Xr[(long)(16 * c + 4 * r) * ldx] = xc[r];
-    }
+    solve16_block<0>(t[0], f, x);
+    solve16_store_block<0>(Xr, ldx, x);
+    solve16_block<1>(t[1], f, x);
+    solve16_store_block<1>(Xr, ldx, x);
+    solve16_block<2>(t[2], f, x);
+    solve16_store_block<2>(Xr, ldx, x);
+    solve16_block<3>(t[3], f, x);
+    solve16_store_block<3>(Xr, ldx, x);
 }
 
 // For a RESIDENT factor: the scratch record trsm_blk_kernel wants -- 64 reciprocal pivots and

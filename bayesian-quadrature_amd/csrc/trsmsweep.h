@@ -106,7 +106,6 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
         __builtin_amdgcn_sched_barrier(0);                                                         \
     }
 
-    const int blk = (lane >> 2) & 3;
     double *Ts = reinterpret_cast<double *>(smem); // the updated tile, column-major 64 x 64
     const int nslab = kb >> 6;
     for (int sl = 0; sl < nslab; ++sl) {
@@ -129,39 +128,12 @@ __global__ __launch_bounds__(256, 4) void trsm_sweep_kernel(double *__restrict__
             ct.load_neg(acc);
         }
         // the tile -> LDS -> rows 16 wave .. + 15 in trsm_blk_kernel's operand form
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    Ts[wr + 16 * tm + l15 + 64 * (wc + 16 * tn + l4 + 4 * ((blk - s) & 3))] =
-                        -acc[tm][tn][s];
+        Tile444<2, 2>::store_neg_lds(acc, Ts, wr, wc);
         __syncthreads();
-        const double *Lss = L11 + 64 * sl + (long)(64 * sl) * ldl + l15 + (long)l4 * ldl;
-        const double *W = rec + (long)sl * BQ_DINV_HALF + 64 + l15 + 16 * l4;
-        const double *Tw = Ts + 16 * wave + l15 + 64 * l4;
-        double *Xr = X + R0 + 16 * wave + l15 + (long)(64 * sl + l4) * ldx;
-        double4_t x[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double4_t a4 = {-Tw[64 * (16 * c)], -Tw[64 * (16 * c + 4)], -Tw[64 * (16 * c + 8)],
-                            -Tw[64 * (16 * c + 12)]};
-            double4_t xc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int bb = 0; bb < c; ++bb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    a4 = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        Lss[16 * c + (long)(16 * bb + 4 * r) * ldl], x[bb][r], a4, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                xc = __builtin_amdgcn_mfma_f64_16x16x4f64(-W[256 * c + 64 * r], a4[r], xc, 0, 0, 0);
-            x[c] = xc;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Xr[(long)(16 * c + 4 * r) * ldx] = xc[r];
-        }
+        const Solve16Stream f(L11 + 64 * sl + (long)(64 * sl) * ldl, ldl,
+                              rec + (long)sl * BQ_DINV_HALF);
+        solve16_tile(Ts + 16 * wave + l15 + 64 * l4, f,
+                     X + R0 + 16 * wave + l15 + (long)(64 * sl + l4) * ldx, ldx);
         // The solved slab is the next slabs' P operand.  Slab sl + 1 stages columns 16 ch .. of my
         // rows in chunk ch: columns of slab 0 from its first fill on, columns of THIS slab not
         // before chunk 4 sl >= 4 -- and every chunk's barrier drains vmcnt first.  So only slab

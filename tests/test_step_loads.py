@@ -76,7 +76,7 @@ def test_sweep_same_bits_and_within_the_contract_bound(engines, ntot, batch, pad
                              "ntot %d batch %d ld %d b %d" % (ntot, batch, ld, b))
 
 
-# the ten lower 16 x 16 blocks of a diagonal tile as DIAG_RB / DIAG_CB deal them to the waves
+# the ten lower 16 x 16 blocks of a diagonal tile as slab_diag_rb / slab_diag_cb deal them to the waves
 BLOCKS = [(rb, cb) for rb in range(4) for cb in range(rb + 1)]
 _BASE = {}
 
@@ -91,7 +91,7 @@ def _base192(engines):
 
 
 # t0 = 64: the tile that workgroup 0 updates and hands to the factor through LDS (the packed
-# blocks); t0 = 128: the diagonal tile that goes back to memory (the stores under DIAG_NB)
+# blocks); t0 = 128: the diagonal tile that goes back to memory (the stores under slab_diag_nb)
 @gpu
 @pytest.mark.parametrize("t0", [64, 128])
 @pytest.mark.parametrize("rb,cb", BLOCKS)
