@@ -136,6 +136,21 @@ class BQ(object):
         l_var[l_var < 0] = 0
         return l_var
 
+    def l_mean_grad(self, x):
+        """d ``l_mean`` / dx at every entry of x, in closed form (gp.GP.dmean_dx)."""
+        self._require_exact()
+        return self.gp_l.dmean_dx(x)
+
+    def l_var_grad(self, x):
+        """d ``l_var`` / dx at every entry of x: the product rule over l_var = v m^2 with v, dv
+        from the log-GP and m, dm from the second GP; exactly 0 where ``l_var`` clamps to 0."""
+        self._require_exact()
+        _, v, _, dv = self.gp_log_l.mean_var_grad(x)
+        m, dm = self.gp_l._mean_grad(x)
+        g = dv * m ** 2 + 2.0 * v * m * dm
+        g[v * m ** 2 < 0] = 0
+        return g
+
     # ---------------------------------------------------------------- moments
     def Z_mean(self):
         self._require_exact()

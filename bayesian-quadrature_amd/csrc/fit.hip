@@ -847,26 +847,25 @@ extern "C" int bq_gp_get(bq_ctx *c, bq_fit *f, int which, double *out)
     }
 }
 
-extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, double *mean,
-                             double *var, double *cov)
+namespace bqh {
+
+static hipError_t grow_to(DevBuf &b, size_t bytes)
 {
-    BQCHK(check_fit(c, f));
-    if (M < 0 || (M && !xo))
-        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
-    if (M == 0)
-        return BQ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int d = f->d, n = f->n, npad = f->npad;
-    const int Mp = (int)roundup(M, 64);
+    return b.bytes >= bytes ? hipSuccess : b.alloc(bytes);
+}
+
+// The staging of a posterior call (bq_gp_predict, bq_gp_predict_grad): the point and result
+// buffers and the pinned staging for M points and nres doubles of results, the points copied into
+// the staging's front; *hmap: the staging as the device sees it, or null (no kernel copies).
+static int predict_stage(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, size_t nres,
+                         double **hmap)
+{
+    const int d = f->d;
     // workspaces live in the fit and only grow: a BQ object predicts thousands of times
-    auto grow = [&](DevBuf &b, size_t bytes) -> hipError_t {
-        return b.bytes >= bytes ? hipSuccess : b.alloc(bytes);
-    };
-    DevBuf &xod = f->wx, &out = f->wout;
-    HIPCHK(c, grow(xod, sizeof(double) * d * M));
-    HIPCHK(c, grow(out, sizeof(double) * 2 * (size_t)Mp));
+    HIPCHK(c, grow_to(f->wx, sizeof(double) * d * M));
+    HIPCHK(c, grow_to(f->wout, sizeof(double) * nres));
     // points up and results down through pinned staging (asynchronous for real)
-    const size_t need = (size_t)d * M + 2 * (size_t)Mp;
+    const size_t need = (size_t)d * M + nres;
     if (f->hio_len < need) {
         if (f->hio)
             (void)hipHostFree(f->hio);
@@ -878,9 +877,68 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
     std::memcpy(f->hio, xo, sizeof(double) * d * M);
     // (points in and results out through kernels on the mapped staging buffer: a copy-engine
     // operation costs the stream 8-9 us, a further kernel 2.9 -- tools/stream_ops_bench.hip)
-    double *hmap = nullptr;
+    *hmap = nullptr;
     if (c->cfg.solve_kcopy)
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hio, 0));
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(hmap), f->hio, 0));
+    return BQ_OK;
+}
+
+// whether the cross Gram may read the points out of the mapped staging buffer (bq_gp_predict says
+// why there is a limit)
+static bool predict_direct_ok(int d, int64_t M, int npad)
+{
+    return (size_t)d * M * sizeof(double) * (size_t)(npad / 64) <= ((size_t)4 << 20);
+}
+
+// The sweep of a posterior with its variance: V = K(xo, x) L^-T into f->wV2 (Mp x npad, ld Mp,
+// Mp = M rounded up to 64) by a forward sweep with rows = prediction points, f->wV left holding
+// the sweep's partial sums; mean (Mp) | var (Mp) at omean.  xq: the points, d x M -- with `direct`
+// the mapped staging buffer, which the cross Gram then reads itself and pads by itself.
+static int predict_sweep(bq_ctx *c, bq_fit *f, const double *xq, bool direct, int64_t M,
+                         double *omean)
+{
+    const int d = f->d, n = f->n, npad = f->npad;
+    const int Mp = (int)roundup(M, 64);
+    const GaussParams g = f->g;
+    WideInv wi;
+    BQCHK(fit_wide(c, f, wi));
+    DevBuf &V0 = f->wV, &V = f->wV2;
+    HIPCHK(c, grow_to(V0, sizeof(double) * (size_t)Mp * npad));
+    HIPCHK(c, grow_to(V, sizeof(double) * (size_t)Mp * npad));
+    if (direct) {
+        BQCHK(launch_gram_cross_pad(c, d, xq, (int)M, Mp, f->pts.d(), n, npad, g, V0.d(), Mp));
+    } else {
+        HIPCHK(c, hipMemsetAsync(V0.p, 0, sizeof(double) * (size_t)Mp * npad, c->stream));
+        BQCHK(launch_gram_cross(c, d, xq, (int)M, f->pts.d(), n, g, V0.d(), Mp));
+    }
+    BQCHK(enqueue_forward_rows(c, V0.d(), V.d(), Mp, Mp, f->A.d(), f->ldl, npad, wi));
+    // z lives in row yrow of the factor with stride ldl: gathered once per (re)fit
+    if (!(f->have & bq_fit::ZC)) {
+        HIPCHK(c, grow_to(f->wz, sizeof(double) * (size_t)npad));
+        BQCHK(launch_gather_row(c, f->wz.d(), f->A.d() + f->L.yrow, f->ldl, npad));
+        f->have |= bq_fit::ZC;
+    }
+    BQCHK(launch_rowdot(c, V.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(), g.c, omean, omean + Mp,
+                        1));
+    return BQ_OK;
+}
+
+} // namespace bqh
+
+extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, double *mean,
+                             double *var, double *cov)
+{
+    BQCHK(check_fit(c, f));
+    if (M < 0 || (M && !xo))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (M == 0)
+        return BQ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, n = f->n, npad = f->npad;
+    const int Mp = (int)roundup(M, 64);
+    DevBuf &xod = f->wx, &out = f->wout;
+    double *hmap = nullptr;
+    BQCHK(predict_stage(c, f, xo, M, 2 * (size_t)Mp, &hmap));
     // mean + variance without the covariance (BQ.l_var, _set_gp_log_l_params: bq.py:227-228,
     // 942-943) is six launches: the cross Gram reads the points out of the mapped staging buffer
     // and writes its own zero padding, the row reductions write the results into it (round 5:
@@ -888,8 +946,7 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
     // (every workgroup column of the cross Gram re-reads the points over PCIe: npad / 64 uncached
     // passes over d M doubles.  Measured a win at N = 1024, M = 256 / 1000; above a few MB of such
     // reads the points go down once through flow_in instead -- ADVICE r05)
-    const bool direct = hmap && var && !cov &&
-                        (size_t)d * M * sizeof(double) * (size_t)(npad / 64) <= ((size_t)4 << 20);
+    const bool direct = hmap && var && !cov && predict_direct_ok(d, M, npad);
     if (direct)
         ;
     else if (hmap)
@@ -903,28 +960,9 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
         BQCHK(fit_alpha(c, f));
         BQCHK(launch_predict_mean(c, d, xod.d(), (int)M, f->pts.d(), n, f->alpha.d(), g, out.d()));
     } else {
-        // V = K(xo, x) L^-T by a forward sweep with rows = prediction points
-        WideInv wi;
-        BQCHK(fit_wide(c, f, wi));
-        DevBuf &V0 = f->wV, &V = f->wV2;
-        HIPCHK(c, grow(V0, sizeof(double) * (size_t)Mp * npad));
-        HIPCHK(c, grow(V, sizeof(double) * (size_t)Mp * npad));
-        if (direct) {
-            BQCHK(launch_gram_cross_pad(c, d, hmap, (int)M, Mp, f->pts.d(), n, npad, g, V0.d(), Mp));
-        } else {
-            HIPCHK(c, hipMemsetAsync(V0.p, 0, sizeof(double) * (size_t)Mp * npad, c->stream));
-            BQCHK(launch_gram_cross(c, d, xod.d(), (int)M, f->pts.d(), n, g, V0.d(), Mp));
-        }
-        BQCHK(enqueue_forward_rows(c, V0.d(), V.d(), Mp, Mp, f->A.d(), f->ldl, npad, wi));
-        // z lives in row yrow of the factor with stride ldl: gathered once per (re)fit
-        if (!(f->have & bq_fit::ZC)) {
-            HIPCHK(c, grow(f->wz, sizeof(double) * (size_t)npad));
-            BQCHK(launch_gather_row(c, f->wz.d(), f->A.d() + f->L.yrow, f->ldl, npad));
-            f->have |= bq_fit::ZC;
-        }
+        DevBuf &V = f->wV2;
         double *omean = direct ? hmap + (size_t)d * M : out.d();
-        BQCHK(launch_rowdot(c, V.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(), g.c, omean, omean + Mp,
-                            1));
+        BQCHK(predict_sweep(c, f, direct ? hmap : xod.d(), direct, M, omean));
         if (cov) {
             // cov = K(xo,xo) - V V^T  (Mp x Mp on device, M x M out)
             DevBuf Cd, gd;
@@ -960,5 +998,83 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
         std::memcpy(mean, hres, sizeof(double) * M);
     if (var)
         std::memcpy(var, hres + Mp, sizeof(double) * M);
+    return BQ_OK;
+}
+
+// The posterior and its gradients with respect to the query points (pgrad.h has the formulas).
+// Mean route (no var, no dvar): alpha, then one fused launch, no sweep and no M x n matrix.  Full
+// route: bq_gp_predict's own staging, cross Gram, forward sweep and row reductions (predict_sweep:
+// mean and var are bq_gp_predict's bits), then -- for dvar -- the backward row sweep
+// beta = V L^-1 out of V into the buffer the cross Gram came in (the forward sweep left partial
+// sums there; V is consumed, so the row reductions ran first), and one launch over beta, alpha
+// and the points.  Results: [mean (Mp) | var (Mp) | dmean (d Mp) | dvar (d Mp)].
+extern "C" int bq_gp_predict_grad(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, double *mean,
+                                  double *var, double *dmean, double *dvar)
+{
+    BQCHK(check_fit(c, f));
+    if (M < 0 || (M && !xo) || (!mean && !var && !dmean && !dvar))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (M == 0)
+        return BQ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, n = f->n, npad = f->npad;
+    const int Mp = (int)roundup(M, 64);
+    const size_t nres = 2 * (size_t)Mp + 2 * (size_t)d * Mp;
+    DevBuf &xod = f->wx, &out = f->wout;
+    double *hmap = nullptr;
+    BQCHK(predict_stage(c, f, xo, M, nres, &hmap));
+    const bool full = var || dvar;
+    // (alpha first: the call that builds it synchronises, which would split the chain below)
+    if (!full || dmean)
+        BQCHK(fit_alpha(c, f));
+    // the full route stages its points as bq_gp_predict does for mean + variance
+    const bool direct = full && hmap && predict_direct_ok(d, M, npad);
+    if (direct)
+        ;
+    else if (hmap)
+        BQCHK(launch_flow_in(c, hmap, d * (int)M, xod.d(), d * (int)M, nullptr, 0));
+    else
+        HIPCHK(c, hipMemcpyAsync(xod.p, f->hio, sizeof(double) * d * M, hipMemcpyHostToDevice,
+                                 c->stream));
+    const double *xq = direct ? hmap : xod.d();
+    double *res = direct ? hmap + (size_t)d * M : out.d();
+    double *odm = res + 2 * (size_t)Mp, *odv = odm + (size_t)d * Mp;
+    size_t nout = 2 * (size_t)Mp; // how much of the results goes back
+    if (!full) {
+        BQCHK(launch_predict_mean_grad(c, d, xq, (int)M, f->pts.d(), n, f->alpha.d(), f->g, res,
+                                       odm));
+        nout += (size_t)d * Mp;
+    } else {
+        BQCHK(predict_sweep(c, f, xq, direct, M, res));
+        if (dvar) {
+            WideInv wi;
+            BQCHK(fit_wide(c, f, wi));
+            BQCHK(enqueue_backward_rows(c, f->wV2.d(), f->wV.d(), Mp, Mp, f->A.d(), f->ldl, npad,
+                                        wi));
+        }
+        if (dmean || dvar) {
+            BQCHK(launch_predict_grad(c, d, dvar ? f->wV.d() : nullptr, (long)Mp, (int)M, Mp, xq,
+                                      f->pts.d(), n, dmean ? f->alpha.d() : nullptr, f->g,
+                                      dmean ? odm : nullptr, dvar ? odv : nullptr));
+            nout = nres;
+        }
+    }
+    double *hres = f->hio + (size_t)d * M;
+    if (direct)
+        ;
+    else if (hmap)
+        BQCHK(launch_flow_out(c, out.d(), (int)nout, hmap + (size_t)d * M));
+    else
+        HIPCHK(c, hipMemcpyAsync(hres, out.p, sizeof(double) * nout, hipMemcpyDeviceToHost,
+                                 c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mean)
+        std::memcpy(mean, hres, sizeof(double) * M);
+    if (var)
+        std::memcpy(var, hres + Mp, sizeof(double) * M);
+    if (dmean)
+        std::memcpy(dmean, hres + 2 * (size_t)Mp, sizeof(double) * d * M);
+    if (dvar)
+        std::memcpy(dvar, hres + 2 * (size_t)Mp + (size_t)d * Mp, sizeof(double) * d * M);
     return BQ_OK;
 }

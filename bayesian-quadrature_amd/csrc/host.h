@@ -16,6 +16,7 @@
 //                                               its fragment loaders and LDS staging)
 //   k_reduce.hip reduce.h trsv.h append.h        read-outs, single-vector sweeps, utilities, the
 //                remove.h kernels               finishing kernels of an append, shrinking a fit
+//                pgrad.h kernels                the posterior's gradients at the query points
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -417,6 +418,12 @@ int launch_rowdot(bq_ctx *c, const double *V, long ldv, int M, int Mp, int npad,
                   double k0, double *mean, double *var, long zstride = 1);
 int launch_predict_mean(bq_ctx *c, int d, const double *xo, int M, const double *pts, int n,
                         const double *alpha, const GaussParams &g, double *mean);
+int launch_predict_grad(bq_ctx *c, int d, const double *beta, long ldb, int M, int Mp,
+                        const double *xo, const double *pts, int n, const double *alpha,
+                        const GaussParams &g, double *dmean, double *dvar);
+int launch_predict_mean_grad(bq_ctx *c, int d, const double *xo, int M, const double *pts, int n,
+                             const double *alpha, const GaussParams &g, double *mean,
+                             double *dmean);
 int launch_neg_identity(bq_ctx *c, double *nr, int B, int npad);
 int launch_pad_identity(bq_ctx *c, double *A, long lda, int n, int ntot);
 int launch_logdet(bq_ctx *c, const double *diag, long stride, int n, double *out);
@@ -693,7 +700,7 @@ struct bq_fit : FitCore {
     //   bit       what is there                                     from        set by
     //   DW        dw: 16 x 16 inverses of the factor's diagonal     the factor  fit_dw
     //   WIDE      wide: -W^T of the B-wide diagonal blocks          DW          fit_wide
-    //   ZC        wz: z = L^-1 y contiguous (the factor's y row     z           bq_gp_predict
+    //   ZC        wz: z = L^-1 y contiguous (the factor's y row     z           predict_sweep
     //             has stride ldl: the row reductions then read
     //             one line per 8 entries, not one per entry)
     //   ALPHA     alpha = L^-T z                                    WIDE, z     fit_alpha
@@ -746,7 +753,8 @@ struct bq_fit : FitCore {
     double *hvec = nullptr; // pinned staging of one vector in / out (npad doubles): a copy from
                             // pageable memory is staged and synchronised by the runtime, which
                             // was half of a single-vector solve's wall time at N = 4096
-    double *hio = nullptr;  // pinned staging of a prediction's points in and mean / variance out
+    double *hio = nullptr;  // pinned staging of a prediction's points in and mean / variance
+                            // (bq_gp_predict_grad: and the gradients) out
     size_t hio_len = 0;
     double *hfit = nullptr; // pinned staging of a (re)fit: [results 8 + 128 | GaussParams | 63 d
                             // border points] -- the hyper-parameter loop's body is three small copies

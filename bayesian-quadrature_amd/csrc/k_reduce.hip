@@ -1,7 +1,9 @@
 // k_reduce.hip -- read-outs, single-vector sweeps and small utilities (reduce.h, trsv.h), the
-// kernels that grow and shrink a resident fit (append.h, remove.h) and their launchers.
+// posterior's gradients at the query points (pgrad.h), the kernels that grow and shrink a
+// resident fit (append.h, remove.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
+#include "pgrad.h"
 #include "trsv.h"
 #include "trsvflow.h"
 #include "append.h"
@@ -60,6 +62,57 @@ int launch_predict_mean(bq_ctx *c, int d, const double *xo, int M, const double 
     default: PM(8); break;
     }
 #undef PM
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// dmean, dvar (d x M each, entry [k + j d]) from beta (Mp x npad, ld ldb; nullptr: no dvar) and
+// alpha (nullptr: no dmean) over the Mp (multiple of 16) rows of beta
+int launch_predict_grad(bq_ctx *c, int d, const double *beta, long ldb, int M, int Mp,
+                        const double *xo, const double *pts, int n, const double *alpha,
+                        const GaussParams &g, double *dmean, double *dvar)
+{
+    Bracket br(c, BQ_K_REDUCE);
+    dim3 grid((unsigned)(Mp / 16));
+#define PG(D_)                                                                                     \
+    hipLaunchKernelGGL(predict_grad_kernel<D_>, grid, dim3(1024), 0, c->stream, beta, ldb, M, xo,  \
+                       pts, n, alpha, g, dmean, dvar)
+    switch (d) {
+    case 1: PG(1); break;
+    case 2: PG(2); break;
+    case 3: PG(3); break;
+    case 4: PG(4); break;
+    case 5: PG(5); break;
+    case 6: PG(6); break;
+    case 7: PG(7); break;
+    default: PG(8); break;
+    }
+#undef PG
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// the fused mean route: mean (M; may be nullptr) and dmean (d x M) in one launch
+int launch_predict_mean_grad(bq_ctx *c, int d, const double *xo, int M, const double *pts, int n,
+                             const double *alpha, const GaussParams &g, double *mean,
+                             double *dmean)
+{
+    Bracket br(c, BQ_K_REDUCE);
+    dim3 grid((unsigned)((M + 3) / 4));
+#define PMG(D_)                                                                                    \
+    hipLaunchKernelGGL(predict_mean_grad_kernel<D_>, grid, dim3(256), 0, c->stream, xo, M, pts, n, \
+                       alpha, g, mean, dmean)
+    switch (d) {
+    case 1: PMG(1); break;
+    case 2: PMG(2); break;
+    case 3: PMG(3); break;
+    case 4: PMG(4); break;
+    case 5: PMG(5); break;
+    case 6: PMG(6); break;
+    case 7: PMG(7); break;
+    default: PMG(8); break;
+    }
+#undef PMG
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

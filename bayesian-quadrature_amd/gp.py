@@ -455,6 +455,40 @@ class GP(object):
         m, v, _ = self._device_fit().predict(xo, want_mean=True, want_var=True)
         return m, v
 
+    @staticmethod
+    def _grad_shape(xo, g):
+        """A gradient as the device returns it, (d, M), in the shape of the points it was asked at:
+        (M,) for a vector of points."""
+        return g[0] if xo.ndim == 1 else g
+
+    def dmean_dx(self, xo):
+        """Gradient of ``mean`` with respect to the points: entry [j] (or [k, j] for d x M points)
+        is d mean(xo_j) / d xo_j, in closed form on the device fit (bq_gp_predict_grad, the route
+        without a sweep)."""
+        return self._mean_grad(xo)[1]
+
+    def _mean_grad(self, xo):
+        """(mean, dmean_dx) from the one fused launch."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            return np.empty(0, dtype=DTYPE), np.empty(xo.shape, dtype=DTYPE)
+        m, _, dm, _ = self._device_fit().predict_grad(xo, want_var=False)
+        return m, self._grad_shape(xo, dm)
+
+    def dvar_dx(self, xo):
+        """Gradient of ``var`` with respect to the points, shaped like ``dmean_dx``'s."""
+        return self.mean_var_grad(xo)[3]
+
+    def mean_var_grad(self, xo):
+        """(mean, var, dmean_dx, dvar_dx) at the points in one device call: the prediction's
+        sweep, one backward sweep and one reduction more (bq_gp_predict_grad)."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            e = np.empty(0, dtype=DTYPE)
+            return e, e.copy(), np.empty(xo.shape, dtype=DTYPE), np.empty(xo.shape, dtype=DTYPE)
+        m, v, dm, dv = self._device_fit().predict_grad(xo, want_var=True)
+        return m, v, self._grad_shape(xo, dm), self._grad_shape(xo, dv)
+
     def cov(self, xo):
         xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
         if xo.size == 0:

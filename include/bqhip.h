@@ -230,6 +230,19 @@ int bq_gp_get(bq_ctx *ctx, bq_fit *fit, int which, double *out_host);
  * covariance, may be NULL). */
 int bq_gp_predict(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double *mean,
                   double *var, double *cov);
+/* The posterior at M points and its gradients with respect to the points themselves, in closed
+ * form on the resident factor (nothing differenced, nothing refitted):
+ *   d mean_j / d xo_jk =      sum_i k(xo_j, x_i) (x_ik - xo_jk) / w_k^2 alpha_i,  alpha  = Kxx^-1 y
+ *   d var_j  / d xo_jk = -2   sum_i k(xo_j, x_i) (x_ik - xo_jk) / w_k^2 beta_ji,  beta_j = Kxx^-1 k_j
+ * xo: d x M column-major like bq_gp_predict.  mean, var: M.  dmean, dvar: d x M, entry [k + j*d] =
+ * d/d xo_jk.  Any output may be NULL, not all four.  Without var and dvar: one fused launch, no
+ * sweep.  Otherwise the sweep of bq_gp_predict -- mean and var are its bits -- and, for dvar, one
+ * backward row sweep more; O(M n^2) like the prediction itself.  Same status rules as
+ * bq_gp_predict, and BQ_ERR_BAD_ARG when all four outputs are NULL; M == 0 touches nothing.  The
+ * same bits on every call; the fit is not disturbed.  Workspaces are bq_gp_predict's, kept with
+ * the fit. */
+int bq_gp_predict_grad(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double *mean,
+                       double *var, double *dmean, double *dvar);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
