@@ -665,6 +665,30 @@ static HessJob fit_hess_job(const bq_fit *f)
     return hj;
 }
 
+namespace bqh {
+// u = Kxx^-1 alpha and z_k = Kxx^-1 (D_k alpha), k < d, as rows 0 .. d of the 64 x npad matrix in
+// dkz (ld 64; its other rows and its columns at or beyond n are zero), built on their first use
+// after a (re)fit or new targets: the right-hand sides [alpha, D_1 alpha ..] by ptheta_dka_kernel,
+// then the forward and the backward row sweep with 64 rows, as bq_gp_predict runs them for one
+// point -- first half -> second half -> first half.
+int fit_dkz(bq_ctx *c, bq_fit *f)
+{
+    if (f->have & bq_fit::DKZ)
+        return BQ_OK;
+    BQCHK(fit_alpha(c, f));
+    WideInv w;
+    BQCHK(fit_wide(c, f, w));
+    const size_t half = (size_t)BQ_PTHETA_ROWS * f->npad;
+    BQCHK(fit_grow(c, f->dkz, sizeof(double) * 2 * half, "hyper-parameter derivative workspace"));
+    double *R = f->dkz.d(), *X = R + half;
+    BQCHK(launch_ptheta_dka(c, f->d, fit_hess_job(f), R));
+    BQCHK(enqueue_forward_rows(c, R, X, BQ_PTHETA_ROWS, BQ_PTHETA_ROWS, f->A.d(), f->ldl, f->npad, w));
+    BQCHK(enqueue_backward_rows(c, X, R, BQ_PTHETA_ROWS, BQ_PTHETA_ROWS, f->A.d(), f->ldl, f->npad, w));
+    f->have |= bq_fit::DKZ;
+    return BQ_OK;
+}
+} // namespace bqh
+
 // d^2 log p / d theta^2 in the gradient's parameter order (hess.h has the formula): Kxx^-1 = Y Y^T
 // into the sweep's idle workspace, one MFMA product Kxx^-1 dK/dw_k per length scale with the
 // derivative generated from the points, tile sums and the quadratic terms on the device; the
@@ -1076,5 +1100,91 @@ extern "C" int bq_gp_predict_grad(bq_ctx *c, bq_fit *f, const double *xo, int64_
         std::memcpy(dmean, hres + 2 * (size_t)Mp, sizeof(double) * d * M);
     if (dvar)
         std::memcpy(dvar, hres + 2 * (size_t)Mp + (size_t)d * Mp, sizeof(double) * d * M);
+    return BQ_OK;
+}
+
+// The posterior and its derivatives in the hyper-parameters theta = [h, w_1 .. w_d, s] (ptheta.h
+// has the formulas).  Mean route (no var, no dvar): alpha and the fit's solved vectors (fit_dkz),
+// then one fused launch, no sweep and no M x n matrix.  Full route: both of those first (they
+// synchronise), bq_gp_predict's own staging, cross Gram, forward sweep and row reductions
+// (predict_sweep: mean and var are bq_gp_predict's bits), then -- for dvar -- the backward row
+// sweep beta = V L^-1 into the buffer the cross Gram came in and one MFMA launch per length scale
+// for q_jk = beta_j^T D_k beta_j, and one launch over beta, the solved vectors and the points.
+// Results: [mean (Mp) | var (Mp) | dmean ((d + 2) Mp) | dvar ((d + 2) Mp)].
+extern "C" int bq_gp_predict_dtheta(bq_ctx *c, bq_fit *f, const double *xo, int64_t M,
+                                    double *mean, double *var, double *dmean, double *dvar)
+{
+    BQCHK(check_fit(c, f));
+    if (M < 0 || (M && !xo) || (!mean && !var && !dmean && !dvar))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (M == 0)
+        return BQ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, np = d + 2, npad = f->npad;
+    const int Mp = (int)roundup(M, 64);
+    const size_t nres = 2 * (size_t)Mp + 2 * (size_t)np * Mp;
+    DevBuf &xod = f->wx, &out = f->wout;
+    double *hmap = nullptr;
+    BQCHK(predict_stage(c, f, xo, M, nres, &hmap));
+    const bool full = var || dvar;
+    // (the fit's own vectors first: building them synchronises, which would split the chain below)
+    if (!full || dmean) {
+        BQCHK(fit_alpha(c, f));
+        BQCHK(fit_dkz(c, f));
+    }
+    if (dvar)
+        BQCHK(fit_grow(c, f->wq, sizeof(double) * ptheta_part_doubles(d, Mp, npad),
+                       "hyper-parameter derivative partial sums"));
+    // the full route stages its points as bq_gp_predict does for mean + variance
+    const bool direct = full && hmap && predict_direct_ok(d, M, npad);
+    if (direct)
+        ;
+    else if (hmap)
+        BQCHK(launch_flow_in(c, hmap, d * (int)M, xod.d(), d * (int)M, nullptr, 0));
+    else
+        HIPCHK(c, hipMemcpyAsync(xod.p, f->hio, sizeof(double) * d * M, hipMemcpyHostToDevice,
+                                 c->stream));
+    const double *xq = direct ? hmap : xod.d();
+    double *res = direct ? hmap + (size_t)d * M : out.d();
+    double *odm = res + 2 * (size_t)Mp, *odv = odm + (size_t)np * Mp;
+    size_t nout = 2 * (size_t)Mp; // how much of the results goes back
+    const HessJob hj = fit_hess_job(f);
+    if (!full) {
+        BQCHK(launch_predict_mean_theta(c, d, xq, (int)M, hj, f->dkz.d(), f->h, f->s, res, odm));
+        nout += (size_t)np * Mp;
+    } else {
+        BQCHK(predict_sweep(c, f, xq, direct, M, res));
+        if (dvar) {
+            WideInv wi;
+            BQCHK(fit_wide(c, f, wi));
+            BQCHK(enqueue_backward_rows(c, f->wV2.d(), f->wV.d(), Mp, Mp, f->A.d(), f->ldl, npad,
+                                        wi));
+            BQCHK(launch_ptheta_quad(c, d, f->wV.d(), (long)Mp, Mp, hj, f->wq.d()));
+        }
+        if (dmean || dvar) {
+            BQCHK(launch_predict_theta(c, d, dvar ? f->wV.d() : nullptr, (long)Mp, (int)M, Mp, xq,
+                                       hj, dmean ? f->dkz.d() : nullptr, res + Mp,
+                                       dvar ? f->wq.d() : nullptr, f->h, f->s,
+                                       dmean ? odm : nullptr, dvar ? odv : nullptr));
+            nout = nres;
+        }
+    }
+    double *hres = f->hio + (size_t)d * M;
+    if (direct)
+        ;
+    else if (hmap)
+        BQCHK(launch_flow_out(c, out.d(), (int)nout, hmap + (size_t)d * M));
+    else
+        HIPCHK(c, hipMemcpyAsync(hres, out.p, sizeof(double) * nout, hipMemcpyDeviceToHost,
+                                 c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mean)
+        std::memcpy(mean, hres, sizeof(double) * M);
+    if (var)
+        std::memcpy(var, hres + Mp, sizeof(double) * M);
+    if (dmean)
+        std::memcpy(dmean, hres + 2 * (size_t)Mp, sizeof(double) * np * M);
+    if (dvar)
+        std::memcpy(dvar, hres + 2 * (size_t)Mp + (size_t)np * Mp, sizeof(double) * np * M);
     return BQ_OK;
 }

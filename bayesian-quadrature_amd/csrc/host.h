@@ -10,6 +10,8 @@
 // libbqhip_probe.so, whose extra entry points include/bqhip_probe.h declares):
 //   k_gram.hip   gram.h kernels                 launch_gram_sym / _cross
 //   k_gemm.hip   gemm.h trsmsweep.h kernels     launch_gemm, launch_gemm_rows, launch_rows_step
+//   k_hess.hip   hess.h loo.h kernels           the log-ML Hessian's sums, leave-one-out
+//                ptheta.h kernels               the posterior's derivatives in the hyper-parameters
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
 //                solve16.h                      (both units: the 16-row solve from block inverses,
@@ -354,6 +356,18 @@ int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const dou
                int npad, double *ws, const double **vecs, const double **total);
 int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const double *alpha,
                     int n, int npad, double h, double s, double s2, double *ws, const double **grad);
+// the posterior's derivatives in the hyper-parameters (ptheta.h): the right-hand sides of the fit's
+// solved vectors, q_jk = beta_j^T D_k beta_j in column-block pieces (ptheta_part_doubles of them),
+// the row sums with the finished derivatives, and the fused mean route
+int launch_ptheta_dka(bq_ctx *c, int d, const HessJob &hj, double *R);
+size_t ptheta_part_doubles(int d, int Mp, int npad);
+int launch_ptheta_quad(bq_ctx *c, int d, const double *beta, long ldb, int Mp, const HessJob &hj,
+                       double *part);
+int launch_predict_theta(bq_ctx *c, int d, const double *beta, long ldb, int M, int Mp,
+                         const double *xo, const HessJob &hj, const double *Z, const double *var,
+                         const double *qpart, double h, double s, double *dmean, double *dvar);
+int launch_predict_mean_theta(bq_ctx *c, int d, const double *xo, int M, const HessJob &hj,
+                              const double *Z, double h, double s, double *mean, double *dmean);
 
 // ---- k_gemm.hip (continued) -----------------------------------------------------------
 // One product C(m x n) -= P(m x k) Q(n x k)^T per batch element, as operands and a shape.
@@ -712,6 +726,9 @@ struct bq_fit : FitCore {
     //   HESS      hess                                              PROD        bq_gp_logml_hess
     //   LOO       loo: mu | var | lp; loo_total                     Y, ALPHA    fit_loo
     //   LOO_GRAD  loo_grad                                          PROD, LOO   bq_gp_loo_grad
+    //   DKZ       dkz: u = Kxx^-1 alpha and z_k = Kxx^-1 (D_k       ALPHA, WIDE fit_dkz
+    //             alpha) as the rows of a 64 x npad matrix (its
+    //             second half: the row sweeps' workspace)
     // (z is the targets through the factor.)  A bit is never set while a bit it is computed from is
     // clear: every producer runs the producers of what it reads first, and both events clear a bit
     // together with everything computed from it.
@@ -725,10 +742,11 @@ struct bq_fit : FitCore {
         HESS = 1u << 6,
         LOO = 1u << 7,
         LOO_GRAD = 1u << 8,
+        DKZ = 1u << 9,
         // the events: a (re)factorisation, an append, a removal ...
-        FACTOR_CHANGED = DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD,
+        FACTOR_CHANGED = DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ,
         // ... and bq_gp_set_y (the factor's own inverses stay)
-        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD,
+        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ,
     };
     unsigned have = 0;
     void drop(unsigned event) { have &= ~event; }
@@ -746,6 +764,10 @@ struct bq_fit : FitCore {
     // density per point and the partial sums (loo_ws_doubles), allocated on the first call
     DevBuf loo;
     double loo_total = 0, loo_grad[BQ_MAXD + 2] = {0};
+    // the posterior's derivatives in the hyper-parameters (bq_gp_predict_dtheta): [u, z_1 .. z_d]
+    // as rows, 64 x npad, and as much again for the two row sweeps that solve them (fit_dkz),
+    // allocated on the first call; the quad product's partial sums, grown on demand and kept
+    DevBuf dkz, wq;
     // the single-vector sweeps (trsv.h): x | y, 2 npad doubles, and their captured launch
     // chains -- [0] solve (forward + backward), [1] backward into alpha, [2] forward; the
     // pointers survive a refit, so the graphs do too
@@ -784,7 +806,7 @@ inline void fit_adopt(bq_fit *f, FitCore &core)
 {
     f->swap(core);
     for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart, &f->hB,
-                      &f->loo})
+                      &f->loo, &f->dkz, &f->wq})
         b->release();
     if (f->hvec)
         (void)hipHostFree(f->hvec);
@@ -801,6 +823,7 @@ int fit_dw(bq_ctx *c, bq_fit *f);
 int fit_wide(bq_ctx *c, bq_fit *f, WideInv &w);
 int fit_vec(bq_ctx *c, bq_fit *f);
 int fit_alpha(bq_ctx *c, bq_fit *f);
+int fit_dkz(bq_ctx *c, bq_fit *f);
 // Replays a chain of sweep launches over a fit's own buffers from the slot's captured hipGraph (a
 // sweep is 2 npad / B launches of 2-8 us each: enqueued one by one the host is the bottleneck).
 template <class F>

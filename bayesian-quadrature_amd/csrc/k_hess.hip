@@ -1,8 +1,10 @@
 // k_hess.hip -- the log-ML Hessian's kernels (hess.h), the leave-one-out kernels that read its
-// products (loo.h), and their launchers.
+// products (loo.h), the posterior's derivatives in the hyper-parameters, which generate the same
+// derivative operand (ptheta.h), and their launchers.
 #include "host.h"
 #include "hess.h"
 #include "loo.h"
+#include "ptheta.h"
 
 namespace bqh {
 
@@ -221,5 +223,114 @@ int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const
     default: return loo_grad_run<8>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
     }
 }
+
+// ---- the posterior's derivatives in the hyper-parameters (ptheta.h; fit.hip, bq_gp_predict_dtheta) ----
+#define BQ_PTHETA_DISPATCH(d_, CALL)                                                               \
+    switch (d_) {                                                                                  \
+    case 1: CALL(1); break;                                                                        \
+    case 2: CALL(2); break;                                                                        \
+    case 3: CALL(3); break;                                                                        \
+    case 4: CALL(4); break;                                                                        \
+    case 5: CALL(5); break;                                                                        \
+    case 6: CALL(6); break;                                                                        \
+    case 7: CALL(7); break;                                                                        \
+    default: CALL(8); break;                                                                       \
+    }
+
+static ThetaScale theta_scale(double h, double s)
+{
+    return ThetaScale{2.0 * (s * s) / h, -2.0 * s, 2.0 / h, 2.0 * s};
+}
+
+// R (64 x npad, ld 64) = [a, D_1 a .. D_d a] as rows, zero elsewhere
+int launch_ptheta_dka(bq_ctx *c, int d, const HessJob &hj, double *R)
+{
+    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
+        return fail(c, BQ_ERR_BAD_ARG, "ptheta_dka: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    Bracket br(c, BQ_K_REDUCE);
+#define PD(D_)                                                                                     \
+    hipLaunchKernelGGL(ptheta_dka_kernel<D_>, dim3((unsigned)hj.npad / 16), dim3(256), 0,          \
+                       c->stream, hj, R)
+    BQ_PTHETA_DISPATCH(d, PD)
+#undef PD
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// Row tile of the quad product, the one rule: the tall 256 x 64 tile (a quarter of the generated
+// operand's exponentials per entry of beta) once its workgroups number at least one per CU and
+// the rows it pads Mp with are at most a quarter of Mp (they are multiplied like any others: at
+// Mp = 64 the tall tile does four times the flops), else 64 x 64 (four times the workgroups).
+// BQ_GEMM_TILE=64|128 forces the small / the tall tile, as it forces the tiles of the gradient's
+// and the Hessian's products (measurements, tests).
+static bool ptheta_tall(const bq_ctx *c, int Mp, int npad)
+{
+    if (c->cfg.gemm_tile == 64 || c->cfg.gemm_tile == 128)
+        return c->cfg.gemm_tile == 128;
+    const long tiles = (Mp + 255) / 256;
+    return tiles * (npad / 64) >= c->cus && 4 * (tiles * 256 - Mp) <= Mp;
+}
+
+size_t ptheta_part_doubles(int d, int Mp, int npad) { return (size_t)d * (npad / 64) * Mp; }
+
+// part[k][npad / 64][Mp], k < d: the column blocks' pieces of q_jk = beta_j^T D_k beta_j, one launch
+// per length scale
+int launch_ptheta_quad(bq_ctx *c, int d, const double *beta, long ldb, int Mp, const HessJob &hj,
+                       double *part)
+{
+    if (d < 1 || d > BQ_MAXD || (hj.npad % 64) || (Mp % 64) || Mp < 64)
+        return fail(c, BQ_ERR_BAD_ARG, "ptheta_quad: d in [1, %d], whole 64-blocks", BQ_MAXD);
+    const bool tall = ptheta_tall(c, Mp, hj.npad);
+    const unsigned gy = (unsigned)hj.npad / 64;
+    for (int k = 0; k < d; ++k) {
+        Bracket br(c, BQ_K_GEMM, 2.0 * Mp * (double)hj.n * hj.npad);
+#define PQ(D_)                                                                                     \
+    if (tall)                                                                                      \
+        hipLaunchKernelGGL((ptheta_quad_kernel<D_, 4, 1, 4, 4>), dim3((unsigned)(Mp + 255) / 256, gy), \
+                           dim3(256), 0, c->stream, beta, ldb, Mp, hj, k, part);                   \
+    else                                                                                           \
+        hipLaunchKernelGGL((ptheta_quad_kernel<D_, 2, 2, 2, 2>), dim3((unsigned)Mp / 64, gy),      \
+                           dim3(256), 0, c->stream, beta, ldb, Mp, hj, k, part)
+        BQ_PTHETA_DISPATCH(d, PQ)
+#undef PQ
+        HIPCHK(c, hipGetLastError());
+    }
+    return BQ_OK;
+}
+
+// dmean, dvar ((d + 2) x M, entry [p + j (d + 2)]) over the Mp (multiple of 16) rows of beta; a
+// null dmean / dvar switches that part off (Z / beta, var and qpart are then not read)
+int launch_predict_theta(bq_ctx *c, int d, const double *beta, long ldb, int M, int Mp,
+                         const double *xo, const HessJob &hj, const double *Z, const double *var,
+                         const double *qpart, double h, double s, double *dmean, double *dvar)
+{
+    Bracket br(c, BQ_K_REDUCE);
+    const ThetaScale sc = theta_scale(h, s);
+    const int ncb = hj.npad / 64;
+#define PT(D_)                                                                                     \
+    hipLaunchKernelGGL(predict_theta_kernel<D_>, dim3((unsigned)(Mp / 16)), dim3(512), 0,          \
+                       c->stream, beta, ldb, M, xo, hj, Z, var, qpart, ncb, (long)Mp, sc, dmean,   \
+                       dvar)
+    BQ_PTHETA_DISPATCH(d, PT)
+#undef PT
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// the fused mean route: mean (M; may be nullptr) and dmean ((d + 2) x M) in one launch
+int launch_predict_mean_theta(bq_ctx *c, int d, const double *xo, int M, const HessJob &hj,
+                              const double *Z, double h, double s, double *mean, double *dmean)
+{
+    Bracket br(c, BQ_K_REDUCE);
+    const ThetaScale sc = theta_scale(h, s);
+#define PMT(D_)                                                                                    \
+    hipLaunchKernelGGL(predict_mean_theta_kernel<D_>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, \
+                       c->stream, xo, M, hj, Z, sc, mean, dmean)
+    BQ_PTHETA_DISPATCH(d, PMT)
+#undef PMT
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+#undef BQ_PTHETA_DISPATCH
 
 } // namespace bqh

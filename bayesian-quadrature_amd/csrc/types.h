@@ -66,6 +66,10 @@ struct HessJob {
     int n, npad;
 };
 
+// rows of the matrix that holds a fit's solved vectors u, z_1 .. z_d (ptheta.h; d + 1 <= 9 of them
+// are used): one 64-row block, the fewest the row sweeps take
+#define BQ_PTHETA_ROWS 64
+
 // the sums' places (D = d): [G sums | trace sums | quadratic terms]
 //   G:     S_K, S_k (d), S_kl (k <= l, row by row), S_ss
 //   trace: sum C o C, sum C o Ki, sum Ki o Ki, sum C o B_k (d), sum Ki o B_k (d), sum B_k o B_l^T (k <= l)

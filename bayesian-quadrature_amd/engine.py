@@ -843,6 +843,24 @@ class Fit(object):
                                            L.dptr(var), L.dptr(dmean), L.dptr(dvar)))
         return mean, var, dmean, dvar
 
+    def predict_dtheta(self, xo, want_var=True):
+        """(mean, var, dmean, dvar) at the points xo: the posterior and its derivatives with
+        respect to the hyper-parameters, in closed form on the resident factor
+        (bq_gp_predict_dtheta).  mean, var: (M,); dmean, dvar: (d + 2, M), entry [p, j] =
+        d/d theta_p at xo[:, j], theta in the order of ``logml_grad``: [h, w_1 .. w_d, s].
+        ``want_var=False`` leaves var and dvar None and takes the route without a sweep."""
+        xo = _pts(xo)
+        if xo.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        M = xo.shape[1]
+        mean, dmean = np.empty(M), np.empty((self.d + 2, M), order="F")
+        var = np.empty(M) if want_var else None
+        dvar = np.empty((self.d + 2, M), order="F") if want_var else None
+        e = self._eng
+        e._check(e._lib.bq_gp_predict_dtheta(e._ctx, self._handle(), L.dptr(xo), M, L.dptr(mean),
+                                             L.dptr(var), L.dptr(dmean), L.dptr(dvar)))
+        return mean, var, dmean, dvar
+
 
 class Pair(object):
     """GP1 over log l at the samples and GP2 over [l_s, exp(mean of GP1 at x_c)] at samples +

@@ -489,6 +489,49 @@ class GP(object):
         m, v, dm, dv = self._device_fit().predict_grad(xo, want_var=True)
         return m, v, self._grad_shape(xo, dm), self._grad_shape(xo, dv)
 
+    def dmean_dtheta(self, xo):
+        """Derivatives of ``mean`` with respect to the hyper-parameters, (3, M) in the order of
+        ``params``: row p is d mean(xo_j) / d [h, w, s][p], in closed form on the device fit
+        (bq_gp_predict_dtheta, the route without a sweep)."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            return np.empty((3, 0), dtype=DTYPE)
+        return self._device_fit().predict_dtheta(xo, want_var=False)[2]
+
+    def dvar_dtheta(self, xo):
+        """Derivatives of ``var`` with respect to the hyper-parameters, shaped like
+        ``dmean_dtheta``'s."""
+        return self.mean_var_dtheta(xo)[3]
+
+    def mean_var_dtheta(self, xo):
+        """(mean, var, dmean_dtheta, dvar_dtheta) at the points in one device call: the
+        prediction's sweep, one backward sweep, one product per length scale and one reduction
+        (bq_gp_predict_dtheta)."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            e = np.empty(0, dtype=DTYPE)
+            return e, e.copy(), np.empty((3, 0), dtype=DTYPE), np.empty((3, 0), dtype=DTYPE)
+        return self._device_fit().predict_dtheta(xo, want_var=True)
+
+    def mean_var_laplace(self, xo, params):
+        """(mean, var + g^T C g): the predictive variance with the named subset of
+        ("h", "w", "s") marginalised to first order around the current parameters -- g the rows
+        of ``dmean_dtheta`` for that subset, C = ``hyper_cov(params)``, the Laplace covariance of
+        an ML-II optimum.  Raises what ``hyper_cov`` raises: ValueError for bad names,
+        numpy.linalg.LinAlgError away from a maximum."""
+        Cov = self.hyper_cov(params)
+        idx = [("h", "w", "s").index(p) for p in params]
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            e = np.empty(0, dtype=DTYPE)
+            return e, e.copy()
+        # (the prediction, then the mean's derivatives on the route without a sweep: dvar's
+        # product per length scale is not needed here)
+        fit = self._device_fit()
+        m, v, _ = fit.predict(xo, want_mean=True, want_var=True)
+        g = fit.predict_dtheta(xo, want_var=False)[2][idx]
+        return m, v + np.einsum("pj,pq,qj->j", g, Cov, g)
+
     def cov(self, xo):
         xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
         if xo.size == 0:

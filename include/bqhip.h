@@ -243,6 +243,24 @@ int bq_gp_predict(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double 
  * the fit. */
 int bq_gp_predict_grad(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double *mean,
                        double *var, double *dmean, double *dvar);
+/* The posterior at M points and its derivatives with respect to the hyper-parameters
+ * theta = [h, w_1 .. w_d, s] (the order of bq_gp_logml_grad), in closed form on the resident factor:
+ * nothing differenced, nothing refitted, no cached result of the fit dropped.  With a = Kxx^-1 y,
+ * beta_j = Kxx^-1 k_j, u = Kxx^-1 a, z_k = Kxx^-1 (D_k a), D_k = d Kxx / d w_k and
+ * g_jik = (xo_jk - x_ik)^2 / w_k^3 - 1 / w_k:
+ *   d mean_j / d h = (2 s^2 / h) k_j.u    d mean_j / d w_k = sum_i k_ji (g_jik a_i - z_k,i)
+ *   d mean_j / d s = -2 s k_j.u
+ *   d var_j / d h = (2 / h)(var_j - s^2 |beta_j|^2)     d var_j / d s = 2 s |beta_j|^2
+ *   d var_j / d w_k = -k(x, x) / w_k - 2 sum_i k_ji g_jik beta_ji + beta_j^T D_k beta_j
+ * xo: d x M column-major like bq_gp_predict.  mean, var: M.  dmean, dvar: (d + 2) x M, entry
+ * [p + j*(d + 2)] = d/d theta_p.  Any output may be NULL, not all four.  Without var and dvar: one
+ * fused launch, no sweep.  Otherwise the sweep of bq_gp_predict -- mean and var are its bits --
+ * and, for dvar, one backward row sweep and one M x n x n product per length scale.  u and z_k
+ * are solved once per fit and kept until it changes.  Same status rules as bq_gp_predict, and
+ * BQ_ERR_BAD_ARG when all four outputs are NULL; M == 0 touches nothing.  The same bits on every
+ * call.  At s == 0 the h entry of dmean and the s entries of both are exactly 0. */
+int bq_gp_predict_dtheta(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double *mean,
+                         double *var, double *dmean, double *dvar);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
