@@ -244,23 +244,43 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
     // (512 threads: both row-block solves at once, the diagonal factor on eight waves, and --
     // diag_pipe -- a diagonal tile's update on waves 4-7 behind the solve's column blocks)
     const bool pipe = w8 && c->cfg.diag_pipe != 0;
-#define BQ_SLAB_STEP(STAMP_, NW_, PIPE_)                                                           \
-    hipLaunchKernelGGL((slab_step_kernel<STAMP_, NW_, PIPE_>), dim3(T * (T + 1) / 2, 1, batch),    \
-                       dim3(64 * NW_), 0, c->cur, A, lda, astride, Sin, Sout, lds, sstride, ntot,  \
-                       j0, dinv_in, dinv_out, dstride, fnext, last, info, col0,                    \
-                       STAMP_ ? stamps : (long long *)nullptr, out)
-    if (stamps && pipe)
-        BQ_SLAB_STEP(true, 8, true);
-    else if (stamps && w8)
-        BQ_SLAB_STEP(true, 8, false);
-    else if (stamps)
-        BQ_SLAB_STEP(true, 4, false);
-    else if (pipe)
-        BQ_SLAB_STEP(false, 8, true);
-    else if (w8)
-        BQ_SLAB_STEP(false, 8, false);
+    // (write-through tile stores, tile_wt: where all workgroups of the step run in ONE round, every
+    // tile but workgroup 0's is done long before workgroup 0 leaves its pivot chain, and what its
+    // stores leave dirty in the L2s is written back at the kernel's end, in front of the next step.
+    // In a step of several rounds or a stacked batch the stores are throughput and stay plain; so
+    // does the last step, which has no chain to hide them under.)
+    const bool wt = w8 && c->cfg.tile_wt != 0 && fnext && wgs <= c->cus;
+    // (the last step of a sweep that carries its read-out emits it and stores no tile)
+    const bool emit = last && out.scal != nullptr;
+#define BQ_SLAB_STEP(STAMP_, NW_, PIPE_, TILES_)                                                   \
+    hipLaunchKernelGGL((slab_step_kernel<STAMP_, NW_, PIPE_, TILES_>),                             \
+                       dim3(T * (T + 1) / 2, 1, batch), dim3(64 * NW_), 0, c->cur, A, lda,         \
+                       astride, Sin, Sout, lds, sstride, ntot, j0, dinv_in, dinv_out, dstride,     \
+                       fnext, last, info, col0, STAMP_ ? stamps : (long long *)nullptr, out)
+#define BQ_SLAB_STEP_NW(STAMP_, NW_, PIPE_)                                                        \
+    do {                                                                                           \
+        if (emit)                                                                                  \
+            BQ_SLAB_STEP(STAMP_, NW_, PIPE_, SLAB_TILES_EMIT);                                     \
+        else if (NW_ == 8 && wt)                                                                   \
+            BQ_SLAB_STEP(STAMP_, 8, PIPE_, SLAB_TILES_WT);                                         \
+        else                                                                                       \
+            BQ_SLAB_STEP(STAMP_, NW_, PIPE_, SLAB_TILES_PLAIN);                                    \
+    } while (0)
+#define BQ_SLAB_STEP_ANY(STAMP_)                                                                   \
+    do {                                                                                           \
+        if (pipe)                                                                                  \
+            BQ_SLAB_STEP_NW(STAMP_, 8, true);                                                      \
+        else if (w8)                                                                               \
+            BQ_SLAB_STEP_NW(STAMP_, 8, false);                                                     \
+        else                                                                                       \
+            BQ_SLAB_STEP_NW(STAMP_, 4, false);                                                     \
+    } while (0)
+    if (stamps)
+        BQ_SLAB_STEP_ANY(true);
     else
-        BQ_SLAB_STEP(false, 4, false);
+        BQ_SLAB_STEP_ANY(false);
+#undef BQ_SLAB_STEP_ANY
+#undef BQ_SLAB_STEP_NW
 #undef BQ_SLAB_STEP
     HIPCHK(c, hipGetLastError());
     return BQ_OK;

@@ -63,6 +63,10 @@
     /* ... whose diagonal tiles are updated by waves 4-7, one k-block behind waves 0-3's solve      \
        (slab_step_kernel; BQ_DIAG_PIPE=0: solve, barrier, update on waves 0-3) */                   \
     X(diag_pipe, "BQ_DIAG_PIPE", 1)                                                                 \
+    /* ... and whose tiles are stored write-through while the step's workgroups all run in one      \
+       round: their write-back under workgroup 0's chain, not at the launch's end (slab_step_kernel, \
+       WT; BQ_TILE_WT=0: plain stores) */                                                           \
+    X(tile_wt, "BQ_TILE_WT", 1)                                                                     \
     /* eight-wave k-split forms of the 64-tile / job kernels (BQ_GEMM_KSPLIT) */                    \
     X(gemm_ksplit, "BQ_GEMM_KSPLIT", 1)                                                             \
     /* 64 / 128: force the LDS kernel's workgroup tile (BQ_GEMM_TILE; measurements) */              \

@@ -786,7 +786,9 @@ extern "C" int bq_probe_first_launch(bq_ctx *c, int64_t batch, int64_t d, int64_
 // diagonal factor's entry / block in registers / pivot chain done / sub-blocks in LDS / end.
 // The pipelined diagonal tile (BQ_DIAG_PIPE, slab.h): (2) wave 0 behind the barrier that
 // publishes the last column block, (3) stays 0, (4) wave 4 behind its last MFMA, (16..18) /
-// (19..21) wave 4's / wave 0's arrivals at the barriers of column blocks 1 .. 3.
+// (19..21) wave 4's / wave 0's arrivals at the barriers of column blocks 1 .. 3.  (24..31) the
+// stores, on s_memrealtime: workgroup 0's entry and end, one off-diagonal workgroup's entry,
+// update and last store acknowledged (slab.h, BQ_SSTAMP_STORES; tools/c2_timeline.py).
 extern "C" int bq_probe_c2_timeline(bq_ctx *c, bq_plan *p, int64_t *stamps, int64_t nsteps)
 {
     if (!c || !p || !stamps || nsteps < 1 || nsteps > 1024)

@@ -60,6 +60,7 @@ struct SlabWg {
     double *dout;
     long lda, lds;
     int j0, r0, Rb, Cb, bx, by, wave, b, factor_next, last, col0;
+    int swg; // (STAMP: the off-diagonal workgroup that stamps its stores, BQ_SSTAMP_STORES)
     int *info;
     long long *stamps;
     // The kernel's own argument, by reference: by value its fields sit in SGPRs across the whole
@@ -106,21 +107,71 @@ __device__ __forceinline__ void slab_emit(const SlabOut &out, int b, int row, in
     }
 }
 
+// What a step does with its updated tiles (slab_step_kernel's TILES; launch_slab_step has the rule):
+//   SLAB_TILES_PLAIN  plain stores.  The code of the steps before there were modes, instruction for
+//                     instruction, its own read-out branch included, which is never taken any more
+//                     (launch_slab_step sends every folded last step to SLAB_TILES_EMIT): without it
+//                     hipcc schedules the update of workgroup 0 differently and a step is 0.1 us
+//                     longer (LABBOOK, "The tiles' way to memory").
+//   SLAB_TILES_WT     write-through stores (launch_config.h, tile_wt): the line leaves the XCD's L2
+//                     when it is stored, under workgroup 0's pivot chain, instead of standing dirty
+//                     until the kernel's end, where its write-back is the next launch's wait.  Same
+//                     value, same address; no workgroup of a launch reads what another one stores,
+//                     so nothing is ordered by it.  The tiles of workgroups 1 and 2 -- (1, 0), the
+//                     next panel's first rows, and (1, 1), the next diagonal block: what the next
+//                     launch's workgroup 0 loads first -- stay plain: 52 KB.
+//   SLAB_TILES_EMIT   the last step with the read-out folded in: slab_emit takes what anybody reads
+//                     of its tiles (the Schur complement of the border), so the tiles are not
+//                     stored, and an off-diagonal tile without the y row that is not in tile column
+//                     0 (whose workgroups store the solved border rows) is not computed: its
+//                     workgroup returns at entry (slab_tile_dead).
+enum { SLAB_TILES_PLAIN = 0, SLAB_TILES_WT = 1, SLAB_TILES_EMIT = 2 };
+
+template <int TILES>
+__device__ __forceinline__ void slab_tile_store(double *p, double v, bool wt)
+{
+    static_assert(TILES != SLAB_TILES_EMIT, "the folded last step stores no tile");
+    if (TILES == SLAB_TILES_WT && wt)
+        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+        *p = v;
+}
+
+// (write-through in this workgroup: wave-uniform)
+__device__ __forceinline__ bool slab_wg_wt() { return blockIdx.x > 2; }
+
+__device__ __forceinline__ bool slab_tile_dead(const SlabOut &out, int bx, int by, int Rb)
+{
+    return bx != by && by > 0 && (out.yrow < Rb || out.yrow >= Rb + 64);
+}
+
+// (does this step emit the read-out: a constant but in SLAB_TILES_PLAIN)
+template <int TILES>
+__device__ __forceinline__ bool slab_emits(const SlabWg &g)
+{
+    if constexpr (TILES == SLAB_TILES_PLAIN)
+        return g.last && g.out.scal != nullptr;
+    return TILES == SLAB_TILES_EMIT;
+}
+
 // Wave w's blocks of an updated diagonal tile (-acc: the accumulators hold the negated tile)
-// back to A, and the read-out of the last step
-template <int NA>
+// back to A, or (SLAB_TILES_EMIT) the read-out of the last step
+template <int TILES, int NA>
 __device__ __forceinline__ void slab_store_diag(const SlabWg &g, int w, const double4_t (&acc)[NA])
 {
     const int l15 = mfma_l15(), l4 = mfma_l4();
-    const bool emit = g.last && g.out.scal != nullptr;
+    const bool wt = slab_wg_wt();
+    const bool emit = slab_emits<TILES>(g);
 #pragma unroll
     for (int sb = 0; sb < 3; ++sb)
         if (sb < slab_diag_nb(w)) {
             double *Cd = g.A + g.Rb + 16 * slab_diag_rb(w, sb) + l15 +
                          (long)(g.Cb + 16 * slab_diag_cb(w, sb) + l4) * g.lda;
+            if constexpr (TILES != SLAB_TILES_EMIT) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Cd[(long)(4 * r) * g.lda] = -acc[sb][r];
+                for (int r = 0; r < 4; ++r)
+                    slab_tile_store<TILES>(Cd + (long)(4 * r) * g.lda, -acc[sb][r], wt);
+            }
             if (emit) {
                 const SlabOut o = g.out; // (by value: every field is read once, not per entry)
 #pragma unroll
@@ -191,13 +242,29 @@ __device__ __forceinline__ void slab_factor_next8(const SlabWg &g, double *plds,
 // STAMP: a profiling instantiation (tools/c2_timeline.py) whose workgroup 0 records s_memtime
 // at its phase boundaries; the shipped launches use STAMP = false and carry no stamp code.
 // tid: the thread of workgroup 0 that records (wave 4's lane 0 is thread 256).
-#define BQ_SSTAMP(stamps_, k, dep, tid)                                                            \
+#define BQ_SSTAMP_AT(stamps_, k, dep, wg, tid, clock)                                              \
     if (STAMP) {                                                                                   \
         asm volatile("" ::"v"(dep));                                                               \
         __builtin_amdgcn_sched_barrier(0);                                                         \
-        if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == (tid))                            \
-            (stamps_)[k] = (long long)__builtin_amdgcn_s_memtime();                                \
+        if ((int)blockIdx.x == (wg) && blockIdx.z == 0 && threadIdx.x == (tid))                    \
+            (stamps_)[k] = (long long)clock();                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+#define BQ_SSTAMP(stamps_, k, dep, tid)                                                            \
+    BQ_SSTAMP_AT(stamps_, k, dep, 0, tid, __builtin_amdgcn_s_memtime)
+// Slots 24 .. 31: the stores.  s_memtime counts per XCD, so what is compared ACROSS workgroups is
+// s_memrealtime (100 MHz, one counter): [24] / [25] workgroup 0 at entry / at its last instruction,
+// which with [0] and the factor's stamps places every phase of it on that clock; [26] / [27] /
+// [28] one off-diagonal workgroup (g.swg: the last tile row's second tile, which also the last
+// step keeps) at entry / behind its update / with its tile's stores acknowledged; [29] .. [31] the
+// same workgroup's s_memtime at the same three places.  `drained`: the wait for the stores.
+#define BQ_SSTAMP_STORES(stamps_, k, dep, wg, tid, drained)                                        \
+    if (STAMP) {                                                                                   \
+        if (drained)                                                                               \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                       \
+        BQ_SSTAMP_AT(stamps_, k, dep, wg, tid, __builtin_amdgcn_s_memrealtime)                     \
+        if ((wg) != 0)                                                                             \
+            BQ_SSTAMP_AT(stamps_, (k) + 3, dep, wg, tid, __builtin_amdgcn_s_memtime)               \
     }
 
 // --- the tile paths of slab_step_kernel, one per row group of the barrier table in front of it ---
@@ -207,7 +274,7 @@ __device__ __forceinline__ void slab_factor_next8(const SlabWg &g, double *plds,
 // slab_diag_rb / slab_diag_cb of wave - 4 and requested RAW before the first barrier; the
 // two-block waves load and update their second block again as a third, which nothing stores (an
 // MFMA ignores EXEC).
-template <bool STAMP>
+template <bool STAMP, int TILES>
 __device__ __forceinline__ void slab_pipe_update(const SlabWg g, double *plds)
 {
     double *const Qs = plds;
@@ -274,7 +341,8 @@ __device__ __forceinline__ void slab_pipe_update(const SlabWg g, double *plds)
         slab_factor_next8(g, plds, nullptr);
         return;
     }
-    slab_store_diag(g, wu, acc);
+    slab_store_diag<TILES>(g, wu, acc);
+    BQ_SSTAMP_STORES(g.stamps, 25, 0, 0, 256, true) // (workgroup 0 stores a tile in the last step only)
 }
 
 // Column block C of the pipelined solve: x_C published in the Q rows the moment it exists, a
@@ -333,6 +401,7 @@ __device__ __forceinline__ void slab_pipe_solve(const SlabWg g, double *plds)
     if (blockIdx.x == 0 && g.factor_next) {
         __syncthreads(); // F
         slab_factor_next8(g, plds, (STAMP && blockIdx.z == 0) ? g.stamps + 5 : nullptr);
+        BQ_SSTAMP_STORES(g.stamps, 25, 0, 0, 0, false)
     }
 }
 
@@ -407,7 +476,7 @@ __device__ __forceinline__ void slab_update_offdiag(const double *Qs,
 // Table rows "off-diagonal tile", waves 0-3: A Q; "diagonal, NW = 4": A Q [T F + factor];
 // "diagonal, NW = 8, !PIPE", waves 0-3: A Q [F + factor] -- the one-phase body (four waves, or
 // waves 0-3 of eight).
-template <bool STAMP, int NW, bool PIPE>
+template <bool STAMP, int NW, bool PIPE, int TILES>
 __device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
 {
     double *const Qs = plds;
@@ -508,6 +577,7 @@ __device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
     else
         slab_update_offdiag(Qs, xp, acc);
     BQ_SSTAMP(g.stamps, 4, acc[1][3] + acc[0][0], 0)
+    BQ_SSTAMP_STORES(g.stamps, 27, acc[1][3] + acc[0][0], g.swg, 0, false)
     // tile column 0 is the next panel: it goes to the scratch column (the diagonal tile,
     // which workgroup 0 factors in place, and the Schur complement of the last step stay in A)
     // (the pipelined form never comes here with a diagonal tile, and workgroup 0 is one)
@@ -521,6 +591,7 @@ __device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
             slab_pack_blocks8(Fs, wave, acc);
             __syncthreads(); // F
             slab_factor_next8(g, plds, (STAMP && blockIdx.z == 0) ? g.stamps + 5 : nullptr);
+            BQ_SSTAMP_STORES(g.stamps, 25, 0, 0, 0, false)
             return;
         }
         // four waves: it lands where the Q rows were: every wave must be through with them
@@ -545,15 +616,19 @@ __device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
                         : g.A + g.Rb + 16 * wave + l15 + (long)(g.Cb + l4) * g.lda;
     const long ldo = to_s ? g.lds : g.lda;
     if (bx == by) {
-        slab_store_diag(g, wave, acc);
+        slab_store_diag<TILES>(g, wave, acc);
+        BQ_SSTAMP_STORES(g.stamps, 25, 0, 0, 0, true)
     } else {
+        if constexpr (TILES != SLAB_TILES_EMIT) {
+            const bool wt = slab_wg_wt();
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
+            for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Cout[(long)(16 * cb + 4 * r) * ldo] = -acc[cb][r];
+                for (int r = 0; r < 4; ++r)
+                    slab_tile_store<TILES>(Cout + (long)(16 * cb + 4 * r) * ldo, -acc[cb][r], wt);
+        }
         // (the last step's tiles are the Schur complement of the border: slab_emit)
-        if (g.last && g.out.scal != nullptr) {
+        if (slab_emits<TILES>(g)) {
             const SlabOut o = g.out; // (by value: every field is read once, not per entry)
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
@@ -562,6 +637,7 @@ __device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
                     slab_emit(o, g.b, g.Rb + 16 * wave + l15, g.Cb + 16 * cb + l4 + 4 * r,
                               -acc[cb][r]);
         }
+        BQ_SSTAMP_STORES(g.stamps, 28, 0, g.swg, 0, true)
     }
 }
 
@@ -593,7 +669,9 @@ __device__ __forceinline__ void slab_one_phase(const SlabWg g, double *plds)
 // LDS; F: updated diagonal block in LDS; [+ factor]: the barriers of the diagonal factor
 // (potf2.h), all waves alike.  `last` has factor_next = 0; workgroup 0 is a diagonal tile; which
 // row a workgroup takes depends on blockIdx and kernel arguments only, never on the wave.
-template <bool STAMP, int NW = 4, bool PIPE = false>
+// TILES (SLAB_TILES_*, above; launch_slab_step has the rule; write-through with NW = 8 only): how the
+// updated tiles leave; the solved rows and everything workgroup 0 stores are plain stores always.
+template <bool STAMP, int NW = 4, bool PIPE = false, int TILES = SLAB_TILES_PLAIN>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(double *__restrict__ A, long lda,
                                                         long astride,
                                                         const double *__restrict__ Sin,
@@ -605,7 +683,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
                                                         int *__restrict__ info, int col0,
                                                         long long *stamps, SlabOut out)
 {
+    static_assert(NW == 8 || TILES != SLAB_TILES_WT, "write-through: the one-round eight-wave steps");
     BQ_SSTAMP(stamps, 0, 0, 0)
+    BQ_SSTAMP_STORES(stamps, 24, 0, 0, 0, false)
     // One region, 52 KiB -- a workgroup of this kernel must fit into what ONE retiring workgroup
     // of the 64-tile product frees on a CU (36 KiB + the 16 KiB four of them leave over), or it
     // starves behind a trailing update running on the other stream.  First 4096 doubles: the Q
@@ -620,17 +700,25 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
     int bx, by;
     tri_decode(blockIdx.x, bx, by);
     const int r0 = j0 + 64;
+    // (the last step's tiles that nobody reads: before the first barrier, the whole workgroup)
+    if constexpr (TILES == SLAB_TILES_EMIT) {
+        if (slab_tile_dead(out, bx, by, r0 + 64 * bx))
+            return;
+    }
+    // (STAMP: tile (T - 1, 1) of a step with at least three tile rows)
+    const int swg = STAMP && gridDim.x >= 6 ? (int)gridDim.x - (ntot - r0) / 64 + 1 : -1;
+    BQ_SSTAMP_STORES(stamps, 26, 0, swg, 0, false)
     const SlabWg g = {A + (long)b * astride, Sin + (long)b * sstride, Sout + (long)b * sstride,
                       din + (long)b * dstride, dout + (long)b * dstride, lda, lds, j0, r0,
-                      r0 + 64 * bx, r0 + 64 * by, bx, by, wave, b, factor_next, last, col0, info,
-                      stamps, out};
+                      r0 + 64 * bx, r0 + 64 * by, bx, by, wave, b, factor_next, last, col0, swg,
+                      info, stamps, out};
     // A diagonal tile of the pipelined form is a path of its own from here to its return:
     // nothing of it is shared with the off-diagonal tiles, whose code and registers stay the
     // one-phase form's.
     if constexpr (NW == 8 && PIPE) {
         if (g.bx == g.by) {
             if (g.wave >= 4) {
-                slab_pipe_update<STAMP>(g, plds);
+                slab_pipe_update<STAMP, TILES>(g, plds);
                 return;
             }
             slab_pipe_solve<STAMP>(g, plds);
@@ -641,9 +729,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void slab_step_kernel(dou
         slab_upper_waves(g, plds);
         return;
     }
-    slab_one_phase<STAMP, NW, PIPE>(g, plds);
+    slab_one_phase<STAMP, NW, PIPE, TILES>(g, plds);
 }
+#undef BQ_SSTAMP_STORES
 #undef BQ_SSTAMP
+#undef BQ_SSTAMP_AT
 
 // The assembly of the bordered system with the first launch of the slab sweep folded in: the
 // tiles of column block 0 also fill the sweep's scratch column, and the workgroup of tile

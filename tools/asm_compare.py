@@ -1,7 +1,11 @@
 """Did a refactor change the code of a kernel?  Compares the ISA of two `make asm` trees, kernel
 by kernel, for the kernels whose names match the patterns given.
 
-    python3 tools/asm_compare.py BEFORE_DIR AFTER_DIR [name-pattern ...]
+    python3 tools/asm_compare.py BEFORE_DIR AFTER_DIR [name-pattern | OLD=>NEW ...]
+
+An argument OLD=>NEW pairs a kernel of BEFORE with the kernel of AFTER whose demangled name is the
+BEFORE name with the text OLD replaced by NEW (a template that gained a parameter: 'true>=>true,
+false>'); several of them pair it with several kernels.  Without one, names pair with themselves.
 
 Per kernel it prints the code-object metadata of both (VGPRs, spilled VGPRs, spilled SGPRs, LDS
 bytes, waves per SIMD), whether the instruction streams are the same text with labels, comments
@@ -73,19 +77,28 @@ def main():
     if len(sys.argv) < 3:
         raise SystemExit(__doc__)
     before, after = kernels(sys.argv[1]), kernels(sys.argv[2])
-    pats = [re.compile(p) for p in sys.argv[3:]] or [re.compile(".")]
+    renames = [a.split("=>") for a in sys.argv[3:] if "=>" in a]
+    pats = [re.compile(p) for p in sys.argv[3:] if "=>" not in p] or [re.compile(".")]
     names = sorted(set(before) | set(after))
     pretty = demangle(names)
+    by_pretty = {pretty[n]: n for n in after}
     bad = 0
     print("kernel | VGPRs, spilled VGPRs, spilled SGPRs, LDS bytes, waves/SIMD: before -> after | code")
+    pairs = []
     for n in names:
         if not any(p.search(pretty[n]) for p in pats):
+            continue
+        if renames:
+            pairs += [(n, by_pretty[pretty[n].replace(a, b)]) for a, b in renames
+                      if n in before and a in pretty[n] and pretty[n].replace(a, b) in by_pretty]
             continue
         if n not in before or n not in after:
             print("%s | only %s" % (pretty[n], "before" if n in before else "after"))
             bad += 1
             continue
-        (b0, i0), (b1, i1) = before[n], after[n]
+        pairs.append((n, n))
+    for n, n1 in pairs:
+        (b0, i0), (b1, i1) = before[n], after[n1]
         op0, op1 = [l.split()[0] for l in b0], [l.split()[0] for l in b1]
         if b0 == b1:
             verdict = "same (%d instructions)" % len(b0)
@@ -99,7 +112,8 @@ def main():
         worse = any(i1.get(k, 0) > i0.get(k, 0) for k in ("vgpr_spill", "sgpr_spill")) or any(
             i1.get(k) != i0.get(k) for k in ("LDSByteSize", "Occupancy"))
         bad += worse
-        print("%s | %s -> %s%s | %s" % (pretty[n], meta(i0), meta(i1), " WORSE" if worse else "", verdict))
+        print("%s%s | %s -> %s%s | %s" % (pretty[n], "" if n1 == n else " -> " + pretty[n1], meta(i0),
+                                          meta(i1), " WORSE" if worse else "", verdict))
     return 1 if bad else 0
 
 

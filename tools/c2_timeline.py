@@ -54,6 +54,35 @@ if __name__ == "__main__":
             float((raw[1:15, 19] - raw[1:15, 1]).mean()),
             float((raw[1:15, 20] - raw[1:15, 19]).mean()),
             float((raw[1:15, 21] - raw[1:15, 20]).mean())]
+    # The stores (slots 24 .. 31, slab.h BQ_SSTAMP_STORES).  s_memtime counts per XCD, so workgroups
+    # are compared on s_memrealtime (10 ns): workgroup 0's [24] entry / [25] end give its own
+    # s_memtime ticks per 10 ns, which places potf2_chain's end ([7]) on that clock; the off-diagonal
+    # workgroup's [26] entry / [27] updated / [28] stores acknowledged, and [29 .. 31] the same in its
+    # own s_memtime.  Negative offdiag_end_minus_chain_end: the tile was in memory before workgroup 0
+    # left its pivot chain.
+    if (raw[1:15, 24:29] != 0).all():
+        def stores(s):
+            f = (raw[s, 9] - raw[s, 0]) / max(1, raw[s, 25] - raw[s, 24])
+            chain_end = raw[s, 24] + (raw[s, 7] - raw[s, 0]) / f
+            return {"offdiag_entry_minus_wg0_entry_us": 0.01 * float(raw[s, 26] - raw[s, 24]),
+                    "offdiag_end_minus_chain_end_us": 0.01 * float(raw[s, 28] - chain_end),
+                    "offdiag_entry_to_updated_ticks": int(raw[s, 30] - raw[s, 29]),
+                    "offdiag_updated_to_stored_ticks": int(raw[s, 31] - raw[s, 30])}
+        out["stores_step_1"] = stores(1)
+        per = [stores(s) for s in range(1, 15)]
+        out["stores_mean_steps_1_14"] = {k: float(np.mean([p[k] for p in per])) for k in per[0]}
+    # The last step (no factor): workgroup 0 from entry to its read-out's stores acknowledged, and
+    # the off-diagonal workgroup of the y row's tile row.
+    ls = nsteps - 1
+    if raw[ls, 25] != 0:
+        lcols = [0, 1, 2, 4]
+        out["last_step"] = {
+            "wg0_phases": {NAMES[b]: int(raw[ls, b] - raw[ls, a]) for a, b in zip(lcols, lcols[1:])},
+            "wg0_entry_to_stored_us": 0.01 * float(raw[ls, 25] - raw[ls, 24]),
+            "offdiag_entry_to_stored_us": 0.01 * float(raw[ls, 28] - raw[ls, 26]),
+            "offdiag_entry_minus_wg0_entry_us": 0.01 * float(raw[ls, 26] - raw[ls, 24]),
+            "offdiag_entry_to_updated_ticks": int(raw[ls, 30] - raw[ls, 29]),
+            "offdiag_updated_to_stored_ticks": int(raw[ls, 31] - raw[ls, 30])}
     print(json.dumps(out, indent=1))
     plan.close()
     e.close()
