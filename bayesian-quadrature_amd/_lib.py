@@ -74,6 +74,8 @@ SIGNATURES = {
     "bq_gp_logml_hess": (C.c_int, [_vp, _vp, _dp]),
     "bq_gp_loo": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp]),
     "bq_gp_loo_grad": (C.c_int, [_vp, _vp, _dp, _dp]),
+    "bq_gp_lgo": (C.c_int, [_vp, _vp, _i64p, _i64p, _i64, _dp, _dp, _dp, _dp]),
+    "bq_gp_lgo_grad": (C.c_int, [_vp, _vp, _i64p, _i64p, _i64, _dp, _dp]),
     "bq_gp_get": (C.c_int, [_vp, _vp, C.c_int, _dp]),
     "bq_gp_predict": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp]),
     "bq_gp_predict_grad": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp, _dp]),

@@ -827,6 +827,149 @@ extern "C" int bq_gp_loo_grad(bq_ctx *c, bq_fit *f, double *total, double *grad)
     return BQ_OK;
 }
 
+static_assert(BQ_LGO_MAX == 64, "lgo.h's blocks are rows of 64 doubles");
+
+// the groups of one leave-group-out call, checked, as the device reads them
+struct LgoGroups {
+    std::vector<int> buf; // idx (T) | start (G + 1) | the pivot flag, cleared | bundle (NB + 1)
+    long T = 0, G = 0, NB = 0; // NB bundles: consecutive groups of at most BQ_LGO_MAX members together
+    int maxb = 0;              // the largest bundle
+};
+
+static int lgo_groups(bq_ctx *c, const bq_fit *f, const int64_t *idx, const int64_t *start,
+                      int64_t G, LgoGroups &g)
+{
+    const int n = f->n;
+    if (!idx || !start || G < 1 || G > n || start[0] != 0)
+        return fail(c, BQ_ERR_BAD_ARG, "lgo: 1 <= G <= n groups, start[0] == 0");
+    for (int64_t q = 0; q < G; ++q) {
+        const int64_t b = start[q + 1] - start[q];
+        if (b < 1 || b > BQ_LGO_MAX)
+            return fail(c, BQ_ERR_BAD_ARG, "lgo: group %lld has %lld members, not 1 .. %d",
+                        (long long)q, (long long)b, BQ_LGO_MAX);
+        if (start[q + 1] > n)
+            return fail(c, BQ_ERR_BAD_ARG, "lgo: more members than the fit's %d points", n);
+    }
+    g.T = (long)start[G];
+    g.G = (long)G;
+    std::vector<char> seen;
+    try {
+        seen.assign((size_t)n, 0);
+        g.buf.assign((size_t)(g.T + 2 * g.G + 3), 0);
+    } catch (const std::bad_alloc &) {
+        return fail(c, BQ_ERR_NOMEM, "out of host memory");
+    }
+    for (long t = 0; t < g.T; ++t) {
+        if (idx[t] < 0 || idx[t] >= n)
+            return fail(c, BQ_ERR_BAD_ARG, "lgo: index %lld out of range [0, %d)",
+                        (long long)idx[t], n);
+        if (seen[(size_t)idx[t]])
+            return fail(c, BQ_ERR_BAD_ARG, "lgo: index %lld given twice", (long long)idx[t]);
+        seen[(size_t)idx[t]] = 1;
+        g.buf[(size_t)t] = (int)idx[t];
+    }
+    for (long q = 0; q <= g.G; ++q)
+        g.buf[(size_t)(g.T + q)] = (int)start[q];
+    int *bundle = g.buf.data() + g.T + g.G + 2;
+    for (long q = 0, first = 0; q <= g.G; ++q)
+        if (q == g.G || start[q + 1] - start[first] > BQ_LGO_MAX) { // group q opens the next bundle
+            g.maxb = std::max(g.maxb, (int)(start[q] - start[first]));
+            bundle[++g.NB] = (int)q;
+            first = q;
+        }
+    return BQ_OK;
+}
+
+// The value stage of both entry points, the same launches in both: mu, var, lp and the groups'
+// Sigma_B and r_B in the workspace, *total on the host.  Every workspace (with grad: the
+// Hessian's too) is there before anything runs.
+static int fit_lgo(bq_ctx *c, bq_fit *f, const LgoGroups &g, bool grad, LgoWs &w, double *total)
+{
+    const int d = f->d, npad = f->npad;
+    if (grad)
+        BQCHK(fit_hess_ws(c, f));
+    BQCHK(fit_grow(c, f->lgo, sizeof(double) * lgo_ws_doubles(npad, d, g.T, g.G, grad),
+                   "leave-group-out workspace"));
+    BQCHK(fit_alpha(c, f));
+    BQCHK(fit_y(c, f));
+    w = lgo_views(f->lgo.d(), npad, d, g.T, g.G);
+    HIPCHK(c, hipMemcpyAsync(w.idx, g.buf.data(), sizeof(int) * g.buf.size(), hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    BQCHK(launch_lgo(c, f->gY.d(), f->alpha.d(), f->y.d(), f->n, npad, d, g.T, g.G, g.NB, g.maxb, w));
+    int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(total, w.out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag)
+        return fail(c, BQ_ERR_NOT_PD,
+                    "lgo: a group's block of Kxx^-1 has a pivot that is not positive and finite");
+    return BQ_OK;
+}
+
+// Leave-group-out cross-validation (lgo.h has the formulas): the predictive mean and variance of
+// every member of every group from the points outside its group, each group's joint log density
+// and their sum, from the groups' blocks of Kxx^-1 = Y Y^T and alpha.  Nothing is kept between
+// calls but the workspace.
+extern "C" int bq_gp_lgo(bq_ctx *c, bq_fit *f, const int64_t *idx, const int64_t *start, int64_t G,
+                         double *mean, double *var, double *logpred, double *total)
+{
+    BQCHK(check_fit(c, f));
+    if (!mean && !var && !logpred && !total)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    LgoGroups g;
+    BQCHK(lgo_groups(c, f, idx, start, G, g));
+    HIPCHK(c, hipSetDevice(c->device));
+    LgoWs w;
+    double tot = 0.0;
+    BQCHK(fit_lgo(c, f, g, false, w, &tot));
+    if (mean)
+        HIPCHK(c, hipMemcpyAsync(mean, w.mu, sizeof(double) * g.T, hipMemcpyDeviceToHost, c->stream));
+    if (var)
+        HIPCHK(c, hipMemcpyAsync(var, w.var, sizeof(double) * g.T, hipMemcpyDeviceToHost, c->stream));
+    if (logpred)
+        HIPCHK(c, hipMemcpyAsync(logpred, w.lp, sizeof(double) * g.G, hipMemcpyDeviceToHost,
+                                 c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (total)
+        *total = tot;
+    return BQ_OK;
+}
+
+// dL_lgo / dtheta in the gradient's parameter order: the value stage, the Hessian's products stage
+// if neither it nor a Hessian nor bq_gp_loo_grad has run since the fit last changed, then the
+// groups' blocks of Q and of the M_k and one workgroup per group for its d + 2 entries.
+extern "C" int bq_gp_lgo_grad(bq_ctx *c, bq_fit *f, const int64_t *idx, const int64_t *start,
+                              int64_t G, double *total, double *grad)
+{
+    BQCHK(check_fit(c, f));
+    if (!grad)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    LgoGroups g;
+    BQCHK(lgo_groups(c, f, idx, start, G, g));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d;
+    LgoWs w;
+    double tot = 0.0;
+    BQCHK(fit_lgo(c, f, g, true, w, &tot));
+    if (!(f->have & bq_fit::PROD)) {
+        const HessJob hj = fit_hess_job(f);
+        BQCHK(launch_hess_products(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h, f->s));
+        f->have |= bq_fit::PROD;
+    }
+    BQCHK(launch_lgo_grad(c, d, f->gX.d(), f->hB.d(), f->n, f->npad, g.T, g.G, g.NB, g.maxb, f->h, f->s,
+                          f->g.s2, w));
+    double gd[BQ_MAXD + 2];
+    HIPCHK(c, hipMemcpyAsync(gd, w.out + 1, sizeof(double) * (d + 2), hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int p = 0; p < d + 2; ++p)
+        grad[p] = gd[p];
+    if (total)
+        *total = tot;
+    return BQ_OK;
+}
+
 extern "C" int bq_gp_get(bq_ctx *c, bq_fit *f, int which, double *out)
 {
     BQCHK(check_fit(c, f));

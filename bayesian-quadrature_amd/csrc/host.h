@@ -10,7 +10,8 @@
 // libbqhip_probe.so, whose extra entry points include/bqhip_probe.h declares):
 //   k_gram.hip   gram.h kernels                 launch_gram_sym / _cross
 //   k_gemm.hip   gemm.h trsmsweep.h kernels     launch_gemm, launch_gemm_rows, launch_rows_step
-//   k_hess.hip   hess.h loo.h kernels           the log-ML Hessian's sums, leave-one-out
+//   k_hess.hip   hess.h loo.h lgo.h kernels     the log-ML Hessian's sums, leave-one-out and
+//                                               leave-group-out
 //                ptheta.h kernels               the posterior's derivatives in the hyper-parameters
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
@@ -356,6 +357,25 @@ int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const dou
                int npad, double *ws, const double **vecs, const double **total);
 int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const double *alpha,
                     int n, int npad, double h, double s, double s2, double *ws, const double **grad);
+// leave-group-out (lgo.h) into its own workspace: G groups of T members in all, packed into NB
+// bundles of consecutive groups with at most 64 members together (group bundle[q] begins bundle
+// q).  The views of one workspace (lgo_ws_doubles; with grad: the partials of Q_BB and the M_k
+// behind the rest)
+struct LgoWs {
+    int *idx, *start, *flag;      // T, G + 1, 1
+    int *bundle;                  // NB + 1 <= G + 1
+    double *sig, *r, *mu, *var;   // T x 64, T, T, T
+    double *lp, *ar, *gpart, *out; // G, G, G (d + 2), total | grad
+    double *part;                 // [nchunk][T][64]; with grad [1 + d][nchunk][T][64] follow
+};
+size_t lgo_ws_doubles(int npad, int d, long T, long G, bool grad);
+LgoWs lgo_views(double *ws, int npad, int d, long T, long G);
+// maxb: the largest bundle.  launch_lgo: mu, var, lp, total (*out) and what the gradient reads
+int launch_lgo(bq_ctx *c, const double *Y, const double *alpha, const double *y, int n, int npad,
+               int d, long T, long G, long NB, int maxb, const LgoWs &w);
+// after launch_lgo on the same workspace: the gradient (out + 1) from the products stage (Ki, hws)
+int launch_lgo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, int n, int npad, long T,
+                    long G, long NB, int maxb, double h, double s, double s2, const LgoWs &w);
 // the posterior's derivatives in the hyper-parameters (ptheta.h): the right-hand sides of the fit's
 // solved vectors, q_jk = beta_j^T D_k beta_j in column-block pieces (ptheta_part_doubles of them),
 // the row sums with the finished derivatives, and the fused mean route
@@ -721,8 +741,9 @@ struct bq_fit : FitCore {
     //   Y         gY: Y = L^-T, zero below its diagonal (gX: the    WIDE        fit_y
     //             sweep's workspace)
     //   PROD      gX, hB: the Hessian's products stage (Kxx^-1,     Y, ALPHA    bq_gp_logml_hess or
-    //             the d products, the vectors D_p a and                         bq_gp_loo_grad,
-    //             Kxx^-1 D_p a), which both of them read                        whichever is first
+    //             the d products, the vectors D_p a and                         bq_gp_loo_grad or
+    //             Kxx^-1 D_p a), which all of them read                         bq_gp_lgo_grad,
+    //                                                                           whichever is first
     //   HESS      hess                                              PROD        bq_gp_logml_hess
     //   LOO       loo: mu | var | lp; loo_total                     Y, ALPHA    fit_loo
     //   LOO_GRAD  loo_grad                                          PROD, LOO   bq_gp_loo_grad
@@ -764,6 +785,10 @@ struct bq_fit : FitCore {
     // density per point and the partial sums (loo_ws_doubles), allocated on the first call
     DevBuf loo;
     double loo_total = 0, loo_grad[BQ_MAXD + 2] = {0};
+    // leave-group-out (bq_gp_lgo, bq_gp_lgo_grad): the groups, their blocks and partial sums
+    // (lgo_ws_doubles), grown on demand and kept.  Nothing of it is a result that `have` tracks:
+    // every call computes its own groups anew.
+    DevBuf lgo;
     // the posterior's derivatives in the hyper-parameters (bq_gp_predict_dtheta): [u, z_1 .. z_d]
     // as rows, 64 x npad, and as much again for the two row sweeps that solve them (fit_dkz),
     // allocated on the first call; the quad product's partial sums, grown on demand and kept
@@ -806,7 +831,7 @@ inline void fit_adopt(bq_fit *f, FitCore &core)
 {
     f->swap(core);
     for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart, &f->hB,
-                      &f->loo, &f->dkz, &f->wq})
+                      &f->loo, &f->lgo, &f->dkz, &f->wq})
         b->release();
     if (f->hvec)
         (void)hipHostFree(f->hvec);

@@ -1,9 +1,10 @@
 // k_hess.hip -- the log-ML Hessian's kernels (hess.h), the leave-one-out kernels that read its
-// products (loo.h), the posterior's derivatives in the hyper-parameters, which generate the same
-// derivative operand (ptheta.h), and their launchers.
+// products (loo.h) and their leave-group-out counterparts (lgo.h), the posterior's derivatives in
+// the hyper-parameters, which generate the same derivative operand (ptheta.h), and their launchers.
 #include "host.h"
 #include "hess.h"
 #include "loo.h"
+#include "lgo.h"
 #include "ptheta.h"
 
 namespace bqh {
@@ -222,6 +223,97 @@ int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const
     case 7: return loo_grad_run<7>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
     default: return loo_grad_run<8>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
     }
+}
+
+// ---- leave-group-out (lgo.h) ------------------------------------------------------------
+static_assert(BQ_LGO_MAXB == BQ_LGO_MAX, "lgo.h's blocks hold the ABI's largest group");
+// Columns per workgroup of the block products: at most 8 chunks (their partials are T x 64
+// doubles per chunk and product), and no chunk below 256 columns
+static int lgo_cw(int npad) { return (std::max(256, npad / 8) + BQ_LGO_SLAB - 1) / BQ_LGO_SLAB * BQ_LGO_SLAB; }
+static int lgo_chunks(int npad) { return (npad + lgo_cw(npad) - 1) / lgo_cw(npad); }
+// idx (T) | start (G + 1) | flag | bundle (up to G + 1), in doubles
+static size_t lgo_ints(long T, long G) { return ((size_t)T + 2 * (size_t)G + 3 + 1) / 2; }
+static size_t lgo_off_part(int d, long T, long G)
+{
+    return lgo_ints(T, G) + (size_t)T * (64 + 3) + (size_t)G * (2 + d + 2) + (size_t)(d + 3);
+}
+static size_t lgo_part_doubles(int npad, long T) { return (size_t)lgo_chunks(npad) * T * 64; }
+size_t lgo_ws_doubles(int npad, int d, long T, long G, bool grad)
+{
+    return lgo_off_part(d, T, G) + (size_t)(grad ? 2 + d : 1) * lgo_part_doubles(npad, T);
+}
+LgoWs lgo_views(double *ws, int npad, int d, long T, long G)
+{
+    LgoWs w;
+    w.idx = reinterpret_cast<int *>(ws);
+    w.start = w.idx + T;
+    w.flag = w.start + G + 1;
+    w.bundle = w.flag + 1;
+    w.sig = ws + lgo_ints(T, G);
+    w.r = w.sig + (size_t)T * 64;
+    w.mu = w.r + T;
+    w.var = w.mu + T;
+    w.lp = w.var + T;
+    w.ar = w.lp + G;
+    w.gpart = w.ar + G;
+    w.out = w.gpart + (size_t)G * (d + 2);
+    w.part = ws + lgo_off_part(d, T, G);
+    return w;
+}
+
+template <int MODE>
+static void lgo_launch_blocks(bq_ctx *c, int maxb, unsigned nprod, const double *A, const double *P,
+                              int n, int npad, long T, long NB, const LgoWs &w, double *part)
+{
+    const dim3 grid((unsigned)NB, (unsigned)lgo_chunks(npad), nprod);
+    const int cw = lgo_cw(npad);
+    if (maxb <= 16)
+        hipLaunchKernelGGL((lgo_block_kernel<MODE, 1>), grid, dim3(256), 0, c->stream, A, P, n, npad,
+                           cw, w.idx, w.start, w.bundle, T, part);
+    else if (maxb <= 32)
+        hipLaunchKernelGGL((lgo_block_kernel<MODE, 2>), grid, dim3(256), 0, c->stream, A, P, n, npad,
+                           cw, w.idx, w.start, w.bundle, T, part);
+    else
+        hipLaunchKernelGGL((lgo_block_kernel<MODE, 4>), grid, dim3(256), 0, c->stream, A, P, n, npad,
+                           cw, w.idx, w.start, w.bundle, T, part);
+}
+
+int launch_lgo(bq_ctx *c, const double *Y, const double *alpha, const double *y, int n, int npad,
+               int d, long T, long G, long NB, int maxb, const LgoWs &w)
+{
+    if (d < 1 || d > BQ_MAXD || (npad % 64) || maxb < 1 || maxb > BQ_LGO_MAXB || G < 1 || T < G ||
+        NB < 1 || NB > G)
+        return fail(c, BQ_ERR_BAD_ARG, "lgo: d in [1, %d], npad a multiple of 64, groups of 1 .. %d",
+                    BQ_MAXD, BQ_LGO_MAXB);
+    Bracket br(c, BQ_K_REDUCE);
+    lgo_launch_blocks<LGO_YY>(c, maxb, 1, Y, nullptr, n, npad, T, NB, w, w.part);
+    hipLaunchKernelGGL(lgo_group_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, w.part,
+                       lgo_chunks(npad), T, w.idx, w.start, alpha, y, w.sig, w.r, w.mu, w.var, w.lp,
+                       w.ar, w.flag);
+    hipLaunchKernelGGL(lgo_fold_kernel, dim3(1), dim3(256), 0, c->stream, w.lp, (int)G, 1, w.out);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_lgo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, int n, int npad, long T,
+                    long G, long NB, int maxb, double h, double s, double s2, const LgoWs &w)
+{
+    if (d < 1 || d > BQ_MAXD || (npad % 64) || maxb < 1 || maxb > BQ_LGO_MAXB || G < 1 || T < G ||
+        NB < 1 || NB > G)
+        return fail(c, BQ_ERR_BAD_ARG, "lgo_grad: d in [1, %d], npad a multiple of 64, groups of 1 .. %d",
+                    BQ_MAXD, BQ_LGO_MAXB);
+    const double *B = hws, *Z = hws + hess_off_v(npad, d) + (size_t)(d + 2) * npad;
+    double *gp = w.part + lgo_part_doubles(npad, T); // [1 + d][nchunk][T][64]
+    Bracket br(c, BQ_K_REDUCE);
+    lgo_launch_blocks<LGO_PP>(c, maxb, 1, nullptr, Ki, n, npad, T, NB, w, gp);
+    lgo_launch_blocks<LGO_BP>(c, maxb, (unsigned)d, B, Ki, n, npad, T, NB, w, gp);
+    hipLaunchKernelGGL(lgo_group_grad_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, gp,
+                       lgo_chunks(npad), T, w.idx, w.start, w.sig, w.r, w.ar, Z, d, npad, h, s, s2,
+                       w.gpart);
+    hipLaunchKernelGGL(lgo_fold_kernel, dim3((unsigned)(d + 2)), dim3(256), 0, c->stream, w.gpart,
+                       (int)G, d + 2, w.out + 1);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
 }
 
 // ---- the posterior's derivatives in the hyper-parameters (ptheta.h; fit.hip, bq_gp_predict_dtheta) ----

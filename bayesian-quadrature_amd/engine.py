@@ -32,6 +32,23 @@ def _wvec(w, d):
     return w
 
 
+def _flat_groups(groups):
+    """A sequence of integer index sequences as (idx, start), int64: group g is
+    idx[start[g]:start[g + 1]] (bq_gp_lgo).  What the indices may be is the library's to check."""
+    try:
+        groups = [np.asarray(g) for g in groups]
+    except TypeError:
+        raise ValueError("groups must be a sequence of integer index sequences")
+    for g in groups:
+        if g.ndim != 1 or (g.size and g.dtype.kind not in "iu"):
+            raise ValueError("every group must be a one-dimensional sequence of integers")
+    idx = np.concatenate([g.astype(np.int64) for g in groups]) if groups \
+        else np.empty(0, dtype=np.int64)
+    start = np.zeros(len(groups) + 1, dtype=np.int64)
+    np.cumsum(np.array([g.size for g in groups], dtype=np.int64), out=start[1:])
+    return np.ascontiguousarray(idx), start
+
+
 class Engine(object):
     """A device context.  Not thread-safe; use one per thread / per GPU."""
 
@@ -782,6 +799,37 @@ class Fit(object):
         e = self._eng
         e._check(e._lib.bq_gp_loo_grad(e._ctx, self._handle(), C.cast(C.byref(total), _dp),
                                        L.dptr(g)))
+        return float(total.value), g
+
+    def lgo(self, groups):
+        """Leave-group-out cross-validation (bq_gp_lgo): (mean, var, logpred, total).  ``groups``
+        is a sequence of integer index sequences, disjoint, of 1 to 64 indices in [0, n) each; they
+        need not cover the fit.  mean and var, (T,) in the order of the concatenated groups: the
+        predictive mean and variance (of the noisy observation) of every member from the points
+        outside its group; logpred, (G,): each group's joint log density at its targets; total:
+        their sum.  ValueError for groups that break these rules, LinAlgError when a group's
+        block of Kxx^-1 is not positive definite."""
+        idx, start = _flat_groups(groups)
+        T, G = idx.size, start.size - 1
+        mean, var, lp = np.empty(T), np.empty(T), np.empty(G)
+        total = C.c_double()
+        e = self._eng
+        e._check(e._lib.bq_gp_lgo(e._ctx, self._handle(), idx.ctypes.data_as(L._i64p),
+                                  start.ctypes.data_as(L._i64p), G, L.dptr(mean), L.dptr(var),
+                                  L.dptr(lp), C.cast(C.byref(total), _dp)))
+        return mean, var, lp, float(total.value)
+
+    def lgo_grad(self, groups):
+        """(total, grad): the leave-group-out log predictive density of ``groups`` (see ``lgo``;
+        the same bits as its total) and its gradient, (d + 2,) in the order of ``logml_grad``
+        (bq_gp_lgo_grad)."""
+        idx, start = _flat_groups(groups)
+        g = np.empty(self.d + 2)
+        total = C.c_double()
+        e = self._eng
+        e._check(e._lib.bq_gp_lgo_grad(e._ctx, self._handle(), idx.ctypes.data_as(L._i64p),
+                                       start.ctypes.data_as(L._i64p), start.size - 1,
+                                       C.cast(C.byref(total), _dp), L.dptr(g)))
         return float(total.value), g
 
     def _get(self, which, shape):

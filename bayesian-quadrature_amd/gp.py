@@ -335,6 +335,59 @@ class GP(object):
         device fit (bq_gp_loo_grad); memoised like ``dloglh_dtheta``."""
         return self._memo("dlogloo_dtheta", lambda: self._device_fit().loo_grad()[1])
 
+    def clusters(self, thresh):
+        """The single-linkage groups of ``x`` on the host: the sorted points are split wherever
+        the gap to the next one exceeds ``thresh``, and a cluster of more than 64 points is cut
+        into runs of at most 64.  Singletons are included: the result, a list of index arrays in
+        the order of the sorted points, is a partition ready for ``lgo``."""
+        thresh = float(thresh)
+        if not thresh >= 0:
+            raise ValueError("invalid value for thresh: %s" % thresh)
+        order = np.argsort(self._x, kind="stable")
+        if order.size == 0:
+            return []
+        cuts = np.flatnonzero(np.diff(self._x[order]) > thresh) + 1
+        out = []
+        for c in np.split(order, cuts):
+            out.extend(c[i:i + 64] for i in range(0, c.size, 64))
+        return out
+
+    @staticmethod
+    def _group_key(groups):
+        """The groups as a tuple of tuples of ints: what the memo is keyed by."""
+        try:
+            arrs = [np.asarray(g) for g in groups]
+        except TypeError:
+            raise ValueError("groups must be a sequence of integer index sequences")
+        if any(a.ndim != 1 or (a.size and a.dtype.kind not in "iu") for a in arrs):
+            raise ValueError("every group must be a one-dimensional sequence of integers")
+        return tuple(tuple(a.tolist()) for a in arrs)
+
+    def _lgo(self, groups):
+        key = self._group_key(groups)
+        return self._memo(("lgo", key), lambda: self._device_fit().lgo(key))
+
+    def lgo(self, groups):
+        """Leave-group-out cross-validation at the current parameters: (mean, var, logpred) with
+        whole groups of observations left out at once -- ``groups`` is a sequence of disjoint
+        index sequences of 1 to 64 indices each, such as ``clusters(thresh)``; a point in no
+        group is never left out.  mean and var follow the concatenated groups, logpred has one
+        joint log density per group (bq_gp_lgo: closed form on the device fit, nothing
+        refitted).  Memoised per tuple of groups, and dropped by what drops ``loo``.  Where
+        samples lie next to each other ``loo`` is flattered by the neighbour that stays in;
+        leaving the cluster out is not."""
+        return self._lgo(groups)[:3]
+
+    def log_lgo(self, groups):
+        """The leave-group-out log predictive density, the sum of ``lgo(groups)[2]``; memoised."""
+        return self._lgo(groups)[3]
+
+    def dloglgo_dtheta(self, groups):
+        """Gradient of ``log_lgo(groups)`` in the order of ``params``, [d/dh, d/dw, d/ds], from
+        the device fit (bq_gp_lgo_grad); memoised like ``lgo``."""
+        key = self._group_key(groups)
+        return self._memo(("dloglgo_dtheta", key), lambda: self._device_fit().lgo_grad(key)[1])
+
     def hyper_cov(self, params):
         """Laplace covariance of the named subset of ("h", "w", "s") at the current parameters:
         the inverse of minus the Hessian of ``log_lh`` restricted to them, in their own units
@@ -353,11 +406,14 @@ class GP(object):
         C = np.linalg.inv(A)
         return 0.5 * (C + C.T)
 
-    def fit_MLII(self, params, method="L-BFGS-B", ntry=10, objective="log_lh"):
+    def fit_MLII(self, params, method="L-BFGS-B", ntry=10, objective="log_lh", groups=None):
         """Maximise ``log_lh`` over the named subset of ("h", "w", "s") with the exact gradient
         (util.find_good_parameters with ``logpdf_grad``).  ``objective="loo"`` maximises the
-        leave-one-out log predictive density ``log_loo`` with ``dlogloo_dtheta`` instead; any
-        other objective is a ValueError.
+        leave-one-out log predictive density ``log_loo`` with ``dlogloo_dtheta`` instead, and
+        ``objective="lgo"`` the leave-group-out density ``log_lgo(groups)`` with
+        ``dloglgo_dtheta(groups)``: ``groups`` (see ``lgo``) is required for it, fixed for the
+        whole optimisation, and must be None for the other objectives.  Any other objective is a
+        ValueError.
 
         Positivity by reparametrisation: the search runs over log h, log w and log s, so every
         point it evaluates has h, w, s > 0 and none lies on the edge s = 0, where Kxx of close
@@ -365,9 +421,16 @@ class GP(object):
         An s that starts at exactly 0 has no logarithm: it is searched as it is, under the
         L-BFGS-B bound s >= 0.  Leaves the GP at the optimum and returns the optimiser's summary
         (x in the parameters' own units); RuntimeError when no optimum is found."""
-        if objective not in ("log_lh", "loo"):
-            raise ValueError("objective: 'log_lh' or 'loo'")
-        loo = objective == "loo"
+        if objective not in ("log_lh", "loo", "lgo"):
+            raise ValueError("objective: 'log_lh', 'loo' or 'lgo'")
+        if (objective == "lgo") != (groups is not None):
+            raise ValueError("groups: required for objective 'lgo', None otherwise")
+        if groups is not None:
+            groups = self._group_key(groups)
+        value = {"log_lh": lambda: self.log_lh, "loo": lambda: self.log_loo,
+                 "lgo": lambda: self.log_lgo(groups)}[objective]
+        gradient = {"log_lh": lambda: self.dloglh_dtheta, "loo": lambda: self.dlogloo_dtheta,
+                    "lgo": lambda: self.dloglgo_dtheta(groups)}[objective]
         names = ("h", "w", "s")
         params = list(params)
         if not params or any(p not in names for p in params) or len(set(params)) != len(params):
@@ -388,7 +451,7 @@ class GP(object):
         def logpdf(u):
             try:
                 set_all(theta(u))
-                return self.log_loo if loo else self.log_lh
+                return value()
             except (ValueError, np.linalg.LinAlgError):
                 return -np.inf
 
@@ -397,7 +460,7 @@ class GP(object):
             if not np.isfinite(f):
                 return f, np.zeros(len(params))
             t = theta(u)
-            g = self.dlogloo_dtheta if loo else self.dloglh_dtheta
+            g = gradient()
             return f, g[idx] * np.where(logp, t, 1.0)
 
         u = util.find_good_parameters(logpdf, u0, method, ntry=ntry, logpdf_grad=logpdf_grad,
@@ -408,7 +471,7 @@ class GP(object):
         x = theta(u)
         set_all(x)
         opt = util.LAST_OPT
-        fun = -(self.log_loo if loo else self.log_lh)
+        fun = -value()
         return optim.OptimizeResult(x=x, fun=fun, success=opt.get("success", False),
                                     nfev=opt.get("nfev", -1), nit=opt.get("nit", -1),
                                     attempts=opt.get("attempts", -1))

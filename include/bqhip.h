@@ -45,6 +45,7 @@ extern "C" {
 #define BQ_ERR_NOMEM 4   /* allocation failure -> MemoryError */
 
 #define BQ_MAX_DIM 8 /* largest input dimension d */
+#define BQ_LGO_MAX 64 /* largest group of bq_gp_lgo / bq_gp_lgo_grad */
 
 typedef struct bq_ctx bq_ctx;
 typedef struct bq_fit bq_fit;
@@ -222,6 +223,28 @@ int bq_gp_loo(bq_ctx *ctx, bq_fit *fit, double *mean, double *var, double *logpr
  * that O((d + 1) n^2).  Device memory: the Hessian's, and (d + 5) npad doubles and partial sums
  * more, all allocated before anything runs: BQ_ERR_NOMEM leaves the fit as it was. */
 int bq_gp_loo_grad(bq_ctx *ctx, bq_fit *fit, double *total, double *grad);
+/* Leave-group-out cross-validation: whole groups of observations left out at once (a cluster of
+ * close samples, a block, a fold).  Group g is idx[start[g] .. start[g + 1]), start[0] = 0,
+ * T = start[G]; the groups are disjoint, hold 1 .. BQ_LGO_MAX indices each and need not cover the
+ * fit (a point in no group is never left out).  mean and var (T doubles each, in the order of
+ * idx): the predictive mean and variance of the noisy observation (s^2 included; the diagonal of
+ * the group's predictive covariance) from the points outside its group; logpred (G doubles): the
+ * joint log density of each group at its targets; *total: their sum.  Any output may be NULL, not
+ * all four.  Closed form from the groups' blocks of Kxx^-1 and Kxx^-1 y: O(n b^2) per group of b
+ * once L^-T is there, nothing refitted.  BQ_ERR_BAD_ARG: a stale fit, G < 1, an empty group or one
+ * above the cap, an index out of range or given twice; BQ_ERR_NOT_PD: a block of Kxx^-1 with a
+ * pivot that is not positive and finite, and then no output is written.  The same bits on every
+ * call, whatever ran before; nothing is kept between calls but the workspace, allocated before
+ * anything runs (BQ_ERR_NOMEM leaves the fit as it was). */
+int bq_gp_lgo(bq_ctx *ctx, bq_fit *fit, const int64_t *idx, const int64_t *start, int64_t G,
+              double *mean, double *var, double *logpred, double *total);
+/* Gradient of that total with respect to the hyper-parameters, in the order of bq_gp_logml_grad:
+ * grad has d + 2 entries on the host (required); total: the value, bit for bit bq_gp_lgo's, or
+ * NULL.  Reads the Hessian's products stage as bq_gp_loo_grad does (built here if it is not
+ * there, and then kept for the Hessian and bq_gp_loo_grad); beyond that O((d + 1) n b^2) per
+ * group. */
+int bq_gp_lgo_grad(bq_ctx *ctx, bq_fit *fit, const int64_t *idx, const int64_t *start, int64_t G,
+                   double *total, double *grad);
 /* which: 0 = L (n x n, strict upper zeroed), 1 = alpha = Kxx^-1 y (n),
  * 2 = z = L^-1 y (n), 3 = Kxx (n x n, recomputed) */
 int bq_gp_get(bq_ctx *ctx, bq_fit *fit, int which, double *out_host);
