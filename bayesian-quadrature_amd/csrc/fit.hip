@@ -33,17 +33,39 @@ static void fit_set_params(bq_fit *f, double h, const double *w, double s, int M
     f->L = make_layout(f->n, M, true); // same ntot: border points share the y row's block
 }
 
-// buf holds at least `bytes` (kept between calls), or the call fails: "<what> (<bytes> bytes): ..."
-static int fit_grow(bq_ctx *c, DevBuf &buf, size_t bytes, const char *what)
+// A pinned staging buffer of a fit as both sides see it.  Its small transfers go through one kernel
+// each on the device's view: a copy-engine operation costs the stream 8-9 us, a further kernel 2.9
+// (tools/stream_ops_bench.hip); a refit at the reference's own sizes is 40 us in all.
+struct Staging {
+    double *host = nullptr;
+    double *dev = nullptr; // null: kernel copies are off (BQ_SOLVE_KCOPY=0), the copy engine moves it
+};
+
+static int stage_view(bq_ctx *c, double *host, Staging &st)
 {
-    if (buf.bytes >= bytes)
-        return BQ_OK;
-    const hipError_t e = buf.alloc(bytes);
-    if (e == hipSuccess)
-        return BQ_OK;
-    (void)hipGetLastError();
-    return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP, "%s (%zu bytes): %s", what,
-                bytes, hipGetErrorString(e));
+    st.host = host;
+    st.dev = nullptr;
+    if (c->cfg.solve_kcopy && host)
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&st.dev), host, 0));
+    return BQ_OK;
+}
+
+// n1 (and n2) 8-byte words between device memory p1 (p2) and the staging at word at1 (at2), `in`:
+// towards the device: one launch, else a copy-engine operation each
+static int stage_copy(bq_ctx *c, const Staging &st, bool in, void *p1, size_t at1, size_t n1,
+                      void *p2 = nullptr, size_t at2 = 0, size_t n2 = 0)
+{
+    if (st.dev) {
+        double *m1 = st.dev + at1, *m2 = n2 ? st.dev + at2 : nullptr;
+        return in ? launch_copy_words2(c, p1, m1, n1, p2, m2, n2)
+                  : launch_copy_words2(c, m1, p1, n1, m2, p2, n2);
+    }
+    const hipMemcpyKind kind = in ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    double *h1 = st.host + at1, *h2 = st.host + at2;
+    HIPCHK(c, hipMemcpyAsync(in ? p1 : h1, in ? h1 : p1, sizeof(double) * n1, kind, c->stream));
+    if (n2)
+        HIPCHK(c, hipMemcpyAsync(in ? p2 : h2, in ? h2 : p2, sizeof(double) * n2, kind, c->stream));
+    return BQ_OK;
 }
 
 // pm / pv: device buffers for the posterior mean / variance of the layout's M border points
@@ -61,37 +83,20 @@ static int fit_factor(bq_ctx *c, bq_fit *f, double *pm = nullptr, double *pv = n
     f->drop(bq_fit::FACTOR_CHANGED);
     BQCHK(fit_stage(c, f));
     std::memcpy(f->hfit + HF_PAR, &f->g, sizeof f->g);
-    // The call's small transfers -- kernel parameters (and border points) in, the record out -- go
-    // through one kernel each on the mapped staging buffer: a copy-engine operation costs the
-    // stream 8-9 us, a further kernel 2.9 (tools/stream_ops_bench.hip); a refit at the reference's
-    // own sizes is 40 us in all.
-    double *hmap = nullptr;
-    if (c->cfg.solve_kcopy)
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hfit, 0));
+    // the call's small transfers: kernel parameters (and border points) in, the record out
+    Staging st;
+    BQCHK(stage_view(c, f->hfit, st));
     static_assert(sizeof(GaussParams) % 8 == 0, "GaussParams is copied in 8-byte words");
-    if (hmap) {
-        BQCHK(launch_copy_words2(c, f->gp.p, hmap + HF_PAR, sizeof f->g / 8,
-                                 f->pts.d() + (size_t)f->d * f->npad, hmap + HF_PTS, npts_words));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(f->gp.p, f->hfit + HF_PAR, sizeof f->g, hipMemcpyHostToDevice,
-                                 c->stream));
-        if (npts_words)
-            HIPCHK(c, hipMemcpyAsync(f->pts.d() + (size_t)f->d * f->npad, f->hfit + HF_PTS,
-                                     sizeof(double) * npts_words, hipMemcpyHostToDevice,
-                                     c->stream));
-    }
+    BQCHK(stage_copy(c, st, true, f->gp.p, HF_PAR, sizeof f->g / 8,
+                     f->pts.d() + (size_t)f->d * f->npad, HF_PTS, npts_words));
     const GramSeed sys{f->pts.d(), 0, f->y.d(), 0, static_cast<const GaussParams *>(f->gp.p), 0,
                        f->L, f->d, 0, 0};
     BQCHK(enqueue_bordered(c, sys, 1, f->A.d(), f->ldl, 0, f->dinv.d() + f->npad, info,
                            f->panel.d(), f->panel.bytes / sizeof(double), scal, pm, pv, 64L, false,
                            0.0));
     // one read-back: misc = [info (int, 8 bytes) | pad | scal[4] | pad | mean[64] | var[64]]
-    double *hm = f->hfit;
-    if (hmap)
-        BQCHK(launch_copy_words2(c, hmap, f->misc.p, hpost ? 8 + 128 : 6, nullptr, nullptr, 0));
-    else
-        HIPCHK(c, hipMemcpyAsync(hm, f->misc.p, sizeof(double) * (hpost ? 8 + 128 : 6),
-                                 hipMemcpyDeviceToHost, c->stream));
+    const double *hm = f->hfit;
+    BQCHK(stage_copy(c, st, false, f->misc.p, 0, hpost ? 8 + 128 : 6));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (hpost)
         std::memcpy(hpost, hm + 8, sizeof(double) * 128);
@@ -140,8 +145,8 @@ int fit_wide(bq_ctx *c, bq_fit *f, WideInv &w)
 {
     if (!(f->have & bq_fit::WIDE)) {
         BQCHK(fit_dw(c, f));
-        if (f->wide.bytes < sizeof(double) * wide_alloc_doubles(f->npad))
-            HIPCHK(c, f->wide.alloc(sizeof(double) * wide_alloc_doubles(f->npad)));
+        BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(f->npad),
+                       "wide block inverses"));
         BQCHK(compute_wide_inverses(c, f->A.d(), f->ldl, f->npad, f->dw.d(), f->wide.d()));
         f->have |= bq_fit::WIDE;
     }
@@ -155,8 +160,7 @@ int fit_vec(bq_ctx *c, bq_fit *f)
     // x | y | the one-launch sweeps' workspace (ticket + x versions) | a solve's second vector
     // and second workspace (bq_gp_solve: both sweeps' slots are filled in one launch)
     const size_t need = 3 * (size_t)f->npad + 2 * trsv_flow_ws_doubles(f->npad, wide_block(f->npad));
-    if (f->vec.bytes < sizeof(double) * need)
-        HIPCHK(c, f->vec.alloc(sizeof(double) * need));
+    BQCHK(fit_grow(c, f->vec, sizeof(double) * need, "single-vector workspace"));
     if (!f->hvec)
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hvec),
                                 sizeof(double) * (size_t)f->npad));
@@ -353,14 +357,13 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
     int *info = reinterpret_cast<int *>(sc.at(oinfo));
 
     // ---- the observations in: through the fit's mapped staging when they fit in it
-    double *hmap = nullptr;
-    if (c->cfg.solve_kcopy && f->hfit)
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&hmap), f->hfit, 0));
+    Staging st;
+    BQCHK(stage_view(c, f->hfit, st));
     const size_t nx = (size_t)d * k;
-    if (hmap && nx + k <= HF_NPTS) {
+    if (st.dev && nx + k <= HF_NPTS) {
         std::memcpy(f->hfit + HF_PTS, x_new, sizeof(double) * nx);
         std::memcpy(f->hfit + HF_PTS + nx, y_new, sizeof(double) * k);
-        BQCHK(launch_copy_words2(c, xn, hmap + HF_PTS, nx, yn, hmap + HF_PTS + nx, (size_t)k));
+        BQCHK(stage_copy(c, st, true, xn, HF_PTS, nx, yn, HF_PTS + nx, (size_t)k));
     } else {
         HIPCHK(c, hipMemcpyAsync(xn, x_new, sizeof(double) * nx, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(yn, y_new, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
@@ -435,11 +438,8 @@ extern "C" int bq_gp_append(bq_ctx *c, bq_fit *f, const double *x_new, const dou
     job.logdet = f->logdet, job.qf = f->qf;
     job.d = d, job.n = n, job.k = k, job.kp = kp, job.yrow = to.L.yrow;
     BQCHK(launch_append_commit(c, job));
-    double *hm = f->hfit;
-    if (hmap)
-        BQCHK(launch_copy_words2(c, hmap, out, 6, nullptr, nullptr, 0));
-    else
-        HIPCHK(c, hipMemcpyAsync(hm, out, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
+    const double *hm = f->hfit;
+    BQCHK(stage_copy(c, st, false, out, 0, 6));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int hinfo = 0;
     std::memcpy(&hinfo, hm, sizeof hinfo);
@@ -626,8 +626,7 @@ extern "C" int bq_gp_logml_grad(bq_ctx *c, bq_fit *f, double *grad)
     BQCHK(fit_alpha(c, f));
     BQCHK(fit_y(c, f));
     const size_t np = grad_parts(npad, d);
-    if (f->gpart.bytes < sizeof(double) * (np + BQ_MAXD + 2))
-        HIPCHK(c, f->gpart.alloc(sizeof(double) * (np + BQ_MAXD + 2)));
+    BQCHK(fit_grow(c, f->gpart, sizeof(double) * (np + BQ_MAXD + 2), "gradient partial sums"));
     GradJob gj;
     gj.alpha = f->alpha.d();
     gj.pts = f->pts.d();
@@ -665,6 +664,22 @@ static HessJob fit_hess_job(const bq_fit *f)
     return hj;
 }
 
+// The Hessian's products stage in gX and hB (Kxx^-1, the d products Kxx^-1 dK/dw_k, the vectors
+// D_p a and Kxx^-1 D_p a), built on its first use after a (re)fit or new targets: the Hessian's sums
+// and both cross-validation gradients read it
+static int fit_prod(bq_ctx *c, bq_fit *f)
+{
+    if (f->have & bq_fit::PROD)
+        return BQ_OK;
+    BQCHK(fit_hess_ws(c, f));
+    BQCHK(fit_alpha(c, f));
+    BQCHK(fit_y(c, f));
+    BQCHK(launch_hess_products(c, f->d, f->gY.d(), f->gX.d(), f->hB.d(), fit_hess_job(f), f->y.d(),
+                               f->h, f->s));
+    f->have |= bq_fit::PROD;
+    return BQ_OK;
+}
+
 namespace bqh {
 // u = Kxx^-1 alpha and z_k = Kxx^-1 (D_k alpha), k < d, as rows 0 .. d of the 64 x npad matrix in
 // dkz (ld 64; its other rows and its columns at or beyond n are zero), built on their first use
@@ -689,10 +704,11 @@ int fit_dkz(bq_ctx *c, bq_fit *f)
 }
 } // namespace bqh
 
-// d^2 log p / d theta^2 in the gradient's parameter order (hess.h has the formula): Kxx^-1 = Y Y^T
-// into the sweep's idle workspace, one MFMA product Kxx^-1 dK/dw_k per length scale with the
-// derivative generated from the points, tile sums and the quadratic terms on the device; the
-// (d + 2)^2 entries are put together here from those sums.  Kept until the fit changes.
+// d^2 log p / d theta^2 in the gradient's parameter order (hess.h has the formula): the products
+// stage (fit_prod: Kxx^-1 = Y Y^T into the sweep's idle workspace, one MFMA product Kxx^-1 dK/dw_k
+// per length scale with the derivative generated from the points), then tile sums and the quadratic
+// terms on the device; the (d + 2)^2 entries are put together here from those sums.  Kept until the
+// fit changes.
 extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
 {
     BQCHK(check_fit(c, f));
@@ -701,14 +717,9 @@ extern "C" int bq_gp_logml_hess(bq_ctx *c, bq_fit *f, double *hess)
     HIPCHK(c, hipSetDevice(c->device));
     const int d = f->d, np = d + 2;
     if (!(f->have & bq_fit::HESS)) {
-        BQCHK(fit_alpha(c, f));
-        BQCHK(fit_y(c, f));
-        BQCHK(fit_hess_ws(c, f));
-        const HessJob hj = fit_hess_job(f);
+        BQCHK(fit_prod(c, f));
         const double *sums = nullptr;
-        BQCHK(launch_logml_hess(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h, f->s,
-                                (f->have & bq_fit::PROD) != 0, &sums));
-        f->have |= bq_fit::PROD;
+        BQCHK(launch_hess_sums(c, d, f->gX.d(), f->hB.d(), fit_hess_job(f), &sums));
         const int ng = hess_ng(d), nt = hess_nt(d), nq = hess_nq(d);
         double hs[hess_ng(BQ_MAXD) + hess_nt(BQ_MAXD) + hess_nq(BQ_MAXD)];
         HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof(double) * (ng + nt + nq), hipMemcpyDeviceToHost,
@@ -791,10 +802,9 @@ extern "C" int bq_gp_loo(bq_ctx *c, bq_fit *f, double *mean, double *var, double
     return BQ_OK;
 }
 
-// dL_loo / dtheta in the gradient's parameter order: the Hessian's products stage (Kxx^-1, the d
-// products Kxx^-1 dK/dw_k, the vectors Kxx^-1 D_p a) if neither it nor a Hessian has run since the
-// fit last changed, then one read of those matrices for the row sums and one workgroup for the
-// d + 2 entries.  Both workspaces are allocated before anything is launched.
+// dL_loo / dtheta in the gradient's parameter order: the Hessian's products stage (fit_prod), then
+// one read of its matrices for the row sums and one workgroup for the d + 2 entries.  Both
+// workspaces are allocated before anything is launched.
 extern "C" int bq_gp_loo_grad(bq_ctx *c, bq_fit *f, double *total, double *grad)
 {
     BQCHK(check_fit(c, f));
@@ -806,12 +816,7 @@ extern "C" int bq_gp_loo_grad(bq_ctx *c, bq_fit *f, double *total, double *grad)
         BQCHK(fit_hess_ws(c, f));
         BQCHK(fit_loo_ws(c, f));
         BQCHK(fit_loo(c, f));
-        if (!(f->have & bq_fit::PROD)) {
-            const HessJob hj = fit_hess_job(f);
-            BQCHK(launch_hess_products(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h,
-                                       f->s));
-            f->have |= bq_fit::PROD;
-        }
+        BQCHK(fit_prod(c, f));
         const double *gd = nullptr;
         BQCHK(launch_loo_grad(c, d, f->gX.d(), f->hB.d(), f->alpha.d(), f->n, f->npad, f->h, f->s,
                               f->g.s2, f->loo.d(), &gd));
@@ -937,8 +942,8 @@ extern "C" int bq_gp_lgo(bq_ctx *c, bq_fit *f, const int64_t *idx, const int64_t
 }
 
 // dL_lgo / dtheta in the gradient's parameter order: the value stage, the Hessian's products stage
-// if neither it nor a Hessian nor bq_gp_loo_grad has run since the fit last changed, then the
-// groups' blocks of Q and of the M_k and one workgroup per group for its d + 2 entries.
+// (fit_prod), then the groups' blocks of Q and of the M_k and one workgroup per group for its d + 2
+// entries.
 extern "C" int bq_gp_lgo_grad(bq_ctx *c, bq_fit *f, const int64_t *idx, const int64_t *start,
                               int64_t G, double *total, double *grad)
 {
@@ -952,11 +957,7 @@ extern "C" int bq_gp_lgo_grad(bq_ctx *c, bq_fit *f, const int64_t *idx, const in
     LgoWs w;
     double tot = 0.0;
     BQCHK(fit_lgo(c, f, g, true, w, &tot));
-    if (!(f->have & bq_fit::PROD)) {
-        const HessJob hj = fit_hess_job(f);
-        BQCHK(launch_hess_products(c, d, f->gY.d(), f->gX.d(), f->hB.d(), hj, f->y.d(), f->h, f->s));
-        f->have |= bq_fit::PROD;
-    }
+    BQCHK(fit_prod(c, f));
     BQCHK(launch_lgo_grad(c, d, f->gX.d(), f->hB.d(), f->n, f->npad, g.T, g.G, g.NB, g.maxb, f->h, f->s,
                           f->g.s2, w));
     double gd[BQ_MAXD + 2];
@@ -1016,40 +1017,6 @@ extern "C" int bq_gp_get(bq_ctx *c, bq_fit *f, int which, double *out)
 
 namespace bqh {
 
-static hipError_t grow_to(DevBuf &b, size_t bytes)
-{
-    return b.bytes >= bytes ? hipSuccess : b.alloc(bytes);
-}
-
-// The staging of a posterior call (bq_gp_predict, bq_gp_predict_grad): the point and result
-// buffers and the pinned staging for M points and nres doubles of results, the points copied into
-// the staging's front; *hmap: the staging as the device sees it, or null (no kernel copies).
-static int predict_stage(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, size_t nres,
-                         double **hmap)
-{
-    const int d = f->d;
-    // workspaces live in the fit and only grow: a BQ object predicts thousands of times
-    HIPCHK(c, grow_to(f->wx, sizeof(double) * d * M));
-    HIPCHK(c, grow_to(f->wout, sizeof(double) * nres));
-    // points up and results down through pinned staging (asynchronous for real)
-    const size_t need = (size_t)d * M + nres;
-    if (f->hio_len < need) {
-        if (f->hio)
-            (void)hipHostFree(f->hio);
-        f->hio = nullptr;
-        f->hio_len = 0;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hio), sizeof(double) * need));
-        f->hio_len = need;
-    }
-    std::memcpy(f->hio, xo, sizeof(double) * d * M);
-    // (points in and results out through kernels on the mapped staging buffer: a copy-engine
-    // operation costs the stream 8-9 us, a further kernel 2.9 -- tools/stream_ops_bench.hip)
-    *hmap = nullptr;
-    if (c->cfg.solve_kcopy)
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(hmap), f->hio, 0));
-    return BQ_OK;
-}
-
 // whether the cross Gram may read the points out of the mapped staging buffer (bq_gp_predict says
 // why there is a limit)
 static bool predict_direct_ok(int d, int64_t M, int npad)
@@ -1057,36 +1024,130 @@ static bool predict_direct_ok(int d, int64_t M, int npad)
     return (size_t)d * M * sizeof(double) * (size_t)(npad / 64) <= ((size_t)4 << 20);
 }
 
+// The staging of a posterior call (bq_gp_predict, bq_gp_predict_grad, bq_gp_predict_dtheta): M
+// points in, results [mean (Mp) | var (Mp) | dmean (nd Mp) | dvar (nd Mp)] out, Mp = M rounded up
+// to 64, nd gradient rows per point.  Three routes, chosen once in begin():
+//   direct   the kernels read the points out of the mapped pinned staging and write the results
+//            into it (the caller asks for it; predict_direct_ok has the limit);
+//   flow     one kernel copies the points down, one the results up (launch_flow_in / _out);
+//   copies   the same by the copy engine (no kernel copies: BQ_SOLVE_KCOPY=0).
+struct PosteriorIO {
+    bq_fit *f = nullptr;
+    int64_t M = 0;
+    int Mp = 0, nd = 0;
+    bool direct = false;
+    Staging st;                // the points, then the results
+    const double *xq = nullptr; // where the kernels read the points (d x M)
+    double *res = nullptr;      // where they write the results
+
+    int begin(bq_ctx *c, bq_fit *fit, const double *xo, int64_t M_, int nd_, bool want_direct)
+    {
+        f = fit, M = M_, nd = nd_;
+        Mp = (int)roundup(M, 64);
+        const int d = f->d;
+        const size_t npts = (size_t)d * M, nres = (2 + 2 * (size_t)nd) * Mp;
+        // workspaces live in the fit and only grow: a BQ object predicts thousands of times
+        BQCHK(fit_grow(c, f->wx, sizeof(double) * npts, "prediction points"));
+        BQCHK(fit_grow(c, f->wout, sizeof(double) * nres, "prediction results"));
+        // points up and results down through pinned staging (asynchronous for real)
+        if (f->hio_len < npts + nres) {
+            if (f->hio)
+                (void)hipHostFree(f->hio);
+            f->hio = nullptr;
+            f->hio_len = 0;
+            HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&f->hio),
+                                    sizeof(double) * (npts + nres)));
+            f->hio_len = npts + nres;
+        }
+        std::memcpy(f->hio, xo, sizeof(double) * npts);
+        BQCHK(stage_view(c, f->hio, st));
+        direct = want_direct && st.dev && predict_direct_ok(d, M, f->npad);
+        if (direct) {
+            xq = st.dev, res = st.dev + npts;
+            return BQ_OK;
+        }
+        xq = f->wx.d(), res = f->wout.d();
+        if (st.dev)
+            return launch_flow_in(c, st.dev, (int)npts, f->wx.d(), (int)npts, nullptr, 0);
+        HIPCHK(c, hipMemcpyAsync(f->wx.p, st.host, sizeof(double) * npts, hipMemcpyHostToDevice,
+                                 c->stream));
+        return BQ_OK;
+    }
+
+    // the first nout doubles of the results back, the stream synchronised, the segments asked for
+    // handed out (dmean, dvar: nd x M each)
+    int finish(bq_ctx *c, size_t nout, double *mean, double *var, double *dmean, double *dvar)
+    {
+        const size_t npts = (size_t)f->d * M;
+        const double *hres = st.host + npts;
+        if (direct)
+            ;
+        else if (st.dev)
+            BQCHK(launch_flow_out(c, res, (int)nout, st.dev + npts));
+        else
+            HIPCHK(c, hipMemcpyAsync(st.host + npts, res, sizeof(double) * nout,
+                                     hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (mean)
+            std::memcpy(mean, hres, sizeof(double) * M);
+        if (var)
+            std::memcpy(var, hres + Mp, sizeof(double) * M);
+        if (dmean)
+            std::memcpy(dmean, hres + 2 * (size_t)Mp, sizeof(double) * nd * M);
+        if (dvar)
+            std::memcpy(dvar, hres + (2 + (size_t)nd) * Mp, sizeof(double) * nd * M);
+        return BQ_OK;
+    }
+};
+
 // The sweep of a posterior with its variance: V = K(xo, x) L^-T into f->wV2 (Mp x npad, ld Mp,
 // Mp = M rounded up to 64) by a forward sweep with rows = prediction points, f->wV left holding
-// the sweep's partial sums; mean (Mp) | var (Mp) at omean.  xq: the points, d x M -- with `direct`
-// the mapped staging buffer, which the cross Gram then reads itself and pads by itself.
-static int predict_sweep(bq_ctx *c, bq_fit *f, const double *xq, bool direct, int64_t M,
-                         double *omean)
+// the sweep's partial sums; mean (Mp) | var (Mp) at io.res.  With io.direct the points are in the
+// mapped staging buffer, which the cross Gram then reads itself and pads by itself.
+static int predict_sweep(bq_ctx *c, bq_fit *f, const PosteriorIO &io)
 {
-    const int d = f->d, n = f->n, npad = f->npad;
-    const int Mp = (int)roundup(M, 64);
+    const int d = f->d, n = f->n, npad = f->npad, M = (int)io.M, Mp = io.Mp;
     const GaussParams g = f->g;
     WideInv wi;
     BQCHK(fit_wide(c, f, wi));
     DevBuf &V0 = f->wV, &V = f->wV2;
-    HIPCHK(c, grow_to(V0, sizeof(double) * (size_t)Mp * npad));
-    HIPCHK(c, grow_to(V, sizeof(double) * (size_t)Mp * npad));
-    if (direct) {
-        BQCHK(launch_gram_cross_pad(c, d, xq, (int)M, Mp, f->pts.d(), n, npad, g, V0.d(), Mp));
+    BQCHK(fit_grow(c, V0, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, V, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    if (io.direct) {
+        BQCHK(launch_gram_cross_pad(c, d, io.xq, M, Mp, f->pts.d(), n, npad, g, V0.d(), Mp));
     } else {
         HIPCHK(c, hipMemsetAsync(V0.p, 0, sizeof(double) * (size_t)Mp * npad, c->stream));
-        BQCHK(launch_gram_cross(c, d, xq, (int)M, f->pts.d(), n, g, V0.d(), Mp));
+        BQCHK(launch_gram_cross(c, d, io.xq, M, f->pts.d(), n, g, V0.d(), Mp));
     }
     BQCHK(enqueue_forward_rows(c, V0.d(), V.d(), Mp, Mp, f->A.d(), f->ldl, npad, wi));
     // z lives in row yrow of the factor with stride ldl: gathered once per (re)fit
     if (!(f->have & bq_fit::ZC)) {
-        HIPCHK(c, grow_to(f->wz, sizeof(double) * (size_t)npad));
+        BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
         BQCHK(launch_gather_row(c, f->wz.d(), f->A.d() + f->L.yrow, f->ldl, npad));
         f->have |= bq_fit::ZC;
     }
-    BQCHK(launch_rowdot(c, V.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(), g.c, omean, omean + Mp,
-                        1));
+    BQCHK(launch_rowdot(c, V.d(), (long)Mp, M, Mp, npad, f->wz.d(), g.c, io.res, io.res + Mp, 1));
+    return BQ_OK;
+}
+
+// beta = V L^-1 out of V (f->wV2) into the buffer the cross Gram came in (f->wV: the forward sweep
+// left partial sums there; V is consumed, so the row reductions ran first)
+static int predict_beta(bq_ctx *c, bq_fit *f, int Mp)
+{
+    WideInv wi;
+    BQCHK(fit_wide(c, f, wi));
+    return enqueue_backward_rows(c, f->wV2.d(), f->wV.d(), Mp, Mp, f->A.d(), f->ldl, f->npad, wi);
+}
+
+// what the three posterior entry points check alike; *none: there is nothing to do
+static int predict_args(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, bool any_out, bool *none)
+{
+    BQCHK(check_fit(c, f));
+    if (M < 0 || (M && !xo) || !any_out)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    *none = M == 0;
+    if (M)
+        HIPCHK(c, hipSetDevice(c->device));
     return BQ_OK;
 }
 
@@ -1095,17 +1156,13 @@ static int predict_sweep(bq_ctx *c, bq_fit *f, const double *xq, bool direct, in
 extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, double *mean,
                              double *var, double *cov)
 {
-    BQCHK(check_fit(c, f));
-    if (M < 0 || (M && !xo))
-        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
-    if (M == 0)
+    bool none;
+    BQCHK(predict_args(c, f, xo, M, true, &none));
+    if (none)
         return BQ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
     const int d = f->d, n = f->n, npad = f->npad;
-    const int Mp = (int)roundup(M, 64);
-    DevBuf &xod = f->wx, &out = f->wout;
-    double *hmap = nullptr;
-    BQCHK(predict_stage(c, f, xo, M, 2 * (size_t)Mp, &hmap));
+    if (!var && !cov)
+        BQCHK(fit_alpha(c, f));
     // mean + variance without the covariance (BQ.l_var, _set_gp_log_l_params: bq.py:227-228,
     // 942-943) is six launches: the cross Gram reads the points out of the mapped staging buffer
     // and writes its own zero padding, the row reductions write the results into it (round 5:
@@ -1113,23 +1170,16 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
     // (every workgroup column of the cross Gram re-reads the points over PCIe: npad / 64 uncached
     // passes over d M doubles.  Measured a win at N = 1024, M = 256 / 1000; above a few MB of such
     // reads the points go down once through flow_in instead -- ADVICE r05)
-    const bool direct = hmap && var && !cov && predict_direct_ok(d, M, npad);
-    if (direct)
-        ;
-    else if (hmap)
-        BQCHK(launch_flow_in(c, hmap, d * (int)M, xod.d(), d * (int)M, nullptr, 0));
-    else
-        HIPCHK(c, hipMemcpyAsync(xod.p, f->hio, sizeof(double) * d * M, hipMemcpyHostToDevice,
-                                 c->stream));
-    GaussParams g = f->g;
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, xo, M, 0, var && !cov));
+    const int Mp = io.Mp;
+    const GaussParams g = f->g;
     if (!var && !cov) {
         // mean only: fused cross-Gram x alpha
-        BQCHK(fit_alpha(c, f));
-        BQCHK(launch_predict_mean(c, d, xod.d(), (int)M, f->pts.d(), n, f->alpha.d(), g, out.d()));
+        BQCHK(launch_predict_mean(c, d, io.xq, (int)M, f->pts.d(), n, f->alpha.d(), g, io.res));
     } else {
         DevBuf &V = f->wV2;
-        double *omean = direct ? hmap + (size_t)d * M : out.d();
-        BQCHK(predict_sweep(c, f, direct ? hmap : xod.d(), direct, M, omean));
+        BQCHK(predict_sweep(c, f, io));
         if (cov) {
             // cov = K(xo,xo) - V V^T  (Mp x Mp on device, M x M out)
             DevBuf Cd, gd;
@@ -1139,8 +1189,8 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
             g0.s2 = 0.0;
             HIPCHK(c, hipMemsetAsync(Cd.p, 0, Cd.bytes, c->stream));
             HIPCHK(c, hipMemcpyAsync(gd.p, &g0, sizeof g0, hipMemcpyHostToDevice, c->stream));
-            BQCHK(launch_gram_sym(c, d, xod.d(), 0, static_cast<GaussParams *>(gd.p), 0, Cd.d(),
-                                  Mp, 0, (int)M, 1));
+            BQCHK(launch_gram_sym(c, d, io.xq, 0, static_cast<GaussParams *>(gd.p), 0, Cd.d(), Mp,
+                                  0, (int)M, 1));
             GemmJob vvt;
             vvt.C = Cd.d(), vvt.ldc = Mp;
             vvt.P = V.d(), vvt.ldp = Mp;
@@ -1152,98 +1202,49 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
             HIPCHK(c, hipStreamSynchronize(c->stream)); // Cd goes out of scope
         }
     }
-    double *hres = f->hio + (size_t)d * M; // [mean (Mp) | var (Mp)], one copy
-    if (direct)
-        ;
-    else if (hmap)
-        BQCHK(launch_flow_out(c, out.d(), 2 * Mp, hmap + (size_t)d * M));
-    else
-        HIPCHK(c, hipMemcpyAsync(hres, out.p, sizeof(double) * 2 * (size_t)Mp,
-                                 hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (mean)
-        std::memcpy(mean, hres, sizeof(double) * M);
-    if (var)
-        std::memcpy(var, hres + Mp, sizeof(double) * M);
-    return BQ_OK;
+    return io.finish(c, 2 * (size_t)Mp, mean, var, nullptr, nullptr); // [mean | var], one copy
 }
 
 // The posterior and its gradients with respect to the query points (pgrad.h has the formulas).
 // Mean route (no var, no dvar): alpha, then one fused launch, no sweep and no M x n matrix.  Full
 // route: bq_gp_predict's own staging, cross Gram, forward sweep and row reductions (predict_sweep:
 // mean and var are bq_gp_predict's bits), then -- for dvar -- the backward row sweep
-// beta = V L^-1 out of V into the buffer the cross Gram came in (the forward sweep left partial
-// sums there; V is consumed, so the row reductions ran first), and one launch over beta, alpha
-// and the points.  Results: [mean (Mp) | var (Mp) | dmean (d Mp) | dvar (d Mp)].
+// beta = V L^-1 (predict_beta), and one launch over beta, alpha and the points.
+// Results: [mean (Mp) | var (Mp) | dmean (d Mp) | dvar (d Mp)].
 extern "C" int bq_gp_predict_grad(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, double *mean,
                                   double *var, double *dmean, double *dvar)
 {
-    BQCHK(check_fit(c, f));
-    if (M < 0 || (M && !xo) || (!mean && !var && !dmean && !dvar))
-        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
-    if (M == 0)
+    bool none;
+    BQCHK(predict_args(c, f, xo, M, mean || var || dmean || dvar, &none));
+    if (none)
         return BQ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int d = f->d, n = f->n, npad = f->npad;
-    const int Mp = (int)roundup(M, 64);
-    const size_t nres = 2 * (size_t)Mp + 2 * (size_t)d * Mp;
-    DevBuf &xod = f->wx, &out = f->wout;
-    double *hmap = nullptr;
-    BQCHK(predict_stage(c, f, xo, M, nres, &hmap));
+    const int d = f->d, n = f->n;
     const bool full = var || dvar;
     // (alpha first: the call that builds it synchronises, which would split the chain below)
     if (!full || dmean)
         BQCHK(fit_alpha(c, f));
     // the full route stages its points as bq_gp_predict does for mean + variance
-    const bool direct = full && hmap && predict_direct_ok(d, M, npad);
-    if (direct)
-        ;
-    else if (hmap)
-        BQCHK(launch_flow_in(c, hmap, d * (int)M, xod.d(), d * (int)M, nullptr, 0));
-    else
-        HIPCHK(c, hipMemcpyAsync(xod.p, f->hio, sizeof(double) * d * M, hipMemcpyHostToDevice,
-                                 c->stream));
-    const double *xq = direct ? hmap : xod.d();
-    double *res = direct ? hmap + (size_t)d * M : out.d();
-    double *odm = res + 2 * (size_t)Mp, *odv = odm + (size_t)d * Mp;
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, xo, M, d, full));
+    const int Mp = io.Mp;
+    double *odm = io.res + 2 * (size_t)Mp, *odv = odm + (size_t)d * Mp;
     size_t nout = 2 * (size_t)Mp; // how much of the results goes back
     if (!full) {
-        BQCHK(launch_predict_mean_grad(c, d, xq, (int)M, f->pts.d(), n, f->alpha.d(), f->g, res,
-                                       odm));
+        BQCHK(launch_predict_mean_grad(c, d, io.xq, (int)M, f->pts.d(), n, f->alpha.d(), f->g,
+                                       io.res, odm));
         nout += (size_t)d * Mp;
     } else {
-        BQCHK(predict_sweep(c, f, xq, direct, M, res));
-        if (dvar) {
-            WideInv wi;
-            BQCHK(fit_wide(c, f, wi));
-            BQCHK(enqueue_backward_rows(c, f->wV2.d(), f->wV.d(), Mp, Mp, f->A.d(), f->ldl, npad,
-                                        wi));
-        }
+        BQCHK(predict_sweep(c, f, io));
+        if (dvar)
+            BQCHK(predict_beta(c, f, Mp));
         if (dmean || dvar) {
-            BQCHK(launch_predict_grad(c, d, dvar ? f->wV.d() : nullptr, (long)Mp, (int)M, Mp, xq,
+            BQCHK(launch_predict_grad(c, d, dvar ? f->wV.d() : nullptr, (long)Mp, (int)M, Mp, io.xq,
                                       f->pts.d(), n, dmean ? f->alpha.d() : nullptr, f->g,
                                       dmean ? odm : nullptr, dvar ? odv : nullptr));
-            nout = nres;
+            nout += 2 * (size_t)d * Mp;
         }
     }
-    double *hres = f->hio + (size_t)d * M;
-    if (direct)
-        ;
-    else if (hmap)
-        BQCHK(launch_flow_out(c, out.d(), (int)nout, hmap + (size_t)d * M));
-    else
-        HIPCHK(c, hipMemcpyAsync(hres, out.p, sizeof(double) * nout, hipMemcpyDeviceToHost,
-                                 c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (mean)
-        std::memcpy(mean, hres, sizeof(double) * M);
-    if (var)
-        std::memcpy(var, hres + Mp, sizeof(double) * M);
-    if (dmean)
-        std::memcpy(dmean, hres + 2 * (size_t)Mp, sizeof(double) * d * M);
-    if (dvar)
-        std::memcpy(dvar, hres + 2 * (size_t)Mp + (size_t)d * Mp, sizeof(double) * d * M);
-    return BQ_OK;
+    return io.finish(c, nout, mean, var, dmean, dvar);
 }
 
 // The posterior and its derivatives in the hyper-parameters theta = [h, w_1 .. w_d, s] (ptheta.h
@@ -1251,24 +1252,17 @@ extern "C" int bq_gp_predict_grad(bq_ctx *c, bq_fit *f, const double *xo, int64_
 // then one fused launch, no sweep and no M x n matrix.  Full route: both of those first (they
 // synchronise), bq_gp_predict's own staging, cross Gram, forward sweep and row reductions
 // (predict_sweep: mean and var are bq_gp_predict's bits), then -- for dvar -- the backward row
-// sweep beta = V L^-1 into the buffer the cross Gram came in and one MFMA launch per length scale
-// for q_jk = beta_j^T D_k beta_j, and one launch over beta, the solved vectors and the points.
+// sweep beta = V L^-1 (predict_beta) and one MFMA launch per length scale for
+// q_jk = beta_j^T D_k beta_j, and one launch over beta, the solved vectors and the points.
 // Results: [mean (Mp) | var (Mp) | dmean ((d + 2) Mp) | dvar ((d + 2) Mp)].
 extern "C" int bq_gp_predict_dtheta(bq_ctx *c, bq_fit *f, const double *xo, int64_t M,
                                     double *mean, double *var, double *dmean, double *dvar)
 {
-    BQCHK(check_fit(c, f));
-    if (M < 0 || (M && !xo) || (!mean && !var && !dmean && !dvar))
-        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
-    if (M == 0)
+    bool none;
+    BQCHK(predict_args(c, f, xo, M, mean || var || dmean || dvar, &none));
+    if (none)
         return BQ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int d = f->d, np = d + 2, npad = f->npad;
-    const int Mp = (int)roundup(M, 64);
-    const size_t nres = 2 * (size_t)Mp + 2 * (size_t)np * Mp;
-    DevBuf &xod = f->wx, &out = f->wout;
-    double *hmap = nullptr;
-    BQCHK(predict_stage(c, f, xo, M, nres, &hmap));
+    const int d = f->d, np = d + 2;
     const bool full = var || dvar;
     // (the fit's own vectors first: building them synchronises, which would split the chain below)
     if (!full || dmean) {
@@ -1276,58 +1270,33 @@ extern "C" int bq_gp_predict_dtheta(bq_ctx *c, bq_fit *f, const double *xo, int6
         BQCHK(fit_dkz(c, f));
     }
     if (dvar)
-        BQCHK(fit_grow(c, f->wq, sizeof(double) * ptheta_part_doubles(d, Mp, npad),
+        BQCHK(fit_grow(c, f->wq,
+                       sizeof(double) * ptheta_part_doubles(d, (int)roundup(M, 64), f->npad),
                        "hyper-parameter derivative partial sums"));
     // the full route stages its points as bq_gp_predict does for mean + variance
-    const bool direct = full && hmap && predict_direct_ok(d, M, npad);
-    if (direct)
-        ;
-    else if (hmap)
-        BQCHK(launch_flow_in(c, hmap, d * (int)M, xod.d(), d * (int)M, nullptr, 0));
-    else
-        HIPCHK(c, hipMemcpyAsync(xod.p, f->hio, sizeof(double) * d * M, hipMemcpyHostToDevice,
-                                 c->stream));
-    const double *xq = direct ? hmap : xod.d();
-    double *res = direct ? hmap + (size_t)d * M : out.d();
-    double *odm = res + 2 * (size_t)Mp, *odv = odm + (size_t)np * Mp;
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, xo, M, np, full));
+    const int Mp = io.Mp;
+    double *odm = io.res + 2 * (size_t)Mp, *odv = odm + (size_t)np * Mp;
     size_t nout = 2 * (size_t)Mp; // how much of the results goes back
     const HessJob hj = fit_hess_job(f);
     if (!full) {
-        BQCHK(launch_predict_mean_theta(c, d, xq, (int)M, hj, f->dkz.d(), f->h, f->s, res, odm));
+        BQCHK(launch_predict_mean_theta(c, d, io.xq, (int)M, hj, f->dkz.d(), f->h, f->s, io.res,
+                                        odm));
         nout += (size_t)np * Mp;
     } else {
-        BQCHK(predict_sweep(c, f, xq, direct, M, res));
+        BQCHK(predict_sweep(c, f, io));
         if (dvar) {
-            WideInv wi;
-            BQCHK(fit_wide(c, f, wi));
-            BQCHK(enqueue_backward_rows(c, f->wV2.d(), f->wV.d(), Mp, Mp, f->A.d(), f->ldl, npad,
-                                        wi));
+            BQCHK(predict_beta(c, f, Mp));
             BQCHK(launch_ptheta_quad(c, d, f->wV.d(), (long)Mp, Mp, hj, f->wq.d()));
         }
         if (dmean || dvar) {
-            BQCHK(launch_predict_theta(c, d, dvar ? f->wV.d() : nullptr, (long)Mp, (int)M, Mp, xq,
-                                       hj, dmean ? f->dkz.d() : nullptr, res + Mp,
+            BQCHK(launch_predict_theta(c, d, dvar ? f->wV.d() : nullptr, (long)Mp, (int)M, Mp, io.xq,
+                                       hj, dmean ? f->dkz.d() : nullptr, io.res + Mp,
                                        dvar ? f->wq.d() : nullptr, f->h, f->s,
                                        dmean ? odm : nullptr, dvar ? odv : nullptr));
-            nout = nres;
+            nout += 2 * (size_t)np * Mp;
         }
     }
-    double *hres = f->hio + (size_t)d * M;
-    if (direct)
-        ;
-    else if (hmap)
-        BQCHK(launch_flow_out(c, out.d(), (int)nout, hmap + (size_t)d * M));
-    else
-        HIPCHK(c, hipMemcpyAsync(hres, out.p, sizeof(double) * nout, hipMemcpyDeviceToHost,
-                                 c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (mean)
-        std::memcpy(mean, hres, sizeof(double) * M);
-    if (var)
-        std::memcpy(var, hres + Mp, sizeof(double) * M);
-    if (dmean)
-        std::memcpy(dmean, hres + 2 * (size_t)Mp, sizeof(double) * np * M);
-    if (dvar)
-        std::memcpy(dvar, hres + 2 * (size_t)Mp + (size_t)np * Mp, sizeof(double) * np * M);
-    return BQ_OK;
+    return io.finish(c, nout, mean, var, dmean, dvar);
 }

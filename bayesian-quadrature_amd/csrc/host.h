@@ -198,6 +198,20 @@ inline int fail(bq_ctx *c, int code, const char *fmt, ...)
 
 inline long roundup(long v, long q) { return (v + q - 1) / q * q; }
 
+// The one switch on the dimension: the statement(s) after d_ with `constexpr int D` bound to it,
+// once per template instantiation D = 1 .. 8 (anything else takes 8: callers check d first)
+#define BQ_DISPATCH_D(d_, ...)                                                                     \
+    switch (d_) {                                                                                  \
+    case 1: { constexpr int D = 1; __VA_ARGS__; } break;                                           \
+    case 2: { constexpr int D = 2; __VA_ARGS__; } break;                                           \
+    case 3: { constexpr int D = 3; __VA_ARGS__; } break;                                           \
+    case 4: { constexpr int D = 4; __VA_ARGS__; } break;                                           \
+    case 5: { constexpr int D = 5; __VA_ARGS__; } break;                                           \
+    case 6: { constexpr int D = 6; __VA_ARGS__; } break;                                           \
+    case 7: { constexpr int D = 7; __VA_ARGS__; } break;                                           \
+    default: { constexpr int D = 8; __VA_ARGS__; } break;                                          \
+    }
+
 // leading dimension for an ntot x ntot column-major matrix: even, and nudged
 // off large powers of two so that the 4 columns of an MFMA fragment do not
 // all map to the same HBM channel / L2 set
@@ -344,13 +358,15 @@ size_t grad_parts(int npad, int d);
 int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob &gj,
                       const GradScale &sc, double *grad);
 // ---- k_hess.hip ----------------------------------------------------------------------
-// the log-ML Hessian's sums (hess.h) into the workspace; *sums: where they are on the device
+// the log-ML Hessian (hess.h) in two stages over one workspace (hess_ws_doubles).  The products
+// stage: Ki = Y Y^T, B_k = Ki D_k, V = D_p a, Z = Ki V (fit_prod runs it; leave-one-out and
+// leave-group-out read it too) ...
 size_t hess_ws_doubles(int npad, int d);
-int launch_logml_hess(bq_ctx *c, int d, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                      const double *y, double h, double s, bool have_prod, const double **sums);
-// its products stage alone (Ki, B_k, D_p a, Ki D_p a); launch_logml_hess with have_prod runs the rest
 int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *ws,
                          const HessJob &hj, const double *y, double h, double s);
+// ... and the sums over what it left in Ki and ws; *sums: where they are on the device
+int launch_hess_sums(bq_ctx *c, int d, const double *Ki, double *ws, const HessJob &hj,
+                     const double **sums);
 // leave-one-out (loo.h) into its own workspace; *vecs: mu | var | lp, npad apart
 size_t loo_ws_doubles(int npad, int d);
 int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const double *y, int n,
@@ -740,10 +756,10 @@ struct bq_fit : FitCore {
     //   ALPHA     alpha = L^-T z                                    WIDE, z     fit_alpha
     //   Y         gY: Y = L^-T, zero below its diagonal (gX: the    WIDE        fit_y
     //             sweep's workspace)
-    //   PROD      gX, hB: the Hessian's products stage (Kxx^-1,     Y, ALPHA    bq_gp_logml_hess or
-    //             the d products, the vectors D_p a and                         bq_gp_loo_grad or
-    //             Kxx^-1 D_p a), which all of them read                         bq_gp_lgo_grad,
-    //                                                                           whichever is first
+    //   PROD      gX, hB: the Hessian's products stage (Kxx^-1,     Y, ALPHA    fit_prod
+    //             the d products, the vectors D_p a and
+    //             Kxx^-1 D_p a), which the Hessian's sums and
+    //             both cross-validation gradients read
     //   HESS      hess                                              PROD        bq_gp_logml_hess
     //   LOO       loo: mu | var | lp; loo_total                     Y, ALPHA    fit_loo
     //   LOO_GRAD  loo_grad                                          PROD, LOO   bq_gp_loo_grad
@@ -824,6 +840,20 @@ struct bq_fit : FitCore {
 };
 
 namespace bqh {
+// An on-demand buffer of a fit: buf holds at least `bytes` (kept between calls), or the call fails
+// with "<what> (<bytes> bytes): <the HIP error>" and buf is left empty
+inline int fit_grow(bq_ctx *c, DevBuf &buf, size_t bytes, const char *what)
+{
+    if (buf.bytes >= bytes)
+        return BQ_OK;
+    const hipError_t e = buf.alloc(bytes);
+    if (e == hipSuccess)
+        return BQ_OK;
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? BQ_ERR_NOMEM : BQ_ERR_HIP, "%s (%zu bytes): %s", what,
+                bytes, hipGetErrorString(e));
+}
+
 // A fit takes over the core of another layout (a growing append, a removal that is not in place;
 // the stream is idle).  Every workspace sized by the old padding goes, and so do the captured
 // sweeps, which hold the old pointers; the old core leaves in `core`, for the caller to free.

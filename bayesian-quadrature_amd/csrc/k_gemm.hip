@@ -284,24 +284,14 @@ int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob
     {
         // (the N^3 / 3 of the lower tiles' k ranges, the flops the kernel has to do)
         Bracket br(c, BQ_K_GEMM, (double)npad * npad * npad / 3.0);
-#define BQ_GRAD(D_)                                                                                \
-    if (t == 128)                                                                                  \
-        hipLaunchKernelGGL(gemm_lds_grad_kernel<D_>, dim3(nwg), dim3(256), BQ_LDS_BYTES, c->cur, Y, \
-                           (long)npad, npad, gj);                                                  \
-    else                                                                                           \
-        hipLaunchKernelGGL(gemm_lds64_grad_kernel<D_>, dim3(nwg), dim3(256), BQ_L64_BYTES, c->cur,  \
-                           Y, (long)npad, npad, gj)
-        switch (d) {
-        case 1: BQ_GRAD(1); break;
-        case 2: BQ_GRAD(2); break;
-        case 3: BQ_GRAD(3); break;
-        case 4: BQ_GRAD(4); break;
-        case 5: BQ_GRAD(5); break;
-        case 6: BQ_GRAD(6); break;
-        case 7: BQ_GRAD(7); break;
-        default: BQ_GRAD(8); break;
-        }
-#undef BQ_GRAD
+        BQ_DISPATCH_D(d, {
+            if (t == 128)
+                hipLaunchKernelGGL(gemm_lds_grad_kernel<D>, dim3(nwg), dim3(256), BQ_LDS_BYTES,
+                                   c->cur, Y, (long)npad, npad, gj);
+            else
+                hipLaunchKernelGGL(gemm_lds64_grad_kernel<D>, dim3(nwg), dim3(256), BQ_L64_BYTES,
+                                   c->cur, Y, (long)npad, npad, gj);
+        });
         HIPCHK(c, hipGetLastError());
     }
     Bracket br(c, BQ_K_REDUCE);

@@ -39,13 +39,14 @@ static void hess_launch_prod(bq_ctx *c, bool tall, double *C, const double *A, c
                            C, A, Q, hj, kdim);
 }
 
-// Ki = Y Y^T and the d products B_k = Ki D_k
+// The products stage: Ki = Y Y^T, the d products B_k = Ki D_k, V = D_p a and Z = Ki V
 template <int D>
-static int hess_run_prods(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj)
+static int hess_run_products(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj,
+                             const double *y, double h, double s)
 {
     const int npad = hj.npad;
     const bool tall = hess_tall(c, npad);
-    double *B = ws;
+    double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
     const double n3 = (double)npad * npad * npad;
     {
         Bracket br(c, BQ_K_GEMM, n3 * 2.0 / 3.0);
@@ -57,44 +58,22 @@ static int hess_run_prods(bq_ctx *c, const double *Y, double *Ki, double *ws, co
         hess_launch_prod<D>(c, tall, B + (size_t)k * npad * npad, Ki, nullptr, hj, k);
         HIPCHK(c, hipGetLastError());
     }
-    return BQ_OK;
-}
-
-// V = D_p a and Z = Ki V
-template <int D>
-static void hess_launch_vecs(bq_ctx *c, const double *Ki, double *ws, const HessJob &hj,
-                             const double *y, double h, double s)
-{
-    const int npad = hj.npad;
-    double *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
+    Bracket br(c, BQ_K_REDUCE);
     hipLaunchKernelGGL(hess_dka_kernel<D>, dim3((unsigned)npad / 16), dim3(256), 0, c->stream, hj, y,
                        2.0 / h, 2.0 * s, V);
     hipLaunchKernelGGL(hess_kiv_kernel, dim3((unsigned)npad / 4), dim3(256), 0, c->stream, Ki, hj.n,
                        npad, D + 2, V, Z);
-}
-
-// The products stage alone (what bq_gp_loo_grad needs of the Hessian): Ki, B_k, V, Z
-template <int D>
-static int hess_run_products(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                             const double *y, double h, double s)
-{
-    BQCHK(hess_run_prods<D>(c, Y, Ki, ws, hj));
-    Bracket br(c, BQ_K_REDUCE);
-    hess_launch_vecs<D>(c, Ki, ws, hj, y, h, s);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
 
-// have_prod: Ki, B_k, V and Z are there (the products stage has run on this fit): only the sums
+// The sums stage, over what the products stage left in Ki and ws
 template <int D>
-static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                    const double *y, double h, double s, bool have_prod)
+static int hess_run_sums(bq_ctx *c, const double *Ki, double *ws, const HessJob &hj)
 {
     const int npad = hj.npad, n = hj.n;
-    double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
+    const double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
     double *part = ws + hess_off_part(npad, D), *sums = ws + hess_off_sums(npad, D);
-    if (!have_prod)
-        BQCHK(hess_run_prods<D>(c, Y, Ki, ws, hj));
     Bracket br(c, BQ_K_REDUCE);
     const unsigned g64 = (unsigned)npad / 64;
     const int nwg = (int)(g64 * g64);
@@ -105,53 +84,36 @@ static int hess_run(bq_ctx *c, const double *Y, double *Ki, double *ws, const He
                        part);
     hipLaunchKernelGGL(hess_finalize_kernel, dim3(hess_nt(D)), dim3(256), 0, c->stream, part, nwg,
                        sums + hess_ng(D));
-    if (!have_prod)
-        hess_launch_vecs<D>(c, Ki, ws, hj, y, h, s);
     hipLaunchKernelGGL(hess_quad_kernel, dim3(1), dim3(256), 0, c->stream, V, Z, n, npad, D + 2,
                        sums + hess_ng(D) + hess_nt(D));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
 
-// The sums of one Hessian (types.h: hess_ng + hess_nt + hess_nq of them, at *sums inside ws) from
-// Y = L^-T (npad x npad, zero below its diagonal) and the fit's alpha.  Ki: npad^2 doubles, left
-// holding Kxx^-1; ws: hess_ws_doubles(npad, d).  have_prod: launch_hess_products has run on these
-// buffers since the fit last changed, and its launches are left out.
-int launch_logml_hess(bq_ctx *c, int d, const double *Y, double *Ki, double *ws, const HessJob &hj,
-                      const double *y, double h, double s, bool have_prod, const double **sums)
-{
-    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
-        return fail(c, BQ_ERR_BAD_ARG, "logml_hess: d in [1, %d], npad a multiple of 64", BQ_MAXD);
-    *sums = ws + hess_off_sums(hj.npad, d);
-    switch (d) {
-    case 1: return hess_run<1>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    case 2: return hess_run<2>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    case 3: return hess_run<3>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    case 4: return hess_run<4>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    case 5: return hess_run<5>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    case 6: return hess_run<6>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    case 7: return hess_run<7>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    default: return hess_run<8>(c, Y, Ki, ws, hj, y, h, s, have_prod);
-    }
-}
-
-// The Hessian's products stage on its own: Ki = Y Y^T, B_k = Ki D_k, V = D_p a, Z = Ki V -- the
-// launches of launch_logml_hess that its sums read, with the same results.
+// The Hessian's products stage: Ki = Y Y^T, B_k = Ki D_k, V = D_p a, Z = Ki V from Y = L^-T (npad x
+// npad, zero below its diagonal) and the fit's alpha.  Ki: npad^2 doubles, left holding Kxx^-1; ws:
+// hess_ws_doubles(npad, d).
 int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *ws,
                          const HessJob &hj, const double *y, double h, double s)
 {
     if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
         return fail(c, BQ_ERR_BAD_ARG, "hess_products: d in [1, %d], npad a multiple of 64", BQ_MAXD);
-    switch (d) {
-    case 1: return hess_run_products<1>(c, Y, Ki, ws, hj, y, h, s);
-    case 2: return hess_run_products<2>(c, Y, Ki, ws, hj, y, h, s);
-    case 3: return hess_run_products<3>(c, Y, Ki, ws, hj, y, h, s);
-    case 4: return hess_run_products<4>(c, Y, Ki, ws, hj, y, h, s);
-    case 5: return hess_run_products<5>(c, Y, Ki, ws, hj, y, h, s);
-    case 6: return hess_run_products<6>(c, Y, Ki, ws, hj, y, h, s);
-    case 7: return hess_run_products<7>(c, Y, Ki, ws, hj, y, h, s);
-    default: return hess_run_products<8>(c, Y, Ki, ws, hj, y, h, s);
-    }
+    int st = BQ_OK;
+    BQ_DISPATCH_D(d, st = hess_run_products<D>(c, Y, Ki, ws, hj, y, h, s));
+    return st;
+}
+
+// The sums of one Hessian (types.h: hess_ng + hess_nt + hess_nq of them, at *sums inside ws) from
+// what launch_hess_products left in Ki and ws since the fit last changed.
+int launch_hess_sums(bq_ctx *c, int d, const double *Ki, double *ws, const HessJob &hj,
+                     const double **sums)
+{
+    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
+        return fail(c, BQ_ERR_BAD_ARG, "hess_sums: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    *sums = ws + hess_off_sums(hj.npad, d);
+    int st = BQ_OK;
+    BQ_DISPATCH_D(d, st = hess_run_sums<D>(c, Ki, ws, hj));
+    return st;
 }
 
 // ---- leave-one-out (loo.h) ---------------------------------------------------------------
@@ -213,16 +175,9 @@ int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const
     if (d < 1 || d > BQ_MAXD || (npad % 64))
         return fail(c, BQ_ERR_BAD_ARG, "loo_grad: d in [1, %d], npad a multiple of 64", BQ_MAXD);
     *grad = ws + loo_off_out(npad, d) + 1;
-    switch (d) {
-    case 1: return loo_grad_run<1>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    case 2: return loo_grad_run<2>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    case 3: return loo_grad_run<3>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    case 4: return loo_grad_run<4>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    case 5: return loo_grad_run<5>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    case 6: return loo_grad_run<6>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    case 7: return loo_grad_run<7>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    default: return loo_grad_run<8>(c, Ki, hws, alpha, n, npad, h, s, s2, ws);
-    }
+    int st = BQ_OK;
+    BQ_DISPATCH_D(d, st = loo_grad_run<D>(c, Ki, hws, alpha, n, npad, h, s, s2, ws));
+    return st;
 }
 
 // ---- leave-group-out (lgo.h) ------------------------------------------------------------
@@ -317,18 +272,6 @@ int launch_lgo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, int n
 }
 
 // ---- the posterior's derivatives in the hyper-parameters (ptheta.h; fit.hip, bq_gp_predict_dtheta) ----
-#define BQ_PTHETA_DISPATCH(d_, CALL)                                                               \
-    switch (d_) {                                                                                  \
-    case 1: CALL(1); break;                                                                        \
-    case 2: CALL(2); break;                                                                        \
-    case 3: CALL(3); break;                                                                        \
-    case 4: CALL(4); break;                                                                        \
-    case 5: CALL(5); break;                                                                        \
-    case 6: CALL(6); break;                                                                        \
-    case 7: CALL(7); break;                                                                        \
-    default: CALL(8); break;                                                                       \
-    }
-
 static ThetaScale theta_scale(double h, double s)
 {
     return ThetaScale{2.0 * (s * s) / h, -2.0 * s, 2.0 / h, 2.0 * s};
@@ -340,11 +283,8 @@ int launch_ptheta_dka(bq_ctx *c, int d, const HessJob &hj, double *R)
     if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
         return fail(c, BQ_ERR_BAD_ARG, "ptheta_dka: d in [1, %d], npad a multiple of 64", BQ_MAXD);
     Bracket br(c, BQ_K_REDUCE);
-#define PD(D_)                                                                                     \
-    hipLaunchKernelGGL(ptheta_dka_kernel<D_>, dim3((unsigned)hj.npad / 16), dim3(256), 0,          \
-                       c->stream, hj, R)
-    BQ_PTHETA_DISPATCH(d, PD)
-#undef PD
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(ptheta_dka_kernel<D>, dim3((unsigned)hj.npad / 16), dim3(256),
+                                        0, c->stream, hj, R));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -376,15 +316,15 @@ int launch_ptheta_quad(bq_ctx *c, int d, const double *beta, long ldb, int Mp, c
     const unsigned gy = (unsigned)hj.npad / 64;
     for (int k = 0; k < d; ++k) {
         Bracket br(c, BQ_K_GEMM, 2.0 * Mp * (double)hj.n * hj.npad);
-#define PQ(D_)                                                                                     \
-    if (tall)                                                                                      \
-        hipLaunchKernelGGL((ptheta_quad_kernel<D_, 4, 1, 4, 4>), dim3((unsigned)(Mp + 255) / 256, gy), \
-                           dim3(256), 0, c->stream, beta, ldb, Mp, hj, k, part);                   \
-    else                                                                                           \
-        hipLaunchKernelGGL((ptheta_quad_kernel<D_, 2, 2, 2, 2>), dim3((unsigned)Mp / 64, gy),      \
-                           dim3(256), 0, c->stream, beta, ldb, Mp, hj, k, part)
-        BQ_PTHETA_DISPATCH(d, PQ)
-#undef PQ
+        BQ_DISPATCH_D(d, {
+            if (tall)
+                hipLaunchKernelGGL((ptheta_quad_kernel<D, 4, 1, 4, 4>),
+                                   dim3((unsigned)(Mp + 255) / 256, gy), dim3(256), 0, c->stream,
+                                   beta, ldb, Mp, hj, k, part);
+            else
+                hipLaunchKernelGGL((ptheta_quad_kernel<D, 2, 2, 2, 2>), dim3((unsigned)Mp / 64, gy),
+                                   dim3(256), 0, c->stream, beta, ldb, Mp, hj, k, part);
+        });
         HIPCHK(c, hipGetLastError());
     }
     return BQ_OK;
@@ -399,12 +339,9 @@ int launch_predict_theta(bq_ctx *c, int d, const double *beta, long ldb, int M, 
     Bracket br(c, BQ_K_REDUCE);
     const ThetaScale sc = theta_scale(h, s);
     const int ncb = hj.npad / 64;
-#define PT(D_)                                                                                     \
-    hipLaunchKernelGGL(predict_theta_kernel<D_>, dim3((unsigned)(Mp / 16)), dim3(512), 0,          \
-                       c->stream, beta, ldb, M, xo, hj, Z, var, qpart, ncb, (long)Mp, sc, dmean,   \
-                       dvar)
-    BQ_PTHETA_DISPATCH(d, PT)
-#undef PT
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(predict_theta_kernel<D>, dim3((unsigned)(Mp / 16)), dim3(512),
+                                        0, c->stream, beta, ldb, M, xo, hj, Z, var, qpart, ncb,
+                                        (long)Mp, sc, dmean, dvar));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -415,14 +352,10 @@ int launch_predict_mean_theta(bq_ctx *c, int d, const double *xo, int M, const H
 {
     Bracket br(c, BQ_K_REDUCE);
     const ThetaScale sc = theta_scale(h, s);
-#define PMT(D_)                                                                                    \
-    hipLaunchKernelGGL(predict_mean_theta_kernel<D_>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, \
-                       c->stream, xo, M, hj, Z, sc, mean, dmean)
-    BQ_PTHETA_DISPATCH(d, PMT)
-#undef PMT
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(predict_mean_theta_kernel<D>, dim3((unsigned)((M + 3) / 4)),
+                                        dim3(256), 0, c->stream, xo, M, hj, Z, sc, mean, dmean));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
-#undef BQ_PTHETA_DISPATCH
 
 } // namespace bqh

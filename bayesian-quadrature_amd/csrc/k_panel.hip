@@ -65,19 +65,12 @@ int launch_assemble(bq_ctx *c, int d, const double *pts, long pstride, const dou
         return fail(c, BQ_ERR_BAD_ARG, "assemble: column limit");
     if (fs.stamps && (!fs.S0 || d != 1))
         return fail(c, BQ_ERR_BAD_ARG, "assemble: the stamped first launch is one-dimensional");
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
     const double cols = jcols > 0 ? jcols : L.ntot;
     Bracket br(c, BQ_K_GRAM, 8.0 * cols * (L.ntot - 0.5 * cols + 0.5) * batch);
-    switch (d) {
-    case 1: launch_assemble_d<1>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 2: launch_assemble_d<2>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 3: launch_assemble_d<3>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 4: launch_assemble_d<4>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 5: launch_assemble_d<5>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 6: launch_assemble_d<6>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 7: launch_assemble_d<7>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    case 8: launch_assemble_d<8>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride, L, batch, fs, jcols); break;
-    default: return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
-    }
+    BQ_DISPATCH_D(d, launch_assemble_d<D>(c, pts, pstride, y, ystride, gp, gpstride, A, lda, astride,
+                                          L, batch, fs, jcols));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -89,27 +82,13 @@ int launch_assemble_region(bq_ctx *c, const GramSeed &sd, double *A, long lda, l
         return BQ_OK;
     if ((m & 63) || (n & 63) || (sd.r & 63) || (sd.c & 63))
         return fail(c, BQ_ERR_BAD_ARG, "assemble_region: multiples of 64");
+    if (sd.d < 1 || sd.d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
     Bracket br(c, BQ_K_GRAM, 8.0 * m * n * batch);
     const dim3 grid((m + 127) / 128, n / 64, batch);
-#define BQ_ASM_REGION(D_)                                                                          \
-    case D_:                                                                                       \
-        hipLaunchKernelGGL(assemble_region_kernel<D_>, grid, dim3(256), 0, c->cur, sd.pts,         \
-                           sd.pstride, sd.y, sd.ystride, sd.gp, sd.gpstride, A, lda, astride, sd.L, \
-                           sd.r, sd.c, m, n);                                                      \
-        break;
-    switch (sd.d) {
-        BQ_ASM_REGION(1)
-        BQ_ASM_REGION(2)
-        BQ_ASM_REGION(3)
-        BQ_ASM_REGION(4)
-        BQ_ASM_REGION(5)
-        BQ_ASM_REGION(6)
-        BQ_ASM_REGION(7)
-        BQ_ASM_REGION(8)
-    default:
-        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
-    }
-#undef BQ_ASM_REGION
+    BQ_DISPATCH_D(sd.d, hipLaunchKernelGGL(assemble_region_kernel<D>, grid, dim3(256), 0, c->cur,
+                                           sd.pts, sd.pstride, sd.y, sd.ystride, sd.gp, sd.gpstride,
+                                           A, lda, astride, sd.L, sd.r, sd.c, m, n));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -48,20 +48,8 @@ int launch_predict_mean(bq_ctx *c, int d, const double *xo, int M, const double 
 {
     Bracket br(c, BQ_K_REDUCE);
     dim3 grid((unsigned)((M + 3) / 4));
-#define PM(D_)                                                                                     \
-    hipLaunchKernelGGL(predict_mean_kernel<D_>, grid, dim3(256), 0, c->stream, xo, M, pts, n,      \
-                       alpha, g, mean)
-    switch (d) {
-    case 1: PM(1); break;
-    case 2: PM(2); break;
-    case 3: PM(3); break;
-    case 4: PM(4); break;
-    case 5: PM(5); break;
-    case 6: PM(6); break;
-    case 7: PM(7); break;
-    default: PM(8); break;
-    }
-#undef PM
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(predict_mean_kernel<D>, grid, dim3(256), 0, c->stream, xo, M,
+                                        pts, n, alpha, g, mean));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -74,20 +62,8 @@ int launch_predict_grad(bq_ctx *c, int d, const double *beta, long ldb, int M, i
 {
     Bracket br(c, BQ_K_REDUCE);
     dim3 grid((unsigned)(Mp / 16));
-#define PG(D_)                                                                                     \
-    hipLaunchKernelGGL(predict_grad_kernel<D_>, grid, dim3(1024), 0, c->stream, beta, ldb, M, xo,  \
-                       pts, n, alpha, g, dmean, dvar)
-    switch (d) {
-    case 1: PG(1); break;
-    case 2: PG(2); break;
-    case 3: PG(3); break;
-    case 4: PG(4); break;
-    case 5: PG(5); break;
-    case 6: PG(6); break;
-    case 7: PG(7); break;
-    default: PG(8); break;
-    }
-#undef PG
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(predict_grad_kernel<D>, grid, dim3(1024), 0, c->stream, beta,
+                                        ldb, M, xo, pts, n, alpha, g, dmean, dvar));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -99,20 +75,8 @@ int launch_predict_mean_grad(bq_ctx *c, int d, const double *xo, int M, const do
 {
     Bracket br(c, BQ_K_REDUCE);
     dim3 grid((unsigned)((M + 3) / 4));
-#define PMG(D_)                                                                                    \
-    hipLaunchKernelGGL(predict_mean_grad_kernel<D_>, grid, dim3(256), 0, c->stream, xo, M, pts, n, \
-                       alpha, g, mean, dmean)
-    switch (d) {
-    case 1: PMG(1); break;
-    case 2: PMG(2); break;
-    case 3: PMG(3); break;
-    case 4: PMG(4); break;
-    case 5: PMG(5); break;
-    case 6: PMG(6); break;
-    case 7: PMG(7); break;
-    default: PMG(8); break;
-    }
-#undef PMG
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(predict_mean_grad_kernel<D>, grid, dim3(256), 0, c->stream, xo,
+                                        M, pts, n, alpha, g, mean, dmean));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

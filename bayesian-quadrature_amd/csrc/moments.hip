@@ -144,18 +144,6 @@ int check_int_args(bq_ctx *c, int64_t d, const double *w, const double *mu, cons
     return BQ_OK;
 }
 
-#define BQ_DISPATCH_D(d_, ...)                                                                     \
-    switch (d_) {                                                                                  \
-    case 1: { constexpr int D = 1; __VA_ARGS__; } break;                                           \
-    case 2: { constexpr int D = 2; __VA_ARGS__; } break;                                           \
-    case 3: { constexpr int D = 3; __VA_ARGS__; } break;                                           \
-    case 4: { constexpr int D = 4; __VA_ARGS__; } break;                                           \
-    case 5: { constexpr int D = 5; __VA_ARGS__; } break;                                           \
-    case 6: { constexpr int D = 6; __VA_ARGS__; } break;                                           \
-    case 7: { constexpr int D = 7; __VA_ARGS__; } break;                                           \
-    default: { constexpr int D = 8; __VA_ARGS__; } break;                                          \
-    }
-
 // ---- device-side pieces shared by the host-buffer entry points and the moments ----
 
 // out_dev[i] = scale exp(add + log N(x_i | mu, C)); with alpha_dev: *sum_dev = sum out alpha

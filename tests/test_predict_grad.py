@@ -16,6 +16,7 @@ import functools
 import numpy as np
 import pytest
 
+from engine_env import engine_env
 from test_predict_grad_host import closed_form, term_sizes
 
 pytestmark = pytest.mark.gpu
@@ -212,6 +213,52 @@ def test_same_bits_twice(engine):
             assert _same(a, b)
         finally:
             fit.close()
+
+
+def _beyond_direct(n, d, M):
+    """predict_direct_ok's rule (fit.hip): the cross Gram reads the points out of the mapped
+    staging npad / 64 times, and does so only up to 4 MiB of such reads."""
+    npad = -(-n // 64) * 64
+    return d * M * 8 * (npad // 64) > 4 << 20
+
+
+def _both_routes(eng, x, y, h, w, s, xo, with_predict=False):
+    fit = eng.gp_fit(x, y, h, w, s)
+    try:
+        out = fit.predict_grad(xo) + fit.predict_grad(xo, want_var=False)
+        return out + fit.predict(xo)[:2] if with_predict else out
+    finally:
+        fit.close()
+
+
+def test_staging_routes(engine, oracle):
+    """The three ways a call's points go in and its results come out give the same bits: the
+    kernels on the mapped staging itself (the full route up to predict_direct_ok's limit), one
+    copy kernel each way (the mean route, and the full route beyond the limit) and the copy engine
+    (every route of an engine with BQ_SOLVE_KCOPY=0).  Two small cases with Mp != M and npad != n,
+    and the smallest shape beyond the limit at d = 8, n = 1000: M = 4100 (Mp = 4160, a partly
+    filled last block).  There mean and var are also predict's bits, and the first and the last 64
+    queries -- a query's results do not depend on the other queries -- meet the reference under the
+    module's measured bound."""
+    with engine_env({"BQ_SOLVE_KCOPY": "0"}) as eng0:
+        for n, d, s, M in ((130, 3, 0.1, 16), (300, 1, 0.1, 300)):
+            assert not _beyond_direct(n, d, M)
+            x, y, h, w, s, xo, _ = _case(n, d, s, M)
+            a, b = (_both_routes(eng, x, y, h, w, s, xo) for eng in (engine, eng0))
+            assert all(a[k] is not None for k in (0, 1, 2, 3, 4, 6)) and _same(a, b)
+        n, d, s, M = 1000, 8, 0.1, 4100
+        assert _beyond_direct(n, d, M) and not _beyond_direct(n, d, M - 4)
+        x, y, h, w, s, xo, on = _case(n, d, s, M)
+        a, b = (_both_routes(eng, x, y, h, w, s, xo, True) for eng in (engine, eng0))
+    assert all(a[k] is not None for k in (0, 1, 2, 3, 4, 6)) and _same(a, b)
+    mean, var, dmean, dvar, mean1, _, dmean1, _, pm, pv = a
+    assert mean.shape == var.shape == (M,) and dmean.shape == dvar.shape == (d, M)
+    assert np.array_equal(mean, pm) and np.array_equal(var, pv)
+    cols = np.r_[0:64, M - 64:M]
+    assert on >= 64 and M - 64 >= on  # (the first 64 lie on training points, the last 64 off them)
+    ref = _reference(oracle, x, y, h, w, s, np.asfortranarray(xo[:, cols]), 64)
+    _check({"dmean": dmean[:, cols], "dvar": dvar[:, cols]}, *ref, ("dmean", "dvar"))
+    _check({"mean": mean1[cols], "dmean": dmean1[:, cols]}, *ref, ("mean", "dmean"))
 
 
 def test_leaves_the_fit_alone(engine):

@@ -1,6 +1,6 @@
-// Host-side soundness of a fit's core buffers (csrc/host.h: FitCore::alloc's failure path,
-// fit_adopt, the drop() of a fit's three captured sweeps), for a machine WITHOUT a device: there every hipMalloc of the
-// real runtime fails, which is the all-or-nothing path.  The release calls (hipFree, hipHostFree,
+// Host-side soundness of a fit's buffers (csrc/host.h: FitCore::alloc's failure path, fit_adopt, the
+// drop() of a fit's three captured sweeps, fit_grow of the on-demand workspaces), for a machine
+// WITHOUT a device: there every hipMalloc of the real runtime fails, which is the all-or-nothing path.  The release calls (hipFree, hipHostFree,
 // hipGraphExecDestroy, hipGraphDestroy) are this program's own: they take a handle out of a set of
 // live ones, so a handle freed twice or never is seen.  Host code only, under the sanitizers:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined tools/fit_core_check.hip \
@@ -131,6 +131,30 @@ int main()
         }
         delete f;
         EXPECT(live.size() == 7); // the old core, until it goes out of scope
+    }
+    EXPECT(live.empty());
+
+    // 3. fit_grow, the one way an on-demand workspace of a fit grows: a failed allocation is a
+    //    status, the caller's words and the byte count at the front of the message, and an empty
+    //    buffer -- also where it replaces a smaller one, which is let go once
+    {
+        DevBuf b;
+        const int st = bqh::fit_grow(&c, b, 4096, "check workspace");
+        EXPECT(st == BQ_ERR_NOMEM || st == BQ_ERR_HIP);
+        EXPECT(std::strncmp(c.err, "check workspace (4096 bytes): ", 30) == 0);
+        EXPECT(!b.p && b.bytes == 0);
+        std::printf("fit_grow without a device: status %d, \"%s\"\n", st, c.err);
+        hold(b, 64);
+        EXPECT(bqh::fit_grow(&c, b, 4096, "again") != BQ_OK);
+        EXPECT(!b.p && b.bytes == 0 && live.empty());
+        // a buffer that is large enough comes back untouched: no allocation was tried (here it
+        // would have failed and left the buffer empty), no message written
+        hold(b, 4096);
+        void *const p = b.p;
+        c.err[0] = 0;
+        EXPECT(bqh::fit_grow(&c, b, 4096, "enough") == BQ_OK);
+        EXPECT(bqh::fit_grow(&c, b, 100, "enough") == BQ_OK);
+        EXPECT(b.p == p && b.bytes == 4096 && live.size() == 1 && c.err[0] == 0);
     }
     EXPECT(live.empty());
     std::printf(bad ? "%d check(s) FAILED\n" : "all checks passed\n", bad);
