@@ -1139,6 +1139,25 @@ static int predict_beta(bq_ctx *c, bq_fit *f, int Mp)
     return enqueue_backward_rows(c, f->wV2.d(), f->wV.d(), Mp, Mp, f->A.d(), f->ldl, f->npad, wi);
 }
 
+// Sigma = K(xo, xo) - V V^T, the posterior covariance of the latent function (no s^2), after
+// predict_sweep: Mp x Mp, ld Mp, into C; its padding rows and columns are zero.  gd: device room
+// for the kernel parameters without s^2.  (bq_gp_predict's cov, bq_gp_sample)
+static int posterior_sigma(bq_ctx *c, bq_fit *f, const PosteriorIO &io, double *C, GaussParams *gd)
+{
+    const int Mp = io.Mp;
+    GaussParams g0 = f->g;
+    g0.s2 = 0.0;
+    HIPCHK(c, hipMemsetAsync(C, 0, sizeof(double) * (size_t)Mp * Mp, c->stream));
+    HIPCHK(c, hipMemcpyAsync(gd, &g0, sizeof g0, hipMemcpyHostToDevice, c->stream));
+    BQCHK(launch_gram_sym(c, f->d, io.xq, 0, gd, 0, C, Mp, 0, (int)io.M, 1));
+    GemmJob vvt;
+    vvt.C = C, vvt.ldc = Mp;
+    vvt.P = f->wV2.d(), vvt.ldp = Mp;
+    vvt.Q = f->wV2.d(), vvt.qsj = 1, vvt.qsk = Mp;
+    vvt.m = Mp, vvt.n = Mp, vvt.k = f->npad;
+    return launch_gemm(c, BQ_K_GEMM, vvt);
+}
+
 // what the three posterior entry points check alike; *none: there is nothing to do
 static int predict_args(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, bool any_out, bool *none)
 {
@@ -1160,7 +1179,7 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
     BQCHK(predict_args(c, f, xo, M, true, &none));
     if (none)
         return BQ_OK;
-    const int d = f->d, n = f->n, npad = f->npad;
+    const int d = f->d, n = f->n;
     if (!var && !cov)
         BQCHK(fit_alpha(c, f));
     // mean + variance without the covariance (BQ.l_var, _set_gp_log_l_params: bq.py:227-228,
@@ -1178,25 +1197,13 @@ extern "C" int bq_gp_predict(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
         // mean only: fused cross-Gram x alpha
         BQCHK(launch_predict_mean(c, d, io.xq, (int)M, f->pts.d(), n, f->alpha.d(), g, io.res));
     } else {
-        DevBuf &V = f->wV2;
         BQCHK(predict_sweep(c, f, io));
         if (cov) {
             // cov = K(xo,xo) - V V^T  (Mp x Mp on device, M x M out)
             DevBuf Cd, gd;
             HIPCHK(c, Cd.alloc(sizeof(double) * (size_t)Mp * Mp));
             HIPCHK(c, gd.alloc(sizeof(GaussParams)));
-            GaussParams g0 = g;
-            g0.s2 = 0.0;
-            HIPCHK(c, hipMemsetAsync(Cd.p, 0, Cd.bytes, c->stream));
-            HIPCHK(c, hipMemcpyAsync(gd.p, &g0, sizeof g0, hipMemcpyHostToDevice, c->stream));
-            BQCHK(launch_gram_sym(c, d, io.xq, 0, static_cast<GaussParams *>(gd.p), 0, Cd.d(), Mp,
-                                  0, (int)M, 1));
-            GemmJob vvt;
-            vvt.C = Cd.d(), vvt.ldc = Mp;
-            vvt.P = V.d(), vvt.ldp = Mp;
-            vvt.Q = V.d(), vvt.qsj = 1, vvt.qsk = Mp;
-            vvt.m = Mp, vvt.n = Mp, vvt.k = npad;
-            BQCHK(launch_gemm(c, BQ_K_GEMM, vvt));
+            BQCHK(posterior_sigma(c, f, io, Cd.d(), static_cast<GaussParams *>(gd.p)));
             HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(double) * M, Cd.p, sizeof(double) * Mp,
                                        sizeof(double) * M, M, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream)); // Cd goes out of scope
@@ -1299,4 +1306,108 @@ extern "C" int bq_gp_predict_dtheta(bq_ctx *c, bq_fit *f, const double *xo, int6
         }
     }
     return io.finish(c, nout, mean, var, dmean, dvar);
+}
+
+// S joint draws of the latent posterior at M points (include/bqhip.h has the contract; sample.h the
+// kernels).  bq_gp_predict's staging, sweep and Sigma (posterior_sigma), formed once; then per
+// ladder entry a copy of Sigma (none when the ladder has one entry: Sigma itself is factored), the
+// jitter on its first M diagonal entries, potrf_one and one read of info; then the normals
+// (uploaded, or normal_fill_kernel), tri_sample_kernel and the downloads.  The factorisation writes
+// the lower triangle alone: above the diagonal the factored matrix still holds Sigma, which the
+// product masks and the host zeroes in chol.  Every device buffer is there before the first
+// launch, and nothing reaches the caller's memory unless a ladder entry has factored.
+extern "C" int bq_gp_sample(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, int64_t S,
+                            const double *z, uint64_t seed, const double *ladder, int64_t nl,
+                            double *out, double *mean, double *chol, double *jitter)
+{
+    static const double default_ladder[5] = {0.0, 1e-12, 1e-10, 1e-8, 1e-6};
+    BQCHK(check_fit(c, f));
+    if (M < 0 || S < 1 || M > BQ_SAMPLE_MAX_M || S > BQ_SAMPLE_MAX_S || !out || (M && !xo))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (!ladder) {
+        ladder = default_ladder;
+        nl = 5;
+    }
+    if (nl < 1)
+        return fail(c, BQ_ERR_BAD_ARG, "sample: a ladder holds at least one entry");
+    for (int64_t t = 0; t < nl; ++t)
+        if (!std::isfinite(ladder[t]))
+            return fail(c, BQ_ERR_BAD_ARG, "sample: ladder entries must be finite");
+    if (M == 0)
+        return BQ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad, m = (int)M, ns = (int)S, Mp = (int)roundup(M, 64);
+    const size_t mm = (size_t)Mp * Mp, ms = (size_t)Mp * ns;
+
+    // ---- every device buffer: the sample's own, the prediction's, the factorisation's
+    auto granule = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+    const size_t ogp = 0, oinfo = granule((sizeof(GaussParams) + 7) / 8), osig = oinfo + 32,
+                 owork = osig + mm, oz = owork + (nl > 1 ? mm : 0), oout = oz + granule(ms);
+    BQCHK(fit_grow(c, f->smp, sizeof(double) * (oout + ms), "posterior sample workspace"));
+    BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(npad), "wide block inverses"));
+    BQCHK(fit_grow(c, f->wV, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, f->wV2, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
+    BQCHK(fit_grow(c, f->wx, sizeof(double) * (size_t)d * M, "prediction points"));
+    BQCHK(fit_grow(c, f->wout, sizeof(double) * 2 * (size_t)Mp, "prediction results"));
+    BQCHK(grow_panel_ws(c, Mp));
+    if (!c->dinv64.p)
+        HIPCHK(c, c->dinv64.alloc(BQ_DINV_STRIDE * sizeof(double)));
+    double *base = f->smp.d(), *Sig = base + osig, *W = nl > 1 ? base + owork : Sig, *Z = base + oz,
+           *O = base + oout;
+    int *info = reinterpret_cast<int *>(base + oinfo);
+
+    // ---- mean | var at io.res, V in f->wV2, Sigma with the identity on its padding diagonal
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, xo, M, 0, false));
+    BQCHK(predict_sweep(c, f, io));
+    BQCHK(posterior_sigma(c, f, io, Sig, reinterpret_cast<GaussParams *>(base + ogp)));
+    if (Mp > m)
+        BQCHK(launch_sample_diag(c, Sig, Mp, m, Mp, 0.0));
+
+    // ---- the first ladder entry whose matrix factors
+    double jit = 0.0;
+    int64_t t = 0;
+    for (; t < nl; ++t) {
+        jit = f->g.c * ladder[t];
+        if (nl > 1)
+            HIPCHK(c, hipMemcpyAsync(W, Sig, sizeof(double) * mm, hipMemcpyDeviceToDevice,
+                                     c->stream));
+        if (jit != 0.0)
+            BQCHK(launch_sample_diag(c, W, Mp, m, Mp, jit));
+        HIPCHK(c, hipMemsetAsync(info, 0, sizeof(int), c->stream));
+        BQCHK(potrf_one(c, W, Mp, Mp, c->dinv64.d(), info));
+        int hinfo = 0;
+        HIPCHK(c, hipMemcpyAsync(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (hinfo == 0)
+            break;
+    }
+    if (t == nl)
+        return fail(c, BQ_ERR_NOT_PD,
+                    "sample: the posterior covariance did not factor with any of the %lld jitters",
+                    (long long)nl);
+
+    // ---- the normals, the product, the downloads
+    if (z) {
+        HIPCHK(c, hipMemsetAsync(Z, 0, sizeof(double) * ms, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(Z, sizeof(double) * Mp, z, sizeof(double) * M,
+                                   sizeof(double) * M, S, hipMemcpyHostToDevice, c->stream));
+    } else {
+        BQCHK(launch_normal_fill(c, Z, Mp, m, Mp, ns, seed));
+    }
+    BQCHK(launch_tri_sample(c, W, Mp, Z, Mp, io.res, O, Mp, m, Mp, ns));
+    HIPCHK(c, hipMemcpy2DAsync(out, sizeof(double) * M, O, sizeof(double) * Mp, sizeof(double) * M,
+                               S, hipMemcpyDeviceToHost, c->stream));
+    if (chol)
+        HIPCHK(c, hipMemcpy2DAsync(chol, sizeof(double) * M, W, sizeof(double) * Mp,
+                                   sizeof(double) * M, M, hipMemcpyDeviceToHost, c->stream));
+    BQCHK(io.finish(c, 2 * (size_t)Mp, mean, nullptr, nullptr, nullptr));
+    if (chol)
+        for (int64_t j = 1; j < M; ++j)
+            for (int64_t i = 0; i < j; ++i)
+                chol[i + j * M] = 0.0;
+    if (jitter)
+        *jitter = jit;
+    return BQ_OK;
 }

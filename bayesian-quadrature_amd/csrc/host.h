@@ -20,6 +20,7 @@
 //   k_reduce.hip reduce.h trsv.h append.h        read-outs, single-vector sweeps, utilities, the
 //                remove.h kernels               finishing kernels of an append, shrinking a fit
 //                pgrad.h kernels                the posterior's gradients at the query points
+//                sample.h kernels               the posterior samples' normals and triangular product
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -474,6 +475,12 @@ int launch_predict_grad(bq_ctx *c, int d, const double *beta, long ldb, int M, i
 int launch_predict_mean_grad(bq_ctx *c, int d, const double *xo, int M, const double *pts, int n,
                              const double *alpha, const GaussParams &g, double *mean,
                              double *dmean);
+// posterior samples (sample.h): the device normals, the diagonal of the matrix to factor (add on
+// its first M entries, 1 on the padding), out = mean 1^T + tril(L) Z
+int launch_normal_fill(bq_ctx *c, double *Z, long ldz, int M, int Mp, int S, uint64_t seed);
+int launch_sample_diag(bq_ctx *c, double *A, long lda, int M, int Mp, double add);
+int launch_tri_sample(bq_ctx *c, const double *L, long ldl, const double *Z, long ldz,
+                      const double *mean, double *out, long ldo, int M, int Mp, int S);
 int launch_neg_identity(bq_ctx *c, double *nr, int B, int npad);
 int launch_pad_identity(bq_ctx *c, double *A, long lda, int n, int ntot);
 int launch_logdet(bq_ctx *c, const double *diag, long stride, int n, double *out);
@@ -658,6 +665,9 @@ int solve_rows_host(bq_ctx *c, const double *L, long ldl, int n, int npad, WideI
 // ---- linalg.hip -----------------------------------------------------------------------
 // factor one ntot x ntot device matrix on the context's panel scratch (dinv: BQ_DINV_STRIDE)
 int potrf_one(bq_ctx *c, double *A, long lda, int ntot, double *dinv, int *info);
+// that scratch grown to what potrf_one of an ntot x ntot matrix uses (a caller that allocates
+// everything before it enqueues anything)
+int grow_panel_ws(bq_ctx *c, int ntot);
 
 } // namespace bqh
 
@@ -789,6 +799,9 @@ struct bq_fit : FitCore {
     void drop(unsigned event) { have &= ~event; }
     DevBuf wide;                  // wide_alloc_doubles(npad), allocated on the first sweep
     DevBuf wV, wV2, wx, wout, wz; // prediction workspaces, grown on demand and kept
+    // posterior samples (bq_gp_sample): GaussParams without s^2 | info | Sigma | the matrix being
+    // factored (a ladder of more than one entry) | Z | out, grown on demand and kept
+    DevBuf smp;
     // the log-ML gradient (bq_gp_logml_grad): Y and the sweep's partial sums (npad x npad each),
     // allocated on the first gradient; the product's partials and the d + 2 results
     DevBuf gY, gX, gpart;

@@ -1,9 +1,11 @@
 // k_reduce.hip -- read-outs, single-vector sweeps and small utilities (reduce.h, trsv.h), the
 // posterior's gradients at the query points (pgrad.h), the kernels that grow and shrink a
-// resident fit (append.h, remove.h) and their launchers.
+// resident fit (append.h, remove.h), the posterior samples' normals and triangular product
+// (sample.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "pgrad.h"
+#include "sample.h"
 #include "trsv.h"
 #include "trsvflow.h"
 #include "append.h"
@@ -77,6 +79,40 @@ int launch_predict_mean_grad(bq_ctx *c, int d, const double *xo, int M, const do
     dim3 grid((unsigned)((M + 3) / 4));
     BQ_DISPATCH_D(d, hipLaunchKernelGGL(predict_mean_grad_kernel<D>, grid, dim3(256), 0, c->stream, xo,
                                         M, pts, n, alpha, g, mean, dmean));
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// ---- posterior samples (sample.h; fit.hip, bq_gp_sample) ----
+// Z (Mp x S, ld ldz): standard normals keyed by (seed, j + M s) in rows < M, zeros below
+int launch_normal_fill(bq_ctx *c, double *Z, long ldz, int M, int Mp, int S, uint64_t seed)
+{
+    Bracket br(c, BQ_K_REDUCE);
+    const long total = (long)Mp * S;
+    hipLaunchKernelGGL(normal_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       c->stream, Z, ldz, M, Mp, S, seed);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// A[i, i] += add for i < M, = 1 for M <= i < Mp
+int launch_sample_diag(bq_ctx *c, double *A, long lda, int M, int Mp, double add)
+{
+    hipLaunchKernelGGL(sample_diag_kernel, dim3((Mp + 255) / 256), dim3(256), 0, c->stream, A, lda,
+                       M, Mp, add);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// out (M x S, ld ldo) = mean 1^T + tril(L) Z; L: Mp x Mp, Z: Mp x S with zero rows M .. Mp
+int launch_tri_sample(bq_ctx *c, const double *L, long ldl, const double *Z, long ldz,
+                      const double *mean, double *out, long ldo, int M, int Mp, int S)
+{
+    if (M < 1 || S < 1 || Mp < M || (Mp & 63))
+        return fail(c, BQ_ERR_BAD_ARG, "tri_sample: M, S >= 1 over whole 64-row blocks");
+    Bracket br(c, BQ_K_GEMM, (double)Mp * Mp * S);
+    hipLaunchKernelGGL(tri_sample_kernel, dim3(Mp / 64, (S + 63) / 64), dim3(256), 0, c->stream, L,
+                       ldl, Z, ldz, mean, out, ldo, M, S);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -23,7 +23,7 @@ static int upload_padded(bq_ctx *c, const double *H, int n, DevBuf &A, int &ntot
 }
 
 // the context's panel scratch, grown to what the sweep of one ntot x ntot matrix uses
-static int grow_panel_ws(bq_ctx *c, int ntot)
+int bqh::grow_panel_ws(bq_ctx *c, int ntot)
 {
     const size_t bytes = sizeof(double) * sweep_route(c, ntot, ntot, 1).ws_doubles;
     if (c->panel_ws.bytes < bytes)

@@ -669,6 +669,10 @@ class Engine(object):
         return out.reshape(64, 4)
 
 
+# bq_gp_sample's default jitter ladder, in multiples of the prior variance k(x, x)
+SAMPLE_LADDER = (0.0, 1e-12, 1e-10, 1e-8, 1e-6)
+
+
 class Fit(object):
     """Device-resident GP fit (bq_fit): L, z = L^-1 y, log-ML; alpha on demand."""
 
@@ -908,6 +912,41 @@ class Fit(object):
         e._check(e._lib.bq_gp_predict_dtheta(e._ctx, self._handle(), L.dptr(xo), M, L.dptr(mean),
                                              L.dptr(var), L.dptr(dmean), L.dptr(dvar)))
         return mean, var, dmean, dvar
+
+    def sample(self, xo, S=1, z=None, seed=0, ladder=None, want_chol=False):
+        """(out, mean, jitter[, chol]): S joint draws of the latent posterior at the points xo,
+        on the device (bq_gp_sample).  out: (M, S) Fortran-ordered, column s one draw
+        mean + L_c z_s with L_c L_c^T = cov + jitter I (no s^2, as ``predict``'s cov); mean: (M,),
+        ``predict``'s bits; jitter: the absolute value added to the diagonal, k(x, x) times the
+        first entry of ``ladder`` that factors (default: SAMPLE_LADDER).  z: (M, S)
+        standard normals of the caller's; None: the device draws them, Philox4x32-10 keyed by the
+        64-bit ``seed`` (ignored when z is given).  ``want_chol`` appends L_c, (M, M), its strict
+        upper triangle zero.  LinAlgError when no ladder entry factors."""
+        xo = _pts(xo)
+        if xo.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        M, S = xo.shape[1], int(S)
+        if z is not None:
+            z = np.asfortranarray(z, dtype=np.float64)
+            if z.shape != (M, S):
+                raise ValueError("z must be (M, S)")
+        if ladder is not None:
+            ladder = np.ascontiguousarray(np.atleast_1d(ladder), dtype=np.float64)
+            if ladder.ndim != 1:
+                raise ValueError("ladder must be a sequence of numbers")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        out, mean = np.empty((M, max(S, 0)), order="F"), np.empty(M)
+        chol = np.empty((M, M), order="F") if want_chol else None
+        jitter = C.c_double()
+        e = self._eng
+        e._check(e._lib.bq_gp_sample(e._ctx, self._handle(), L.dptr(xo), M, S, L.dptr(z), seed,
+                                     L.dptr(ladder), 0 if ladder is None else ladder.size,
+                                     L.dptr(out), L.dptr(mean), L.dptr(chol),
+                                     C.cast(C.byref(jitter), _dp)))
+        res = (out, mean, float(jitter.value))
+        return res + (chol,) if want_chol else res
 
 
 class Pair(object):

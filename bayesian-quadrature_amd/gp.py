@@ -602,6 +602,39 @@ class GP(object):
         c = self._device_fit().predict(xo, want_mean=False, want_var=True, want_cov=True)[2]
         return np.ascontiguousarray(c)
 
+    def sample(self, xo, n=1, seed=None, z=None, ladder=None, return_info=False):
+        """``n`` joint draws of the latent function at the points, (n, M): row i is
+        ``mean(xo) + L_c z_i`` with ``L_c L_c^T = cov(xo) + jitter I`` (no s^2, as ``cov``), all on
+        the device fit (bq_gp_sample) -- sample paths, Thompson draws over a candidate grid,
+        Monte-Carlo propagation of the posterior.  ``xo`` is a vector of points, or d x M as for
+        ``dmean_dx``.  A smooth posterior at dense points is numerically singular, so the jitter
+        is part of the contract: k(x, x) times the first entry of ``ladder`` (default 0, 1e-12,
+        1e-10, 1e-8, 1e-6) at which the covariance factors; numpy.linalg.LinAlgError when none
+        does.  ``z``: (n, M) standard normals to use; None: the device draws them from ``seed``,
+        and ``seed=None`` takes a 64-bit seed from ``numpy.random``, so ``np.random.seed`` makes a
+        script reproducible.  ``return_info`` appends {"mean", "jitter"}."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        n = int(n)
+        if n < 1:
+            raise ValueError("invalid value for n: %s" % n)
+        M = xo.shape[-1] if xo.ndim <= 2 else -1
+        if z is not None:
+            z = np.asarray(z, dtype=DTYPE)
+            if z.shape != (n, M):
+                raise ValueError("z must be (n, M)")
+        if xo.size == 0:
+            out = np.empty((n, 0), dtype=DTYPE)
+            info = {"mean": np.empty(0, dtype=DTYPE), "jitter": 0.0}
+            return (out, info) if return_info else out
+        if z is None and seed is None:
+            seed = int(np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+                       .dot(np.array([1, 2 ** 32], dtype=np.uint64)))
+        out, mean, jitter = self._device_fit().sample(
+            xo, S=n, z=None if z is None else z.T, seed=0 if seed is None else seed,
+            ladder=ladder)
+        out = np.ascontiguousarray(out.T)
+        return (out, {"mean": mean, "jitter": jitter}) if return_info else out
+
     # -- pickling / copying: only data and parameters travel -------------------
     def __getstate__(self):
         state = {"K": self.K, "x": self._x, "y": self._y, "s": self._s}

@@ -284,6 +284,38 @@ int bq_gp_predict_grad(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, do
  * call.  At s == 0 the h entry of dmean and the s entries of both are exactly 0. */
 int bq_gp_predict_dtheta(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double *mean,
                          double *var, double *dmean, double *dvar);
+/* S joint draws of the latent posterior at M points, on the device: the sweep of bq_gp_predict,
+ * Sigma = K(xo, xo) - V V^T (no s^2: the matrix bq_gp_predict returns as cov), its device Cholesky
+ * factor and one triangular product:
+ *   out[:, s] = mean + L_c z_s,   L_c L_c^T = Sigma + jitter I.
+ * xo: d x M column-major like bq_gp_predict.  out: M x S column-major on the host (required).
+ * z: M x S column-major standard normals of the caller's, or NULL: then element e = j + M s is drawn
+ * on the device from Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (e & 0xffffffff, e >> 32, 0, 0), outputs r0 .. r3:
+ *   u1 = ((r0 >> 5) 2^26 + (r1 >> 6) + 1) 2^-53,  u2 = ((r2 >> 5) 2^26 + (r3 >> 6)) 2^-53,
+ *   z = sqrt(-2 ln u1) cos(2 pi u2)
+ * -- a value depends on (seed, e) alone, so a host program can reproduce it.  seed is ignored when
+ * z is given.
+ * ladder: nl >= 1 finite multiples of k0 = k(x, x), the prior variance, tried in order on the one
+ * Sigma that was formed; the first whose Sigma + k0 ladder[t] I factors is used (entries may be
+ * negative).  NULL: the default ladder 0, 1e-12, 1e-10, 1e-8, 1e-6 (nl is ignored).  A smooth
+ * posterior at dense points is numerically singular: the jitter is part of the contract.
+ * mean (M, or NULL): the bits bq_gp_predict returns when asked for mean and var.  chol (M x M
+ * column-major, or NULL): L_c, its strict upper triangle exact zeros.  jitter (one double, or
+ * NULL): the absolute value added, k0 ladder[t].
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG for M < 0, S < 1,
+ * M > BQ_SAMPLE_MAX_M, S > BQ_SAMPLE_MAX_S, out == NULL, a ladder entry that is not finite, nl < 1
+ * with a ladder -- all checked before anything is allocated; M == 0 touches nothing.
+ * BQ_ERR_NOT_PD: every ladder entry failed; no output is written.  Device memory (the prediction's
+ * workspaces, one or two Mp x Mp matrices and two Mp x S ones, Mp = M rounded up to 64; kept with
+ * the fit) is allocated before anything is enqueued: BQ_ERR_NOMEM leaves the fit as it was.  The
+ * fit is not disturbed; the same inputs give the same bits on every call, and column s of out does
+ * not depend on S. */
+#define BQ_SAMPLE_MAX_M 16384
+#define BQ_SAMPLE_MAX_S 4096
+int bq_gp_sample(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, int64_t S,
+                 const double *z, uint64_t seed, const double *ladder, int64_t nl,
+                 double *out, double *mean, double *chol, double *jitter);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
