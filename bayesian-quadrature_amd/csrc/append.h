@@ -9,6 +9,7 @@
 // every sum has a fixed order, the results are the same bits from run to run.
 #pragma once
 #include "common.h"
+#include "wgsum.h"
 
 #define BQ_APPEND_CHUNK 256                  // columns of V per workgroup of append_part_kernel
 #define BQ_APPEND_PART (64 * 64 + 64)        // doubles per workgroup: V V^T (ld 64), then V z
@@ -196,6 +197,7 @@ __global__ __launch_bounds__(256) void append_rhs_kernel(const double *__restric
         if (!(l * l > tol) && i < mine)
             mine = i;
     }
+    // (wgsum.h's tree in its min form, written out: through wg_tree this kernel compiles to other code)
     first[t] = mine;
     __syncthreads();
     for (int off = 128; off > 0; off >>= 1) {
@@ -225,16 +227,7 @@ __global__ __launch_bounds__(256) void append_commit_kernel(AppendJob a)
                 const double z = a.zn[(long)i * a.zstride];
                 sq = fma(z, z, sq);
             }
-        pl[t] = sl;
-        pq[t] = sq;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if (t < off) {
-                pl[t] += pl[t + off];
-                pq[t] += pq[t + off];
-            }
-            __syncthreads();
-        }
+        wg_tree_add2(sl, sq, pl, pq);
         if (t == 0) {
             reinterpret_cast<int *>(a.out)[0] = bad;
             const double logdet = a.logdet + 2.0 * pl[0], qf = a.qf + pq[0];

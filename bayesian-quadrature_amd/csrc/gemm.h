@@ -2,9 +2,11 @@
 // Part of the libbqhip.so kernel set; compiled into k_gemm.hip (host.h lists the units).
 #pragma once
 #include "common.h"
+#include "dk.h"
 #include "potf2.h"
 #include "seed.h"
 #include "solve16.h"
+#include "wgsum.h"
 
 
 // one wave tile of C -= P Q^T (see gemm_sub_kernel); C, P, Q already point at the batch element
@@ -557,14 +559,8 @@ __device__ __forceinline__ void grad_tile_reduce(const double (&acc)[TM][TN][4],
                     if (j >= gj.n)
                         continue;
                     const double G = -acc[tm][tn][s];
-                    double r2[D], q = 0.0; // gauss_q's arithmetic
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        const double t = xi[k] - gj.pts[k + (long)j * D];
-                        r2[k] = t * t;
-                        q += r2[k] * g.nh[k];
-                    }
-                    const double gk = G * (g.c * exp_gauss(q));
+                    double r2[D];
+                    const double gk = G * gauss_k0<D>(xi, gj.pts + (long)j * D, g, r2);
                     sum[0] += gk;
 #pragma unroll
                     for (int k = 0; k < D; ++k) // r^2 / w^2 = -2 nh r^2
@@ -578,22 +574,10 @@ __device__ __forceinline__ void grad_tile_reduce(const double (&acc)[TM][TN][4],
         for (int c = 0; c < NC; ++c)
             sum[c] *= wt;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            sum[c] += __shfl_xor(sum[c], off);
-    // the staging buffers are free once every wave is past its last chunk
-    double *red = reinterpret_cast<double *>(smem);
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            red[wave * NC + c] = sum[c];
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < NC)
-        gj.part[(long)blockIdx.x * NC + t] = ((red[t] + red[NC + t]) + red[2 * NC + t]) + red[3 * NC + t];
+    // (the staging buffers are free once every wave is past its last chunk: wg_wave_sums' barrier)
+    const double v = wg_wave_sums<NC>(sum, reinterpret_cast<double *>(smem), lane, wave);
+    if (threadIdx.x < NC)
+        gj.part[(long)blockIdx.x * NC + threadIdx.x] = v;
 }
 
 // SD > 0: C has not been written yet -- the accumulators start as minus the bordered system's own
@@ -754,31 +738,7 @@ __global__ __launch_bounds__(256, 2) void gemm_lds_grad_kernel(const double *__r
                         0x7fffffff, nullptr, &gj);
 }
 
-// Sums the partials of gemm_lds(64)_grad_kernel in a fixed order (same bits on every call) and scales
-// them into the gradient: grad = [S_K / h, S_k / (2 w_k), s S_s]
-__global__ __launch_bounds__(256) void grad_finalize_kernel(const double *__restrict__ part,
-                                                            int nwg, int nc, GradScale sc,
-                                                            double *__restrict__ grad)
-{
-    __shared__ double red[256];
-    const int t = threadIdx.x;
-    for (int c = 0; c < nc; ++c) {
-        double v = 0.0;
-        for (int i = t; i < nwg; i += 256)
-            v += part[(long)i * nc + c];
-        red[t] = v;
-        __syncthreads();
-        for (int h = 128; h > 0; h >>= 1) {
-            if (t < h)
-                red[t] += red[t + h];
-            __syncthreads();
-        }
-        if (t == 0)
-            grad[c] = red[0] * sc.f[c];
-        __syncthreads();
-    }
-}
-
+// (fold_kernel<GradScale>, wgsum.h, sums the partials and scales: [S_K / h, S_k / (2 w_k), s S_s])
 // ... its tile of C computed, not loaded (the first product over a region the assembly left out)
 template <int SD>
 __global__ __launch_bounds__(256, 2) void gemm_lds_seed_kernel(

@@ -5,7 +5,8 @@
 //   H_pq = 1/2 sum(G o D_pq) - (D_p a)^T Ki (D_q a) + 1/2 tr(Ki D_p Ki D_q)
 // Ki D_h = (2 / h) C with C = I - s^2 Ki and Ki D_s = 2 s Ki need no product; B_k = Ki D_k is the
 // one n x n x n product per length scale.  Its D_k operand is generated from the resident points
-// chunk by chunk, never stored.
+// chunk by chunk, never stored (dk.h: its entries and the rows of D_k a; wgsum.h: the workgroup's
+// fixed-order sums and fold_kernel, which folds the tiles' partials).
 //
 //   hess_prod_kernel<0>    Ki = Y Y^T, all of it (a tile's k range starts at its first row or
 //                          column, whichever is later: Y is upper triangular)
@@ -15,27 +16,11 @@
 //   hess_dka_kernel<D>     the vectors D_p a
 //   hess_kiv_kernel        Ki (D_p a)
 //   hess_quad_kernel       the dot products (D_p a)^T Ki (D_q a), p <= q
-//   hess_finalize_kernel   the tiles' partial sums in a fixed order
 // Rows and columns at or beyond n (the identity padding) are masked out of every sum.
 #pragma once
 #include "common.h"
-
-#define BQ_HESS_KC 16 // k columns per chunk
-
-// K0(i, j) and r_k^2 from the points, gauss_q's arithmetic
-template <int D>
-__device__ __forceinline__ double hess_k0(const double (&xi)[D], const double *__restrict__ xj,
-                                          const GaussParams &g, double (&r2)[D])
-{
-    double q = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double t = xi[k] - xj[k];
-        r2[k] = t * t;
-        q += r2[k] * g.nh[k];
-    }
-    return g.c * exp_gauss(q);
-}
+#include "dk.h"
+#include "wgsum.h"
 
 // C (npad x npad, ld npad) = A Q^T over k in [0, npad).
 // D == 0: Q is a matrix like A (both Y = L^-T: C = Ki); the k range starts at max(R0, C0).
@@ -58,9 +43,9 @@ __global__ __launch_bounds__(256, 2) void hess_prod_kernel(double *__restrict__ 
     static_assert(COLS == 64, "the generated operand is dealt as 64 columns x 4 k rows");
     // (row strides of 16 mod 32 doubles: the four k rows of a fragment read fall in disjoint banks)
     constexpr int LDA = ROWS + 16, LDQ = COLS + 16;
-    constexpr int NA = ROWS * BQ_HESS_KC / 256, NQ = COLS * BQ_HESS_KC / 256;
-    __shared__ double sA[BQ_HESS_KC * LDA];
-    __shared__ double sQ[BQ_HESS_KC * LDQ];
+    constexpr int NA = ROWS * BQ_DK_KC / 256, NQ = COLS * BQ_DK_KC / 256;
+    __shared__ double sA[BQ_DK_KC * LDA];
+    __shared__ double sQ[BQ_DK_KC * LDQ];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int npad = hj.npad;
@@ -105,11 +90,11 @@ __global__ __launch_bounds__(256, 2) void hess_prod_kernel(double *__restrict__ 
                 double v = 0.0;
                 if (jq < hj.n && k < hj.n) {
                     double r2[D], rk = 0.0;
-                    const double k0v = hess_k0<D>(xj, hj.pts + (long)k * D, hj.g, r2);
+                    const double k0v = gauss_k0<D>(xj, hj.pts + (long)k * D, hj.g, r2);
 #pragma unroll
                     for (int m = 0; m < D; ++m)
                         rk = m == kdim ? r2[m] : rk;
-                    v = k0v * ((iw2 * rk - 1.0) * iw);
+                    v = k0v * dk_weight(iw, iw2, rk);
                 }
                 rq[e] = v;
             }
@@ -118,11 +103,11 @@ __global__ __launch_bounds__(256, 2) void hess_prod_kernel(double *__restrict__ 
 
     int kbeg = 0;
     if constexpr (D == 0) // Y(i, k) = 0 for k < i
-        kbeg = max(R0, C0) & ~(BQ_HESS_KC - 1);
-    const int kend = D == 0 ? npad : (int)((hj.n + BQ_HESS_KC - 1) & ~(BQ_HESS_KC - 1));
+        kbeg = max(R0, C0) & ~(BQ_DK_KC - 1);
+    const int kend = D == 0 ? npad : (int)((hj.n + BQ_DK_KC - 1) & ~(BQ_DK_KC - 1));
     if (kbeg < kend)
         fetch(kbeg);
-    for (int k0 = kbeg; k0 < kend; k0 += BQ_HESS_KC) {
+    for (int k0 = kbeg; k0 < kend; k0 += BQ_DK_KC) {
         __syncthreads(); // every wave is done with the chunk before
 #pragma unroll
         for (int e = 0; e < NA; ++e) {
@@ -133,10 +118,10 @@ __global__ __launch_bounds__(256, 2) void hess_prod_kernel(double *__restrict__ 
         for (int e = 0; e < NQ; ++e)
             sQ[(kq + 4 * e) * LDQ + (t & 63)] = rq[e];
         __syncthreads();
-        if (k0 + BQ_HESS_KC < kend)
-            fetch(k0 + BQ_HESS_KC);
+        if (k0 + BQ_DK_KC < kend)
+            fetch(k0 + BQ_DK_KC);
 #pragma unroll
-        for (int ks = 0; ks < BQ_HESS_KC / 4; ++ks) {
+        for (int ks = 0; ks < BQ_DK_KC / 4; ++ks) {
             double fa[TM], fq[TN];
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
@@ -166,26 +151,14 @@ __global__ __launch_bounds__(256, 2) void hess_prod_kernel(double *__restrict__ 
     }
 }
 
-// One workgroup's NC sums: lanes by shuffles, the four waves through LDS, both in a fixed order.
-// part: [NC][nwg], this workgroup's column wg.
+// One workgroup's NC sums (wg_wave_sums, wgsum.h) into part: [NC][nwg], this workgroup's column wg
 template <int NC>
 __device__ __forceinline__ void hess_block_sums(double (&sum)[NC], double *red,
                                                 double *__restrict__ part, int wg, int nwg)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            sum[c] += __shfl_xor(sum[c], off);
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            red[wave * NC + c] = sum[c];
-    __syncthreads();
-    for (int c = threadIdx.x; c < NC; c += 256)
-        part[(long)c * nwg + wg] = ((red[c] + red[NC + c]) + red[2 * NC + c]) + red[3 * NC + c];
+    const double v = wg_wave_sums<NC>(sum, red, threadIdx.x & 63, threadIdx.x >> 6);
+    if (threadIdx.x < NC)
+        part[(long)threadIdx.x * nwg + wg] = v;
 }
 
 // The sums of G = a a^T - Ki against K0 and its weights, one 64 x 64 tile per workgroup
@@ -218,11 +191,11 @@ __global__ __launch_bounds__(256) void hess_gsum_kernel(const double *__restrict
                 continue;
             const double G = ai * hj.alpha[j] - Ki[i + j * ld];
             double r2[D], u[D];
-            const double gk = G * hess_k0<D>(xi, hj.pts + (long)j * D, hj.g, r2);
+            const double gk = G * gauss_k0<D>(xi, hj.pts + (long)j * D, hj.g, r2);
             sum[0] += gk;
 #pragma unroll
             for (int k = 0; k < D; ++k) {
-                u[k] = (iw2[k] * r2[k] - 1.0) * iw[k];
+                u[k] = dk_weight(iw[k], iw2[k], r2[k]);
                 sum[1 + k] += gk * u[k];
             }
 #pragma unroll
@@ -311,30 +284,7 @@ __global__ __launch_bounds__(256) void hess_dka_kernel(HessJob hj, const double 
 {
     const int t = threadIdx.x, i = blockIdx.x * 16 + (t >> 4), jl = t & 15;
     double sum[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-        sum[k] = 0.0;
-    if (i < hj.n) {
-        double xi[D], iw[D], iw2[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            xi[k] = hj.pts[k + (long)i * D];
-            iw[k] = hj.iw[k];
-            iw2[k] = iw[k] * iw[k];
-        }
-        for (int j = jl; j < hj.n; j += 16) {
-            double r2[D];
-            const double ka = hess_k0<D>(xi, hj.pts + (long)j * D, hj.g, r2) * hj.alpha[j];
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-                sum[k] += ka * ((iw2[k] * r2[k] - 1.0) * iw[k]);
-        }
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-            sum[k] += __shfl_xor(sum[k], off);
+    dka_sums<D>(hj, i, jl, sum);
     if (jl == 0) {
         const long ld = hj.npad;
         const bool in = i < hj.n;
@@ -392,6 +342,7 @@ __global__ __launch_bounds__(256) void hess_quad_kernel(const double *__restrict
             double v = 0.0;
             for (int i = t; i < n; i += 256)
                 v += V[(long)p * npad + i] * Z[(long)q * npad + i];
+            // (wgsum.h's tree, written out: through wg_tree_sum the kernel compiles differently)
             red[t] = v;
             __syncthreads();
             for (int h = 128; h > 0; h >>= 1) {
@@ -403,24 +354,4 @@ __global__ __launch_bounds__(256) void hess_quad_kernel(const double *__restrict
                 out[o] = red[0];
             __syncthreads();
         }
-}
-
-// out[c] = the sum of part[c][0 .. nwg) in a fixed order (same bits on every call); grid: the sums
-__global__ __launch_bounds__(256) void hess_finalize_kernel(const double *__restrict__ part,
-                                                            int nwg, double *__restrict__ out)
-{
-    __shared__ double red[256];
-    const int t = threadIdx.x, c = blockIdx.x;
-    double v = 0.0;
-    for (int i = t; i < nwg; i += 256)
-        v += part[(long)c * nwg + i];
-    red[t] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h)
-            red[t] += red[t + h];
-        __syncthreads();
-    }
-    if (t == 0)
-        out[c] = red[0];
 }

@@ -13,6 +13,8 @@
 //   k_hess.hip   hess.h loo.h lgo.h kernels     the log-ML Hessian's sums, leave-one-out and
 //                                               leave-group-out
 //                ptheta.h kernels               the posterior's derivatives in the hyper-parameters
+//                dk.h wgsum.h                   (shared: the derivative operand's entries and D_k a
+//                                               rows; a workgroup's fixed-order sums, fold_kernel)
 //   k_panel.hip  potf2.h trsm.h slab.h kernels  launch_assemble, launch_potf2, launch_trsm_blk,
 //                                               the one-launch steps
 //                solve16.h                      (both units: the 16-row solve from block inverses,
@@ -353,7 +355,7 @@ int launch_slab_step(bq_ctx *c, double *A, long lda, long astride, int batch, do
 
 // ---- k_gemm.hip -----------------------------------------------------------------------
 int gemm_init(bq_ctx *c); // function attributes of the LDS-staged kernels, once per context
-// the log-ML gradient's product and finalize (gemm_lds_grad_kernel, grad_finalize_kernel)
+// the log-ML gradient's product and finalize (gemm_lds_grad_kernel, fold_kernel<GradScale>)
 int grad_tile(const bq_ctx *c, int npad); // 128 / 64: its workgroup tile (the Hessian's follows it)
 size_t grad_parts(int npad, int d);
 int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob &gj,

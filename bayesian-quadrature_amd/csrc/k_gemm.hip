@@ -255,7 +255,7 @@ int launch_gemm(bq_ctx *c, int cls, const GemmJob &g, GemmRoute *ran)
 // The log-ML gradient from Y = L^-T (npad x npad, ld npad, zero below its diagonal) and the fit's
 // alpha: the lower tiles of G = alpha alpha^T - Y Y^T, each reduced against the kernel's
 // derivatives into d + 2 partials (gemm_lds(64)_grad_kernel), then one workgroup sums them in a
-// fixed order and scales them (grad_finalize_kernel).  part: grad_parts(npad, d) doubles; grad: d + 2.
+// fixed order and scales them (fold_kernel<GradScale>, wgsum.h).  part: grad_parts(npad, d) doubles; grad: d + 2.
 //
 // Workgroup tile: 128 x 128 once the lower 128-tiles number at least kGrad128PerCu per CU, else
 // 64 x 64 (four times the workgroups).  BQ_GEMM_TILE=64|128 forces one (measurements).
@@ -295,8 +295,9 @@ int launch_logml_grad(bq_ctx *c, int d, const double *Y, int npad, const GradJob
         HIPCHK(c, hipGetLastError());
     }
     Bracket br(c, BQ_K_REDUCE);
-    hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, c->cur, gj.part, (int)nwg,
-                       d + 2, sc, grad);
+    // (one workgroup takes the d + 2 sums in turn; a partial's sums lie side by side)
+    hipLaunchKernelGGL(fold_kernel<GradScale>, dim3(1), dim3(256), 0, c->cur, gj.part, (int)nwg,
+                       (long)(d + 2), 1L, d + 2, sc, grad);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }

@@ -21,6 +21,30 @@ size_t hess_ws_doubles(int npad, int d)
 {
     return hess_off_sums(npad, d) + (size_t)(hess_ng(d) + hess_nt(d) + hess_nq(d));
 }
+// its views; T = const double for the stages that only read it (loo_grad_run, launch_lgo_grad)
+template <class T>
+struct HessWs { T *B, *V, *Z, *part, *sums; };
+template <class T>
+static HessWs<T> hess_views(T *ws, int npad, int d)
+{
+    T *V = ws + hess_off_v(npad, d);
+    return {ws, V, V + (size_t)(d + 2) * npad, ws + hess_off_part(npad, d), ws + hess_off_sums(npad, d)};
+}
+
+// what every launcher of this unit asks of d and npad, and the message of those that ask no more
+static bool bad_d_npad(int d, int npad) { return d < 1 || d > BQ_MAXD || (npad % 64); }
+static int fail_d_npad(bq_ctx *c, const char *what)
+{
+    return fail(c, BQ_ERR_BAD_ARG, "%s: d in [1, %d], npad a multiple of 64", what, BQ_MAXD);
+}
+
+// out[c] = the sum over i < nitem of part[i item_stride + c c_stride], c < nc, a workgroup per c
+static void launch_fold(bq_ctx *c, const double *part, int nitem, long item_stride, long c_stride,
+                        int nc, double *out)
+{
+    hipLaunchKernelGGL(fold_kernel<FoldPlain>, dim3((unsigned)nc), dim3(256), 0, c->stream, part, nitem,
+                       item_stride, c_stride, nc, FoldPlain{}, out);
+}
 
 // Workgroup tile of the products: the tall 256 x 64 tile where the gradient's product takes its
 // 128 x 128 tile (as many workgroups), else 64 x 64
@@ -46,7 +70,7 @@ static int hess_run_products(bq_ctx *c, const double *Y, double *Ki, double *ws,
 {
     const int npad = hj.npad;
     const bool tall = hess_tall(c, npad);
-    double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
+    const HessWs<double> w = hess_views(ws, npad, D);
     const double n3 = (double)npad * npad * npad;
     {
         Bracket br(c, BQ_K_GEMM, n3 * 2.0 / 3.0);
@@ -55,14 +79,14 @@ static int hess_run_products(bq_ctx *c, const double *Y, double *Ki, double *ws,
     }
     for (int k = 0; k < D; ++k) {
         Bracket br(c, BQ_K_GEMM, 2.0 * n3);
-        hess_launch_prod<D>(c, tall, B + (size_t)k * npad * npad, Ki, nullptr, hj, k);
+        hess_launch_prod<D>(c, tall, w.B + (size_t)k * npad * npad, Ki, nullptr, hj, k);
         HIPCHK(c, hipGetLastError());
     }
     Bracket br(c, BQ_K_REDUCE);
     hipLaunchKernelGGL(hess_dka_kernel<D>, dim3((unsigned)npad / 16), dim3(256), 0, c->stream, hj, y,
-                       2.0 / h, 2.0 * s, V);
+                       2.0 / h, 2.0 * s, w.V);
     hipLaunchKernelGGL(hess_kiv_kernel, dim3((unsigned)npad / 4), dim3(256), 0, c->stream, Ki, hj.n,
-                       npad, D + 2, V, Z);
+                       npad, D + 2, w.V, w.Z);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -72,20 +96,18 @@ template <int D>
 static int hess_run_sums(bq_ctx *c, const double *Ki, double *ws, const HessJob &hj)
 {
     const int npad = hj.npad, n = hj.n;
-    const double *B = ws, *V = ws + hess_off_v(npad, D), *Z = V + (size_t)(D + 2) * npad;
-    double *part = ws + hess_off_part(npad, D), *sums = ws + hess_off_sums(npad, D);
+    const HessWs<double> w = hess_views(ws, npad, D);
     Bracket br(c, BQ_K_REDUCE);
     const unsigned g64 = (unsigned)npad / 64;
     const int nwg = (int)(g64 * g64);
-    hipLaunchKernelGGL(hess_gsum_kernel<D>, dim3(g64, g64), dim3(256), 0, c->stream, Ki, hj, part);
-    hipLaunchKernelGGL(hess_finalize_kernel, dim3(hess_ng(D)), dim3(256), 0, c->stream, part, nwg,
-                       sums);
-    hipLaunchKernelGGL(hess_trace_kernel<D>, dim3(g64, g64), dim3(256), 0, c->stream, Ki, B, hj,
-                       part);
-    hipLaunchKernelGGL(hess_finalize_kernel, dim3(hess_nt(D)), dim3(256), 0, c->stream, part, nwg,
-                       sums + hess_ng(D));
-    hipLaunchKernelGGL(hess_quad_kernel, dim3(1), dim3(256), 0, c->stream, V, Z, n, npad, D + 2,
-                       sums + hess_ng(D) + hess_nt(D));
+    // (a tile's partial of sum c at part[c nwg + tile])
+    hipLaunchKernelGGL(hess_gsum_kernel<D>, dim3(g64, g64), dim3(256), 0, c->stream, Ki, hj, w.part);
+    launch_fold(c, w.part, nwg, 1, nwg, hess_ng(D), w.sums);
+    hipLaunchKernelGGL(hess_trace_kernel<D>, dim3(g64, g64), dim3(256), 0, c->stream, Ki, w.B, hj,
+                       w.part);
+    launch_fold(c, w.part, nwg, 1, nwg, hess_nt(D), w.sums + hess_ng(D));
+    hipLaunchKernelGGL(hess_quad_kernel, dim3(1), dim3(256), 0, c->stream, w.V, w.Z, n, npad, D + 2,
+                       w.sums + hess_ng(D) + hess_nt(D));
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -96,8 +118,8 @@ static int hess_run_sums(bq_ctx *c, const double *Ki, double *ws, const HessJob 
 int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *ws,
                          const HessJob &hj, const double *y, double h, double s)
 {
-    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
-        return fail(c, BQ_ERR_BAD_ARG, "hess_products: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    if (bad_d_npad(d, hj.npad))
+        return fail_d_npad(c, "hess_products");
     int st = BQ_OK;
     BQ_DISPATCH_D(d, st = hess_run_products<D>(c, Y, Ki, ws, hj, y, h, s));
     return st;
@@ -108,10 +130,10 @@ int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *
 int launch_hess_sums(bq_ctx *c, int d, const double *Ki, double *ws, const HessJob &hj,
                      const double **sums)
 {
-    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
-        return fail(c, BQ_ERR_BAD_ARG, "hess_sums: d in [1, %d], npad a multiple of 64", BQ_MAXD);
-    *sums = ws + hess_off_sums(hj.npad, d);
+    if (bad_d_npad(d, hj.npad))
+        return fail_d_npad(c, "hess_sums");
     int st = BQ_OK;
+    *sums = hess_views(ws, hj.npad, d).sums;
     BQ_DISPATCH_D(d, st = hess_run_sums<D>(c, Ki, ws, hj));
     return st;
 }
@@ -130,8 +152,8 @@ size_t loo_ws_doubles(int npad, int d) { return loo_off_out(npad, d) + (size_t)(
 int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const double *y, int n,
                int npad, double *ws, const double **vecs, const double **total)
 {
-    if (d < 1 || d > BQ_MAXD || (npad % 64))
-        return fail(c, BQ_ERR_BAD_ARG, "loo: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    if (bad_d_npad(d, npad))
+        return fail_d_npad(c, "loo");
     double *kd = ws, *mu = ws + (size_t)(d + 2) * npad;
     double *part = ws + loo_off_part(npad, d), *out = ws + loo_off_out(npad, d);
     const int nch = loo_chunks(npad);
@@ -152,17 +174,17 @@ template <int D>
 static int loo_grad_run(bq_ctx *c, const double *Ki, const double *hws, const double *alpha, int n,
                         int npad, double h, double s, double s2, double *ws)
 {
-    const double *B = hws, *Z = hws + hess_off_v(npad, D) + (size_t)(D + 2) * npad;
+    const HessWs<const double> hw = hess_views(hws, npad, D);
     double *kd = ws, *q = ws + npad;
     double *part = ws + loo_off_part(npad, D), *out = ws + loo_off_out(npad, D);
     const int nch = loo_chunks(npad);
     Bracket br(c, BQ_K_REDUCE);
     hipLaunchKernelGGL(loo_rows_kernel<D>, dim3((unsigned)npad / 64, (unsigned)nch), dim3(256), 0,
-                       c->stream, Ki, B, n, npad, part);
+                       c->stream, Ki, hw.B, n, npad, part);
     hipLaunchKernelGGL(loo_fold_kernel, dim3((unsigned)(npad + 255) / 256, 1 + D), dim3(256), 0,
                        c->stream, part, nch, npad, q);
     hipLaunchKernelGGL(loo_grad_kernel<D>, dim3(1), dim3(256), 0, c->stream, alpha, kd, q,
-                       q + npad, Z, n, npad, 2.0 / h, s, s2, out + 1);
+                       q + npad, hw.Z, n, npad, 2.0 / h, s, s2, out + 1);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -172,10 +194,10 @@ static int loo_grad_run(bq_ctx *c, const double *Ki, const double *hws, const do
 int launch_loo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, const double *alpha,
                     int n, int npad, double h, double s, double s2, double *ws, const double **grad)
 {
-    if (d < 1 || d > BQ_MAXD || (npad % 64))
-        return fail(c, BQ_ERR_BAD_ARG, "loo_grad: d in [1, %d], npad a multiple of 64", BQ_MAXD);
-    *grad = ws + loo_off_out(npad, d) + 1;
+    if (bad_d_npad(d, npad))
+        return fail_d_npad(c, "loo_grad");
     int st = BQ_OK;
+    *grad = ws + loo_off_out(npad, d) + 1;
     BQ_DISPATCH_D(d, st = loo_grad_run<D>(c, Ki, hws, alpha, n, npad, h, s, s2, ws));
     return st;
 }
@@ -236,7 +258,7 @@ static void lgo_launch_blocks(bq_ctx *c, int maxb, unsigned nprod, const double 
 int launch_lgo(bq_ctx *c, const double *Y, const double *alpha, const double *y, int n, int npad,
                int d, long T, long G, long NB, int maxb, const LgoWs &w)
 {
-    if (d < 1 || d > BQ_MAXD || (npad % 64) || maxb < 1 || maxb > BQ_LGO_MAXB || G < 1 || T < G ||
+    if (bad_d_npad(d, npad) || maxb < 1 || maxb > BQ_LGO_MAXB || G < 1 || T < G ||
         NB < 1 || NB > G)
         return fail(c, BQ_ERR_BAD_ARG, "lgo: d in [1, %d], npad a multiple of 64, groups of 1 .. %d",
                     BQ_MAXD, BQ_LGO_MAXB);
@@ -245,7 +267,7 @@ int launch_lgo(bq_ctx *c, const double *Y, const double *alpha, const double *y,
     hipLaunchKernelGGL(lgo_group_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, w.part,
                        lgo_chunks(npad), T, w.idx, w.start, alpha, y, w.sig, w.r, w.mu, w.var, w.lp,
                        w.ar, w.flag);
-    hipLaunchKernelGGL(lgo_fold_kernel, dim3(1), dim3(256), 0, c->stream, w.lp, (int)G, 1, w.out);
+    launch_fold(c, w.lp, (int)G, 1, 1, 1, w.out);
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -253,20 +275,19 @@ int launch_lgo(bq_ctx *c, const double *Y, const double *alpha, const double *y,
 int launch_lgo_grad(bq_ctx *c, int d, const double *Ki, const double *hws, int n, int npad, long T,
                     long G, long NB, int maxb, double h, double s, double s2, const LgoWs &w)
 {
-    if (d < 1 || d > BQ_MAXD || (npad % 64) || maxb < 1 || maxb > BQ_LGO_MAXB || G < 1 || T < G ||
+    if (bad_d_npad(d, npad) || maxb < 1 || maxb > BQ_LGO_MAXB || G < 1 || T < G ||
         NB < 1 || NB > G)
         return fail(c, BQ_ERR_BAD_ARG, "lgo_grad: d in [1, %d], npad a multiple of 64, groups of 1 .. %d",
                     BQ_MAXD, BQ_LGO_MAXB);
-    const double *B = hws, *Z = hws + hess_off_v(npad, d) + (size_t)(d + 2) * npad;
+    const HessWs<const double> hw = hess_views(hws, npad, d);
     double *gp = w.part + lgo_part_doubles(npad, T); // [1 + d][nchunk][T][64]
     Bracket br(c, BQ_K_REDUCE);
     lgo_launch_blocks<LGO_PP>(c, maxb, 1, nullptr, Ki, n, npad, T, NB, w, gp);
-    lgo_launch_blocks<LGO_BP>(c, maxb, (unsigned)d, B, Ki, n, npad, T, NB, w, gp);
+    lgo_launch_blocks<LGO_BP>(c, maxb, (unsigned)d, hw.B, Ki, n, npad, T, NB, w, gp);
     hipLaunchKernelGGL(lgo_group_grad_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, gp,
-                       lgo_chunks(npad), T, w.idx, w.start, w.sig, w.r, w.ar, Z, d, npad, h, s, s2,
+                       lgo_chunks(npad), T, w.idx, w.start, w.sig, w.r, w.ar, hw.Z, d, npad, h, s, s2,
                        w.gpart);
-    hipLaunchKernelGGL(lgo_fold_kernel, dim3((unsigned)(d + 2)), dim3(256), 0, c->stream, w.gpart,
-                       (int)G, d + 2, w.out + 1);
+    launch_fold(c, w.gpart, (int)G, d + 2, 1, d + 2, w.out + 1); // (gpart[group][d + 2])
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -280,8 +301,8 @@ static ThetaScale theta_scale(double h, double s)
 // R (64 x npad, ld 64) = [a, D_1 a .. D_d a] as rows, zero elsewhere
 int launch_ptheta_dka(bq_ctx *c, int d, const HessJob &hj, double *R)
 {
-    if (d < 1 || d > BQ_MAXD || (hj.npad % 64))
-        return fail(c, BQ_ERR_BAD_ARG, "ptheta_dka: d in [1, %d], npad a multiple of 64", BQ_MAXD);
+    if (bad_d_npad(d, hj.npad))
+        return fail_d_npad(c, "ptheta_dka");
     Bracket br(c, BQ_K_REDUCE);
     BQ_DISPATCH_D(d, hipLaunchKernelGGL(ptheta_dka_kernel<D>, dim3((unsigned)hj.npad / 16), dim3(256),
                                         0, c->stream, hj, R));
@@ -310,7 +331,7 @@ size_t ptheta_part_doubles(int d, int Mp, int npad) { return (size_t)d * (npad /
 int launch_ptheta_quad(bq_ctx *c, int d, const double *beta, long ldb, int Mp, const HessJob &hj,
                        double *part)
 {
-    if (d < 1 || d > BQ_MAXD || (hj.npad % 64) || (Mp % 64) || Mp < 64)
+    if (bad_d_npad(d, hj.npad) || (Mp % 64) || Mp < 64)
         return fail(c, BQ_ERR_BAD_ARG, "ptheta_quad: d in [1, %d], whole 64-blocks", BQ_MAXD);
     const bool tall = ptheta_tall(c, Mp, hj.npad);
     const unsigned gy = (unsigned)hj.npad / 64;

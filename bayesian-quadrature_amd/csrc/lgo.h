@@ -20,13 +20,15 @@
 //                               diag Sigma_B, lp
 //   lgo_group_grad_kernel       per group: the d + 2 gradient entries from Sigma_B, r_B and the
 //                               partials of Q_BB and the M_k
-//   lgo_fold_kernel             the groups' lp, and gradient entries, summed in group order
+// The groups' lp, and their gradient entries, are summed in group order by wgsum.h's fold_kernel
+// (launched from k_hess.hip).
 // loo.h's rules: no atomics, every sum in a fixed order (the same bits on every call), rows and
 // columns at or beyond n stay out of every sum.  A block is stored as b rows of 64 doubles: member
 // t of the flattened index list owns row t, so the blocks of all groups are T x 64 per chunk.
 #pragma once
 #include "common.h"
 #include "loo.h"
+#include "wgsum.h"
 
 #define BQ_LGO_MAXB 64 // = BQ_LGO_MAX (bqhip.h)
 #define BQ_LGO_SLAB 32 // columns staged in LDS at a time
@@ -304,8 +306,8 @@ __global__ __launch_bounds__(256) void lgo_group_grad_kernel(
                 v2 += sig[(long)(s0 + i) * 64 + j] * xv; // (Sigma_B is symmetric)
             }
         }
-        v1 = loo_tree_sum(v1, red);
-        v2 = loo_tree_sum(v2, red);
+        v1 = wg_tree_sum(v1, red);
+        v2 = wg_tree_sum(v2, red);
         if (t == 0) {
             rXr[z] = v1;
             trSX[z] = v2;
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(256) void lgo_group_grad_kernel(
     }
     for (int p = 0; p < d + 2; ++p) {
         double v = t < b ? rv[t] * Z[(long)p * npad + idx[s0 + t]] : 0.0;
-        v = loo_tree_sum(v, red);
+        v = wg_tree_sum(v, red);
         if (t == 0)
             rZ[p] = v;
     }
@@ -325,19 +327,4 @@ __global__ __launch_bounds__(256) void lgo_group_grad_kernel(
             g[k] = rZ[k] - 0.5 * (rXr[k] + trSX[k]);
         g[d + 1] = rZ[d + 1] - s * (rXr[0] + trSX[0]);
     }
-}
-
-// out[c] = sum over the groups of vals[group][c], c < count (= gridDim.x): each thread its groups
-// in their order, then the fixed tree.  grid: (count)
-__global__ __launch_bounds__(256) void lgo_fold_kernel(const double *__restrict__ vals, int G,
-                                                       int count, double *__restrict__ out)
-{
-    __shared__ double red[256];
-    const int c = blockIdx.x;
-    double v = 0.0;
-    for (int g = threadIdx.x; g < G; g += 256)
-        v += vals[(long)g * count + c];
-    v = loo_tree_sum(v, red);
-    if (threadIdx.x == 0)
-        out[c] = v;
 }

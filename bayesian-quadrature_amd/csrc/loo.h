@@ -18,9 +18,10 @@
 // All matrices are column-major with ld npad: lanes go along rows, so a wave's load of one column
 // is 64 consecutive doubles.  A workgroup owns 64 rows and BQ_LOO_CW columns, its four waves take
 // every fourth column; rows and columns at or beyond n (the identity padding) stay out of every
-// sum.  No atomics: the same bits on every call.
+// sum.  No atomics: the same bits on every call (the workgroup-wide sums are wgsum.h's tree).
 #pragma once
 #include "common.h"
+#include "wgsum.h"
 
 #define BQ_LOO_CW 256 // columns per workgroup
 
@@ -112,22 +113,6 @@ __global__ __launch_bounds__(256) void loo_fold_kernel(const double *__restrict_
     out[(long)c * npad + i] = v;
 }
 
-// one workgroup's sum of its 256 threads' v, the same tree on every call; red: 256 doubles
-__device__ __forceinline__ double loo_tree_sum(double v, double *red)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h)
-            red[t] += red[t + h];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // mu, var, lp for i < n and *total = L_loo.  One workgroup.
 __global__ __launch_bounds__(256) void loo_point_kernel(const double *__restrict__ y,
                                                         const double *__restrict__ a,
@@ -148,7 +133,7 @@ __global__ __launch_bounds__(256) void loo_point_kernel(const double *__restrict
         lp[i] = l;
         v += l;
     }
-    v = loo_tree_sum(v, red);
+    v = wg_tree_sum(v, red);
     if (threadIdx.x == 0)
         *total = v;
 }
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(256) void loo_grad_kernel(const double *__restrict_
                 dg = tk[(long)(p - 1) * npad + i];
             v += (ai * Z[(long)p * npad + i] - 0.5 * (1.0 + ai * ai / ki) * dg) / ki;
         }
-        v = loo_tree_sum(v, red);
+        v = wg_tree_sum(v, red);
         if (threadIdx.x == 0)
             out[p] = v;
     }

@@ -1,6 +1,7 @@
 // ptheta.h -- derivatives of the posterior mean and variance with respect to the hyper-parameters
-// theta = [h, w_1 .. w_d, s] (bq_gp_predict_dtheta, fit.hip).  Compiled into k_hess.hip, whose
-// hess.h has the generated derivative operand (host.h lists the units).
+// theta = [h, w_1 .. w_d, s] (bq_gp_predict_dtheta, fit.hip).  Compiled into k_hess.hip (host.h
+// lists the units); dk.h has the derivative operand's entries and the rows of D_k a, which the
+// Hessian shares.
 //
 // With K = K0 + s^2 I, Ki = K^-1, a = Ki y, k_ji = k(xo_j, x_i), beta_j = Ki k_j, k0 = k(x, x),
 // D_k = K0 o (r_k^2 / w_k^3 - 1 / w_k), g_jik = (xo_jk - x_ik)^2 / w_k^3 - 1 / w_k, and the solved
@@ -24,42 +25,18 @@
 // columns and points are never read into a sum; indices are clamped, values masked.
 #pragma once
 #include "common.h"
-#include "hess.h"
+#include "dk.h"
 
 // R (64 x npad, ld 64, point i in column i): row 0 = a, row 1 + k = D_k a, the other rows and the
 // columns at or beyond n zero -- the shape the row sweeps take (R Ki = [u, z_1 .. z_d] as rows).
-// hess_dka_kernel's decomposition and arithmetic: 16 points per workgroup, a point's columns dealt
-// to 16 lanes and summed by shuffles.  grid: npad / 16
+// 16 points per workgroup, 16 lanes per point (dka_sums, dk.h).  grid: npad / 16
 template <int D>
 __global__ __launch_bounds__(256) void ptheta_dka_kernel(HessJob hj, double *__restrict__ R)
 {
     const int t = threadIdx.x, i = blockIdx.x * 16 + (t >> 4), jl = t & 15;
     const bool in = i < hj.n;
     double sum[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-        sum[k] = 0.0;
-    if (in) {
-        double xi[D], iw[D], iw2[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            xi[k] = hj.pts[k + (long)i * D];
-            iw[k] = hj.iw[k];
-            iw2[k] = iw[k] * iw[k];
-        }
-        for (int j = jl; j < hj.n; j += 16) {
-            double r2[D];
-            const double ka = hess_k0<D>(xi, hj.pts + (long)j * D, hj.g, r2) * hj.alpha[j];
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-                sum[k] += ka * ((iw2[k] * r2[k] - 1.0) * iw[k]);
-        }
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-            sum[k] += __shfl_xor(sum[k], off);
+    dka_sums<D>(hj, i, jl, sum);
     // every lane of the point holds the sums: lane jl writes rows jl, jl + 16, jl + 32, jl + 48
     const double a = in ? hj.alpha[i] : 0.0;
 #pragma unroll
@@ -76,10 +53,10 @@ __global__ __launch_bounds__(256) void ptheta_dka_kernel(HessJob hj, double *__r
 // part[kdim][column block][row] = sum over the block's columns i < n of T(row, i) beta(row, i),
 // T = beta D_kdim -- the q_jk of one length scale, in npad / 64 pieces per row that the finishing
 // kernel adds in index order.  beta: Mp x npad, ld = ldb, rows along the fast index (what the
-// backward row sweep leaves).  hess_prod_kernel<D>'s structure: four waves as WR x WC on
-// v_mfma_f64_16x16x4, wave tile 16 TM x 16 TN, 16-deep k chunks of both operands through registers
-// into LDS, the D_k entries of chunk c + 1 generated from the points (hess_k0) while the MFMAs of
-// chunk c run, k < n and column < n masked.  What differs: the left operand has Mp rows and its own
+// backward row sweep leaves).  hess_prod_kernel<D>'s structure, written out in both (dk.h says why):
+// four waves as WR x WC on v_mfma_f64_16x16x4, wave tile 16 TM x 16 TN, 16-deep k chunks of both
+// operands through registers into LDS, the D_k entries of chunk c + 1 generated from the points
+// (gauss_k0, dk_weight) while the MFMAs of chunk c run, k < n and column < n masked.  What differs: the left operand has Mp rows and its own
 // ld (rows clamped to Mp - 1, k columns at or beyond n read as zero); T is never stored -- the
 // epilogue multiplies the accumulators by the matching beta, sums a row's 64 columns in a fixed
 // order (a lane's 4 TN entries in sequence, the four 16-lane groups by two shuffles, the WC waves
@@ -96,9 +73,9 @@ __global__ __launch_bounds__(256, 2) void ptheta_quad_kernel(const double *__res
     static_assert(COLS == 64, "the generated operand is dealt as 64 columns x 4 k rows");
     static_assert(ROWS <= 256, "a thread per row folds the waves");
     constexpr int LDA = ROWS + 16, LDQ = COLS + 16;
-    constexpr int NA = ROWS * BQ_HESS_KC / 256, NQ = COLS * BQ_HESS_KC / 256;
-    __shared__ double sA[BQ_HESS_KC * LDA];
-    __shared__ double sQ[BQ_HESS_KC * LDQ];
+    constexpr int NA = ROWS * BQ_DK_KC / 256, NQ = COLS * BQ_DK_KC / 256;
+    __shared__ double sA[BQ_DK_KC * LDA];
+    __shared__ double sQ[BQ_DK_KC * LDQ];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int n = hj.n;
@@ -134,19 +111,19 @@ __global__ __launch_bounds__(256, 2) void ptheta_quad_kernel(const double *__res
             double v = 0.0;
             if (jq < n && k < n) {
                 double r2[D], rk = 0.0;
-                const double k0v = hess_k0<D>(xj, hj.pts + (long)k * D, hj.g, r2);
+                const double k0v = gauss_k0<D>(xj, hj.pts + (long)k * D, hj.g, r2);
 #pragma unroll
                 for (int m = 0; m < D; ++m)
                     rk = m == kdim ? r2[m] : rk;
-                v = k0v * ((iw2 * rk - 1.0) * iw);
+                v = k0v * dk_weight(iw, iw2, rk);
             }
             rq[e] = v;
         }
     };
 
-    const int kend = (n + BQ_HESS_KC - 1) & ~(BQ_HESS_KC - 1);
+    const int kend = (n + BQ_DK_KC - 1) & ~(BQ_DK_KC - 1);
     fetch(0);
-    for (int k0 = 0; k0 < kend; k0 += BQ_HESS_KC) {
+    for (int k0 = 0; k0 < kend; k0 += BQ_DK_KC) {
         __syncthreads(); // every wave is done with the chunk before
 #pragma unroll
         for (int e = 0; e < NA; ++e) {
@@ -157,10 +134,10 @@ __global__ __launch_bounds__(256, 2) void ptheta_quad_kernel(const double *__res
         for (int e = 0; e < NQ; ++e)
             sQ[(kq + 4 * e) * LDQ + (t & 63)] = rq[e];
         __syncthreads();
-        if (k0 + BQ_HESS_KC < kend)
-            fetch(k0 + BQ_HESS_KC);
+        if (k0 + BQ_DK_KC < kend)
+            fetch(k0 + BQ_DK_KC);
 #pragma unroll
-        for (int ks = 0; ks < BQ_HESS_KC / 4; ++ks) {
+        for (int ks = 0; ks < BQ_DK_KC / 4; ++ks) {
             double fa[TM], fq[TN];
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
@@ -268,7 +245,7 @@ __global__ __launch_bounds__(512) void predict_theta_kernel(const double *__rest
                 const double tt = p[k] - hj.pts[k + (long)i * D];
                 const double r2 = tt * tt;
                 qq += r2 * hj.g.nh[k];
-                gk[k] = (iw2[k] * r2 - 1.0) * iw[k];
+                gk[k] = dk_weight(iw[k], iw2[k], r2);
             }
             const double kk = exp_gauss(qq);
             if (zp) {
@@ -371,7 +348,7 @@ __global__ __launch_bounds__(256) void predict_mean_theta_kernel(const double *_
             const double tt = p[k] - hj.pts[k + (long)j * D];
             const double r2 = tt * tt;
             qq += r2 * hj.g.nh[k];
-            gk[k] = (iw2[k] * r2 - 1.0) * iw[k];
+            gk[k] = dk_weight(iw[k], iw2[k], r2);
         }
         const double kk = exp_gauss(qq), ka = kk * hj.alpha[j];
         const double *zj = Z + (long)BQ_PTHETA_ROWS * j;

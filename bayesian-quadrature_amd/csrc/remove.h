@@ -19,6 +19,7 @@
 // fixed order: the same bits from run to run.
 #pragma once
 #include "common.h"
+#include "wgsum.h"
 
 #define BQ_REMOVE_LD 65                              // leading dimension of the LDS tiles
 #define BQ_REMOVE_TILE (64 * BQ_REMOVE_LD)
@@ -300,16 +301,7 @@ __global__ __launch_bounds__(256) void remove_finish_kernel(const double *__rest
             sq = fma(z, z, sq);
         }
     }
-    pl[t] = sl;
-    pq[t] = sq;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) {
-            pl[t] += pl[t + off];
-            pq[t] += pq[t + off];
-        }
-        __syncthreads();
-    }
+    wg_tree_add2(sl, sq, pl, pq);
     if (t == 0) {
         reinterpret_cast<int *>(out)[0] = 0;
         const double logdet = 2.0 * pl[0], qf = pq[0];

@@ -52,7 +52,7 @@ struct GradJob {
     int n;
 };
 
-// the scalings of the gradient's d + 2 sums (grad_finalize_kernel)
+// the scalings of the gradient's d + 2 sums (fold_kernel<GradScale>, wgsum.h)
 struct GradScale {
     double f[BQ_MAXD + 2];
 };
