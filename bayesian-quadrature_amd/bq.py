@@ -151,6 +151,13 @@ class BQ(object):
         g[v * m ** 2 < 0] = 0
         return g
 
+    def log_l_design(self, x_c, q):
+        """The indices of the (at most) ``q`` entries of ``x_c`` at which the log-GP is jointly
+        most uncertain: its max-variance sequential design (gp.GP.greedy_design), a batch to
+        evaluate next -- ``l_var``'s ``q`` largest entries would be neighbours on one peak."""
+        self._require_exact()
+        return self.gp_log_l.greedy_design(x_c, q)
+
     # ---------------------------------------------------------------- moments
     def Z_mean(self):
         self._require_exact()

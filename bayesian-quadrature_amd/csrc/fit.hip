@@ -1411,3 +1411,72 @@ extern "C" int bq_gp_sample(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, i
         *jitter = jit;
     return BQ_OK;
 }
+
+// The pivoted partial Cholesky of the posterior covariance at M points (include/bqhip.h has the
+// contract; pivchol.h the kernels).  bq_gp_predict's staging and sweep with q more columns behind
+// V in f->wV2 -- W = [V | C] is one matrix, ld Mp -- then the start and the q steps, enqueued one
+// after the other with nothing read back in between: the pivot and the done flag stay on the
+// device, and after the flag a step's kernels return at once.  One download of the workspace's
+// head (state | gain | piv | d) into pinned staging and one synchronise; then the rank columns of
+// C.  Every device buffer is there before the first launch.
+extern "C" int bq_gp_pivchol(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, int64_t q,
+                             double nugget, double tol, int64_t *piv, double *C, double *resid,
+                             double *gain, int64_t *rank)
+{
+    BQCHK(check_fit(c, f));
+    if (M < 0 || q < 1 || (M && q > M) || M > BQ_PIVCHOL_MAX_M || q > BQ_PIVCHOL_MAX_Q ||
+        !(nugget >= 0.0) || !(tol >= 0.0) || !std::isfinite(nugget) || !std::isfinite(tol) ||
+        !piv || !gain || !rank || (M && !xo))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (M == 0) {
+        for (int64_t j = 0; j < q; ++j)
+            piv[j] = -1, gain[j] = 0.0;
+        *rank = 0;
+        return BQ_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad, m = (int)M, nq = (int)q, Mp = (int)roundup(M, 64);
+    const PivcholPlan pl = pivchol_plan(Mp, npad, nq);
+
+    // ---- every device buffer: the factorisation's own, the prediction's with q more columns
+    BQCHK(fit_grow(c, f->pvc, sizeof(double) * pl.total, "pivoted Cholesky workspace"));
+    BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(npad), "wide block inverses"));
+    BQCHK(fit_grow(c, f->wV, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, f->wV2, sizeof(double) * (size_t)Mp * ((size_t)npad + nq),
+                   "prediction sweep workspace and the factor's columns"));
+    BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
+    double *hs, *ds;
+    BQCHK(ctx_stage(c, pl.head, &hs, &ds));
+    double *ws = f->pvc.d(), *W = f->wV2.d();
+
+    // ---- mean | var at io.res, V in the first npad columns of W; the factor's columns zero
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, xo, M, 0, false));
+    BQCHK(predict_sweep(c, f, io));
+    HIPCHK(c, hipMemsetAsync(W + (size_t)Mp * npad, 0, sizeof(double) * (size_t)Mp * nq, c->stream));
+
+    // ---- the steps
+    const double thr = tol * f->g.c;
+    BQCHK(launch_pivchol_init(c, pl, ws, io.res + Mp, m, Mp, nq, thr));
+    for (int j = 0; j < nq; ++j)
+        BQCHK(launch_pivchol_step(c, pl, ws, W, d, io.xq, f->g, m, Mp, npad, nq, j, nugget, thr));
+
+    // ---- the download
+    HIPCHK(c, hipMemcpyAsync(hs, ws, sizeof(double) * pl.head, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int r = reinterpret_cast<const PivcholState *>(hs)->rank;
+    if (r < 0 || r > nq)
+        return fail(c, BQ_ERR_HIP, "pivchol: the device left rank %d of %d steps", r, nq);
+    if (C) {
+        if (r > 0)
+            HIPCHK(c, hipMemcpy2D(C, sizeof(double) * M, W + (size_t)Mp * npad, sizeof(double) * Mp,
+                                  sizeof(double) * M, r, hipMemcpyDeviceToHost));
+        std::memset(C + (size_t)M * r, 0, sizeof(double) * (size_t)M * (nq - r));
+    }
+    std::memcpy(gain, hs + pl.o_gain, sizeof(double) * nq);
+    std::memcpy(piv, hs + pl.o_piv, sizeof(int64_t) * nq);
+    if (resid)
+        std::memcpy(resid, hs + pl.o_d, sizeof(double) * M);
+    *rank = r;
+    return BQ_OK;
+}

@@ -23,6 +23,7 @@
 //                remove.h kernels               finishing kernels of an append, shrinking a fit
 //                pgrad.h kernels                the posterior's gradients at the query points
 //                sample.h kernels               the posterior samples' normals and triangular product
+//                pivchol.h kernels              the pivoted partial Cholesky of a posterior
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -483,6 +484,20 @@ int launch_normal_fill(bq_ctx *c, double *Z, long ldz, int M, int Mp, int S, uin
 int launch_sample_diag(bq_ctx *c, double *A, long lda, int M, int Mp, double add);
 int launch_tri_sample(bq_ctx *c, const double *L, long ldl, const double *Z, long ldz,
                       const double *mean, double *out, long ldo, int M, int Mp, int S);
+// the pivoted partial Cholesky of a posterior (pivchol.h): the shape of q steps and the places of
+// the workspace's parts in doubles -- [PivcholState | gain q | piv q (int64) | d Mp], the `head`
+// doubles that go back to the host, then taken (Mp ints) | the workgroups' candidates | part
+// (nsl x Mp); the start (d = var at the M real rows, step 0's pivot) and step j
+struct PivcholPlan {
+    int rb, ks, nblk, nsl;
+    size_t o_gain, o_piv, o_d, head, o_taken, o_candv, o_candi, o_part, total;
+};
+PivcholPlan pivchol_plan(int Mp, int npad, int q);
+int launch_pivchol_init(bq_ctx *c, const PivcholPlan &pl, double *ws, const double *var, int M,
+                        int Mp, int q, double thr);
+int launch_pivchol_step(bq_ctx *c, const PivcholPlan &pl, double *ws, double *W, int d,
+                        const double *xq, const GaussParams &g, int M, int Mp, int npad, int q,
+                        int j, double nugget, double thr);
 int launch_neg_identity(bq_ctx *c, double *nr, int B, int npad);
 int launch_pad_identity(bq_ctx *c, double *A, long lda, int n, int ntot);
 int launch_logdet(bq_ctx *c, const double *diag, long stride, int n, double *out);
@@ -804,6 +819,10 @@ struct bq_fit : FitCore {
     // posterior samples (bq_gp_sample): GaussParams without s^2 | info | Sigma | the matrix being
     // factored (a ladder of more than one entry) | Z | out, grown on demand and kept
     DevBuf smp;
+    // pivoted partial Cholesky of a posterior (bq_gp_pivchol): the device state | gain | piv | d |
+    // the taken rows | the workgroups' candidates | the slices' partial sums (PivcholPlan), grown
+    // on demand and kept; the factor's columns follow V in wV2
+    DevBuf pvc;
     // the log-ML gradient (bq_gp_logml_grad): Y and the sweep's partial sums (npad x npad each),
     // allocated on the first gradient; the product's partials and the d + 2 results
     DevBuf gY, gX, gpart;

@@ -1,11 +1,12 @@
 // k_reduce.hip -- read-outs, single-vector sweeps and small utilities (reduce.h, trsv.h), the
 // posterior's gradients at the query points (pgrad.h), the kernels that grow and shrink a
 // resident fit (append.h, remove.h), the posterior samples' normals and triangular product
-// (sample.h) and their launchers.
+// (sample.h), the pivoted partial Cholesky of a posterior (pivchol.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "pgrad.h"
 #include "sample.h"
+#include "pivchol.h"
 #include "trsv.h"
 #include "trsvflow.h"
 #include "append.h"
@@ -114,6 +115,93 @@ int launch_tri_sample(bq_ctx *c, const double *L, long ldl, const double *Z, lon
     hipLaunchKernelGGL(tri_sample_kernel, dim3(Mp / 64, (S + 63) / 64), dim3(256), 0, c->stream, L,
                        ldl, Z, ldz, mean, out, ldo, M, S);
     HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// ---- pivoted partial Cholesky of a posterior (pivchol.h; fit.hip, bq_gp_pivchol) ----
+// The shape of q steps over Mp rows behind npad columns of V, from (Mp, npad) alone but for the
+// sizes that q sets: rows per workgroup of the column kernel (64 below 16384 rows, so that small M
+// still fills the chip by slices), columns per slice (about 1024 workgroups at step 0, whole
+// 64-column blocks, 64 .. BQ_PIVCHOL_KS_MAX), and the places of the workspace's parts, in doubles.
+PivcholPlan pivchol_plan(int Mp, int npad, int q)
+{
+    auto granule = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+    PivcholPlan pl{};
+    pl.rb = (Mp >= 16384 && (Mp % 256) == 0) ? 256 : 64;
+    const long want = (1024 + Mp / pl.rb - 1) / (Mp / pl.rb);
+    pl.ks = (int)std::min<long>(BQ_PIVCHOL_KS_MAX, std::max<long>(64, npad / want / 64 * 64));
+    pl.nblk = (Mp + 255) / 256;
+    pl.nsl = (npad + q - 1 + pl.ks - 1) / pl.ks; // slices of the last step's npad + q - 1 columns
+    pl.o_gain = granule((sizeof(PivcholState) + 7) / 8);
+    pl.o_piv = pl.o_gain + (size_t)q;
+    pl.o_d = pl.o_piv + (size_t)q;
+    pl.head = pl.o_d + (size_t)Mp;
+    pl.o_taken = granule(pl.head);
+    pl.o_candv = pl.o_taken + granule(((size_t)Mp + 1) / 2);
+    pl.o_candi = pl.o_candv + granule((size_t)pl.nblk);
+    pl.o_part = pl.o_candi + granule(((size_t)pl.nblk + 1) / 2);
+    pl.total = pl.o_part + (size_t)pl.nsl * Mp;
+    return pl;
+}
+
+// d = var, nothing taken, the state, piv = -1 and gain = 0, then step 0's pivot
+int launch_pivchol_init(bq_ctx *c, const PivcholPlan &pl, double *ws, const double *var, int M,
+                        int Mp, int q, double thr)
+{
+    PivcholState *st = reinterpret_cast<PivcholState *>(ws);
+    long long *piv = reinterpret_cast<long long *>(ws + pl.o_piv);
+    int *taken = reinterpret_cast<int *>(ws + pl.o_taken);
+    int *candi = reinterpret_cast<int *>(ws + pl.o_candi);
+    Bracket br(c, BQ_K_REDUCE, 16.0 * Mp);
+    hipLaunchKernelGGL(pivchol_init_kernel, dim3(pl.nblk), dim3(256), 0, c->stream, var, M, Mp, q,
+                       st, piv, ws + pl.o_gain, ws + pl.o_d, taken, ws + pl.o_candv, candi);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(pivchol_select_kernel, dim3(1), dim3(256), 0, c->stream, st,
+                       ws + pl.o_candv, candi, pl.nblk, 0, thr, piv, ws + pl.o_gain);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// step j < q: column npad + j of W (Mp x (npad + q), ld Mp) and the new d; then, for j + 1 < q,
+// step j + 1's pivot.  xq: the d x M points; g: the fit's kernel parameters
+int launch_pivchol_step(bq_ctx *c, const PivcholPlan &pl, double *ws, double *W, int d,
+                        const double *xq, const GaussParams &g, int M, int Mp, int npad, int q,
+                        int j, double nugget, double thr)
+{
+    if (M < 1 || Mp < M || (Mp & 63) || j < 0 || j >= q || npad < 0)
+        return fail(c, BQ_ERR_BAD_ARG, "pivchol: step %d of %d over %d rows", j, q, M);
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    PivcholState *st = reinterpret_cast<PivcholState *>(ws);
+    long long *piv = reinterpret_cast<long long *>(ws + pl.o_piv);
+    int *taken = reinterpret_cast<int *>(ws + pl.o_taken);
+    int *candi = reinterpret_cast<int *>(ws + pl.o_candi);
+    double *part = ws + pl.o_part;
+    const int K = npad + j, nsl = (K + pl.ks - 1) / pl.ks;
+    const long ld = Mp;
+    if (nsl > 0) {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * Mp * K);
+        const dim3 grid((unsigned)(Mp / pl.rb), (unsigned)nsl);
+        if (pl.rb == 256)
+            hipLaunchKernelGGL(pivchol_col_kernel<256>, grid, dim3(256), 0, c->stream, W, ld, K,
+                               pl.ks, st, part);
+        else
+            hipLaunchKernelGGL(pivchol_col_kernel<64>, grid, dim3(64), 0, c->stream, W, ld, K, pl.ks,
+                               st, part);
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * Mp * (nsl + 3.0));
+        BQ_DISPATCH_D(d, hipLaunchKernelGGL(pivchol_finish_kernel<D>, dim3(pl.nblk), dim3(256), 0,
+                                            c->stream, W, ld, K, M, Mp, part, nsl, xq, g, nugget, st,
+                                            ws + pl.o_d, taken, ws + pl.o_candv, candi));
+        HIPCHK(c, hipGetLastError());
+    }
+    if (j + 1 < q) {
+        hipLaunchKernelGGL(pivchol_select_kernel, dim3(1), dim3(256), 0, c->stream, st,
+                           ws + pl.o_candv, candi, pl.nblk, j + 1, thr, piv, ws + pl.o_gain);
+        HIPCHK(c, hipGetLastError());
+    }
     return BQ_OK;
 }
 

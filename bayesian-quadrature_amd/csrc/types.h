@@ -103,6 +103,13 @@ struct AppendJob {
     int d, n, k, kp, yrow;
 };
 
+// The pivoted partial Cholesky of a posterior (pivchol.h): what a step's kernels read instead of
+// asking the host -- the current pivot and its gain, and whether the factorisation has ended.
+struct PivcholState {
+    int done, rank, p, pad;
+    double gain;
+};
+
 // Removing k observations from a resident fit (remove.h): what remove_compact_kernel reads of the
 // old fit and writes into buffers of the new layout.
 #define BQ_REMOVE_M_DOUBLES (128 * 128) // the 128 x 128 transform of one block column (scratch)

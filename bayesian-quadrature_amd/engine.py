@@ -948,6 +948,32 @@ class Fit(object):
         res = (out, mean, float(jitter.value))
         return res + (chol,) if want_chol else res
 
+    def pivoted_cholesky(self, xo, q, nugget=0.0, tol=0.0, want_factor=True):
+        """(piv, C, resid, gain): the greedy, diagonally pivoted partial Cholesky factorisation of
+        the latent posterior covariance at the points xo, at most q steps, on the device and
+        without forming the covariance (bq_gp_pivchol).  Each step takes the point with the
+        largest remaining variance (the lowest index among equals): piv, (rank,) int64, is the
+        max-variance sequential design; gain, (rank,), the variance each pivot had when taken;
+        C, (M, rank) Fortran-ordered (None without ``want_factor``), the factor's columns
+        c_j = (cov[:, p_j] - sum_{i<j} c_i c_i[p_j]) / sqrt(gain_j + nugget); resid, (M,), the
+        variances left, diag(cov - C C^T).  ``nugget`` >= 0 is absolute: with s^2, resid is the
+        variance after noisy observations at the pivots.  The factorisation ends early, rank < q,
+        at a gain of at most ``tol`` k(x, x), or one that is not positive."""
+        xo = _pts(xo)
+        if xo.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        M, q = xo.shape[1], int(q)
+        piv, gain = np.empty(max(q, 0), dtype=np.int64), np.empty(max(q, 0))
+        fac = np.empty((M, max(q, 0)), order="F") if want_factor else None
+        resid = np.empty(M)
+        rank = C.c_int64()
+        e = self._eng
+        e._check(e._lib.bq_gp_pivchol(e._ctx, self._handle(), L.dptr(xo), M, q, float(nugget),
+                                      float(tol), piv.ctypes.data_as(L._i64p), L.dptr(fac),
+                                      L.dptr(resid), L.dptr(gain), C.byref(rank)))
+        r = int(rank.value)
+        return piv[:r], (fac[:, :r] if want_factor else None), resid, gain[:r]
+
 
 class Pair(object):
     """GP1 over log l at the samples and GP2 over [l_s, exp(mean of GP1 at x_c)] at samples +

@@ -635,6 +635,43 @@ class GP(object):
         out = np.ascontiguousarray(out.T)
         return (out, {"mean": mean, "jitter": jitter}) if return_info else out
 
+    def pivoted_cholesky(self, xo, q, noisy=False, tol=0.0):
+        """(piv, C, resid, gain): the greedy, diagonally pivoted partial Cholesky factorisation of
+        ``cov(xo)`` in at most ``q`` steps, on the device fit and without forming the covariance
+        (bq_gp_pivchol) -- a candidate grid far too large for ``cov`` is fine.  Each step takes the
+        point whose remaining variance is largest.  piv: the chosen indices into ``xo``, (rank,);
+        C: (M, rank) Fortran-ordered, the best greedy rank-``rank`` factor, ``C C^T ~ cov(xo)``;
+        resid: (M,), the variance left at every point, ``diag(cov - C C^T)``; gain: (rank,), the
+        variance each pivot had when it was taken.  ``noisy`` puts the nugget s^2 under the square
+        root: resid is then the posterior variance after noisy observations at the pivots, a
+        point may be taken twice, and nothing is zeroed; without it a taken point keeps resid 0.
+        rank < q when a gain falls to ``tol`` k(x, x) or is not positive.  ``xo`` is a vector of
+        points, or d x M as for ``dmean_dx``."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        q = int(q)
+        if q < 1:
+            raise ValueError("invalid value for q: %s" % q)
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("invalid value for tol: %s" % tol)
+        if xo.size == 0:
+            return (np.empty(0, dtype=np.int64), np.empty((0, 0), dtype=DTYPE, order="F"),
+                    np.empty(0, dtype=DTYPE), np.empty(0, dtype=DTYPE))
+        M = xo.shape[-1]
+        if q > M:
+            raise ValueError("q = %d steps over %d points" % (q, M))
+        return self._device_fit().pivoted_cholesky(
+            xo, q, nugget=float(self._s) ** 2 if noisy else 0.0, tol=float(tol))
+
+    def greedy_design(self, xo, q, noisy=True, tol=0.0, return_info=False):
+        """The indices into ``xo`` of a batch of at most ``q`` points to evaluate next: the
+        max-variance sequential design, each point chosen where the variance is largest once the
+        points before it count as observed -- ``pivoted_cholesky``'s pivots; unlike the ``q``
+        largest marginal variances they do not crowd one peak.  ``noisy`` (the default) counts an
+        observation with the noise s^2, as ``append`` would.  ``return_info`` appends {"gain",
+        "resid"}: the variance each chosen point had, and the variance left everywhere."""
+        piv, _, resid, gain = self.pivoted_cholesky(xo, q, noisy=noisy, tol=tol)
+        return (piv, {"gain": gain, "resid": resid}) if return_info else piv
+
     # -- pickling / copying: only data and parameters travel -------------------
     def __getstate__(self):
         state = {"K": self.K, "x": self._x, "y": self._y, "s": self._s}

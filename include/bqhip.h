@@ -316,6 +316,44 @@ int bq_gp_predict_dtheta(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, 
 int bq_gp_sample(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, int64_t S,
                  const double *z, uint64_t seed, const double *ladder, int64_t nl,
                  double *out, double *mean, double *chol, double *jitter);
+/* The greedy, diagonally pivoted partial Cholesky factorisation of the latent posterior
+ * covariance Sigma = K(xo, xo) - V V^T (no s^2: the matrix bq_gp_predict returns as cov) at M
+ * points, on the device and without forming Sigma: the sweep of bq_gp_predict, then at most q
+ * steps.  xo: d x M column-major like bq_gp_predict.  nugget >= 0 in absolute units; tol >= 0 in
+ * multiples of k0 = k(x, x), the prior variance (as bq_gp_sample's ladder is).
+ * With d^(0) = diag Sigma (the var bq_gp_predict returns less s^2), for j = 0 .. q - 1:
+ *   p_j    = argmax_i d^(j)_i over the M points, the lowest index among equals;
+ *   gain_j = d^(j)[p_j]; the factorisation ends with rank = j when gain_j <= tol k0, when
+ *            gain_j <= 0 or when it is not finite -- no step divides by a non-positive number;
+ *   c_j    = (K(xo, xo_{p_j}) - V V[p_j, :]^T - sum_{i<j} c_i c_i[p_j]) / sqrt(gain_j + nugget);
+ *   d^(j+1) = d^(j) - c_j o c_j.
+ * The pivots are the max-variance sequential design.  With L the q x q lower triangle of
+ * C[piv, :] whose diagonal is sqrt(gain_j + nugget), L L^T = Sigma[piv, piv] + nugget I and
+ * C L^T = Sigma[:, piv], so that d^(rank) = diag(Sigma - Sigma[:, P] (Sigma[P, P] + nugget I)^-1
+ * Sigma[P, :]): with nugget = s^2 the posterior variances after noisy observations at the chosen
+ * points, whatever their targets.  C[p_j, j] itself is gain_j / sqrt(gain_j + nugget).
+ * nugget == 0: C[p_j, j] = sqrt(gain_j) and L = C[piv, :], lower triangular; a taken row keeps
+ * d = 0 exactly, stores an exact 0 in every later column and is never taken twice.  nugget > 0: a
+ * row may be taken again (two noisy observations at one place) and nothing is zeroed.
+ * Outputs on the host: piv (q, -1 from rank on), gain (q, 0 from rank on) and rank (one value) are
+ * required; C (M x q column-major, zero columns from rank on) and resid (M: d^(rank)) may be NULL.
+ * The same inputs give the same bits on every call, and the first j pivots, gains and columns of
+ * a q-step call are bit for bit those of a j-step call.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG for M < 0, q < 1, q > M (but for
+ * M == 0), M > BQ_PIVCHOL_MAX_M, q > BQ_PIVCHOL_MAX_Q, a negative or non-finite nugget or tol, or
+ * piv, gain or rank == NULL -- all checked before anything is allocated.  M == 0 writes rank = 0,
+ * piv = -1 and gain = 0 and touches nothing else.  The limits: M rounded up to 64 makes at most
+ * 16384 row blocks, which every kernel of the sweep and of the steps holds in any grid dimension,
+ * and the steps' slices of the npad + q columns stay below a grid's second dimension; offsets into
+ * the M x (N + q) matrix are 64-bit throughout.  Device memory (the prediction's workspaces with
+ * q more columns, Mp (1 + slices) doubles more; kept with the fit) is allocated before anything
+ * is enqueued: BQ_ERR_NOMEM leaves the fit as it was.  All steps are enqueued without waiting
+ * for the device; nothing reaches the caller's memory unless every kernel has completed.  The
+ * fit is not disturbed. */
+#define BQ_PIVCHOL_MAX_M 1048576
+#define BQ_PIVCHOL_MAX_Q 65536
+int bq_gp_pivchol(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, int64_t q, double nugget,
+                  double tol, int64_t *piv, double *C, double *resid, double *gain, int64_t *rank);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
