@@ -158,6 +158,23 @@ class BQ(object):
         self._require_exact()
         return self.gp_log_l.greedy_design(x_c, q)
 
+    def log_l_ivr_design(self, x_c, q, x_r=None):
+        """The indices of the (at most) ``q`` entries of ``x_c`` whose evaluation lowers the
+        log-GP's posterior variance, integrated against the prior N(x_mean, x_var) over the
+        reference points ``x_r`` (default: ``x_c``), the most (gp.GP.ivr_design): where
+        ``log_l_design`` goes to the edge of the candidates, where the variance is largest and
+        the prior has no mass, this stays where the integrand lives.  The weights are the prior's
+        density at the reference points, normalised to sum 1."""
+        self._require_exact()
+        x_c = np.atleast_1d(np.asarray(x_c, dtype=DTYPE))
+        ref = x_c if x_r is None else np.atleast_1d(np.asarray(x_r, dtype=DTYPE))
+        if x_c.size == 0 or ref.size == 0:  # nothing to choose from, or an error: said there
+            return self.gp_log_l.ivr_design(x_c, q, ref=None if x_r is None else ref)
+        mean, var = float(self.options["x_mean"][0]), float(self.options["x_cov"][0, 0])
+        dens = np.exp(-0.5 * (ref.ravel() - mean) ** 2 / var)
+        return self.gp_log_l.ivr_design(x_c, q, ref=None if x_r is None else ref,
+                                        weights=dens / dens.sum())
+
     # ---------------------------------------------------------------- moments
     def Z_mean(self):
         self._require_exact()

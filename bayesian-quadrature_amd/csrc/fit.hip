@@ -1480,3 +1480,125 @@ extern "C" int bq_gp_pivchol(bq_ctx *c, bq_fit *f, const double *xo, int64_t M, 
     *rank = r;
     return BQ_OK;
 }
+
+// The greedy design that minimises the integrated posterior variance (include/bqhip.h has the
+// contract; ivr.h the kernels).  One staging and one sweep over the joint point set [reference
+// points, padded to a multiple of 64 by repeating the last one with weight 0 | candidates] -- so
+// the candidate rows of V start on a 64-row boundary; xr == NULL: the candidates alone -- with q
+// more columns behind V in f->wV2 for the candidates' c.  T = K(xc, xr) - V_c V_r^T by the cross
+// Gram and one product (gemm_route picks its kernel), dc and dr the sweep's variances; then the q
+// steps, enqueued one after the other with nothing read back in between.  One download of the
+// workspace's head into pinned staging and one synchronise.  Every device buffer is there before
+// the first launch.
+extern "C" int bq_gp_ivr(bq_ctx *c, bq_fit *f, const double *xr, int64_t R, const double *rho,
+                         const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                         int64_t *piv, double *gain, double *ivar0, double *resid_r,
+                         double *resid_c, double *score0, int64_t *rank)
+{
+    BQCHK(check_fit(c, f));
+    const bool self = R == 0 && !xr;
+    if (A < 0 || R < 0 || A > BQ_PIVCHOL_MAX_M || R > BQ_PIVCHOL_MAX_M ||
+        R + A > BQ_PIVCHOL_MAX_M || q < 1 || (A && q > A) || q > BQ_PIVCHOL_MAX_Q ||
+        !(nugget >= 0.0) || !(tol >= 0.0) || !std::isfinite(nugget) || !std::isfinite(tol) ||
+        !piv || !gain || !ivar0 || !rank || (A && (!xc || !rho)) || ((R > 0) != (xr != nullptr)))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    const int64_t Ap64 = roundup(A, 64), Rp64 = self ? Ap64 : roundup(R, 64);
+    if (Ap64 * Rp64 > BQ_IVR_MAX_CELLS)
+        return fail(c, BQ_ERR_BAD_ARG, "ivr: %lld x %lld entries of T, at most %lld",
+                    (long long)Ap64, (long long)Rp64, (long long)BQ_IVR_MAX_CELLS);
+    const int64_t nw = self ? A : R;
+    double wsum = 0.0;
+    for (int64_t j = 0; A && j < nw; ++j) {
+        if (!(rho[j] >= 0.0) || !std::isfinite(rho[j]))
+            return fail(c, BQ_ERR_BAD_ARG, "ivr: weight %lld is negative or not finite",
+                        (long long)j);
+        wsum += rho[j];
+    }
+    if (A == 0) {
+        for (int64_t j = 0; j < q; ++j)
+            piv[j] = -1, gain[j] = 0.0;
+        *ivar0 = 0.0;
+        *rank = 0;
+        return BQ_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad, nq = (int)q;
+    const IvrPlan pl = ivr_plan((int)A, (int)R, self, npad, nq);
+    const int Ap = pl.Ap, Rp = pl.Rp, Mp = pl.Mp;
+    const int64_t M = (int64_t)pl.cand0 + A; // the joint set's points
+
+    // ---- the joint point set on the host
+    std::vector<double> joint;
+    if (!self) {
+        try {
+            joint.resize((size_t)d * M);
+        } catch (const std::bad_alloc &) {
+            return fail(c, BQ_ERR_NOMEM, "ivr: the joint point set (%zu bytes)",
+                        sizeof(double) * (size_t)d * M);
+        }
+        std::memcpy(joint.data(), xr, sizeof(double) * (size_t)d * R);
+        for (int64_t j = R; j < Rp; ++j)
+            std::memcpy(joint.data() + (size_t)d * j, xr + (size_t)d * (R - 1), sizeof(double) * d);
+        std::memcpy(joint.data() + (size_t)d * Rp, xc, sizeof(double) * (size_t)d * A);
+    }
+
+    // ---- every device buffer: the steps' own, T, the prediction's with q more columns
+    BQCHK(fit_grow(c, f->ivr, sizeof(double) * pl.total, "integrated variance workspace"));
+    BQCHK(fit_grow(c, f->ivrT, sizeof(double) * (size_t)Ap * Rp,
+                   "candidate-reference covariance"));
+    BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(npad), "wide block inverses"));
+    BQCHK(fit_grow(c, f->wV, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, f->wV2, sizeof(double) * (size_t)Mp * ((size_t)npad + nq),
+                   "prediction sweep workspace and the candidates' columns"));
+    BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
+    double *hs, *ds;
+    BQCHK(ctx_stage(c, pl.head + (size_t)Rp, &hs, &ds));
+    double *ws = f->ivr.d(), *W = f->wV2.d(), *T = f->ivrT.d();
+
+    // ---- the weights, 0 on the padding
+    double *hrho = hs + pl.head;
+    std::memcpy(hrho, rho, sizeof(double) * nw);
+    std::fill(hrho + nw, hrho + Rp, 0.0);
+
+    // ---- mean | var at io.res, V in the first npad columns of W
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, self ? xc : joint.data(), M, 0, false));
+    BQCHK(predict_sweep(c, f, io));
+    const double *xcd = io.xq + (size_t)d * pl.cand0;
+    HIPCHK(c, hipMemcpyAsync(ws + pl.o_rho, hrho, sizeof(double) * Rp, hipMemcpyHostToDevice,
+                             c->stream));
+
+    // ---- T = K(xc, xr) - V_c V_r^T; its padding rows stay zero
+    HIPCHK(c, hipMemsetAsync(T, 0, sizeof(double) * (size_t)Ap * Rp, c->stream));
+    BQCHK(launch_gram_cross(c, d, xcd, (int)A, io.xq, self ? (int)A : Rp, f->g, T, Ap));
+    GemmJob vvt;
+    vvt.C = T, vvt.ldc = Ap;
+    vvt.P = W + pl.cand0, vvt.ldp = Mp;
+    vvt.Q = W, vvt.qsj = 1, vvt.qsk = Mp;
+    vvt.m = Ap, vvt.n = Rp, vvt.k = npad;
+    BQCHK(launch_gemm(c, BQ_K_GEMM, vvt));
+
+    // ---- the steps
+    const double thr = tol * f->g.c * wsum;
+    BQCHK(launch_ivr_init(c, pl, ws, io.res + Mp));
+    for (int t = 0; t < nq; ++t)
+        BQCHK(launch_ivr_step(c, pl, ws, T, W, d, xcd, f->g, t, nugget, thr));
+
+    // ---- the download
+    HIPCHK(c, hipMemcpyAsync(hs, ws, sizeof(double) * pl.head, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int r = reinterpret_cast<const PivcholState *>(hs)->rank;
+    if (r < 0 || r > nq)
+        return fail(c, BQ_ERR_HIP, "ivr: the device left rank %d of %d steps", r, nq);
+    std::memcpy(gain, hs + pl.o_gain, sizeof(double) * nq);
+    std::memcpy(piv, hs + pl.o_piv, sizeof(int64_t) * nq);
+    *ivar0 = hs[pl.o_ivar];
+    if (resid_r)
+        std::memcpy(resid_r, hs + pl.o_dr, sizeof(double) * nw);
+    if (resid_c)
+        std::memcpy(resid_c, hs + pl.o_dc, sizeof(double) * A);
+    if (score0)
+        std::memcpy(score0, hs + pl.o_score0, sizeof(double) * A);
+    *rank = r;
+    return BQ_OK;
+}

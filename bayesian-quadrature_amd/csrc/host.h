@@ -24,6 +24,7 @@
 //                pgrad.h kernels                the posterior's gradients at the query points
 //                sample.h kernels               the posterior samples' normals and triangular product
 //                pivchol.h kernels              the pivoted partial Cholesky of a posterior
+//                ivr.h kernels                  designs that minimise the integrated variance
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -498,6 +499,24 @@ int launch_pivchol_init(bq_ctx *c, const PivcholPlan &pl, double *ws, const doub
 int launch_pivchol_step(bq_ctx *c, const PivcholPlan &pl, double *ws, double *W, int d,
                         const double *xq, const GaussParams &g, int M, int Mp, int npad, int q,
                         int j, double nugget, double thr);
+// designs that minimise the integrated posterior variance (ivr.h): A candidates (Ap rows of T,
+// rows cand0 .. of the Mp-row workspace W), R reference points (Rp columns of T; self: they are the
+// candidates, Rp = Ap, dr is dc).  The places of the workspace's parts in doubles --
+// [PivcholState | dc[p] + nugget | sum rho dr | gain q | piv q (int64) | dc Ap | dr Rp | score0 Ap],
+// the `head` doubles that go back to the host, then taken (Ap ints) | the workgroups' candidates |
+// c Ap | u Rp | rho Rp | part (nsl x Ap) | the product's part (wnsl x Mp); the start and step t
+struct IvrPlan {
+    int A, Ap, R, Rp, Mp, cand0, npad, q;
+    bool self;
+    int rb, js, nsl, nblk;  // the pass over T: rows per workgroup, columns per slice, slices
+    int wrb, wks, wnsl;     // pivchol_col_kernel over the candidate rows of W
+    size_t o_den, o_ivar, o_gain, o_piv, o_dc, o_dr, o_score0, head, o_taken, o_candv, o_candi,
+        o_c, o_u, o_rho, o_part, o_wpart, total;
+};
+IvrPlan ivr_plan(int A, int R, bool self, int npad, int q);
+int launch_ivr_init(bq_ctx *c, const IvrPlan &pl, double *ws, const double *var);
+int launch_ivr_step(bq_ctx *c, const IvrPlan &pl, double *ws, double *T, double *W, int d,
+                    const double *xc, const GaussParams &g, int t, double nugget, double thr);
 int launch_neg_identity(bq_ctx *c, double *nr, int B, int npad);
 int launch_pad_identity(bq_ctx *c, double *A, long lda, int n, int ntot);
 int launch_logdet(bq_ctx *c, const double *diag, long stride, int n, double *out);
@@ -823,6 +842,9 @@ struct bq_fit : FitCore {
     // the taken rows | the workgroups' candidates | the slices' partial sums (PivcholPlan), grown
     // on demand and kept; the factor's columns follow V in wV2
     DevBuf pvc;
+    // designs that minimise the integrated variance (bq_gp_ivr): the steps' workspace (IvrPlan)
+    // and T = Sigma(xc, xr), Ap x Rp, grown on demand and kept; the c columns follow V in wV2
+    DevBuf ivr, ivrT;
     // the log-ML gradient (bq_gp_logml_grad): Y and the sweep's partial sums (npad x npad each),
     // allocated on the first gradient; the product's partials and the d + 2 results
     DevBuf gY, gX, gpart;

@@ -1,12 +1,14 @@
 // k_reduce.hip -- read-outs, single-vector sweeps and small utilities (reduce.h, trsv.h), the
 // posterior's gradients at the query points (pgrad.h), the kernels that grow and shrink a
 // resident fit (append.h, remove.h), the posterior samples' normals and triangular product
-// (sample.h), the pivoted partial Cholesky of a posterior (pivchol.h) and their launchers.
+// (sample.h), the pivoted partial Cholesky of a posterior (pivchol.h), the designs that minimise
+// the integrated variance (ivr.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "pgrad.h"
 #include "sample.h"
 #include "pivchol.h"
+#include "ivr.h"
 #include "trsv.h"
 #include "trsvflow.h"
 #include "append.h"
@@ -200,6 +202,138 @@ int launch_pivchol_step(bq_ctx *c, const PivcholPlan &pl, double *ws, double *W,
     if (j + 1 < q) {
         hipLaunchKernelGGL(pivchol_select_kernel, dim3(1), dim3(256), 0, c->stream, st,
                            ws + pl.o_candv, candi, pl.nblk, j + 1, thr, piv, ws + pl.o_gain);
+        HIPCHK(c, hipGetLastError());
+    }
+    return BQ_OK;
+}
+
+// ---- designs that minimise the integrated posterior variance (ivr.h; fit.hip, bq_gp_ivr) ----
+// The shape of q steps.  The joint point set is [reference points, padded to Rp | candidates], so
+// that the candidate rows of W start on a 64-row boundary; self: the candidates alone.  The pass
+// over T is shaped like pivchol's product, from (Ap, Rp) alone: 256 candidates per workgroup from
+// 16384 on, 64 below so that few candidates still fill the chip by slices; about 1024 workgroups,
+// whole 64-column blocks, 64 .. BQ_IVR_JS_MAX columns per slice.  The product over the candidate
+// rows of W is pivchol_plan's for Ap rows.
+IvrPlan ivr_plan(int A, int R, bool self, int npad, int q)
+{
+    auto granule = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+    IvrPlan pl{};
+    pl.A = A, pl.R = self ? A : R, pl.self = self, pl.npad = npad, pl.q = q;
+    pl.Ap = (A + 63) / 64 * 64;
+    pl.Rp = self ? pl.Ap : (R + 63) / 64 * 64;
+    pl.cand0 = self ? 0 : pl.Rp;
+    pl.Mp = pl.cand0 + pl.Ap;
+    pl.rb = (pl.Ap >= 16384 && (pl.Ap % 256) == 0) ? 256 : 64;
+    const long want = (1024 + pl.Ap / pl.rb - 1) / (pl.Ap / pl.rb);
+    pl.js = (int)std::min<long>(BQ_IVR_JS_MAX, std::max<long>(64, pl.Rp / want / 64 * 64));
+    pl.nsl = (pl.Rp + pl.js - 1) / pl.js;
+    pl.nblk = (pl.Ap + 255) / 256;
+    const PivcholPlan pw = pivchol_plan(pl.Ap, npad, q);
+    pl.wrb = pw.rb, pl.wks = pw.ks, pl.wnsl = pw.nsl;
+    pl.o_den = granule((sizeof(PivcholState) + 7) / 8);
+    pl.o_ivar = pl.o_den + 1;
+    pl.o_gain = pl.o_ivar + 1;
+    pl.o_piv = pl.o_gain + (size_t)q;
+    pl.o_dc = pl.o_piv + (size_t)q;
+    pl.o_dr = self ? pl.o_dc : pl.o_dc + (size_t)pl.Ap;
+    pl.o_score0 = pl.o_dr + (size_t)pl.Rp;
+    pl.head = pl.o_score0 + (size_t)pl.Ap;
+    pl.o_taken = granule(pl.head);
+    pl.o_candv = pl.o_taken + granule(((size_t)pl.Ap + 1) / 2);
+    pl.o_candi = pl.o_candv + granule((size_t)pl.nblk);
+    pl.o_c = pl.o_candi + granule(((size_t)pl.nblk + 1) / 2);
+    pl.o_u = pl.o_c + (size_t)pl.Ap;
+    pl.o_rho = pl.o_u + (size_t)pl.Rp;
+    pl.o_part = pl.o_rho + (size_t)pl.Rp;
+    pl.o_wpart = pl.o_part + (size_t)pl.nsl * pl.Ap;
+    pl.total = pl.o_wpart + (size_t)pl.wnsl * pl.Mp;
+    return pl;
+}
+
+// dc, dr = the sweep's variances (var: Mp of them, the joint set's), nothing taken, the state,
+// piv = -1 and gain = 0; then sum rho dr.  rho is in the workspace already.
+int launch_ivr_init(bq_ctx *c, const IvrPlan &pl, double *ws, const double *var)
+{
+    PivcholState *st = reinterpret_cast<PivcholState *>(ws);
+    long long *piv = reinterpret_cast<long long *>(ws + pl.o_piv);
+    int *taken = reinterpret_cast<int *>(ws + pl.o_taken);
+    Bracket br(c, BQ_K_REDUCE, 16.0 * pl.Mp);
+    hipLaunchKernelGGL(ivr_init_kernel, dim3((std::max(pl.Ap, pl.Rp) + 255) / 256), dim3(256), 0,
+                       c->stream, var + pl.cand0, var, pl.A, pl.Ap, pl.R, pl.Rp, pl.q, st,
+                       ws + pl.o_den, piv, ws + pl.o_gain, ws + pl.o_dc, ws + pl.o_dr, taken);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(ivr_ivar_kernel, dim3(1), dim3(256), 0, c->stream, ws + pl.o_rho,
+                       ws + pl.o_dr, pl.Rp, ws + pl.o_ivar);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// step t < q: the pass over T (Ap x Rp, ld Ap) that applies step t - 1's update and sums step t's
+// numerators, the scores and the pivot, then c (column npad + t of the candidate rows of W, Mp x
+// (npad + q), ld Mp) and u with the new dc and dr.  xc: the candidates' points; g: the fit's
+// kernel parameters
+int launch_ivr_step(bq_ctx *c, const IvrPlan &pl, double *ws, double *T, double *W, int d,
+                    const double *xc, const GaussParams &g, int t, double nugget, double thr)
+{
+    if (pl.A < 1 || pl.R < 1 || t < 0 || t >= pl.q || (pl.Rp & 63) || (pl.js & 63) ||
+        pl.js > BQ_IVR_JS_MAX || (pl.Ap % pl.rb))
+        return fail(c, BQ_ERR_BAD_ARG, "ivr: step %d of %d over %d candidates", t, pl.q, pl.A);
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    PivcholState *st = reinterpret_cast<PivcholState *>(ws);
+    long long *piv = reinterpret_cast<long long *>(ws + pl.o_piv);
+    int *taken = reinterpret_cast<int *>(ws + pl.o_taken);
+    int *candi = reinterpret_cast<int *>(ws + pl.o_candi);
+    double *part = ws + pl.o_part, *wpart = ws + pl.o_wpart, *cb = ws + pl.o_c, *ub = ws + pl.o_u;
+    double *Wc = W + pl.cand0;
+    const long ldt = pl.Ap, ldw = pl.Mp;
+    {
+        Bracket br(c, BQ_K_REDUCE, (t ? 16.0 : 8.0) * pl.Ap * pl.Rp);
+        const dim3 grid((unsigned)(pl.Ap / pl.rb), (unsigned)pl.nsl);
+#define BQ_IVR_PASS(RB, UPD)                                                                      \
+    hipLaunchKernelGGL((ivr_deflate_score_kernel<RB, UPD>), grid, dim3(RB), 0, c->stream, T, ldt,   \
+                       pl.Rp, pl.js, st, cb, ub, ws + pl.o_rho, part)
+        if (pl.rb == 256 && t)
+            BQ_IVR_PASS(256, true);
+        else if (pl.rb == 256)
+            BQ_IVR_PASS(256, false);
+        else if (t)
+            BQ_IVR_PASS(64, true);
+        else
+            BQ_IVR_PASS(64, false);
+#undef BQ_IVR_PASS
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * pl.Ap * (pl.nsl + 2.0));
+        hipLaunchKernelGGL(ivr_score_kernel, dim3(pl.nblk), dim3(256), 0, c->stream, part, ldt,
+                           pl.nsl, pl.A, ws + pl.o_dc, taken, nugget, st,
+                           t == 0 ? ws + pl.o_score0 : nullptr, ws + pl.o_candv, candi);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(ivr_pick_kernel, dim3(1), dim3(256), 0, c->stream, st, ws + pl.o_den,
+                           ws + pl.o_candv, candi, pl.nblk, t, thr, nugget, ws + pl.o_dc, piv,
+                           ws + pl.o_gain);
+        HIPCHK(c, hipGetLastError());
+    }
+    const int K = pl.npad + t, wnsl = (K + pl.wks - 1) / pl.wks;
+    if (wnsl > 0) {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * pl.Ap * K);
+        const dim3 grid((unsigned)(pl.Ap / pl.wrb), (unsigned)wnsl);
+        if (pl.wrb == 256)
+            hipLaunchKernelGGL(pivchol_col_kernel<256>, grid, dim3(256), 0, c->stream, Wc, ldw, K,
+                               pl.wks, st, wpart);
+        else
+            hipLaunchKernelGGL(pivchol_col_kernel<64>, grid, dim3(64), 0, c->stream, Wc, ldw, K,
+                               pl.wks, st, wpart);
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * (pl.Ap * (wnsl + 4.0) + 3.0 * pl.Rp));
+        const int nbr = (pl.Rp + 255) / 256;
+        BQ_DISPATCH_D(d, hipLaunchKernelGGL(ivr_column_kernel<D>, dim3(pl.nblk + nbr), dim3(256), 0,
+                                            c->stream, Wc, ldw, K, pl.A, pl.Ap, pl.nblk, wpart, wnsl,
+                                            xc, g, nugget, st, ws + pl.o_den, ws + pl.o_dc, taken, cb,
+                                            T, pl.Rp, ub, pl.self ? nullptr : ws + pl.o_dr));
         HIPCHK(c, hipGetLastError());
     }
     return BQ_OK;

@@ -974,6 +974,50 @@ class Fit(object):
         r = int(rank.value)
         return piv[:r], (fac[:, :r] if want_factor else None), resid, gain[:r]
 
+    def ivr_design(self, xc, q, xr=None, rho=None, nugget=0.0, tol=0.0, want_scores=False):
+        """(piv, gain, ivar0, resid_r, resid_c[, score0]): the greedy design that minimises the
+        integrated posterior variance sum_j rho_j var(xr_j) by observing at most q of the
+        candidates xc, on the device (bq_gp_ivr).  Each step takes the candidate whose observation
+        (with noise ``nugget`` >= 0, absolute) lowers the integral the most, the lowest index
+        among equals: piv, (rank,) int64; gain, (rank,), the drop each step brought; ivar0 the
+        integral before the first step, so that ivar0 - gain.sum() is what is left; resid_r, (R,),
+        and resid_c, (A,), the latent variances left at the reference points and at the
+        candidates -- with nugget = s^2 those after ``append`` of the chosen points.  ``xr`` None:
+        the candidates are the reference points (one sweep over them) and resid_r is resid_c.
+        ``rho`` None: uniform weights 1 / R.  ``want_scores`` appends step 0's scores, (A,): the
+        acquisition surface, 0 where a candidate is not eligible.  The run ends early, rank < q,
+        at a gain of at most ``tol`` k(x, x) sum(rho), or one that is not positive."""
+        xc = _pts(xc)
+        if xc.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        A, q = xc.shape[1], int(q)
+        if xr is not None:
+            xr = _pts(xr)
+            if xr.shape[0] != self.d:
+                raise ValueError("dimension mismatch")
+            if xr.shape[1] == 0:
+                raise ValueError("no reference points")
+        R = A if xr is None else xr.shape[1]
+        if rho is None:
+            rho = np.full(R, 1.0 / max(R, 1))
+        rho = np.ascontiguousarray(rho, dtype=np.float64).ravel()
+        if rho.shape[0] != R:
+            raise ValueError("%d weights for %d reference points" % (rho.shape[0], R))
+        piv, gain = np.empty(max(q, 0), dtype=np.int64), np.empty(max(q, 0))
+        resid_c = np.empty(A)
+        resid_r = None if xr is None else np.empty(R)
+        score0 = np.empty(A) if want_scores else None
+        ivar0, rank = C.c_double(), C.c_int64()
+        e = self._eng
+        e._check(e._lib.bq_gp_ivr(e._ctx, self._handle(), L.dptr(xr), 0 if xr is None else R,
+                                  L.dptr(rho), L.dptr(xc), A, q, float(nugget), float(tol),
+                                  piv.ctypes.data_as(L._i64p), L.dptr(gain), C.byref(ivar0),
+                                  L.dptr(resid_r), L.dptr(resid_c), L.dptr(score0),
+                                  C.byref(rank)))
+        r = int(rank.value)
+        res = (piv[:r], gain[:r], float(ivar0.value), resid_c if xr is None else resid_r, resid_c)
+        return res + (score0,) if want_scores else res
+
 
 class Pair(object):
     """GP1 over log l at the samples and GP2 over [l_s, exp(mean of GP1 at x_c)] at samples +

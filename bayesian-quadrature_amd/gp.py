@@ -672,6 +672,69 @@ class GP(object):
         piv, _, resid, gain = self.pivoted_cholesky(xo, q, noisy=noisy, tol=tol)
         return (piv, {"gain": gain, "resid": resid}) if return_info else piv
 
+    def _ivr(self, xo, q, ref, weights, noisy, tol, want_scores):
+        """The checked arguments of ``ivr_design`` / ``ivr_scores`` and the device call; None for
+        empty ``xo``."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        q = int(q)
+        if q < 1:
+            raise ValueError("invalid value for q: %s" % q)
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("invalid value for tol: %s" % tol)
+        if xo.ndim > 2 or (ref is not None and np.ndim(ref) > 2):
+            raise ValueError("points must be a vector or a d x M matrix")
+        if xo.size == 0:
+            return None
+        if q > xo.shape[-1]:
+            raise ValueError("q = %d steps over %d points" % (q, xo.shape[-1]))
+        d = 1 if xo.ndim == 1 else xo.shape[0]
+        if ref is not None:
+            ref = np.atleast_1d(np.asarray(ref, dtype=DTYPE))
+            if ref.size == 0:
+                raise ValueError("no reference points")
+            if (1 if ref.ndim == 1 else ref.shape[0]) != d:
+                raise ValueError("dimension mismatch")
+        R = (xo if ref is None else ref).shape[-1]
+        if weights is not None:
+            weights = np.atleast_1d(np.asarray(weights, dtype=DTYPE))
+            if weights.shape != (R,):
+                raise ValueError("%s weights for %d reference points" % (weights.shape, R))
+            if not (np.all(np.isfinite(weights)) and np.all(weights >= 0)):
+                raise ValueError("weights must be finite and not negative")
+        return self._device_fit().ivr_design(
+            xo, q, xr=ref, rho=weights, nugget=float(self._s) ** 2 if noisy else 0.0,
+            tol=float(tol), want_scores=want_scores)
+
+    def ivr_design(self, xo, q, ref=None, weights=None, noisy=True, tol=0.0, return_info=False):
+        """The indices into ``xo`` of a batch of at most ``q`` points to evaluate next, chosen to
+        lower the integrated posterior variance ``sum_j weights_j var(ref_j)`` the most, one point
+        at a time with the points before it counted as observed (integrated variance reduction;
+        ALC, IMSPE) -- on the device fit (bq_gp_ivr).  ``greedy_design`` asks where the model is
+        least sure, which is the edge of the candidate box; this asks which observation teaches
+        the most about the region that ``ref`` and ``weights`` describe: a grid or a sample of the
+        measure one integrates against.  ``ref`` None: the candidates themselves; ``weights``
+        None: uniform.  ``noisy`` (the default) counts an observation with the noise s^2, as
+        ``append`` would, and a point may then be chosen twice.  Fewer than ``q`` indices come
+        back when a step's gain falls to ``tol`` k(x, x) sum(weights) or is not positive.
+        ``return_info`` appends {"gain": the drop each step brought, "ivar0": the integral before,
+        "resid": the variance left at ``xo``, "resid_ref": at ``ref``}.  ``xo`` and ``ref`` are
+        vectors of points, or d x M as for ``pivoted_cholesky``."""
+        out = self._ivr(xo, q, ref, weights, noisy, tol, False)
+        if out is None:
+            piv, gain, ivar0 = np.empty(0, dtype=np.int64), np.empty(0, dtype=DTYPE), 0.0
+            resid_r = resid_c = np.empty(0, dtype=DTYPE)
+        else:
+            piv, gain, ivar0, resid_r, resid_c = out
+        info = {"gain": gain, "ivar0": ivar0, "resid": resid_c, "resid_ref": resid_r}
+        return (piv, info) if return_info else piv
+
+    def ivr_scores(self, xo, ref=None, weights=None, noisy=True):
+        """(M,): how much observing each point of ``xo`` alone would lower the integrated
+        posterior variance ``sum_j weights_j var(ref_j)`` -- the acquisition surface that
+        ``ivr_design``'s first step takes the maximum of (arguments as there)."""
+        out = self._ivr(xo, 1, ref, weights, noisy, 0.0, True)
+        return np.empty(0, dtype=DTYPE) if out is None else out[5]
+
     # -- pickling / copying: only data and parameters travel -------------------
     def __getstate__(self):
         state = {"K": self.K, "x": self._x, "y": self._y, "s": self._s}

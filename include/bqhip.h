@@ -354,6 +354,54 @@ int bq_gp_sample(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, int64_t 
 #define BQ_PIVCHOL_MAX_Q 65536
 int bq_gp_pivchol(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, int64_t q, double nugget,
                   double tol, int64_t *piv, double *C, double *resid, double *gain, int64_t *rank);
+/* The greedy design that minimises the integrated posterior variance (integrated variance
+ * reduction; ALC, IMSPE): which q of A candidates xc (d x A column-major) to observe so that
+ * sum_j rho_j var(r_j) over R reference points xr (d x R) with weights rho (R, finite, >= 0)
+ * drops the most, one point at a time.  The reference points and weights describe the measure the
+ * variance is integrated against: a grid or a sample of it.  On the device, after one sweep of
+ * bq_gp_predict over the joint point set.  Sigma is the latent posterior covariance (no s^2) over
+ * [xr | xc]; nugget >= 0 in absolute units is an observation's noise; tol >= 0 in multiples of
+ * k0 sum_j rho_j, k0 = k(x, x).
+ * With T = Sigma(xc, xr) (A x R), dc = diag Sigma(xc, xc), dr = diag Sigma(xr, xr) and
+ * ivar0 = sum_j rho_j dr[j], for t = 0 .. q - 1:
+ *   eligible  a candidate with dc[a] + nugget > 0 that, when nugget == 0, has not been taken;
+ *   score[a] = (sum_j rho_j T[a, j]^2) / (dc[a] + nugget): exactly the drop of sum_j rho_j dr[j]
+ *             when xc_a is observed with noise nugget;
+ *   p_t      = the eligible candidate with the largest score, the lowest index among equals; a
+ *             NaN score comes first;
+ *   gain_t   = score[p_t]; the run ends with rank = t unless gain_t > tol k0 sum rho, is positive
+ *             and is finite;
+ *   c        = (K(xc, xc_p) - V_c V_c[p]^T - sum_{i<t} c_i c_i[p]) / sqrt(dc[p] + nugget),
+ *   u        = T[p, :] / sqrt(dc[p] + nugget);
+ *   T -= c u^T, dc -= c o c, dr -= u o u (each entry one fma).
+ * nugget == 0: c[p] = sqrt(dc[p]), a taken candidate keeps dc = 0 exactly, has c = 0 from then on
+ * and is never taken twice.  nugget > 0: a candidate may be taken again (two noisy observations
+ * at one place).  So sum_j rho_j dr^(t+1)[j] = sum_j rho_j dr^(t)[j] - gain_t, and with
+ * nugget = s^2 the final dr and dc are the variances a fit has at xr and xc after bq_gp_append of
+ * the chosen points, whatever their targets.  Step 0's scores are the acquisition surface.
+ * xr == NULL with R == 0: the candidates are the reference points, rho has A entries, one sweep
+ * runs over the A points (not over two copies of them), dr is dc, and resid_r, if given, receives
+ * the same A values as resid_c.
+ * Outputs on the host: piv (q, -1 from rank on), gain (q, 0 from rank on), ivar0 and rank (one
+ * value each) are required; resid_r (R: dr after the last step), resid_c (A: dc) and score0 (A:
+ * step 0's scores, 0 where a candidate is not eligible) may be NULL.
+ * The same inputs give the same bits on every call, and the first j pivots and gains of a q-step
+ * call are bit for bit those of a j-step call.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG for A < 0, R < 0, q < 1, q > A (but
+ * for A == 0), R + A > BQ_PIVCHOL_MAX_M, q > BQ_PIVCHOL_MAX_Q, more than BQ_IVR_MAX_CELLS entries
+ * of T (A and R each rounded up to 64), a negative or non-finite nugget, tol or weight, xr == NULL
+ * with R > 0 or the reverse, or piv, gain, ivar0, rank or -- unless A == 0 -- rho or xc == NULL:
+ * all checked before anything is allocated, and nothing is written.  A == 0 writes rank = 0,
+ * piv = -1, gain = 0 and ivar0 = 0 and touches nothing else.  Device memory (T; the prediction's
+ * workspaces over R + A points with q more columns; a few vectors; kept with the fit) is
+ * allocated before anything is enqueued: BQ_ERR_NOMEM leaves the fit as it was.  All steps are
+ * enqueued without waiting for the device; nothing reaches the caller's memory unless every
+ * kernel has completed.  The fit is not disturbed. */
+#define BQ_IVR_MAX_CELLS 268435456
+int bq_gp_ivr(bq_ctx *ctx, bq_fit *fit, const double *xr, int64_t R, const double *rho,
+              const double *xc, int64_t A, int64_t q, double nugget, double tol, int64_t *piv,
+              double *gain, double *ivar0, double *resid_r, double *resid_c, double *score0,
+              int64_t *rank);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
