@@ -80,6 +80,9 @@ SIGNATURES = {
     "bq_gp_predict": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp]),
     "bq_gp_predict_grad": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp, _dp]),
     "bq_gp_predict_dtheta": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp, _dp]),
+    "bq_gp_trend": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "bq_gp_predict_trend": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp]),
+    "bq_gp_trend_last_route": (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bq_gp_sample": (C.c_int, [_vp, _vp, _dp, _i64, _i64, _dp, C.c_uint64, _dp, _i64, _dp, _dp, _dp,
                                _dp]),
     "bq_gp_pivchol": (C.c_int, [_vp, _vp, _dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp, _dp, _i64p]),

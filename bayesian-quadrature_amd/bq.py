@@ -175,6 +175,21 @@ class BQ(object):
         return self.gp_log_l.ivr_design(x_c, q, ref=None if x_r is None else ref,
                                         weights=dens / dens.sum())
 
+    def log_l_mean_trend(self, x, degree=2):
+        """Posterior mean of the log-GP with a polynomial trend of ``degree`` whose coefficients
+        are marginalised (gp.GP.mean_trend): the log of a peaked likelihood is close to a
+        quadratic, and away from the samples this mean follows it where the zero-mean
+        ``gp_log_l.mean`` goes back to 0.  A view of the log-GP only: ``Z_mean``, ``Z_var``,
+        the acquisition, the designs and the hyper-parameter fits stay zero-mean."""
+        self._require_exact()
+        return self.gp_log_l.mean_trend(x, degree=degree)
+
+    def log_l_var_trend(self, x, degree=2):
+        """Posterior variance of the log-GP under that trend (gp.GP.var_trend): the zero-mean
+        variance plus the uncertainty of the trend's coefficients."""
+        self._require_exact()
+        return self.gp_log_l.var_trend(x, degree=degree)
+
     # ---------------------------------------------------------------- moments
     def Z_mean(self):
         self._require_exact()

@@ -1104,7 +1104,27 @@ struct PosteriorIO {
 // Mp = M rounded up to 64) by a forward sweep with rows = prediction points, f->wV left holding
 // the sweep's partial sums; mean (Mp) | var (Mp) at io.res.  With io.direct the points are in the
 // mapped staging buffer, which the cross Gram then reads itself and pads by itself.
+// (predict_v: everything but the row reductions, which bq_gp_predict_trend runs in its own form)
+static int predict_v(bq_ctx *c, bq_fit *f, const PosteriorIO &io);
 static int predict_sweep(bq_ctx *c, bq_fit *f, const PosteriorIO &io)
+{
+    BQCHK(predict_v(c, f, io));
+    return launch_rowdot(c, f->wV2.d(), (long)io.Mp, (int)io.M, io.Mp, f->npad, f->wz.d(), f->g.c,
+                         io.res, io.res + io.Mp, 1);
+}
+
+// z lives in row yrow of the factor with stride ldl: gathered once per (re)fit
+int fit_zc(bq_ctx *c, bq_fit *f)
+{
+    if (!(f->have & bq_fit::ZC)) {
+        BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)f->npad, "contiguous z"));
+        BQCHK(launch_gather_row(c, f->wz.d(), f->A.d() + f->L.yrow, f->ldl, f->npad));
+        f->have |= bq_fit::ZC;
+    }
+    return BQ_OK;
+}
+
+static int predict_v(bq_ctx *c, bq_fit *f, const PosteriorIO &io)
 {
     const int d = f->d, n = f->n, npad = f->npad, M = (int)io.M, Mp = io.Mp;
     const GaussParams g = f->g;
@@ -1120,14 +1140,7 @@ static int predict_sweep(bq_ctx *c, bq_fit *f, const PosteriorIO &io)
         BQCHK(launch_gram_cross(c, d, io.xq, M, f->pts.d(), n, g, V0.d(), Mp));
     }
     BQCHK(enqueue_forward_rows(c, V0.d(), V.d(), Mp, Mp, f->A.d(), f->ldl, npad, wi));
-    // z lives in row yrow of the factor with stride ldl: gathered once per (re)fit
-    if (!(f->have & bq_fit::ZC)) {
-        BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
-        BQCHK(launch_gather_row(c, f->wz.d(), f->A.d() + f->L.yrow, f->ldl, npad));
-        f->have |= bq_fit::ZC;
-    }
-    BQCHK(launch_rowdot(c, V.d(), (long)Mp, M, Mp, npad, f->wz.d(), g.c, io.res, io.res + Mp, 1));
-    return BQ_OK;
+    return fit_zc(c, f);
 }
 
 // beta = V L^-1 out of V (f->wV2) into the buffer the cross Gram came in (f->wV: the forward sweep
@@ -1306,6 +1319,218 @@ extern "C" int bq_gp_predict_dtheta(bq_ctx *c, bq_fit *f, const double *xo, int6
         }
     }
     return io.finish(c, nout, mean, var, dmean, dvar);
+}
+
+// ===========================================================================
+// The polynomial trend of a fit, its coefficients marginalised (include/bqhip.h has the contract;
+// trend.h the kernels)
+// ===========================================================================
+namespace bqh {
+
+// the basis of a trend call, checked against the fit: the key of the state (entries from d on are
+// fixed, so that two keys compare byte by byte)
+static int trend_basis(bq_ctx *c, const bq_fit *f, int degree, const double *center,
+                       const double *scale, TrendBasis &tb)
+{
+    if (degree < 0 || degree > 2)
+        return fail(c, BQ_ERR_BAD_ARG, "trend: degree %d, not 0 .. 2", degree);
+    if (!center || !scale)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    tb = TrendBasis{};
+    tb.degree = degree;
+    tb.p = trend_p(degree, f->d);
+    for (int k = 0; k < BQ_MAXD; ++k) {
+        tb.c[k] = k < f->d ? center[k] : 0.0;
+        tb.rho[k] = k < f->d ? scale[k] : 1.0;
+        if (!std::isfinite(tb.c[k]))
+            return fail(c, BQ_ERR_BAD_ARG, "trend: the centre must be finite");
+        if (!(tb.rho[k] > 0.0) || !std::isfinite(tb.rho[k]))
+            return fail(c, BQ_ERR_BAD_ARG, "trend: the scale must be positive and finite");
+    }
+    if (f->n < tb.p)
+        return fail(c, BQ_ERR_BAD_ARG, "trend: %d observations for %d basis functions", f->n, tb.p);
+    return BQ_OK;
+}
+
+static bool trend_current(const bq_fit *f, const TrendBasis &tb)
+{
+    return (f->have & bq_fit::TREND) && std::memcmp(&f->tr_key, &tb, sizeof tb) == 0;
+}
+
+// every buffer the producer touches, there before its first launch
+static int trend_alloc(bq_ctx *c, bq_fit *f)
+{
+    BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(f->npad), "wide block inverses"));
+    BQCHK(fit_vec(c, f));
+    BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)f->npad, "contiguous z"));
+    return fit_grow(c, f->trend, sizeof(double) * trend_plan(f->npad).total, "trend state");
+}
+
+// The producer of TREND, first half: its launches, nothing read back.  H by the basis kernel, G =
+// L^-1 H by the forward row sweep with 64 rows (fit_dkz's form), A and b in slices and one fold,
+// the one-workgroup solve, which leaves z - G beta in the single-vector workspace, and the
+// backward single-vector sweep from there into the state's own alpha_t.  The bit is dropped first:
+// the state belongs to no key until fit_trend has seen the status.
+static int trend_enqueue(bq_ctx *c, bq_fit *f, const TrendBasis &tb)
+{
+    const int npad = f->npad;
+    const TrendPlan pl = trend_plan(npad);
+    double *ws = f->trend.d();
+    f->drop(bq_fit::TREND);
+    WideInv w;
+    BQCHK(fit_wide(c, f, w));
+    BQCHK(fit_zc(c, f));
+    BQCHK(launch_trend_basis(c, f->d, f->pts.d(), f->n, npad, tb, ws + pl.o_H, 1, BQ_TREND_ROWS));
+    BQCHK(enqueue_forward_rows(c, ws + pl.o_H, ws + pl.o_G, BQ_TREND_ROWS, BQ_TREND_ROWS, f->A.d(),
+                               f->ldl, npad, w));
+    BQCHK(launch_trend_sums(c, ws + pl.o_G, f->wz.d(), npad, tb.p, ws + pl.o_part, ws + pl.o_sums));
+    BQCHK(launch_trend_solve(c, ws + pl.o_sums, tb.p, ws + pl.o_G, f->wz.d(), npad, ws + pl.o_tr,
+                             f->vec.d()));
+    return enqueue_backward_vec(c, f->vec.d(), ws + pl.o_alpha, f->A.d(), f->ldl, npad, w,
+                                f->vec.d() + 2 * (size_t)npad);
+}
+
+// ... second half, once the stream is synchronised and the solve's status is on the host: the
+// state is the key's, or nobody's
+static int fit_trend(bq_ctx *c, bq_fit *f, const TrendBasis &tb, double status)
+{
+    if (status != 0.0) {
+        f->drop(bq_fit::TREND);
+        return fail(c, BQ_ERR_NOT_PD,
+                    "trend: H^T Kxx^-1 H has a pivot that is not positive and finite");
+    }
+    f->tr_key = tb;
+    f->have |= bq_fit::TREND;
+    return BQ_OK;
+}
+
+} // namespace bqh
+
+extern "C" int bq_gp_trend(bq_ctx *c, bq_fit *f, int degree, const double *center,
+                           const double *scale, double *beta, double *cov_beta, double *logml_t,
+                           double *alpha_t)
+{
+    BQCHK(check_fit(c, f));
+    TrendBasis tb;
+    BQCHK(trend_basis(c, f, degree, center, scale, tb));
+    if (!beta && !cov_beta && !logml_t && !alpha_t)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    BQCHK(trend_alloc(c, f));
+    double *hs, *ds;
+    BQCHK(ctx_stage(c, BQ_TREND_HEAD, &hs, &ds));
+    const int p = tb.p, n = f->n;
+    const bool fresh = !trend_current(f, tb);
+    const TrendPlan pl = trend_plan(f->npad);
+    const double *ws = f->trend.d();
+    // one read-back: the head of the state and alpha_t into pinned staging
+    BQCHK(with_flow_fallback(c, [&]() -> int {
+        if (fresh)
+            BQCHK(trend_enqueue(c, f, tb));
+        HIPCHK(c, hipMemcpyAsync(hs, ws + pl.o_tr, sizeof(double) * BQ_TREND_HEAD,
+                                 hipMemcpyDeviceToHost, c->stream));
+        if (alpha_t)
+            HIPCHK(c, hipMemcpyAsync(f->hvec, ws + pl.o_alpha, sizeof(double) * n,
+                                     hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BQ_OK;
+    }));
+    BQCHK(fit_trend(c, f, tb, hs[BQ_TREND_STATUS]));
+    if (beta)
+        std::memcpy(beta, hs + BQ_TREND_BETA, sizeof(double) * p);
+    if (cov_beta)
+        std::memcpy(cov_beta, hs + BQ_TREND_AINV, sizeof(double) * p * p);
+    if (logml_t)
+        *logml_t = -0.5 * (f->qf - hs[BQ_TREND_BTB]) - 0.5 * f->logdet - 0.5 * hs[BQ_TREND_LOGDET] -
+                   0.5 * (double)(n - p) * 1.8378770664093453; // log 2 pi
+    if (alpha_t)
+        std::memcpy(alpha_t, f->hvec, sizeof(double) * n);
+    return BQ_OK;
+}
+
+// The trend posterior at M points.  Mean route (no var): the state, then one fused launch over
+// alpha_t, no sweep and no M x n matrix.  Full route: bq_gp_predict's staging, cross Gram and
+// forward sweep (predict_v), the basis rows of the points, then the row reductions with the p
+// sums v_j.G_k in the same pass (trend_route: p <= 8) or bq_gp_predict's own reductions and one
+// product R = Phi - V G^T, and one finishing launch.  Where the state is not there for this key its
+// producer is enqueued in front: either way one read-back, which carries the solve's status.
+extern "C" int bq_gp_predict_trend(bq_ctx *c, bq_fit *f, int degree, const double *center,
+                                   const double *scale, const double *xo, int64_t M, double *mean,
+                                   double *var)
+{
+    BQCHK(check_fit(c, f));
+    TrendBasis tb;
+    BQCHK(trend_basis(c, f, degree, center, scale, tb));
+    if (M < 0 || (M && !xo) || (!mean && !var))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (M == 0)
+        return BQ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, n = f->n, npad = f->npad, p = tb.p, Mp = (int)roundup(M, 64);
+    const bool full = var != nullptr;
+    const TrendRoute route = trend_route(p, full);
+    BQCHK(trend_alloc(c, f));
+    if (full) {
+        BQCHK(fit_grow(c, f->wV, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+        BQCHK(fit_grow(c, f->wV2, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+        BQCHK(fit_grow(c, f->wphi, sizeof(double) * (size_t)Mp * BQ_TREND_ROWS,
+                       "basis rows of the prediction points"));
+    }
+    const bool fresh = !trend_current(f, tb);
+    const TrendPlan pl = trend_plan(npad);
+    const double *ws = f->trend.d(), *G = ws + pl.o_G, *tr = ws + pl.o_tr;
+    PosteriorIO io;
+    GemmRoute ran{};
+    BQCHK(with_flow_fallback(c, [&]() -> int {
+        if (fresh)
+            BQCHK(trend_enqueue(c, f, tb));
+        BQCHK(io.begin(c, f, xo, M, 1, full)); // (nd = 1: room for the status behind mean | var)
+        double *status = io.res + 2 * (size_t)Mp;
+        if (!full) {
+            BQCHK(launch_trend_mean(c, d, io.xq, (int)M, f->pts.d(), n, ws + pl.o_alpha, f->g, tb, tr,
+                                    io.res, status));
+        } else {
+            BQCHK(predict_v(c, f, io));
+            double *R = f->wphi.d();
+            BQCHK(launch_trend_basis(c, d, io.xq, (int)M, Mp, tb, R, Mp, 1));
+            if (route == TrendRoute::OnePass) {
+                BQCHK(launch_rowdot_trend(c, f->wV2.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(),
+                                          f->g.c, G, p, io.res, io.res + Mp, R));
+            } else {
+                BQCHK(launch_rowdot(c, f->wV2.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(), f->g.c,
+                                    io.res, io.res + Mp, 1));
+                GemmJob vg;
+                vg.C = R, vg.ldc = Mp;
+                vg.P = f->wV2.d(), vg.ldp = Mp;
+                vg.Q = G, vg.qsj = 1, vg.qsk = BQ_TREND_ROWS;
+                vg.m = Mp, vg.n = BQ_TREND_ROWS, vg.k = npad;
+                BQCHK(launch_gemm(c, BQ_K_GEMM, vg, &ran));
+            }
+            BQCHK(launch_trend_finish(c, R, (long)Mp, (int)M, p, tr, io.res, io.res + Mp, status));
+        }
+        return io.finish(c, 2 * (size_t)Mp + 1, nullptr, nullptr, nullptr, nullptr);
+    }));
+    const double *hres = io.st.host + (size_t)d * M;
+    BQCHK(fit_trend(c, f, tb, hres[2 * (size_t)Mp]));
+    f->tr_route = (int)route;
+    f->tr_gemm = route == TrendRoute::Gemm ? (int)ran.kernel : -1;
+    if (mean)
+        std::memcpy(mean, hres, sizeof(double) * M);
+    if (var)
+        std::memcpy(var, hres + Mp, sizeof(double) * M);
+    return BQ_OK;
+}
+
+extern "C" int bq_gp_trend_last_route(bq_ctx *c, bq_fit *f, int *route, int *gemm_kernel)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (!f || !route)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    *route = f->tr_route;
+    if (gemm_kernel)
+        *gemm_kernel = f->tr_gemm;
+    return BQ_OK;
 }
 
 // S joint draws of the latent posterior at M points (include/bqhip.h has the contract; sample.h the

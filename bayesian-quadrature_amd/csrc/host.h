@@ -25,6 +25,7 @@
 //                sample.h kernels               the posterior samples' normals and triangular product
 //                pivchol.h kernels              the pivoted partial Cholesky of a posterior
 //                ivr.h kernels                  designs that minimise the integrated variance
+//                trend.h kernels                the polynomial trend of a fit, marginalised
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
 //   sweeps.hip   sweeps over a resident factor (no kernels of its own)
@@ -372,6 +373,10 @@ int launch_hess_products(bq_ctx *c, int d, const double *Y, double *Ki, double *
 // ... and the sums over what it left in Ki and ws; *sums: where they are on the device
 int launch_hess_sums(bq_ctx *c, int d, const double *Ki, double *ws, const HessJob &hj,
                      const double **sums);
+// out[c] = the sum over i < nitem of part[i item_stride + c c_stride], c < nc, a workgroup per c
+// (fold_kernel<FoldPlain>, wgsum.h: the unit's one instantiation serves the others' partial sums)
+void launch_fold(bq_ctx *c, const double *part, int nitem, long item_stride, long c_stride, int nc,
+                 double *out);
 // leave-one-out (loo.h) into its own workspace; *vecs: mu | var | lp, npad apart
 size_t loo_ws_doubles(int npad, int d);
 int launch_loo(bq_ctx *c, int d, const double *Y, const double *alpha, const double *y, int n,
@@ -517,6 +522,38 @@ IvrPlan ivr_plan(int A, int R, bool self, int npad, int q);
 int launch_ivr_init(bq_ctx *c, const IvrPlan &pl, double *ws, const double *var);
 int launch_ivr_step(bq_ctx *c, const IvrPlan &pl, double *ws, double *T, double *W, int d,
                     const double *xc, const GaussParams &g, int t, double nugget, double thr);
+// the polynomial trend of a fit (trend.h).  The places of the state's parts in doubles, from npad
+// alone: [H, then the sweep's partial sums (64 x npad) | G = L^-1 H as rows (64 x npad) | alpha_t
+// (npad) | the slices' shares of A and b (npad / 64 slices of 64 columns, the largest basis) | A, b
+// | what trend_solve_kernel leaves (BQ_TREND_STATE)]
+struct TrendPlan {
+    int nsl;
+    size_t o_H, o_G, o_alpha, o_part, o_sums, o_tr, total;
+};
+TrendPlan trend_plan(int npad);
+// How bq_gp_predict_trend's reductions go out, decided in ONE place (trend_route): Mean, the fused
+// launch without a sweep; OnePass, rowdot_trend_kernel; Gemm, launch_rowdot and one GemmJob
+enum class TrendRoute { Mean = 0, OnePass = 1, Gemm = 2 };
+TrendRoute trend_route(int p, bool want_var);
+// phi of the d x m points x into out[k rs + j cs], zero for m <= j < mp and on rows p .. 63
+int launch_trend_basis(bq_ctx *c, int d, const double *x, int m, int mp, const TrendBasis &tb,
+                       double *out, long rs, long cs);
+// A = G G^T (p x p) | b = G z (p) into sums, through part (TrendPlan::o_part)
+int launch_trend_sums(bq_ctx *c, const double *G, const double *z, int npad, int p, double *part,
+                      double *sums);
+int launch_trend_solve(bq_ctx *c, const double *sums, int p, const double *G, const double *z,
+                       int npad, double *tr, double *zt);
+// launch_rowdot's mean and var, and R (Mp x 64, ld Mp; phi on entry) -= V G^T in its first p <=
+// BQ_TREND_ONEPASS_MAXP columns
+int launch_rowdot_trend(bq_ctx *c, const double *V, long ldv, int M, int Mp, int npad,
+                        const double *z, double k0, const double *G, int p, double *mean,
+                        double *var, double *R);
+// mean += R beta, var += |L_A^-1 r|^2 over the M rows of R; status[0] = the solve's status
+int launch_trend_finish(bq_ctx *c, const double *R, long ldr, int M, int p, const double *tr,
+                        double *mean, double *var, double *status);
+int launch_trend_mean(bq_ctx *c, int d, const double *xo, int M, const double *pts, int n,
+                      const double *alpha_t, const GaussParams &g, const TrendBasis &tb,
+                      const double *tr, double *mean, double *status);
 int launch_neg_identity(bq_ctx *c, double *nr, int B, int npad);
 int launch_pad_identity(bq_ctx *c, double *A, long lda, int n, int ntot);
 int launch_logdet(bq_ctx *c, const double *diag, long stride, int n, double *out);
@@ -796,7 +833,7 @@ struct bq_fit : FitCore {
     //   bit       what is there                                     from        set by
     //   DW        dw: 16 x 16 inverses of the factor's diagonal     the factor  fit_dw
     //   WIDE      wide: -W^T of the B-wide diagonal blocks          DW          fit_wide
-    //   ZC        wz: z = L^-1 y contiguous (the factor's y row     z           predict_sweep
+    //   ZC        wz: z = L^-1 y contiguous (the factor's y row     z           fit_zc
     //             has stride ldl: the row reductions then read
     //             one line per 8 entries, not one per entry)
     //   ALPHA     alpha = L^-T z                                    WIDE, z     fit_alpha
@@ -812,6 +849,11 @@ struct bq_fit : FitCore {
     //   DKZ       dkz: u = Kxx^-1 alpha and z_k = Kxx^-1 (D_k       ALPHA, WIDE fit_dkz
     //             alpha) as the rows of a 64 x npad matrix (its
     //             second half: the row sweeps' workspace)
+    //   TREND     trend: G = L^-1 H as rows, the factor of          WIDE, z,    fit_trend
+    //             A = G^T G, A^-1, beta, alpha_t and the scalars    the key
+    //             of the polynomial trend with the key (degree,
+    //             c, rho) in tr_key; a call with another key
+    //             recomputes it
     // (z is the targets through the factor.)  A bit is never set while a bit it is computed from is
     // clear: every producer runs the producers of what it reads first, and both events clear a bit
     // together with everything computed from it.
@@ -826,10 +868,11 @@ struct bq_fit : FitCore {
         LOO = 1u << 7,
         LOO_GRAD = 1u << 8,
         DKZ = 1u << 9,
+        TREND = 1u << 10,
         // the events: a (re)factorisation, an append, a removal ...
-        FACTOR_CHANGED = DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ,
+        FACTOR_CHANGED = DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND,
         // ... and bq_gp_set_y (the factor's own inverses stay)
-        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ,
+        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND,
     };
     unsigned have = 0;
     void drop(unsigned event) { have &= ~event; }
@@ -865,6 +908,13 @@ struct bq_fit : FitCore {
     // as rows, 64 x npad, and as much again for the two row sweeps that solve them (fit_dkz),
     // allocated on the first call; the quad product's partial sums, grown on demand and kept
     DevBuf dkz, wq;
+    // the polynomial trend (bq_gp_trend, bq_gp_predict_trend): the state (TrendPlan), allocated on
+    // the first call and kept, and the basis it was computed for; the basis rows of a prediction's
+    // points (Mp x 64), grown on demand and kept; the route the last prediction took
+    // (bq_gp_trend_last_route)
+    DevBuf trend, wphi;
+    TrendBasis tr_key{};
+    int tr_route = -1, tr_gemm = -1;
     // the single-vector sweeps (trsv.h): x | y, 2 npad doubles, and their captured launch
     // chains -- [0] solve (forward + backward), [1] backward into alpha, [2] forward; the
     // pointers survive a refit, so the graphs do too
@@ -917,7 +967,7 @@ inline void fit_adopt(bq_fit *f, FitCore &core)
 {
     f->swap(core);
     for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart, &f->hB,
-                      &f->loo, &f->lgo, &f->dkz, &f->wq})
+                      &f->loo, &f->lgo, &f->dkz, &f->wq, &f->trend})
         b->release();
     if (f->hvec)
         (void)hipHostFree(f->hvec);
@@ -935,6 +985,7 @@ int fit_wide(bq_ctx *c, bq_fit *f, WideInv &w);
 int fit_vec(bq_ctx *c, bq_fit *f);
 int fit_alpha(bq_ctx *c, bq_fit *f);
 int fit_dkz(bq_ctx *c, bq_fit *f);
+int fit_zc(bq_ctx *c, bq_fit *f);
 // Replays a chain of sweep launches over a fit's own buffers from the slot's captured hipGraph (a
 // sweep is 2 npad / B launches of 2-8 us each: enqueued one by one the host is the bottleneck).
 template <class F>

@@ -39,7 +39,8 @@ static int fail_d_npad(bq_ctx *c, const char *what)
 }
 
 // out[c] = the sum over i < nitem of part[i item_stride + c c_stride], c < nc, a workgroup per c
-static void launch_fold(bq_ctx *c, const double *part, int nitem, long item_stride, long c_stride,
+// (host.h: k_reduce.hip folds the trend's sums with it)
+void launch_fold(bq_ctx *c, const double *part, int nitem, long item_stride, long c_stride,
                         int nc, double *out)
 {
     hipLaunchKernelGGL(fold_kernel<FoldPlain>, dim3((unsigned)nc), dim3(256), 0, c->stream, part, nitem,

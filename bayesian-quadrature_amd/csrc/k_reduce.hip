@@ -2,13 +2,14 @@
 // posterior's gradients at the query points (pgrad.h), the kernels that grow and shrink a
 // resident fit (append.h, remove.h), the posterior samples' normals and triangular product
 // (sample.h), the pivoted partial Cholesky of a posterior (pivchol.h), the designs that minimise
-// the integrated variance (ivr.h) and their launchers.
+// the integrated variance (ivr.h), the polynomial trend of a fit (trend.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "pgrad.h"
 #include "sample.h"
 #include "pivchol.h"
 #include "ivr.h"
+#include "trend.h"
 #include "trsv.h"
 #include "trsvflow.h"
 #include "append.h"
@@ -336,6 +337,128 @@ int launch_ivr_step(bq_ctx *c, const IvrPlan &pl, double *ws, double *T, double 
                                             T, pl.Rp, ub, pl.self ? nullptr : ws + pl.o_dr));
         HIPCHK(c, hipGetLastError());
     }
+    return BQ_OK;
+}
+
+// ---- the polynomial trend of a fit (trend.h; fit.hip, bq_gp_trend, bq_gp_predict_trend) ----
+// The places of the state's parts, from npad alone: the slices are the 64-column blocks of G, and
+// the partial sums have room for the largest basis, so that a call with another key reuses them.
+TrendPlan trend_plan(int npad)
+{
+    auto granule = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+    constexpr size_t ne_max = (size_t)BQ_TREND_MAXP * (BQ_TREND_MAXP + 1);
+    TrendPlan pl{};
+    pl.nsl = npad / 64;
+    pl.o_H = 0;
+    pl.o_G = (size_t)BQ_TREND_ROWS * npad;
+    pl.o_alpha = 2 * pl.o_G;
+    pl.o_part = pl.o_alpha + (size_t)npad;
+    pl.o_sums = pl.o_part + granule((size_t)pl.nsl * ne_max);
+    pl.o_tr = pl.o_sums + granule(ne_max);
+    pl.total = pl.o_tr + BQ_TREND_STATE;
+    return pl;
+}
+
+// Without the variance there is no sweep; with it the p sums per point ride in the row reductions'
+// one pass over V while a thread's registers hold them, and go out as a product from there on
+TrendRoute trend_route(int p, bool want_var)
+{
+    if (!want_var)
+        return TrendRoute::Mean;
+    return p <= BQ_TREND_ONEPASS_MAXP ? TrendRoute::OnePass : TrendRoute::Gemm;
+}
+
+int launch_trend_basis(bq_ctx *c, int d, const double *x, int m, int mp, const TrendBasis &tb,
+                       double *out, long rs, long cs)
+{
+    if (d < 1 || d > BQ_MAXD || m < 0 || mp < m || tb.p != trend_p(tb.degree, d) ||
+        tb.p > BQ_TREND_MAXP)
+        return fail(c, BQ_ERR_BAD_ARG, "trend: a basis of degree %d over %d of %d points", tb.degree,
+                    m, mp);
+    Bracket br(c, BQ_K_REDUCE, 8.0 * BQ_TREND_ROWS * mp);
+    const dim3 grid((unsigned)((mp + 255) / 256));
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(trend_basis_kernel<D>, grid, dim3(256), 0, c->stream, x, m, mp,
+                                        tb, out, rs, cs));
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_trend_sums(bq_ctx *c, const double *G, const double *z, int npad, int p, double *part,
+                      double *sums)
+{
+    if (p < 1 || p > BQ_TREND_MAXP || npad <= 0 || (npad & 63))
+        return fail(c, BQ_ERR_BAD_ARG, "trend: %d basis rows over %d columns", p, npad);
+    const int ne = p * p + p, nsl = npad / 64;
+    Bracket br(c, BQ_K_REDUCE, 8.0 * BQ_TREND_ROWS * npad);
+    hipLaunchKernelGGL(trend_sums_kernel, dim3((unsigned)nsl), dim3(256), 0, c->stream, G, z, p, part);
+    HIPCHK(c, hipGetLastError());
+    launch_fold(c, part, nsl, ne, 1, ne, sums);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_trend_solve(bq_ctx *c, const double *sums, int p, const double *G, const double *z,
+                       int npad, double *tr, double *zt)
+{
+    if (p < 1 || p > BQ_TREND_MAXP || npad <= 0)
+        return fail(c, BQ_ERR_BAD_ARG, "trend: %d basis rows over %d columns", p, npad);
+    Bracket br(c, BQ_K_POTF2, (double)p * p * p / 3.0);
+    hipLaunchKernelGGL(trend_solve_kernel, dim3(1), dim3(256), 0, c->stream, sums, p, G, z, npad, tr,
+                       zt);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_rowdot_trend(bq_ctx *c, const double *V, long ldv, int M, int Mp, int npad,
+                        const double *z, double k0, const double *G, int p, double *mean,
+                        double *var, double *R)
+{
+    if (p < 1 || p > BQ_TREND_ONEPASS_MAXP || M < 1 || Mp < M || (Mp & 15) || !z || !mean || !var)
+        return fail(c, BQ_ERR_BAD_ARG, "trend: %d sums in one pass over %d rows", p, M);
+    Bracket br(c, BQ_K_REDUCE);
+#define BQ_ROWDOT_TREND(NB_)                                                                       \
+    case NB_:                                                                                      \
+        hipLaunchKernelGGL(rowdot_trend_kernel<NB_>, dim3(Mp / 16), dim3(1024), 0, c->stream, V,   \
+                           ldv, M, npad, z, k0, G, mean, var, R, (long)Mp);                        \
+        break
+    switch (p) {
+        BQ_ROWDOT_TREND(1);
+        BQ_ROWDOT_TREND(2);
+        BQ_ROWDOT_TREND(3);
+        BQ_ROWDOT_TREND(4);
+        BQ_ROWDOT_TREND(5);
+        BQ_ROWDOT_TREND(6);
+        BQ_ROWDOT_TREND(7);
+        BQ_ROWDOT_TREND(8);
+    }
+#undef BQ_ROWDOT_TREND
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_trend_finish(bq_ctx *c, const double *R, long ldr, int M, int p, const double *tr,
+                        double *mean, double *var, double *status)
+{
+    if (p < 1 || p > BQ_TREND_MAXP || M < 1)
+        return fail(c, BQ_ERR_BAD_ARG, "trend: %d basis columns at %d points", p, M);
+    Bracket br(c, BQ_K_REDUCE, 8.0 * (double)M * p);
+    hipLaunchKernelGGL(trend_finish_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, c->stream,
+                       R, ldr, M, p, tr, mean, var, status);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int launch_trend_mean(bq_ctx *c, int d, const double *xo, int M, const double *pts, int n,
+                      const double *alpha_t, const GaussParams &g, const TrendBasis &tb,
+                      const double *tr, double *mean, double *status)
+{
+    if (d < 1 || d > BQ_MAXD || M < 1 || tb.p != trend_p(tb.degree, d))
+        return fail(c, BQ_ERR_BAD_ARG, "trend: a basis of degree %d at %d points", tb.degree, M);
+    Bracket br(c, BQ_K_REDUCE);
+    dim3 grid((unsigned)((M + 3) / 4));
+    BQ_DISPATCH_D(d, hipLaunchKernelGGL(trend_mean_kernel<D>, grid, dim3(256), 0, c->stream, xo, M,
+                                        pts, n, alpha_t, g, tb, tr, mean, status));
+    HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
 

@@ -70,6 +70,33 @@ struct HessJob {
 // are used): one 64-row block, the fewest the row sweeps take
 #define BQ_PTHETA_ROWS 64
 
+// The polynomial trend of a fit (trend.h).  The basis: degree 0 .. 2 over t = (x - c) / rho, p
+// columns -- 1; t_1 .. t_d; t_k t_l (k <= l, k outer) -- at most 45 at d = BQ_MAXD.
+struct TrendBasis {
+    int degree, p;
+    double c[BQ_MAXD], rho[BQ_MAXD];
+};
+constexpr int trend_p(int degree, int d)
+{
+    return degree == 0 ? 1 : degree == 1 ? 1 + d : 1 + d + d * (d + 1) / 2;
+}
+// rows of the matrix that holds G = L^-1 H as rows (one 64-row block, like BQ_PTHETA_ROWS)
+#define BQ_TREND_ROWS 64
+#define BQ_TREND_MAXP 45
+// the largest p whose sums v.G_k ride in the row reductions' pass over V (rowdot_trend_kernel)
+#define BQ_TREND_ONEPASS_MAXP 8
+// what trend_solve_kernel leaves on the device, in doubles: the status (0: A factored), log|A|,
+// b^T beta | beta (64, zero from p on) | A^-1 (p x p, ld p) -- so far the head that goes back to
+// the host -- | L_A (p x p, ld p, zero above its diagonal)
+#define BQ_TREND_STATUS 0
+#define BQ_TREND_LOGDET 1
+#define BQ_TREND_BTB 2
+#define BQ_TREND_BETA 8
+#define BQ_TREND_AINV (BQ_TREND_BETA + BQ_TREND_ROWS)
+#define BQ_TREND_HEAD (BQ_TREND_AINV + 2048)
+#define BQ_TREND_LA BQ_TREND_HEAD
+#define BQ_TREND_STATE (BQ_TREND_LA + 2048)
+
 // the sums' places (D = d): [G sums | trace sums | quadratic terms]
 //   G:     S_K, S_k (d), S_kl (k <= l, row by row), S_ss
 //   trace: sum C o C, sum C o Ki, sum Ki o Ki, sum C o B_k (d), sum Ki o B_k (d), sum B_k o B_l^T (k <= l)

@@ -913,6 +913,63 @@ class Fit(object):
                                              L.dptr(var), L.dptr(dmean), L.dptr(dvar)))
         return mean, var, dmean, dvar
 
+    def _trend_key(self, degree, center, scale):
+        """(degree, center, scale, p) of a trend call as the library takes them; what they may be
+        is the library's to check."""
+        degree = int(degree)
+        center = np.ascontiguousarray(np.atleast_1d(center), dtype=np.float64).ravel()
+        scale = np.ascontiguousarray(np.atleast_1d(scale), dtype=np.float64).ravel()
+        if center.shape != (self.d,) or scale.shape != (self.d,):
+            raise ValueError("center and scale must have d entries")
+        if degree not in (0, 1, 2):
+            raise ValueError("trend: degree %d, not 0 .. 2" % degree)
+        p = (1, 1 + self.d, 1 + self.d + self.d * (self.d + 1) // 2)[degree]
+        return degree, center, scale, p
+
+    def trend(self, degree, center, scale):
+        """(beta, cov_beta, logml_t, alpha_t): the polynomial trend of the fit with its
+        coefficients marginalised under a flat prior (bq_gp_trend).  The basis over
+        t = (x - center) / scale: 1; t_1 .. t_d (degree >= 1); t_k t_l, k <= l, k outer (degree
+        2).  beta, (p,): the coefficients' posterior mean; cov_beta, (p, p): their covariance;
+        logml_t: the log marginal likelihood with beta integrated out (its constant is that of
+        the scaled basis); alpha_t, (n,): Kxx^-1 (y - H beta).  ValueError for a bad degree,
+        centre or scale or fewer observations than basis functions, LinAlgError when
+        H^T Kxx^-1 H is not positive definite.  The fit itself stays zero-mean."""
+        degree, center, scale, p = self._trend_key(degree, center, scale)
+        beta, cov, alpha = np.empty(p), np.empty((p, p), order="F"), np.empty(self.n)
+        logml = C.c_double()
+        e = self._eng
+        e._check(e._lib.bq_gp_trend(e._ctx, self._handle(), degree, L.dptr(center), L.dptr(scale),
+                                    L.dptr(beta), L.dptr(cov), C.cast(C.byref(logml), _dp),
+                                    L.dptr(alpha)))
+        return beta, cov, float(logml.value), alpha
+
+    def predict_trend(self, xo, degree, center, scale, want_var=True):
+        """(mean, var) of the trend posterior at the points xo (bq_gp_predict_trend; the basis as
+        in ``trend``): the mean follows the trend away from the data, and var -- latent, like
+        ``predict``'s -- carries the coefficients' uncertainty on top of ``predict``'s.
+        ``want_var=False`` leaves var None and takes the route without a sweep."""
+        xo = _pts(xo)
+        if xo.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        degree, center, scale, _ = self._trend_key(degree, center, scale)
+        M = xo.shape[1]
+        mean = np.empty(M)
+        var = np.empty(M) if want_var else None
+        e = self._eng
+        e._check(e._lib.bq_gp_predict_trend(e._ctx, self._handle(), degree, L.dptr(center),
+                                            L.dptr(scale), L.dptr(xo), M, L.dptr(mean),
+                                            L.dptr(var)))
+        return mean, var
+
+    def trend_last_route(self):
+        """(route, gemm_kernel) of the last ``predict_trend``: 0 the fused mean launch, 1 the
+        one-pass row reductions, 2 the product (bq_gp_trend_last_route)."""
+        r, k = C.c_int(), C.c_int()
+        e = self._eng
+        e._check(e._lib.bq_gp_trend_last_route(e._ctx, self._handle(), C.byref(r), C.byref(k)))
+        return int(r.value), int(k.value)
+
     def sample(self, xo, S=1, z=None, seed=0, ladder=None, want_chol=False):
         """(out, mean, jitter[, chol]): S joint draws of the latent posterior at the points xo,
         on the device (bq_gp_sample).  out: (M, S) Fortran-ordered, column s one draw

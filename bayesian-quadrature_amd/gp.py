@@ -595,6 +595,64 @@ class GP(object):
         g = fit.predict_dtheta(xo, want_var=False)[2][idx]
         return m, v + np.einsum("pj,pq,qj->j", g, Cov, g)
 
+    # -- the polynomial trend, its coefficients marginalised -------------------
+    @staticmethod
+    def _trend_degree(degree):
+        if isinstance(degree, bool) or degree not in (0, 1, 2):
+            raise ValueError("invalid value for degree: %s" % (degree,))
+        return int(degree)
+
+    def _trend_basis(self):
+        """(center, scale) of the trend's basis: the mean of ``x`` and the largest ``|x - center|``
+        (1 where that is 0), so that the scaled points fill [-1, 1]; memoised with the data."""
+        def make():
+            c = float(np.mean(self._x))
+            r = float(np.max(np.abs(self._x - c)))
+            return np.array([c], dtype=DTYPE), np.array([r if r > 0 else 1.0], dtype=DTYPE)
+        return self._memo("trend_basis", make)
+
+    def trend(self, degree=2):
+        """(beta, cov_beta, logml_t, alpha_t): a polynomial trend of ``degree`` 0, 1 or 2 under the
+        GP, ``y = phi(x)^T beta + f(x) + noise`` with a flat prior on beta that is integrated out
+        (universal kriging; engine.Fit.trend, bq_gp_trend).  phi is [1, t, t^2][:degree + 1] in
+        ``t = (x - center) / scale`` with ``_trend_basis``'s centre and scale.  beta: the
+        coefficients' posterior mean; cov_beta: their covariance; logml_t: ``log_lh_trend``;
+        alpha_t: ``Kxx^-1 (y - H beta)``.  A view of the fit, memoised like ``log_lh``:
+        ``mean``, ``var``, ``log_lh`` and everything else stay those of the zero-mean GP."""
+        degree = self._trend_degree(degree)
+        return self._memo(("trend", degree),
+                          lambda: self._device_fit().trend(degree, *self._trend_basis()))
+
+    def log_lh_trend(self, degree=2):
+        """The log marginal likelihood with the trend's coefficients integrated out (Rasmussen &
+        Williams 2.45).  The flat prior leaves its additive constant to the basis: values compare
+        across hyper-parameters of one data set, not across degrees or rescaled data."""
+        return self.trend(degree)[2]
+
+    def mean_trend(self, xo, degree=2):
+        """Posterior mean under the trend (bq_gp_predict_trend, the route without a sweep): away
+        from the data it follows the fitted polynomial where ``mean`` goes back to 0."""
+        degree = self._trend_degree(degree)
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            return np.empty(0, dtype=DTYPE)
+        return self._device_fit().predict_trend(xo, degree, *self._trend_basis(),
+                                                want_var=False)[0]
+
+    def var_trend(self, xo, degree=2):
+        """Posterior variance under the trend: ``var`` plus the uncertainty of the coefficients."""
+        return self.mean_var_trend(xo, degree)[1]
+
+    def mean_var_trend(self, xo, degree=2):
+        """(mean_trend, var_trend) at the points in one device call: the prediction's sweep with
+        the trend's sums in its row reductions (bq_gp_predict_trend)."""
+        degree = self._trend_degree(degree)
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        if xo.size == 0:
+            e = np.empty(0, dtype=DTYPE)
+            return e, e.copy()
+        return self._device_fit().predict_trend(xo, degree, *self._trend_basis(), want_var=True)
+
     def cov(self, xo):
         xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
         if xo.size == 0:

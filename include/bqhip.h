@@ -284,6 +284,57 @@ int bq_gp_predict_grad(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, do
  * call.  At s == 0 the h entry of dmean and the s entries of both are exactly 0. */
 int bq_gp_predict_dtheta(bq_ctx *ctx, bq_fit *fit, const double *xo, int64_t M, double *mean,
                          double *var, double *dmean, double *dvar);
+/* The polynomial trend of a fit, its coefficients marginalised (universal kriging; Rasmussen &
+ * Williams 2.7): y = phi(x)^T beta + f(x) + eps with f the fit's zero-mean GP and a flat prior on
+ * beta, which is integrated out.  A stateless view of the fit like bq_gp_loo or bq_gp_sample: the
+ * fit itself stays zero-mean for every other entry point.
+ * The basis is fixed by degree in {0, 1, 2}, a centre c and a scale rho (d entries each, finite,
+ * rho_k > 0).  With t = (x - c) / rho the columns of phi(x) are, in this order: 1; for degree >= 1
+ * t_1 .. t_d; for degree 2 t_k t_l for k = 1 .. d, l = k .. d (k outer) -- p = 1, 1 + d or
+ * 1 + d + d (d + 1) / 2 of them, at most 45.  Centring and scaling are part of the contract: they
+ * are what keeps H^T Kxx^-1 H well conditioned.
+ * With H (n x p, rows phi(x_i)^T), L L^T = Kxx, z = L^-1 y, G = L^-1 H, A = G^T G, b = G^T z:
+ *   beta     = A^-1 b                                  cov_beta = A^-1
+ *   alpha_t  = Kxx^-1 (y - H beta) = L^-T (z - G beta)   (so that H^T alpha_t = 0)
+ *   logml_t  = -1/2 (|z|^2 - b^T beta) - 1/2 log|Kxx| - 1/2 log|A| - 1/2 (n - p) log 2 pi
+ * logml_t is R&W (2.45) for a flat prior.  Its log|A| term is that of the SCALED basis: an
+ * improper prior leaves an additive constant free, and another (c, rho) of the same degree moves
+ * logml_t by log|det| of the change of basis -- compare values of one basis only.
+ * Host outputs: beta (p), cov_beta (p x p column-major), logml_t (one value), alpha_t (n).  Any
+ * may be NULL, not all four.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG for a degree outside 0 .. 2, a
+ * centre that is not finite, a scale that is not finite and positive, n < p -- all checked before
+ * anything is allocated; BQ_ERR_NOT_PD when a pivot of A is not positive and finite, and then no
+ * output is written.  One row sweep of 64 rows over the resident factor, slices of A and b folded
+ * in a fixed order, one workgroup for the p x p system, one single-vector sweep: O(p n^2).  The
+ * result is kept with the fit for the key (degree, c, rho) until the factor or the targets change;
+ * a call with another key recomputes it.  Device memory (130 npad doubles and the partial sums,
+ * kept with the fit) is allocated before anything is enqueued: BQ_ERR_NOMEM leaves the fit as it
+ * was.  The fit is not disturbed; the same inputs give the same bits on every call, whether or
+ * not the state was there and whatever ran before. */
+int bq_gp_trend(bq_ctx *ctx, bq_fit *fit, int degree, const double *center, const double *scale,
+                double *beta, double *cov_beta, double *logml_t, double *alpha_t);
+/* The posterior of that model at M points xo (d x M column-major like bq_gp_predict).  With
+ * v_j = L^-1 k(x, xo_j) and r_j = phi(xo_j) - G^T v_j:
+ *   mean_j = v_j.z + r_j.beta                    (= k_j^T alpha_t + phi(xo_j)^T beta)
+ *   var_j  = k(x, x) - |v_j|^2 + r_j^T A^-1 r_j  (latent, like bq_gp_predict's var)
+ * -- the last term carries the uncertainty of the coefficients, so var_j >= bq_gp_predict's.
+ * mean and var (M each) may be NULL, not both.  Without var: one fused launch over alpha_t, no
+ * sweep.  With it: the cross Gram and sweep of bq_gp_predict; the p sums v_j.G_k ride in its row
+ * reductions' one pass over V for p <= 8 (v_j.z and |v_j|^2 are then bq_gp_predict's bits), and
+ * are one product more beyond; p^2 flops per point finish.  The state of bq_gp_trend is used when
+ * it is there for this key and computed (and kept) when it is not: either way everything is
+ * enqueued without waiting for the device and read back once, the bits are the same, and nothing
+ * reaches the caller's memory on BQ_ERR_NOT_PD.  Arguments and statuses as bq_gp_trend, and
+ * BQ_ERR_BAD_ARG for M < 0 or mean == var == NULL; M == 0 touches nothing.  Workspaces are
+ * bq_gp_predict's and 64 M doubles, kept with the fit. */
+int bq_gp_predict_trend(bq_ctx *ctx, bq_fit *fit, int degree, const double *center,
+                        const double *scale, const double *xo, int64_t M, double *mean,
+                        double *var);
+/* The route the fit's last bq_gp_predict_trend took (tests): *route = 0 the fused mean launch, 1
+ * the one-pass row reductions, 2 the product (then *gemm_kernel, if given, is the product's
+ * kernel as launch_gemm numbers them; else -1); -1 before the first call. */
+int bq_gp_trend_last_route(bq_ctx *ctx, bq_fit *fit, int *route, int *gemm_kernel);
 /* S joint draws of the latent posterior at M points, on the device: the sweep of bq_gp_predict,
  * Sigma = K(xo, xo) - V V^T (no s^2: the matrix bq_gp_predict returns as cov), its device Cholesky
  * factor and one triangular product:
