@@ -175,6 +175,21 @@ class BQ(object):
         return self.gp_log_l.ivr_design(x_c, q, ref=None if x_r is None else ref,
                                         weights=dens / dens.sum())
 
+    def l_integral(self):
+        """(mean, var): vanilla Bayesian quadrature of the second GP alone, the posterior of
+        ``int l(x) N(x | x_mean, x_var) dx`` under ``gp_l`` (gp.GP.integral).  The mean is
+        ``Z_mean()`` by another route; the variance ignores the uncertainty of the log-GP that
+        ``Z_var`` carries."""
+        self._require_exact()
+        return self.gp_l.integral(self.options["x_mean"], self.options["x_cov"])
+
+    def l_integral_design(self, x_c, q):
+        """The indices of the (at most) ``q`` entries of ``x_c`` whose evaluation lowers the
+        variance of ``l_integral`` the most (gp.GP.integral_design): sequential Bayesian
+        quadrature on ``gp_l``, with no reference points."""
+        self._require_exact()
+        return self.gp_l.integral_design(x_c, q, self.options["x_mean"], self.options["x_cov"])
+
     def log_l_mean_trend(self, x, degree=2):
         """Posterior mean of the log-GP with a polynomial trend of ``degree`` whose coefficients
         are marginalised (gp.GP.mean_trend): the log of a peaked likelihood is close to a

@@ -1827,3 +1827,197 @@ extern "C" int bq_gp_ivr(bq_ctx *c, bq_fit *f, const double *xr, int64_t R, cons
     *rank = r;
     return BQ_OK;
 }
+
+namespace bqh {
+
+// the measure of an integral call as the key of the KMEAN state: [mu d | Sigma d x d], zeros behind,
+// so that two keys compare byte by byte
+static void kmean_key(const bq_fit *f, const double *mu, const double *cov, double *key)
+{
+    std::memset(key, 0, sizeof f->km_key);
+    std::memcpy(key, mu, sizeof(double) * f->d);
+    std::memcpy(key + f->d, cov, sizeof(double) * f->d * f->d);
+}
+
+static bool kmean_current(const bq_fit *f, const double *key)
+{
+    return (f->have & bq_fit::KMEAN) && std::memcmp(f->km_key, key, sizeof f->km_key) == 0;
+}
+
+// every buffer the producer touches, there before its first launch
+static int kmean_alloc(bq_ctx *c, bq_fit *f)
+{
+    BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(f->npad), "wide block inverses"));
+    BQCHK(fit_vec(c, f));
+    BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)f->npad, "contiguous z"));
+    return fit_grow(c, f->kmean, sizeof(double) * (2 * (size_t)f->npad + 32), "kernel mean state");
+}
+
+// The producer of KMEAN, first half: its launches, nothing read back.  kappa_X by int_K_kernel on
+// the resident points (zero on the padding), a copy into the single-vector workspace, which the
+// sweep consumes, b = L^-1 kappa_X by the fit's forward single-vector sweep, and b.b.  The bit is
+// dropped first: the state belongs to no key until fit_kmean has the sum on the host.
+static int kmean_enqueue(bq_ctx *c, bq_fit *f, const double *mu, const double *cov)
+{
+    const int npad = f->npad;
+    double *kap = f->kmean.d(), *b = kap + npad, *scal = b + npad;
+    f->drop(bq_fit::KMEAN);
+    WideInv w;
+    BQCHK(fit_wide(c, f, w));
+    HIPCHK(c, hipMemsetAsync(kap, 0, sizeof(double) * (size_t)npad, c->stream));
+    BQCHK(launch_kernel_mean(c, f->d, f->pts.d(), f->n, f->h, f->w, mu, cov, kap, &f->km_kk));
+    BQCHK(launch_gather_row(c, f->vec.d(), kap, 1, npad));
+    BQCHK(enqueue_forward_vec(c, f->vec.d(), b, f->A.d(), f->ldl, npad, w,
+                              f->vec.d() + 2 * (size_t)npad));
+    return launch_zd_dot(c, b, b, npad, scal);
+}
+
+// ... second half, once the stream is synchronised and b.b is on the host
+static void fit_kmean(bq_fit *f, const double *key, double bb)
+{
+    std::memcpy(f->km_key, key, sizeof f->km_key);
+    f->km_bb = bb;
+    f->have |= bq_fit::KMEAN;
+}
+
+// what the two integral entry points check alike
+static int integral_args(bq_ctx *c, bq_fit *f, const double *mu, const double *cov, double *kk)
+{
+    BQCHK(check_fit(c, f));
+    if (!mu || !cov)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    return launch_kernel_mean(c, f->d, nullptr, 0, f->h, f->w, mu, cov, nullptr, kk);
+}
+
+} // namespace bqh
+
+// The integral of the fit under N(mu, Sigma) (include/bqhip.h has the contract).  Where the KMEAN
+// state is not there for this measure its producer is enqueued in front; then b.z against the
+// current z, for the weights one backward single-vector sweep from a copy of b, and one read-back
+// of the two sums (and the weights).
+extern "C" int bq_gp_integral(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                              double *mean, double *var, double *weights)
+{
+    double kk;
+    BQCHK(integral_args(c, f, mu, cov, &kk));
+    if (!mean && !var && !weights)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    BQCHK(kmean_alloc(c, f));
+    double key[sizeof f->km_key / sizeof(double)];
+    kmean_key(f, mu, cov, key);
+    const bool fresh = !kmean_current(f, key);
+    const int n = f->n, npad = f->npad;
+    double *b = f->kmean.d() + npad, *scal = b + npad;
+    double *hs, *ds;
+    BQCHK(ctx_stage(c, 2, &hs, &ds));
+    BQCHK(with_flow_fallback(c, [&]() -> int {
+        if (fresh)
+            BQCHK(kmean_enqueue(c, f, mu, cov));
+        BQCHK(fit_zc(c, f));
+        BQCHK(launch_zd_dot(c, b, f->wz.d(), npad, scal + 1));
+        if (weights) {
+            WideInv w;
+            BQCHK(fit_wide(c, f, w));
+            BQCHK(launch_gather_row(c, f->vec.d(), b, 1, npad));
+            BQCHK(enqueue_backward_vec(c, f->vec.d(), f->vec.d() + npad, f->A.d(), f->ldl, npad, w,
+                                       f->vec.d() + 2 * (size_t)npad));
+            HIPCHK(c, hipMemcpyAsync(f->hvec, f->vec.d() + npad, sizeof(double) * n,
+                                     hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(hs, scal, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BQ_OK;
+    }));
+    if (fresh)
+        fit_kmean(f, key, hs[0]);
+    if (mean)
+        *mean = hs[1];
+    if (var)
+        *var = f->km_kk - f->km_bb;
+    if (weights)
+        std::memcpy(weights, f->hvec, sizeof(double) * n);
+    return BQ_OK;
+}
+
+// The greedy design that lowers the variance of the integral the most (include/bqhip.h has the
+// contract; zdesign.h the kernels).  bq_gp_predict's staging and sweep with q more columns behind
+// V in f->wV2 -- W = [V | C] is one matrix, ld Ap --, kappa at the staged candidates, V b by one
+// pass over V shaped like a step's product; then the start and the q steps, enqueued
+// one after the other with nothing read back in between.  One download of the workspace's head
+// (with b.b behind it when the KMEAN state was computed on the way) into pinned staging and one
+// synchronise.  Every device buffer is there before the first launch.
+extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                             const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                             int64_t *piv, double *gain, double *zvar0, double *resid_u,
+                             double *resid_c, double *score0, int64_t *rank)
+{
+    double kk;
+    BQCHK(integral_args(c, f, mu, cov, &kk));
+    if (A < 0 || q < 1 || (A && q > A) || A > BQ_PIVCHOL_MAX_M || q > BQ_PIVCHOL_MAX_Q ||
+        !(nugget >= 0.0) || !(tol >= 0.0) || !std::isfinite(nugget) || !std::isfinite(tol) ||
+        !piv || !gain || !zvar0 || !rank || (A && !xc))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    if (A == 0) {
+        BQCHK(bq_gp_integral(c, f, mu, cov, nullptr, zvar0, nullptr));
+        for (int64_t j = 0; j < q; ++j)
+            piv[j] = -1, gain[j] = 0.0;
+        *rank = 0;
+        return BQ_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad, nq = (int)q;
+    const ZdPlan pl = zd_plan((int)A, npad, nq);
+    const int Ap = pl.Ap;
+
+    // ---- every device buffer: the state's, the steps' own, the prediction's with q more columns
+    BQCHK(kmean_alloc(c, f));
+    BQCHK(fit_grow(c, f->zd, sizeof(double) * pl.total, "integral design workspace"));
+    BQCHK(fit_grow(c, f->wV, sizeof(double) * (size_t)Ap * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, f->wV2, sizeof(double) * (size_t)Ap * ((size_t)npad + nq),
+                   "prediction sweep workspace and the candidates' columns"));
+    double *hs, *ds;
+    BQCHK(ctx_stage(c, pl.head + 1, &hs, &ds));
+    double key[sizeof f->km_key / sizeof(double)];
+    kmean_key(f, mu, cov, key);
+    const bool fresh = !kmean_current(f, key);
+    double *b = f->kmean.d() + npad, *scal = b + npad;
+    double *ws = f->zd.d(), *W = f->wV2.d();
+
+    BQCHK(with_flow_fallback(c, [&]() -> int {
+        if (fresh)
+            BQCHK(kmean_enqueue(c, f, mu, cov));
+        // ---- mean | var at io.res, V in the first npad columns of W
+        PosteriorIO io;
+        BQCHK(io.begin(c, f, xc, A, 0, false));
+        BQCHK(predict_sweep(c, f, io));
+        // ---- kappa(xc); V b, u, dc and step 0's pivot; the steps
+        BQCHK(launch_kernel_mean(c, d, io.xq, (int)A, f->h, f->w, mu, cov, ws + pl.o_kap, nullptr));
+        const double thr = tol * kk;
+        BQCHK(launch_zd_start(c, pl, ws, W, b, io.res + Ap, nugget, thr));
+        for (int t = 0; t < nq; ++t)
+            BQCHK(launch_zd_step(c, pl, ws, W, d, io.xq, f->g, t, nugget, thr));
+        // ---- the download
+        HIPCHK(c, hipMemcpyAsync(hs, ws, sizeof(double) * pl.head, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(hs + pl.head, scal, sizeof(double), hipMemcpyDeviceToHost,
+                                 c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BQ_OK;
+    }));
+    if (fresh)
+        fit_kmean(f, key, hs[pl.head]);
+    *zvar0 = f->km_kk - f->km_bb;
+    const int r = reinterpret_cast<const PivcholState *>(hs)->rank;
+    if (r < 0 || r > nq)
+        return fail(c, BQ_ERR_HIP, "zdesign: the device left rank %d of %d steps", r, nq);
+    std::memcpy(gain, hs + pl.o_gain, sizeof(double) * nq);
+    std::memcpy(piv, hs + pl.o_piv, sizeof(int64_t) * nq);
+    if (resid_u)
+        std::memcpy(resid_u, hs + pl.o_u, sizeof(double) * A);
+    if (resid_c)
+        std::memcpy(resid_c, hs + pl.o_dc, sizeof(double) * A);
+    if (score0)
+        std::memcpy(score0, hs + pl.o_score0, sizeof(double) * A);
+    *rank = r;
+    return BQ_OK;
+}

@@ -25,6 +25,7 @@
 //                sample.h kernels               the posterior samples' normals and triangular product
 //                pivchol.h kernels              the pivoted partial Cholesky of a posterior
 //                ivr.h kernels                  designs that minimise the integrated variance
+//                zdesign.h kernels              the integral of a fit, designs that lower its variance
 //                trend.h kernels                the polynomial trend of a fit, marginalised
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
@@ -522,6 +523,24 @@ IvrPlan ivr_plan(int A, int R, bool self, int npad, int q);
 int launch_ivr_init(bq_ctx *c, const IvrPlan &pl, double *ws, const double *var);
 int launch_ivr_step(bq_ctx *c, const IvrPlan &pl, double *ws, double *T, double *W, int d,
                     const double *xc, const GaussParams &g, int t, double nugget, double thr);
+// the integral of a fit and the designs that lower its variance (zdesign.h): A candidates, the Ap
+// rows of the workspace W = [V | C].  The places of the workspace's parts in doubles --
+// [PivcholState | dc[p] + nugget, u_p | gain q | piv q (int64) | dc Ap | u Ap | score0 Ap], the
+// `head` doubles that go back to the host, then taken (Ap ints) | the workgroups' candidates |
+// kappa(xc) Ap | the product's part (nsl x Ap; first V b's slices); a . b over n entries; the start
+// (V: the first npad columns of W; b: npad) and step t
+struct ZdPlan {
+    int A, Ap, npad, q;
+    int rb, ks, nsl, nblk; // pivchol_plan's for Ap rows
+    size_t o_den, o_gain, o_piv, o_dc, o_u, o_score0, head, o_taken, o_candv, o_candi, o_kap,
+        o_part, total;
+};
+ZdPlan zd_plan(int A, int npad, int q);
+int launch_zd_dot(bq_ctx *c, const double *a, const double *b, int n, double *out);
+int launch_zd_start(bq_ctx *c, const ZdPlan &pl, double *ws, const double *W, const double *b,
+                    const double *var, double nugget, double thr);
+int launch_zd_step(bq_ctx *c, const ZdPlan &pl, double *ws, double *W, int d, const double *xc,
+                   const GaussParams &g, int t, double nugget, double thr);
 // the polynomial trend of a fit (trend.h).  The places of the state's parts in doubles, from npad
 // alone: [H, then the sweep's partial sums (64 x npad) | G = L^-1 H as rows (64 x npad) | alpha_t
 // (npad) | the slices' shares of A and b (npad / 64 slices of 64 columns, the largest basis) | A, b
@@ -735,6 +754,15 @@ int enqueue_backward_rows(bq_ctx *c, double *Xin, double *Xout, long ldx, int mr
 int solve_rows_host(bq_ctx *c, const double *L, long ldl, int n, int npad, WideInv w,
                     const double *B, int64_t nrhs, double *X);
 
+// ---- moments.hip ----------------------------------------------------------------------
+// The kernel mean of the measure N(mu, cov) (cov: d x d column-major) under k = h^2 N(. | .,
+// diag(w^2)): out[i] = h^2 N(x_i | mu, diag(w^2) + cov) at the n device points x, d x n, by
+// int_K_kernel on the context's stream (n == 0: no launch), and *kk = h^2 N(0 | 0, diag(w^2) +
+// 2 cov) on the host.  BQ_ERR_BAD_ARG, before anything is enqueued, for a mu or cov that is not
+// finite and for a diag(w^2) + cov or diag(w^2) + 2 cov whose host factor (GaussForm) fails.
+int launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, const double *w,
+                       const double *mu, const double *cov, double *out, double *kk);
+
 // ---- linalg.hip -----------------------------------------------------------------------
 // factor one ntot x ntot device matrix on the context's panel scratch (dinv: BQ_DINV_STRIDE)
 int potrf_one(bq_ctx *c, double *A, long lda, int ntot, double *dinv, int *info);
@@ -854,6 +882,13 @@ struct bq_fit : FitCore {
     //             of the polynomial trend with the key (degree,
     //             c, rho) in tr_key; a call with another key
     //             recomputes it
+    //   KMEAN     kmean: kappa_X = the kernel mean of the measure   WIDE,       fit_kmean
+    //             N(mu, Sigma) at the fit's points, b = L^-1        the key
+    //             kappa_X, b.b; km_kk = the prior variance of the
+    //             integral, with the key (mu, Sigma) in km_key; a
+    //             call with another key recomputes it.  Nothing of
+    //             it depends on the targets: bq_gp_integral's mean
+    //             is one dot product b.z with the current z
     // (z is the targets through the factor.)  A bit is never set while a bit it is computed from is
     // clear: every producer runs the producers of what it reads first, and both events clear a bit
     // together with everything computed from it.
@@ -869,9 +904,11 @@ struct bq_fit : FitCore {
         LOO_GRAD = 1u << 8,
         DKZ = 1u << 9,
         TREND = 1u << 10,
+        KMEAN = 1u << 11,
         // the events: a (re)factorisation, an append, a removal ...
-        FACTOR_CHANGED = DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND,
-        // ... and bq_gp_set_y (the factor's own inverses stay)
+        FACTOR_CHANGED =
+            DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND | KMEAN,
+        // ... and bq_gp_set_y (the factor's own inverses stay, and so does KMEAN)
         TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND,
     };
     unsigned have = 0;
@@ -888,6 +925,15 @@ struct bq_fit : FitCore {
     // designs that minimise the integrated variance (bq_gp_ivr): the steps' workspace (IvrPlan)
     // and T = Sigma(xc, xr), Ap x Rp, grown on demand and kept; the c columns follow V in wV2
     DevBuf ivr, ivrT;
+    // the integral of the fit under a Gaussian measure (bq_gp_integral, bq_gp_zdesign): kappa_X
+    // (npad) | b (npad) | b.b, b.z, allocated on the first call and kept; the measure it was
+    // computed for, [mu d | Sigma d x d] with zeros behind, and the host's share of the state
+    DevBuf kmean;
+    double km_key[BQ_MAXD + BQ_MAXD * BQ_MAXD] = {0};
+    double km_kk = 0, km_bb = 0;
+    // designs that lower the integral's variance (bq_gp_zdesign): the steps' workspace (ZdPlan),
+    // grown on demand and kept; the c columns follow V in wV2
+    DevBuf zd;
     // the log-ML gradient (bq_gp_logml_grad): Y and the sweep's partial sums (npad x npad each),
     // allocated on the first gradient; the product's partials and the d + 2 results
     DevBuf gY, gX, gpart;
@@ -967,7 +1013,7 @@ inline void fit_adopt(bq_fit *f, FitCore &core)
 {
     f->swap(core);
     for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart, &f->hB,
-                      &f->loo, &f->lgo, &f->dkz, &f->wq, &f->trend})
+                      &f->loo, &f->lgo, &f->dkz, &f->wq, &f->trend, &f->kmean})
         b->release();
     if (f->hvec)
         (void)hipHostFree(f->hvec);

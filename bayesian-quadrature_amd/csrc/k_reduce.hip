@@ -2,13 +2,15 @@
 // posterior's gradients at the query points (pgrad.h), the kernels that grow and shrink a
 // resident fit (append.h, remove.h), the posterior samples' normals and triangular product
 // (sample.h), the pivoted partial Cholesky of a posterior (pivchol.h), the designs that minimise
-// the integrated variance (ivr.h), the polynomial trend of a fit (trend.h) and their launchers.
+// the integrated variance (ivr.h), the integral of a fit and the designs that lower its variance
+// (zdesign.h), the polynomial trend of a fit (trend.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "pgrad.h"
 #include "sample.h"
 #include "pivchol.h"
 #include "ivr.h"
+#include "zdesign.h"
 #include "trend.h"
 #include "trsv.h"
 #include "trsvflow.h"
@@ -335,6 +337,125 @@ int launch_ivr_step(bq_ctx *c, const IvrPlan &pl, double *ws, double *T, double 
                                             c->stream, Wc, ldw, K, pl.A, pl.Ap, pl.nblk, wpart, wnsl,
                                             xc, g, nugget, st, ws + pl.o_den, ws + pl.o_dc, taken, cb,
                                             T, pl.Rp, ub, pl.self ? nullptr : ws + pl.o_dr));
+        HIPCHK(c, hipGetLastError());
+    }
+    return BQ_OK;
+}
+
+// ---- the integral of a fit and the designs that lower its variance (zdesign.h; fit.hip,
+// bq_gp_integral, bq_gp_zdesign) ----
+// The shape of q steps over A candidates: the product over the Ap rows of W is pivchol_plan's, and
+// so are the workgroups of the vector kernels.
+ZdPlan zd_plan(int A, int npad, int q)
+{
+    auto granule = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+    ZdPlan pl{};
+    pl.A = A, pl.npad = npad, pl.q = q;
+    pl.Ap = (A + 63) / 64 * 64;
+    const PivcholPlan pw = pivchol_plan(pl.Ap, npad, q);
+    pl.rb = pw.rb, pl.ks = pw.ks, pl.nsl = pw.nsl, pl.nblk = pw.nblk;
+    pl.o_den = granule((sizeof(PivcholState) + 7) / 8);
+    pl.o_gain = pl.o_den + 2;
+    pl.o_piv = pl.o_gain + (size_t)q;
+    pl.o_dc = pl.o_piv + (size_t)q;
+    pl.o_u = pl.o_dc + (size_t)pl.Ap;
+    pl.o_score0 = pl.o_u + (size_t)pl.Ap;
+    pl.head = pl.o_score0 + (size_t)pl.Ap;
+    pl.o_taken = granule(pl.head);
+    pl.o_candv = pl.o_taken + granule(((size_t)pl.Ap + 1) / 2);
+    pl.o_candi = pl.o_candv + granule((size_t)pl.nblk);
+    pl.o_kap = pl.o_candi + granule(((size_t)pl.nblk + 1) / 2);
+    pl.o_part = pl.o_kap + (size_t)pl.Ap;
+    pl.total = pl.o_part + (size_t)pl.nsl * pl.Ap;
+    return pl;
+}
+
+int launch_zd_dot(bq_ctx *c, const double *a, const double *b, int n, double *out)
+{
+    hipLaunchKernelGGL(zd_dot_kernel, dim3(1), dim3(256), 0, c->stream, a, b, n, out);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// V b over the npad columns of V = W (Ap x npad, ld Ap) in the product's slices; dc = var (Ap of
+// them, the sweep's) and u = kappa(xc) - V b (kappa in the workspace already), nothing taken, the
+// state, piv = -1 and gain = 0, step 0's scores; then step 0's pivot
+int launch_zd_start(bq_ctx *c, const ZdPlan &pl, double *ws, const double *W, const double *b,
+                    const double *var, double nugget, double thr)
+{
+    if (pl.A < 1 || pl.q < 1 || pl.npad < 1 || (pl.Ap & 63) || (pl.Ap % pl.rb) ||
+        pl.ks > BQ_PIVCHOL_KS_MAX)
+        return fail(c, BQ_ERR_BAD_ARG, "zdesign: %d steps over %d candidates", pl.q, pl.A);
+    const long ld = pl.Ap;
+    const int nsl0 = (pl.npad + pl.ks - 1) / pl.ks; // <= pl.nsl, the slices of npad + q - 1 columns
+    {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * pl.Ap * pl.npad);
+        const dim3 grid((unsigned)(pl.Ap / pl.rb), (unsigned)nsl0);
+        if (pl.rb == 256)
+            hipLaunchKernelGGL(zd_vb_kernel<256>, grid, dim3(256), 0, c->stream, W, ld, pl.npad,
+                               pl.ks, b, ws + pl.o_part);
+        else
+            hipLaunchKernelGGL(zd_vb_kernel<64>, grid, dim3(64), 0, c->stream, W, ld, pl.npad, pl.ks,
+                               b, ws + pl.o_part);
+        HIPCHK(c, hipGetLastError());
+    }
+    PivcholState *st = reinterpret_cast<PivcholState *>(ws);
+    long long *piv = reinterpret_cast<long long *>(ws + pl.o_piv);
+    int *taken = reinterpret_cast<int *>(ws + pl.o_taken);
+    int *candi = reinterpret_cast<int *>(ws + pl.o_candi);
+    Bracket br(c, BQ_K_REDUCE, 48.0 * pl.Ap);
+    hipLaunchKernelGGL(zd_start_kernel, dim3(pl.nblk), dim3(256), 0, c->stream, var, ws + pl.o_kap,
+                       ws + pl.o_part, ld, nsl0, pl.A, pl.Ap, pl.q, nugget, st, ws + pl.o_den, piv,
+                       ws + pl.o_gain, ws + pl.o_dc, ws + pl.o_u, taken, ws + pl.o_score0,
+                       ws + pl.o_candv, candi);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(zd_pick_kernel, dim3(1), dim3(256), 0, c->stream, st, ws + pl.o_den,
+                       ws + pl.o_candv, candi, pl.nblk, 0, thr, nugget, ws + pl.o_dc, ws + pl.o_u,
+                       piv, ws + pl.o_gain);
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// step t < q: c (column npad + t of W, Ap x (npad + q), ld Ap) with the new dc and u; then, for
+// t + 1 < q, step t + 1's pivot.  xc: the candidates' points; g: the fit's kernel parameters
+int launch_zd_step(bq_ctx *c, const ZdPlan &pl, double *ws, double *W, int d, const double *xc,
+                   const GaussParams &g, int t, double nugget, double thr)
+{
+    if (pl.A < 1 || t < 0 || t >= pl.q || pl.npad < 0 || (pl.Ap & 63) || (pl.Ap % pl.rb) ||
+        pl.ks > BQ_PIVCHOL_KS_MAX)
+        return fail(c, BQ_ERR_BAD_ARG, "zdesign: step %d of %d over %d candidates", t, pl.q, pl.A);
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    PivcholState *st = reinterpret_cast<PivcholState *>(ws);
+    long long *piv = reinterpret_cast<long long *>(ws + pl.o_piv);
+    int *taken = reinterpret_cast<int *>(ws + pl.o_taken);
+    int *candi = reinterpret_cast<int *>(ws + pl.o_candi);
+    double *part = ws + pl.o_part;
+    const int K = pl.npad + t, nsl = (K + pl.ks - 1) / pl.ks;
+    const long ld = pl.Ap;
+    if (nsl > 0) {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * pl.Ap * K);
+        const dim3 grid((unsigned)(pl.Ap / pl.rb), (unsigned)nsl);
+        if (pl.rb == 256)
+            hipLaunchKernelGGL(pivchol_col_kernel<256>, grid, dim3(256), 0, c->stream, W, ld, K,
+                               pl.ks, st, part);
+        else
+            hipLaunchKernelGGL(pivchol_col_kernel<64>, grid, dim3(64), 0, c->stream, W, ld, K, pl.ks,
+                               st, part);
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        Bracket br(c, BQ_K_REDUCE, 8.0 * pl.Ap * (nsl + 5.0));
+        BQ_DISPATCH_D(d, hipLaunchKernelGGL(zd_finish_kernel<D>, dim3(pl.nblk), dim3(256), 0,
+                                            c->stream, W, ld, K, pl.A, pl.Ap, part, nsl, xc, g, nugget,
+                                            st, ws + pl.o_den, ws + pl.o_dc, ws + pl.o_u, taken,
+                                            ws + pl.o_candv, candi));
+        HIPCHK(c, hipGetLastError());
+    }
+    if (t + 1 < pl.q) {
+        hipLaunchKernelGGL(zd_pick_kernel, dim3(1), dim3(256), 0, c->stream, st, ws + pl.o_den,
+                           ws + pl.o_candv, candi, pl.nblk, t + 1, thr, nugget, ws + pl.o_dc,
+                           ws + pl.o_u, piv, ws + pl.o_gain);
         HIPCHK(c, hipGetLastError());
     }
     return BQ_OK;

@@ -250,6 +250,34 @@ int dev_iikk(bq_ctx *c, int d, const double *x_dev, int n, double h1, const doub
 
 } // namespace
 
+// the kernel mean of a Gaussian measure at device points and the prior variance of the integral
+// (host.h; fit.hip, fit_kmean and bq_gp_zdesign)
+int bqh::launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, const double *w,
+                            const double *mu, const double *cov, double *out, double *kk)
+{
+    for (int k = 0; k < d; ++k)
+        if (!std::isfinite(mu[k]))
+            return fail(c, BQ_ERR_BAD_ARG, "the measure's mean must be finite");
+    for (int k = 0; k < d * d; ++k)
+        if (!std::isfinite(cov[k]))
+            return fail(c, BQ_ERR_BAD_ARG, "the measure's covariance must be finite");
+    const Small S = small_from_colmajor(cov, d);
+    const Small C1 = cov_plus_w2(S, w, 1.0);
+    Small L1 = C1, L2 = cov_plus_w2(S, w, 2.0);
+    if (!small_chol(L1) || !small_chol(L2))
+        return fail(c, BQ_ERR_BAD_ARG,
+                    "the measure's covariance plus diag(w^2) is not positive definite");
+    if (kk) {
+        double logdet = 0.0;
+        for (int r = 0; r < d; ++r)
+            logdet += 2.0 * std::log(L2(r, r));
+        *kk = h * h * std::exp(-0.5 * (d * LOG_2PI + logdet));
+    }
+    if (n == 0)
+        return BQ_OK;
+    return dev_int_K(c, d, x, n, mu, C1, h * h, 0.0, out, nullptr, nullptr, nullptr);
+}
+
 // ===========================================================================
 // gauss_c drop-ins: host buffers in and out
 // ===========================================================================

@@ -1075,6 +1075,54 @@ class Fit(object):
         res = (piv[:r], gain[:r], float(ivar0.value), resid_c if xr is None else resid_r, resid_c)
         return res + (score0,) if want_scores else res
 
+    def integral(self, mu, cov, want_weights=False):
+        """(mean, var[, weights]): vanilla Bayesian quadrature of the fit, the posterior mean and
+        variance of Z = int f(x) N(x | mu, cov) dx (bq_gp_integral).  var is latent, like
+        ``predict``'s, and not clamped at 0.  ``want_weights`` appends the quadrature weights
+        Kxx^-1 kappa_X, (n,): mean = weights . y.  The kernel means of the measure at the fit's
+        points stay with the fit: a second call with the same measure is one dot product.
+        ValueError for a measure that is not finite or whose covariance is not positive
+        definite."""
+        e = self._eng
+        mu, cov = e._mc(self.d, mu, cov)
+        mean, var = C.c_double(), C.c_double()
+        wts = np.empty(self.n) if want_weights else None
+        e._check(e._lib.bq_gp_integral(e._ctx, self._handle(), L.dptr(mu), L.dptr(cov),
+                                       C.byref(mean), C.byref(var), L.dptr(wts)))
+        res = (float(mean.value), float(var.value))
+        return res + (wts,) if want_weights else res
+
+    def integral_design(self, xc, q, mu, cov, nugget=0.0, tol=0.0, want_scores=False):
+        """(piv, gain, zvar0, resid_u, resid_c[, score0]): the greedy design that minimises the
+        posterior variance of Z = int f(x) N(x | mu, cov) dx by observing at most q of the
+        candidates xc, on the device (bq_gp_zdesign; sequential Bayesian quadrature).  Each step
+        takes the candidate whose observation (with noise ``nugget`` >= 0, absolute) lowers var Z
+        the most, the lowest index among equals: piv, (rank,) int64; gain, (rank,), the drop each
+        step brought; zvar0 is ``integral``'s var, so that zvar0 - gain.sum() is what is left --
+        with nugget = s^2 the var after ``append`` of the chosen points; resid_u, (A,), the
+        covariances of Z with the latent function at the candidates that are left and resid_c,
+        (A,), the latent variances left there.  ``want_scores`` appends step 0's scores, (A,): the
+        acquisition surface, 0 where a candidate is not eligible.  The run ends early, rank < q,
+        at a gain of at most ``tol`` times the prior variance of Z, or one that is not positive."""
+        xc = _pts(xc)
+        if xc.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        e = self._eng
+        mu, cov = e._mc(self.d, mu, cov)
+        A, q = xc.shape[1], int(q)
+        piv, gain = np.empty(max(q, 0), dtype=np.int64), np.empty(max(q, 0))
+        resid_u, resid_c = np.empty(A), np.empty(A)
+        score0 = np.empty(A) if want_scores else None
+        zvar0, rank = C.c_double(), C.c_int64()
+        e._check(e._lib.bq_gp_zdesign(e._ctx, self._handle(), L.dptr(mu), L.dptr(cov), L.dptr(xc),
+                                      A, q, float(nugget), float(tol),
+                                      piv.ctypes.data_as(L._i64p), L.dptr(gain), C.byref(zvar0),
+                                      L.dptr(resid_u), L.dptr(resid_c), L.dptr(score0),
+                                      C.byref(rank)))
+        r = int(rank.value)
+        res = (piv[:r], gain[:r], float(zvar0.value), resid_u, resid_c)
+        return res + (score0,) if want_scores else res
+
 
 class Pair(object):
     """GP1 over log l at the samples and GP2 over [l_s, exp(mean of GP1 at x_c)] at samples +

@@ -793,6 +793,87 @@ class GP(object):
         out = self._ivr(xo, 1, ref, weights, noisy, 0.0, True)
         return np.empty(0, dtype=DTYPE) if out is None else out[5]
 
+    def _measure(self, mu, cov):
+        """(mu, cov, key): the Gaussian measure of an integral as a (d,) vector and a (d, d)
+        matrix, checked, and its memoisation key."""
+        d = 1 if self._x.ndim == 1 else self._x.shape[0]
+        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=DTYPE)
+        cov = np.ascontiguousarray(np.atleast_2d(cov), dtype=DTYPE)
+        if mu.shape != (d,):
+            raise ValueError("mu has invalid shape")
+        if cov.shape != (d, d):
+            raise ValueError("cov has invalid shape")
+        if not (np.all(np.isfinite(mu)) and np.all(np.isfinite(cov))):
+            raise ValueError("the measure must be finite")
+        return mu, cov, (mu.tobytes(), cov.tobytes())
+
+    def _integral(self, mu, cov):
+        mu, cov, key = self._measure(mu, cov)
+        return self._memo(("integral", key),
+                          lambda: self._device_fit().integral(mu, cov, want_weights=True))
+
+    def integral(self, mu, cov):
+        """(mean, var): vanilla Bayesian quadrature of the GP, the posterior mean and variance of
+        ``Z = int f(x) N(x | mu, cov) dx`` (engine.Fit.integral, bq_gp_integral): for the Gaussian
+        kernel and a Gaussian measure every ingredient is closed form.  ``var`` is latent, like
+        ``var(xo)`` without s^2.  A view of the fit, memoised like ``log_lh``."""
+        return self._integral(mu, cov)[:2]
+
+    def integral_weights(self, mu, cov):
+        """(n,): the quadrature weights ``Kxx^-1 kappa_X`` of ``integral``, whose mean is
+        ``integral_weights . y``."""
+        return self._integral(mu, cov)[2].copy()
+
+    def _zdesign(self, xo, q, mu, cov, noisy, tol, want_scores):
+        """The checked arguments of ``integral_design`` / ``integral_scores`` and the device
+        call; None for empty ``xo``."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        q = int(q)
+        if q < 1:
+            raise ValueError("invalid value for q: %s" % q)
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("invalid value for tol: %s" % tol)
+        if xo.ndim > 2:
+            raise ValueError("points must be a vector or a d x M matrix")
+        mu, cov, _ = self._measure(mu, cov)
+        if xo.size == 0:
+            return None
+        if q > xo.shape[-1]:
+            raise ValueError("q = %d steps over %d points" % (q, xo.shape[-1]))
+        return self._device_fit().integral_design(
+            xo, q, mu, cov, nugget=float(self._s) ** 2 if noisy else 0.0, tol=float(tol),
+            want_scores=want_scores)
+
+    def integral_design(self, xo, q, mu, cov, noisy=True, tol=0.0, return_info=False):
+        """The indices into ``xo`` of a batch of at most ``q`` points to evaluate next, chosen to
+        lower the posterior variance of ``Z = int f(x) N(x | mu, cov) dx`` the most, one point at
+        a time with the points before it counted as observed (sequential Bayesian quadrature) --
+        on the device fit (bq_gp_zdesign).  ``ivr_design`` lowers the variance of the function
+        averaged over reference points that stand for the measure; this lowers the variance of
+        the integral itself and needs no reference points.  ``noisy`` (the default) counts an
+        observation with the noise s^2, as ``append`` would, and a point may then be chosen
+        twice.  Fewer than ``q`` indices come back when a step's gain falls to ``tol`` times the
+        prior variance of Z or is not positive.  ``return_info`` appends {"gain": the drop of
+        var Z each step brought, "zvar0": ``integral``'s var before, "resid": the variance left
+        at ``xo``, "resid_u": the covariance of Z with the function at ``xo`` that is left}.
+        ``xo`` is a vector of points, or d x M as for ``pivoted_cholesky``."""
+        out = self._zdesign(xo, q, mu, cov, noisy, tol, False)
+        if out is None:
+            piv, gain = np.empty(0, dtype=np.int64), np.empty(0, dtype=DTYPE)
+            zvar0 = self.integral(mu, cov)[1]
+            resid_u = resid_c = np.empty(0, dtype=DTYPE)
+        else:
+            piv, gain, zvar0, resid_u, resid_c = out
+        info = {"gain": gain, "zvar0": zvar0, "resid": resid_c, "resid_u": resid_u}
+        return (piv, info) if return_info else piv
+
+    def integral_scores(self, xo, mu, cov, noisy=True):
+        """(M,): how much observing each point of ``xo`` alone would lower the posterior variance
+        of ``Z = int f(x) N(x | mu, cov) dx`` -- the acquisition surface that
+        ``integral_design``'s first step takes the maximum of (arguments as there)."""
+        out = self._zdesign(xo, 1, mu, cov, noisy, 0.0, True)
+        return np.empty(0, dtype=DTYPE) if out is None else out[5]
+
     # -- pickling / copying: only data and parameters travel -------------------
     def __getstate__(self):
         state = {"K": self.K, "x": self._x, "y": self._y, "s": self._s}

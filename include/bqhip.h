@@ -453,6 +453,70 @@ int bq_gp_ivr(bq_ctx *ctx, bq_fit *fit, const double *xr, int64_t R, const doubl
               const double *xc, int64_t A, int64_t q, double nugget, double tol, int64_t *piv,
               double *gain, double *ivar0, double *resid_r, double *resid_c, double *score0,
               int64_t *rank);
+/* Vanilla Bayesian quadrature of a resident fit: the posterior of Z = int f(x) N(x | mu, Sigma) dx
+ * under the fit's GP.  mu: d; cov: Sigma, d x d symmetric positive definite, column-major, as
+ * bq_int_K takes them.  With k = h^2 N(. | ., diag(w^2)), Kxx = K + s^2 I = L L^T, z = L^-1 y,
+ *   kappa(x) = int k(x, x') N(x' | mu, Sigma) dx' = h^2 N(x | mu, diag(w^2) + Sigma)  (bq_int_K),
+ *   kk       = int int k N N                      = h^2 N(0 | 0, diag(w^2) + 2 Sigma),
+ *   kappa_X  = kappa at the fit's points,  b = L^-1 kappa_X:
+ *   *mean   = b . z;
+ *   *var    = kk - b . b: latent, like bq_gp_predict's variance, and like it NOT clamped at 0 -- the
+ *             project's variance reductions subtract and store, so rounding may leave a variance
+ *             of a few ulp of kk below 0;
+ *   weights = L^-T b = Kxx^-1 kappa_X (n doubles): the quadrature weights, mean = weights . y.
+ * Any output may be NULL, but not all three.  kappa_X, b, b.b and kk are kept with the fit for
+ * the measure they were computed for: a call with the same (mu, Sigma) costs one dot product b.z
+ * against the current z (and one single-vector backward sweep for the weights); a call with
+ * another measure recomputes them (int_K_kernel on the resident points, one single-vector
+ * forward sweep, one reduction -- enqueued without waiting, one read-back).  A refit, an append and
+ * a removal discard them; new targets do not, since b does not depend on y.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG for mu or cov == NULL, all three
+ * outputs NULL, a non-finite entry of mu or cov, or a diag(w^2) + Sigma (or + 2 Sigma) that is
+ * not positive definite -- all checked before anything is allocated, and nothing is written. */
+int bq_gp_integral(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov, double *mean,
+                   double *var, double *weights);
+/* The greedy design that minimises the posterior variance of the integral Z of bq_gp_integral
+ * (sequential Bayesian quadrature, Huszar & Duvenaud 2012): which q of A candidates xc (d x A
+ * column-major) to observe so that var Z drops the most, one point at a time.  Every ingredient is
+ * closed form: no reference points stand for the measure.  On the device, after one sweep of
+ * bq_gp_predict over the candidates.  Sigma_c is the latent posterior covariance (no s^2) over xc
+ * with v_a = L^-1 k(x, xc_a) the rows of the sweep's V; nugget >= 0 in absolute units is an
+ * observation's noise; tol >= 0 in multiples of kk, the prior variance of Z.
+ * With dc = diag Sigma_c (bq_gp_predict's variance bits), u_a = kappa(xc_a) - v_a . b =
+ * Cov(Z, f(xc_a) | data) and *zvar0 = bq_gp_integral's var, for t = 0 .. q - 1:
+ *   eligible  a candidate with dc[a] + nugget > 0 that, when nugget == 0, has not been taken;
+ *   score[a] = u_a^2 / (dc[a] + nugget): exactly the drop of var Z when xc_a is observed with noise
+ *             nugget;
+ *   p_t      = the eligible candidate with the largest score, the lowest index among equals; a
+ *             NaN score comes first;
+ *   gain_t   = score[p_t]; the run ends with rank = t unless gain_t > tol kk, is positive and is
+ *             finite;
+ *   den      = sqrt(dc[p] + nugget),
+ *   c        = (K(xc, xc_p) - V V[p]^T - sum_{i<t} c_i c_i[p]) / den;
+ *   u -= c (u_p / den), dc -= c o c (each entry one fma).
+ * nugget == 0: c[p] = den, a taken candidate keeps dc = 0 and u = 0 exactly, has c = 0 from then
+ * on and is never taken twice.  nugget > 0: a candidate may be taken again (two noisy observations
+ * at one place) and nothing is zeroed.  So var Z after t steps is zvar0 - sum_{i<t} gain_i, and
+ * with nugget = s^2 that is the var bq_gp_integral returns after bq_gp_append of the chosen points,
+ * whatever their targets.  Step 0's scores are the acquisition surface.
+ * Outputs on the host: piv (q, -1 from rank on), gain (q, 0 from rank on), zvar0 and rank (one
+ * value each) are required; resid_u (A: u after the last step), resid_c (A: dc) and score0 (A:
+ * step 0's scores, 0 where a candidate is not eligible) may be NULL.
+ * The same inputs give the same bits on every call, and the first j pivots and gains of a q-step
+ * call are bit for bit those of a j-step call.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG as in bq_gp_integral for mu and
+ * cov, and for A < 0, q < 1, q > A (but for A == 0), A > BQ_PIVCHOL_MAX_M, q > BQ_PIVCHOL_MAX_Q, a
+ * negative or non-finite nugget or tol, or piv, gain, zvar0, rank or -- unless A == 0 -- xc ==
+ * NULL: all checked before anything is allocated, and nothing is written.  A == 0 writes
+ * rank = 0, piv = -1, gain = 0 and zvar0 and touches nothing else.  Device memory (the prediction's
+ * workspaces with q more columns, Ap (5 + slices) doubles more; kept with the fit) is allocated
+ * before anything is enqueued: BQ_ERR_NOMEM leaves the fit as it was.  All steps are enqueued
+ * without waiting for the device; nothing reaches the caller's memory unless every kernel has
+ * completed.  The fit is not disturbed; bq_gp_integral's state for (mu, Sigma) is computed on the
+ * way where it is not there. */
+int bq_gp_zdesign(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov, const double *xc,
+                  int64_t A, int64_t q, double nugget, double tol, int64_t *piv, double *gain,
+                  double *zvar0, double *resid_u, double *resid_c, double *score0, int64_t *rank);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
