@@ -91,6 +91,9 @@ SIGNATURES = {
     "bq_gp_integral": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "bq_gp_zdesign": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp,
                                 _dp, _dp, _dp, _i64p]),
+    "bq_gp_sqintegral": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
+    "bq_gp_sqdesign": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp,
+                                 _dp, _dp, _dp, _i64p]),
     "bq_fit_predict": (C.c_int, [_vp, _dp, _dp, _i64, _i64, _dbl, _dp, _dbl, _dp, _i64, _dp, _dp,
                                  _dp]),
     "bq_gp_logml_grid": (C.c_int, [_vp, _dp, _dp, _i64, _i64, _dp, _dp, _dbl, _i64, _dp, _i64]),

@@ -190,6 +190,17 @@ class BQ(object):
         self._require_exact()
         return self.gp_l.integral_design(x_c, q, self.options["x_mean"], self.options["x_cov"])
 
+    def sqrt_bq(self, params, alpha0=None):
+        """A ``wsabi.SqrtBQ`` over the samples ``x_s``, ``l_s`` and this object's prior: square-root-
+        warped Bayesian quadrature (WSABI-L) with one GP of parameters ``params`` = (h, w, s) over
+        sqrt(2 (l - alpha0)), which keeps the approximation of l at or above alpha0 >= 0 without
+        the log-GP, the candidate points and the second GP.  It shares nothing with this object's
+        two GPs and needs no ``init``."""
+        self._require_exact()
+        from .wsabi import SqrtBQ
+        return SqrtBQ(self.x_s, self.l_s, self.options["kernel"](*params[:-1]), params[-1],
+                      self.options["x_mean"], self.options["x_cov"], alpha0=alpha0)
+
     def log_l_mean_trend(self, x, degree=2):
         """Posterior mean of the log-GP with a polynomial trend of ``degree`` whose coefficients
         are marginalised (gp.GP.mean_trend): the log of a peaked likelihood is close to a

@@ -1940,74 +1940,73 @@ extern "C" int bq_gp_integral(bq_ctx *c, bq_fit *f, const double *mu, const doub
     return BQ_OK;
 }
 
-// The greedy design that lowers the variance of the integral the most (include/bqhip.h has the
-// contract; zdesign.h the kernels).  bq_gp_predict's staging and sweep with q more columns behind
-// V in f->wV2 -- W = [V | C] is one matrix, ld Ap --, kappa at the staged candidates, V b by one
-// pass over V shaped like a step's product; then the start and the q steps, enqueued
-// one after the other with nothing read back in between.  One download of the workspace's head
-// (with b.b behind it when the KMEAN state was computed on the way) into pinned staging and one
-// synchronise.  Every device buffer is there before the first launch.
-extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
-                             const double *xc, int64_t A, int64_t q, double nugget, double tol,
-                             int64_t *piv, double *gain, double *zvar0, double *resid_u,
-                             double *resid_c, double *score0, int64_t *rank)
+namespace bqh {
+
+// what the two design entry points check alike, after the measure
+static int zd_args(bq_ctx *c, const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                   const int64_t *piv, const double *gain, const double *zvar0, const int64_t *rank)
 {
-    double kk;
-    BQCHK(integral_args(c, f, mu, cov, &kk));
     if (A < 0 || q < 1 || (A && q > A) || A > BQ_PIVCHOL_MAX_M || q > BQ_PIVCHOL_MAX_Q ||
         !(nugget >= 0.0) || !(tol >= 0.0) || !std::isfinite(nugget) || !std::isfinite(tol) ||
         !piv || !gain || !zvar0 || !rank || (A && !xc))
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
-    if (A == 0) {
-        BQCHK(bq_gp_integral(c, f, mu, cov, nullptr, zvar0, nullptr));
-        for (int64_t j = 0; j < q; ++j)
-            piv[j] = -1, gain[j] = 0.0;
-        *rank = 0;
-        return BQ_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int d = f->d, npad = f->npad, nq = (int)q;
-    const ZdPlan pl = zd_plan((int)A, npad, nq);
-    const int Ap = pl.Ap;
+    return BQ_OK;
+}
 
-    // ---- every device buffer: the state's, the steps' own, the prediction's with q more columns
-    BQCHK(kmean_alloc(c, f));
+// every device buffer of a design's steps: their own, the prediction's with q more columns
+static int zd_alloc(bq_ctx *c, bq_fit *f, const ZdPlan &pl)
+{
+    const size_t Ap = pl.Ap, npad = pl.npad;
     BQCHK(fit_grow(c, f->zd, sizeof(double) * pl.total, "integral design workspace"));
-    BQCHK(fit_grow(c, f->wV, sizeof(double) * (size_t)Ap * npad, "prediction sweep workspace"));
-    BQCHK(fit_grow(c, f->wV2, sizeof(double) * (size_t)Ap * ((size_t)npad + nq),
-                   "prediction sweep workspace and the candidates' columns"));
+    BQCHK(fit_grow(c, f->wV, sizeof(double) * Ap * npad, "prediction sweep workspace"));
+    return fit_grow(c, f->wV2, sizeof(double) * Ap * (npad + pl.q),
+                    "prediction sweep workspace and the candidates' columns");
+}
+
+// The body the designs of a linear functional Z of the fit share (zdesign.h): bq_gp_predict's
+// staging and sweep with q more columns behind V in f->wV2 -- W = [V | C] is one matrix, ld Ap --,
+// kap(xc on the device, out) for Cov(Z, f(xc_a)) a priori, V b by one pass over V shaped like a
+// step's product (b = L^-1 of the functional's kernel means at the fit's points); then the start
+// and the q steps, enqueued one after the other with nothing read back in between.  One download
+// of the workspace's head (with the device word `extra` behind it, if given) into pinned staging,
+// left in *head, and one synchronise.  pre() enqueues what b needs in front.
+template <class Pre, class Kap>
+static int zd_run(bq_ctx *c, bq_fit *f, const ZdPlan &pl, const double *xc, int64_t A,
+                  double nugget, double thr, const double *b, const double *extra, Pre &&pre,
+                  Kap &&kap, double **head)
+{
+    const int d = f->d, nq = pl.q, Ap = pl.Ap;
     double *hs, *ds;
     BQCHK(ctx_stage(c, pl.head + 1, &hs, &ds));
-    double key[sizeof f->km_key / sizeof(double)];
-    kmean_key(f, mu, cov, key);
-    const bool fresh = !kmean_current(f, key);
-    double *b = f->kmean.d() + npad, *scal = b + npad;
     double *ws = f->zd.d(), *W = f->wV2.d();
-
     BQCHK(with_flow_fallback(c, [&]() -> int {
-        if (fresh)
-            BQCHK(kmean_enqueue(c, f, mu, cov));
+        BQCHK(pre());
         // ---- mean | var at io.res, V in the first npad columns of W
         PosteriorIO io;
         BQCHK(io.begin(c, f, xc, A, 0, false));
         BQCHK(predict_sweep(c, f, io));
-        // ---- kappa(xc); V b, u, dc and step 0's pivot; the steps
-        BQCHK(launch_kernel_mean(c, d, io.xq, (int)A, f->h, f->w, mu, cov, ws + pl.o_kap, nullptr));
-        const double thr = tol * kk;
+        // ---- the kernel means at xc; V b, u, dc and step 0's pivot; the steps
+        BQCHK(kap(io.xq, ws + pl.o_kap));
         BQCHK(launch_zd_start(c, pl, ws, W, b, io.res + Ap, nugget, thr));
         for (int t = 0; t < nq; ++t)
             BQCHK(launch_zd_step(c, pl, ws, W, d, io.xq, f->g, t, nugget, thr));
         // ---- the download
         HIPCHK(c, hipMemcpyAsync(hs, ws, sizeof(double) * pl.head, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hs + pl.head, scal, sizeof(double), hipMemcpyDeviceToHost,
-                                 c->stream));
+        if (extra)
+            HIPCHK(c, hipMemcpyAsync(hs + pl.head, extra, sizeof(double), hipMemcpyDeviceToHost,
+                                     c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return BQ_OK;
     }));
-    if (fresh)
-        fit_kmean(f, key, hs[pl.head]);
-    *zvar0 = f->km_kk - f->km_bb;
-    const int r = reinterpret_cast<const PivcholState *>(hs)->rank;
+    *head = hs;
+    return BQ_OK;
+}
+
+// ... and what they hand out of the head
+static int zd_results(bq_ctx *c, const ZdPlan &pl, const double *hs, int64_t A, int64_t *piv,
+                      double *gain, double *resid_u, double *resid_c, double *score0, int64_t *rank)
+{
+    const int nq = pl.q, r = reinterpret_cast<const PivcholState *>(hs)->rank;
     if (r < 0 || r > nq)
         return fail(c, BQ_ERR_HIP, "zdesign: the device left rank %d of %d steps", r, nq);
     std::memcpy(gain, hs + pl.o_gain, sizeof(double) * nq);
@@ -2021,3 +2020,225 @@ extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const doubl
     *rank = r;
     return BQ_OK;
 }
+
+} // namespace bqh
+
+// The greedy design that lowers the variance of the integral the most (include/bqhip.h has the
+// contract; zdesign.h the kernels): zd_run with kappa at the staged candidates and b of the KMEAN
+// state, whose producer is enqueued in front where it is not there for this measure (b.b then
+// rides behind the head).  Every device buffer is there before the first launch.
+extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                             const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                             int64_t *piv, double *gain, double *zvar0, double *resid_u,
+                             double *resid_c, double *score0, int64_t *rank)
+{
+    double kk;
+    BQCHK(integral_args(c, f, mu, cov, &kk));
+    BQCHK(zd_args(c, xc, A, q, nugget, tol, piv, gain, zvar0, rank));
+    if (A == 0) {
+        BQCHK(bq_gp_integral(c, f, mu, cov, nullptr, zvar0, nullptr));
+        for (int64_t j = 0; j < q; ++j)
+            piv[j] = -1, gain[j] = 0.0;
+        *rank = 0;
+        return BQ_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, npad = f->npad;
+    const ZdPlan pl = zd_plan((int)A, npad, (int)q);
+
+    BQCHK(kmean_alloc(c, f));
+    BQCHK(zd_alloc(c, f, pl));
+    double key[sizeof f->km_key / sizeof(double)];
+    kmean_key(f, mu, cov, key);
+    const bool fresh = !kmean_current(f, key);
+    double *b = f->kmean.d() + npad, *scal = b + npad, *hs;
+    BQCHK(zd_run(
+        c, f, pl, xc, A, nugget, tol * kk, b, scal,
+        [&]() -> int { return fresh ? kmean_enqueue(c, f, mu, cov) : BQ_OK; },
+        [&](const double *xq, double *out) -> int {
+            return launch_kernel_mean(c, d, xq, (int)A, f->h, f->w, mu, cov, out, nullptr);
+        },
+        &hs));
+    if (fresh)
+        fit_kmean(f, key, hs[pl.head]);
+    *zvar0 = f->km_kk - f->km_bb;
+    return zd_results(c, pl, hs, A, piv, gain, resid_u, resid_c, score0, rank);
+}
+
+namespace bqh {
+
+// the places of the SQW state's parts and of its producer's scratch in f->sqw, in doubles, from
+// npad and d alone (host.h, bq_fit::sqw, names them); the slices have room for every n <= npad
+struct SqwPlan {
+    size_t o_r, o_b, o_scal, o_tx, o_wt, o_tq, o_wq, o_tmp, o_part, total;
+};
+static SqwPlan sqw_plan(int npad, int d)
+{
+    SqwPlan p{};
+    const size_t np = (size_t)npad;
+    p.o_r = 0, p.o_b = np, p.o_scal = 2 * np;
+    p.o_tx = p.o_scal + 32;
+    p.o_wt = p.o_tx + np * 2 * d;
+    p.o_tq = p.o_wt + np;
+    p.o_wq = p.o_tq + np * d;
+    p.o_tmp = p.o_wq + np;
+    p.o_part = p.o_tmp + np;
+    const size_t tiles = (np + BQ_SQ_TJ - 1) / BQ_SQ_TJ;
+    p.total = p.o_part + std::min<size_t>(tiles, BQ_SQ_MAX_SLICES) * np;
+    return p;
+}
+
+static bool sqw_current(const bq_fit *f, const double *key)
+{
+    return (f->have & bq_fit::SQW) && std::memcmp(f->sq_key, key, sizeof f->sq_key) == 0;
+}
+
+// every buffer the producer touches, there before its first launch
+static int sqw_alloc(bq_ctx *c, bq_fit *f)
+{
+    BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(f->npad), "wide block inverses"));
+    BQCHK(fit_vec(c, f));
+    return fit_grow(c, f->sqw, sizeof(double) * sqw_plan(f->npad, f->d).total,
+                    "square-root-warped quadrature state");
+}
+
+// The producer of SQW: its launches, nothing read back.  The fit's 2 d coordinates with alpha,
+// r = W(X, X) alpha by the pair sum of the fit's points against themselves (zero on the padding),
+// a copy into the single-vector workspace, b_w = L^-1 r by the fit's forward single-vector sweep,
+// b_w.b_w and sq = alpha.r; then the d difference coordinates of Q with alpha n(x) for weights,
+// Q's row sums and qq.  ALPHA is there (the callers run fit_alpha first).  The bit is dropped
+// first: the state belongs to no key until fit_sqw has the sums on the host.
+static int sqw_enqueue(bq_ctx *c, bq_fit *f, const SqForms &fm)
+{
+    const int d = f->d, n = f->n, npad = f->npad;
+    const SqwPlan p = sqw_plan(npad, d);
+    double *st = f->sqw.d(), *scal = st + p.o_scal;
+    f->drop(bq_fit::SQW);
+    WideInv w;
+    BQCHK(fit_wide(c, f, w));
+    BQCHK(launch_sq_xform(c, d, true, f->pts.d(), n, npad, fm, f->alpha.d(), st + p.o_tx,
+                          st + p.o_wt));
+    BQCHK(launch_sq_pair(c, d, true, st + p.o_tx, n, npad, st + p.o_tx, st + p.o_wt, n, fm.cw,
+                         st + p.o_part, st + p.o_r));
+    BQCHK(launch_gather_row(c, f->vec.d(), st + p.o_r, 1, npad));
+    BQCHK(enqueue_forward_vec(c, f->vec.d(), st + p.o_b, f->A.d(), f->ldl, npad, w,
+                              f->vec.d() + 2 * (size_t)npad));
+    BQCHK(launch_zd_dot(c, st + p.o_b, st + p.o_b, npad, scal));
+    BQCHK(launch_zd_dot(c, st + p.o_wt, st + p.o_r, npad, scal + 2));
+    BQCHK(launch_sq_xform(c, d, false, f->pts.d(), n, npad, fm, f->alpha.d(), st + p.o_tq,
+                          st + p.o_wq));
+    BQCHK(launch_sq_pair(c, d, false, st + p.o_tq, n, npad, st + p.o_tq, st + p.o_wq, n, fm.cq,
+                         st + p.o_part, st + p.o_tmp));
+    return launch_zd_dot(c, st + p.o_wq, st + p.o_tmp, npad, scal + 1);
+}
+
+// The SQW state for this key: there already, or its producer and one read-back of the three sums
+static int fit_sqw(bq_ctx *c, bq_fit *f, const SqForms &fm, const double *key)
+{
+    if (sqw_current(f, key))
+        return BQ_OK;
+    BQCHK(fit_alpha(c, f));
+    double *hs, *ds;
+    BQCHK(ctx_stage(c, 3, &hs, &ds));
+    BQCHK(with_flow_fallback(c, [&]() -> int {
+        BQCHK(sqw_enqueue(c, f, fm));
+        HIPCHK(c, hipMemcpyAsync(hs, f->sqw.d() + sqw_plan(f->npad, f->d).o_scal,
+                                 sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BQ_OK;
+    }));
+    std::memcpy(f->sq_key, key, sizeof f->sq_key);
+    f->sq_bb = hs[0], f->sq_qq = hs[1], f->sq_sq = hs[2];
+    f->have |= bq_fit::SQW;
+    return BQ_OK;
+}
+
+// what the two warped entry points check alike: the handle, the measure, its forms
+static int sq_args(bq_ctx *c, bq_fit *f, const double *mu, const double *cov, SqForms *fm)
+{
+    double kk;
+    BQCHK(integral_args(c, f, mu, cov, &kk));
+    return sq_forms(c, f->d, f->h, f->w, mu, cov, fm);
+}
+
+} // namespace bqh
+
+// Square-root-warped quadrature of the fit under N(mu, Sigma) (include/bqhip.h has the contract).
+// Where the SQW state is not there for this measure its producer runs; the outputs are the
+// state's own.
+extern "C" int bq_gp_sqintegral(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                                double *sq, double *var, double *r)
+{
+    SqForms fm;
+    BQCHK(sq_args(c, f, mu, cov, &fm));
+    if (!sq && !var && !r)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    HIPCHK(c, hipSetDevice(c->device));
+    BQCHK(sqw_alloc(c, f));
+    double key[sizeof f->sq_key / sizeof(double)];
+    kmean_key(f, mu, cov, key);
+    BQCHK(fit_sqw(c, f, fm, key));
+    if (r) {
+        HIPCHK(c, hipMemcpyAsync(f->hvec, f->sqw.d() + sqw_plan(f->npad, f->d).o_r,
+                                 sizeof(double) * f->n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::memcpy(r, f->hvec, sizeof(double) * f->n);
+    }
+    if (sq)
+        *sq = f->sq_sq;
+    if (var)
+        *var = f->sq_qq - f->sq_bb;
+    return BQ_OK;
+}
+
+// The greedy design that lowers the variance of the warped integral the most (include/bqhip.h has
+// the contract): zd_run with the pair sum of the staged candidates against the fit's transformed
+// points for the kernel means and b_w of the SQW state, which is computed first where it is not
+// there (qq scales the stop level, so it has to be on the host before the steps are enqueued).
+// Every device buffer is there before the first launch.
+extern "C" int bq_gp_sqdesign(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                              const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                              int64_t *piv, double *gain, double *zvar0, double *resid_u,
+                              double *resid_c, double *score0, int64_t *rank)
+{
+    SqForms fm;
+    BQCHK(sq_args(c, f, mu, cov, &fm));
+    BQCHK(zd_args(c, xc, A, q, nugget, tol, piv, gain, zvar0, rank));
+    if (A == 0) {
+        BQCHK(bq_gp_sqintegral(c, f, mu, cov, nullptr, zvar0, nullptr));
+        for (int64_t j = 0; j < q; ++j)
+            piv[j] = -1, gain[j] = 0.0;
+        *rank = 0;
+        return BQ_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = f->d, n = f->n, npad = f->npad;
+    const ZdPlan pl = zd_plan((int)A, npad, (int)q);
+    const size_t Ap = pl.Ap;
+
+    BQCHK(sqw_alloc(c, f));
+    BQCHK(zd_alloc(c, f, pl));
+    BQCHK(fit_grow(c, f->sqc, sizeof(double) * Ap * (2 * (size_t)d + sq_pair_plan(pl.Ap, n).nsl),
+                   "candidates' coordinates and pair sums"));
+    BQCHK(fit_grow(c, f->wx, sizeof(double) * (size_t)d * A, "prediction points"));
+    BQCHK(fit_grow(c, f->wout, sizeof(double) * 2 * Ap, "prediction results"));
+    BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
+    double key[sizeof f->sq_key / sizeof(double)];
+    kmean_key(f, mu, cov, key);
+    BQCHK(fit_sqw(c, f, fm, key));
+    const SqwPlan sp = sqw_plan(npad, d);
+    const double *st = f->sqw.d();
+    double *tp = f->sqc.d(), *part = tp + Ap * 2 * d, *hs;
+    BQCHK(zd_run(
+        c, f, pl, xc, A, nugget, tol * f->sq_qq, st + sp.o_b, nullptr,
+        []() -> int { return BQ_OK; },
+        [&](const double *xq, double *out) -> int {
+            BQCHK(launch_sq_xform(c, d, true, xq, (int)A, (int)A, fm, nullptr, tp, nullptr));
+            return launch_sq_pair(c, d, true, tp, (int)A, pl.Ap, st + sp.o_tx, st + sp.o_wt, n,
+                                  fm.cw, part, out);
+        },
+        &hs));
+    *zvar0 = f->sq_qq - f->sq_bb;
+    return zd_results(c, pl, hs, A, piv, gain, resid_u, resid_c, score0, rank);
+}
+

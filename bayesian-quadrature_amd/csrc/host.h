@@ -26,6 +26,7 @@
 //                pivchol.h kernels              the pivoted partial Cholesky of a posterior
 //                ivr.h kernels                  designs that minimise the integrated variance
 //                zdesign.h kernels              the integral of a fit, designs that lower its variance
+//                sqwarp.h kernels               the pair sums of square-root-warped quadrature
 //                trend.h kernels                the polynomial trend of a fit, marginalised
 //   potrf.hip    the sweep route (sweep_route), the blocked factorisation's launch sequences
 //                and the bordered pass of plans and fits (no kernels of its own)
@@ -541,6 +542,19 @@ int launch_zd_start(bq_ctx *c, const ZdPlan &pl, double *ws, const double *W, co
                     const double *var, double nugget, double thr);
 int launch_zd_step(bq_ctx *c, const ZdPlan &pl, double *ws, double *W, int d, const double *xc,
                    const GaussParams &g, int t, double nugget, double thr);
+// square-root-warped quadrature of a fit (sqwarp.h): the column slices of a pair sum over ldp
+// stored rows and n columns (js columns each, a multiple of BQ_SQ_TJ) from the shapes alone; a
+// point set's coordinates and weights (`sums`: the 2 d coordinates of W, else the d of Q); and
+// out[a] = scale sum_j pair(tp_a, tx_j) wt_j over R rows (Rp stored, zero from R on), part:
+// nsl x Rp doubles
+struct SqPlan {
+    int nsl, js;
+};
+SqPlan sq_pair_plan(long ldp, int n);
+int launch_sq_xform(bq_ctx *c, int d, bool sums, const double *x, int n, int np, const SqForms &f,
+                    const double *alpha, double *t, double *wt);
+int launch_sq_pair(bq_ctx *c, int d, bool sums, const double *tp, int R, int Rp, const double *tx,
+                   const double *wt, int n, double scale, double *part, double *out);
 // the polynomial trend of a fit (trend.h).  The places of the state's parts in doubles, from npad
 // alone: [H, then the sweep's partial sums (64 x npad) | G = L^-1 H as rows (64 x npad) | alpha_t
 // (npad) | the slices' shares of A and b (npad / 64 slices of 64 columns, the largest basis) | A, b
@@ -762,6 +776,11 @@ int solve_rows_host(bq_ctx *c, const double *L, long ldl, int n, int npad, WideI
 // finite and for a diag(w^2) + cov or diag(w^2) + 2 cov whose host factor (GaussForm) fails.
 int launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, const double *w,
                        const double *mu, const double *cov, double *out, double *kk);
+// the transforms and constants of square-root-warped quadrature (types.h, SqForms) for the kernel
+// (h, w) and the measure N(mu, cov), on the host.  BQ_ERR_BAD_ARG as launch_kernel_mean, and for a
+// diag(w^2) + 2 S, S = (diag(w^-2) + cov^-1)^-1, whose host factor fails.
+int sq_forms(bq_ctx *c, int d, double h, const double *w, const double *mu, const double *cov,
+             SqForms *out);
 
 // ---- linalg.hip -----------------------------------------------------------------------
 // factor one ntot x ntot device matrix on the context's panel scratch (dinv: BQ_DINV_STRIDE)
@@ -889,6 +908,13 @@ struct bq_fit : FitCore {
     //             call with another key recomputes it.  Nothing of
     //             it depends on the targets: bq_gp_integral's mean
     //             is one dot product b.z with the current z
+    //   SQW       sqw: square-root-warped quadrature under the      WIDE, ALPHA, fit_sqw
+    //             measure N(mu, Sigma): r = W(X, X) alpha, b_w =    the key
+    //             L^-1 r, the fit's transformed points with alpha,
+    //             and on the host b_w.b_w, qq = alpha^T Q alpha and
+    //             sq = alpha.r, with the key (mu, Sigma) in sq_key;
+    //             a call with another key recomputes it.  All of
+    //             it depends on the targets
     // (z is the targets through the factor.)  A bit is never set while a bit it is computed from is
     // clear: every producer runs the producers of what it reads first, and both events clear a bit
     // together with everything computed from it.
@@ -905,11 +931,12 @@ struct bq_fit : FitCore {
         DKZ = 1u << 9,
         TREND = 1u << 10,
         KMEAN = 1u << 11,
+        SQW = 1u << 12,
         // the events: a (re)factorisation, an append, a removal ...
         FACTOR_CHANGED =
-            DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND | KMEAN,
+            DW | WIDE | ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND | KMEAN | SQW,
         // ... and bq_gp_set_y (the factor's own inverses stay, and so does KMEAN)
-        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND,
+        TARGETS_CHANGED = ZC | ALPHA | Y | PROD | HESS | LOO | LOO_GRAD | DKZ | TREND | SQW,
     };
     unsigned have = 0;
     void drop(unsigned event) { have &= ~event; }
@@ -934,6 +961,15 @@ struct bq_fit : FitCore {
     // designs that lower the integral's variance (bq_gp_zdesign): the steps' workspace (ZdPlan),
     // grown on demand and kept; the c columns follow V in wV2
     DevBuf zd;
+    // square-root-warped quadrature (bq_gp_sqintegral, bq_gp_sqdesign): the state r (npad) | b_w
+    // (npad) | b_w.b_w, qq, sq (32) | the fit's 2 d coordinates (npad x 2 d) | their weights alpha
+    // (npad), then scratch: the d coordinates of Q | their weights | Q's row sums | the pair sums'
+    // slices -- allocated on the first call and kept; the measure it was computed for and the
+    // host's share of the state; the candidates' coordinates and slices of a design, grown on
+    // demand and kept
+    DevBuf sqw, sqc;
+    double sq_key[BQ_MAXD + BQ_MAXD * BQ_MAXD] = {0};
+    double sq_bb = 0, sq_qq = 0, sq_sq = 0;
     // the log-ML gradient (bq_gp_logml_grad): Y and the sweep's partial sums (npad x npad each),
     // allocated on the first gradient; the product's partials and the d + 2 results
     DevBuf gY, gX, gpart;
@@ -1013,7 +1049,7 @@ inline void fit_adopt(bq_fit *f, FitCore &core)
 {
     f->swap(core);
     for (DevBuf *b : {&f->wide, &f->vec, &f->wV, &f->wV2, &f->wz, &f->gY, &f->gX, &f->gpart, &f->hB,
-                      &f->loo, &f->lgo, &f->dkz, &f->wq, &f->trend, &f->kmean})
+                      &f->loo, &f->lgo, &f->dkz, &f->wq, &f->trend, &f->kmean, &f->sqw})
         b->release();
     if (f->hvec)
         (void)hipHostFree(f->hvec);

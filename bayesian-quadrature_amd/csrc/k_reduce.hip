@@ -3,7 +3,8 @@
 // resident fit (append.h, remove.h), the posterior samples' normals and triangular product
 // (sample.h), the pivoted partial Cholesky of a posterior (pivchol.h), the designs that minimise
 // the integrated variance (ivr.h), the integral of a fit and the designs that lower its variance
-// (zdesign.h), the polynomial trend of a fit (trend.h) and their launchers.
+// (zdesign.h), the pair sums of square-root-warped quadrature (sqwarp.h), the polynomial trend of a
+// fit (trend.h) and their launchers.
 #include "host.h"
 #include "reduce.h"
 #include "pgrad.h"
@@ -11,6 +12,7 @@
 #include "pivchol.h"
 #include "ivr.h"
 #include "zdesign.h"
+#include "sqwarp.h"
 #include "trend.h"
 #include "trsv.h"
 #include "trsvflow.h"
@@ -458,6 +460,87 @@ int launch_zd_step(bq_ctx *c, const ZdPlan &pl, double *ws, double *W, int d, co
                            ws + pl.o_u, piv, ws + pl.o_gain);
         HIPCHK(c, hipGetLastError());
     }
+    return BQ_OK;
+}
+
+// ---- square-root-warped quadrature of a fit (sqwarp.h; fit.hip, bq_gp_sqintegral,
+// bq_gp_sqdesign) ----
+// The column slices of a pair sum of R rows (ldp of them stored) against n columns, from the shapes
+// alone: the row blocks by themselves where they give every CU eight workgroups (2048 of them:
+// the kernel is bound by its arithmetic, and with two workgroups per CU it ran at 0.50-0.64e12
+// pairs a second, LABBOOK), else as many slices of whole tiles as reach that, at most
+// BQ_SQ_MAX_SLICES.
+SqPlan sq_pair_plan(long ldp, int n)
+{
+    SqPlan pl{};
+    const long rblk = (ldp + BQ_SQ_RB - 1) / BQ_SQ_RB;
+    const int tiles = std::max(1, (n + BQ_SQ_TJ - 1) / BQ_SQ_TJ);
+    long want = rblk >= 2048 ? 1 : (2048 + rblk - 1) / std::max(1L, rblk);
+    want = std::min<long>({want, (long)tiles, (long)BQ_SQ_MAX_SLICES});
+    pl.js = (int)((tiles + want - 1) / want) * BQ_SQ_TJ;
+    pl.nsl = std::max(1, (n + pl.js - 1) / pl.js);
+    return pl;
+}
+
+// the coordinates of the n points x (d x n) into t (np x (d or 2 d)) and their weights into wt (np,
+// or NULL): `sums` -- the 2 d coordinates of W with weight alpha; else the d difference
+// coordinates of Q with weight alpha times the point's Gaussian factor.  alpha NULL: weight 1
+int launch_sq_xform(bq_ctx *c, int d, bool sums, const double *x, int n, int np, const SqForms &f,
+                    const double *alpha, double *t, double *wt)
+{
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    if (n < 0 || np < n || np < 1)
+        return fail(c, BQ_ERR_BAD_ARG, "sqwarp: %d points in %d places", n, np);
+    const dim3 grid((unsigned)((np + 255) / 256));
+    BQ_DISPATCH_D(d, {
+        SqXform<D> g{};
+        for (int k = 0; k < D * D; ++k) {
+            g.a1[k] = sums ? f.a1w[k] : f.a1q[k];
+            g.a2[k] = f.a2w[k];
+            g.kl[k] = f.kl[k];
+        }
+        for (int k = 0; k < D; ++k)
+            g.m2[k] = g.km[k] = f.mu[k];
+        g.klogc = f.klogc;
+        if (sums)
+            hipLaunchKernelGGL((sq_xform_kernel<D, D>), grid, dim3(256), 0, c->stream, x, n, np, g,
+                               alpha, t, wt);
+        else
+            hipLaunchKernelGGL((sq_xform_kernel<D, 0>), grid, dim3(256), 0, c->stream, x, n, np, g,
+                               alpha, t, wt);
+    });
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+// out[a] = scale sum_j pair(tp_a, tx_j) wt_j for the R row points (Rp entries of out, zero from R
+// on) against the n column points; part: sq_pair_plan(Rp, n).nsl x Rp doubles
+int launch_sq_pair(bq_ctx *c, int d, bool sums, const double *tp, int R, int Rp, const double *tx,
+                   const double *wt, int n, double scale, double *part, double *out)
+{
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    if (R < 1 || Rp < R || n < 1)
+        return fail(c, BQ_ERR_BAD_ARG, "sqwarp: %d of %d rows against %d columns", R, Rp, n);
+    const SqPlan pl = sq_pair_plan(Rp, n);
+    const long ldp = Rp;
+    {
+        Bracket br(c, BQ_K_REDUCE, (double)R * n);
+        const dim3 grid((unsigned)((Rp + BQ_SQ_RB - 1) / BQ_SQ_RB), (unsigned)pl.nsl);
+        BQ_DISPATCH_D(d, {
+            if (sums)
+                hipLaunchKernelGGL((sq_pair_kernel<D, D>), grid, dim3(BQ_SQ_RB), 0, c->stream, tp, R,
+                                   ldp, tx, wt, n, pl.js, part);
+            else
+                hipLaunchKernelGGL((sq_pair_kernel<D, 0>), grid, dim3(BQ_SQ_RB), 0, c->stream, tp, R,
+                                   ldp, tx, wt, n, pl.js, part);
+        });
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(sq_fold_kernel, dim3((unsigned)((Rp + 255) / 256)), dim3(256), 0, c->stream,
+                       part, ldp, pl.nsl, R, Rp, scale, out);
+    HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
 

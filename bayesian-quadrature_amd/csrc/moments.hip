@@ -278,6 +278,63 @@ int bqh::launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, 
     return dev_int_K(c, d, x, n, mu, C1, h * h, 0.0, out, nullptr, nullptr, nullptr);
 }
 
+// the transforms and constants of square-root-warped quadrature (host.h; types.h, SqForms; fit.hip,
+// bq_gp_sqintegral and bq_gp_sqdesign).  With Lambda = diag(w^2), S = cov:
+//   W(p, q) = h^4 N(p - q | 0, 2 Lambda) N((p + q) / 2 | mu, Lambda / 2 + S)
+//   Q_ij    = h^6 n_i n_j N(G (x_i - x_j) | 0, Lambda + 2 S - 2 G S),  G = S (Lambda + S)^-1,
+//             n = N(x | mu, Lambda + S)          (dev_iikk's algebra with K1 = K2)
+int bqh::sq_forms(bq_ctx *c, int d, double h, const double *w, const double *mu, const double *cov,
+                  SqForms *out)
+{
+    for (int k = 0; k < d; ++k)
+        if (!std::isfinite(mu[k]))
+            return fail(c, BQ_ERR_BAD_ARG, "the measure's mean must be finite");
+    for (int k = 0; k < d * d; ++k)
+        if (!std::isfinite(cov[k]))
+            return fail(c, BQ_ERR_BAD_ARG, "the measure's covariance must be finite");
+    const Small S = small_from_colmajor(cov, d);
+    const Small C1 = cov_plus_w2(S, w, 1.0);
+    Small L1 = C1, L2 = cov_plus_w2(S, w, 2.0), C1inv;
+    for (int k = 0; k < d * d; ++k)
+        L2.a[k] *= 0.5; // Lambda / 2 + S
+    if (!small_chol(L1) || !small_chol(L2) || !small_spd_inv(C1, C1inv))
+        return fail(c, BQ_ERR_BAD_ARG,
+                    "the measure's covariance plus diag(w^2) is not positive definite");
+    const Small G = small_mul(S, C1inv), GS = small_mul(G, S);
+    Small L3;
+    L3.n = d;
+    for (int r = 0; r < d; ++r)
+        for (int q = 0; q < d; ++q)
+            L3(r, q) = (r == q ? w[r] * w[r] : 0.0) + 2.0 * S(r, q) - (GS(r, q) + GS(q, r));
+    if (!small_chol(L3))
+        return fail(c, BQ_ERR_BAD_ARG,
+                    "the measure's covariance gives no positive definite diag(w^2) + 2 (diag(w^-2) "
+                    "+ cov^-1)^-1");
+    const Small Li1 = small_inv_lower(L1), Li2 = small_inv_lower(L2);
+    const Small A3 = small_mul(small_inv_lower(L3), G);
+    SqForms f{};
+    double ld1 = 0.0, ld2 = 0.0, ld3 = 0.0, ldw = 0.0;
+    for (int r = 0; r < d; ++r) {
+        ld1 += 2.0 * std::log(L1(r, r));
+        ld2 += 2.0 * std::log(L2(r, r));
+        ld3 += 2.0 * std::log(L3(r, r));
+        ldw += std::log(2.0 * w[r] * w[r]);
+        f.mu[r] = mu[r];
+        f.a1w[r * d + r] = 1.0 / (std::sqrt(2.0) * w[r]);
+        for (int q = 0; q < d; ++q) {
+            f.a2w[r * d + q] = 0.5 * Li2(r, q);
+            f.kl[r * d + q] = Li1(r, q);
+            f.a1q[r * d + q] = A3(r, q);
+        }
+    }
+    const double h2 = h * h;
+    f.klogc = -0.5 * (d * LOG_2PI + ld1);
+    f.cw = h2 * h2 * std::exp(-0.5 * (d * LOG_2PI + ldw) - 0.5 * (d * LOG_2PI + ld2));
+    f.cq = h2 * h2 * h2 * std::exp(-0.5 * (d * LOG_2PI + ld3));
+    *out = f;
+    return BQ_OK;
+}
+
 // ===========================================================================
 // gauss_c drop-ins: host buffers in and out
 // ===========================================================================

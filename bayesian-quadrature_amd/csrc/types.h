@@ -137,6 +137,30 @@ struct PivcholState {
     double gain;
 };
 
+// Square-root-warped quadrature of a fit (sqwarp.h): what sq_xform_kernel reads of the measure.
+// A point x becomes t = [a1 x | a2 (x - m2)] (a1, a2: D x D, row-major; the second half only for
+// the pair sums that take sums of coordinates), and, where the weight carries the density of a
+// Gaussian form, exp(klogc - |kl (x - km)|^2 / 2) times its weight (kl lower triangular).
+template <int D>
+struct SqXform {
+    double a1[D * D], a2[D * D], m2[D];
+    double kl[D * D], km[D], klogc;
+};
+// ... and the same for every d, as the host computes it from (h, w, mu, Sigma) (moments.hip,
+// sq_forms): the two transforms with the constants in front of their pair sums,
+//   W(p, q) = cw exp(-|t1(p) - t1(q)|^2 / 2 - |t2(p) + t2(q)|^2 / 2),
+//   Q_ij    = cq n_i n_j exp(-|tq(x_i) - tq(x_j)|^2 / 2),  n = exp(klogc - |kl (x - mu)|^2 / 2)
+struct SqForms {
+    double a1w[BQ_MAXD * BQ_MAXD], a2w[BQ_MAXD * BQ_MAXD], cw;
+    double a1q[BQ_MAXD * BQ_MAXD], kl[BQ_MAXD * BQ_MAXD], klogc, cq;
+    double mu[BQ_MAXD];
+};
+// the pair sums' tile: columns staged through LDS at a time, and the granule of a column slice;
+// rows per workgroup; the most slices
+#define BQ_SQ_TJ 128
+#define BQ_SQ_RB 256
+#define BQ_SQ_MAX_SLICES 64
+
 // Removing k observations from a resident fit (remove.h): what remove_compact_kernel reads of the
 // old fit and writes into buffers of the new layout.
 #define BQ_REMOVE_M_DOUBLES (128 * 128) // the 128 x 128 transform of one block column (scratch)

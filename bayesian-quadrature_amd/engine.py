@@ -1123,6 +1123,51 @@ class Fit(object):
         res = (piv[:r], gain[:r], float(zvar0.value), resid_u, resid_c)
         return res + (score0,) if want_scores else res
 
+    def sq_integral(self, mu, cov, want_r=False):
+        """(sq, var[, r]): square-root-warped Bayesian quadrature of the fit (WSABI-L,
+        bq_gp_sqintegral).  The fit's targets are g = sqrt(2 (l - alpha0)) of an integrand
+        l >= alpha0, and l = alpha0 + g^2 / 2 is linearised about the posterior mean m of g:
+        sq = int m(x)^2 N(x | mu, cov) dx, so that the integral of l has mean alpha0 + sq / 2, and
+        var is its variance, latent and not clamped at 0.  ``want_r`` appends r = W(X, X) alpha,
+        (n,), the kernel means of the linearised integral at the fit's points (sq = alpha . r).
+        The state stays with the fit per measure until its targets or its factor change.
+        ValueError for a measure that is not finite or whose covariance is not positive
+        definite."""
+        e = self._eng
+        mu, cov = e._mc(self.d, mu, cov)
+        sq, var = C.c_double(), C.c_double()
+        r = np.empty(self.n) if want_r else None
+        e._check(e._lib.bq_gp_sqintegral(e._ctx, self._handle(), L.dptr(mu), L.dptr(cov),
+                                         C.byref(sq), C.byref(var), L.dptr(r)))
+        res = (float(sq.value), float(var.value))
+        return res + (r,) if want_r else res
+
+    def sq_integral_design(self, xc, q, mu, cov, nugget=0.0, tol=0.0, want_scores=False):
+        """(piv, gain, zvar0, resid_u, resid_c[, score0]): ``integral_design`` for the
+        square-root-warped integral of ``sq_integral`` (bq_gp_sqdesign): each step takes the
+        candidate whose observation (of g, with noise ``nugget``) lowers the variance of the
+        linearised integral the most with the posterior mean held at its current value.  zvar0 is
+        ``sq_integral``'s var; ``tol`` is in multiples of the prior variance of that integral.
+        Everything else is as in ``integral_design``."""
+        xc = _pts(xc)
+        if xc.shape[0] != self.d:
+            raise ValueError("dimension mismatch")
+        e = self._eng
+        mu, cov = e._mc(self.d, mu, cov)
+        A, q = xc.shape[1], int(q)
+        piv, gain = np.empty(max(q, 0), dtype=np.int64), np.empty(max(q, 0))
+        resid_u, resid_c = np.empty(A), np.empty(A)
+        score0 = np.empty(A) if want_scores else None
+        zvar0, rank = C.c_double(), C.c_int64()
+        e._check(e._lib.bq_gp_sqdesign(e._ctx, self._handle(), L.dptr(mu), L.dptr(cov), L.dptr(xc),
+                                       A, q, float(nugget), float(tol),
+                                       piv.ctypes.data_as(L._i64p), L.dptr(gain), C.byref(zvar0),
+                                       L.dptr(resid_u), L.dptr(resid_c), L.dptr(score0),
+                                       C.byref(rank)))
+        r = int(rank.value)
+        res = (piv[:r], gain[:r], float(zvar0.value), resid_u, resid_c)
+        return res + (score0,) if want_scores else res
+
 
 class Pair(object):
     """GP1 over log l at the samples and GP2 over [l_s, exp(mean of GP1 at x_c)] at samples +

@@ -874,6 +874,58 @@ class GP(object):
         out = self._zdesign(xo, 1, mu, cov, noisy, 0.0, True)
         return np.empty(0, dtype=DTYPE) if out is None else out[5]
 
+    def sq_integral(self, mu, cov):
+        """(sq, var): square-root-warped Bayesian quadrature of the GP (WSABI-L; engine.Fit.
+        sq_integral, bq_gp_sqintegral).  With the GP's targets g = sqrt(2 (l - alpha0)) of an
+        integrand l >= alpha0 and l = alpha0 + g^2 / 2 linearised about the posterior mean m,
+        ``sq = int m(x)^2 N(x | mu, cov) dx`` -- the integral of l has mean alpha0 + sq / 2 -- and
+        ``var`` is its variance, latent like ``integral``'s.  ``wsabi.SqrtBQ`` keeps alpha0.  A view
+        of the fit, memoised like ``integral``."""
+        mu, cov, key = self._measure(mu, cov)
+        return self._memo(("sq_integral", key), lambda: self._device_fit().sq_integral(mu, cov))
+
+    def _sqdesign(self, xo, q, mu, cov, noisy, tol, want_scores):
+        """``_zdesign`` for the warped integral."""
+        xo = np.atleast_1d(np.asarray(xo, dtype=DTYPE))
+        q = int(q)
+        if q < 1:
+            raise ValueError("invalid value for q: %s" % q)
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError("invalid value for tol: %s" % tol)
+        if xo.ndim > 2:
+            raise ValueError("points must be a vector or a d x M matrix")
+        mu, cov, _ = self._measure(mu, cov)
+        if xo.size == 0:
+            return None
+        if q > xo.shape[-1]:
+            raise ValueError("q = %d steps over %d points" % (q, xo.shape[-1]))
+        return self._device_fit().sq_integral_design(
+            xo, q, mu, cov, nugget=float(self._s) ** 2 if noisy else 0.0, tol=float(tol),
+            want_scores=want_scores)
+
+    def sq_integral_design(self, xo, q, mu, cov, noisy=True, tol=0.0, return_info=False):
+        """``integral_design`` for the square-root-warped integral of ``sq_integral``: the indices
+        into ``xo`` of at most ``q`` points whose observation lowers the variance of the
+        linearised integral the most, one at a time, with the posterior mean about which the
+        integrand is linearised held at its current value (bq_gp_sqdesign).  ``tol`` is in
+        multiples of the prior variance of that integral; ``return_info`` appends {"gain",
+        "zvar0": ``sq_integral``'s var before, "resid", "resid_u"} as ``integral_design`` does."""
+        out = self._sqdesign(xo, q, mu, cov, noisy, tol, False)
+        if out is None:
+            piv, gain = np.empty(0, dtype=np.int64), np.empty(0, dtype=DTYPE)
+            zvar0 = self.sq_integral(mu, cov)[1]
+            resid_u = resid_c = np.empty(0, dtype=DTYPE)
+        else:
+            piv, gain, zvar0, resid_u, resid_c = out
+        info = {"gain": gain, "zvar0": zvar0, "resid": resid_c, "resid_u": resid_u}
+        return (piv, info) if return_info else piv
+
+    def sq_integral_scores(self, xo, mu, cov, noisy=True):
+        """(M,): how much observing each point of ``xo`` alone would lower the variance of the
+        square-root-warped integral -- step 0's surface of ``sq_integral_design``."""
+        out = self._sqdesign(xo, 1, mu, cov, noisy, 0.0, True)
+        return np.empty(0, dtype=DTYPE) if out is None else out[5]
+
     # -- pickling / copying: only data and parameters travel -------------------
     def __getstate__(self):
         state = {"K": self.K, "x": self._x, "y": self._y, "s": self._s}

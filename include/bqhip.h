@@ -517,6 +517,85 @@ int bq_gp_integral(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov
 int bq_gp_zdesign(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov, const double *xc,
                   int64_t A, int64_t q, double nugget, double tol, int64_t *piv, double *gain,
                   double *zvar0, double *resid_u, double *resid_c, double *score0, int64_t *rank);
+/* Square-root-warped Bayesian quadrature of a resident fit (WSABI-L, Gunter et al. 2014) for an
+ * integrand l >= alpha0: the fit's targets are g = sqrt(2 (l - alpha0)), one zero-mean GP, and
+ * l = alpha0 + g^2 / 2 is linearised about the posterior mean m(x) = k(x, X) alpha, alpha =
+ * Kxx^-1 y.  Then l is a GP again with mean alpha0 + m^2 / 2 >= alpha0 and covariance m(x)
+ * Sigma(x, x') m(x'), and int l N(. | mu, Sigma) has mean alpha0 + sq / 2 and the variance of
+ * Z = int m(x) g(x) N(x | mu, Sigma) dx -- closed form for this kernel, no candidate points and no
+ * second GP.  mu, cov as bq_gp_integral takes them.  With Lambda = diag(w^2), Kxx = L L^T,
+ *   W(p, q) = int k(p, t) k(t, q) N(t | mu, Sigma) dt
+ *           = h^4 N(p - q | 0, 2 Lambda) N((p + q) / 2 | mu, Lambda / 2 + Sigma),
+ *   r       = W(X, X) alpha                       (n entries: the kernel means of Z at the fit),
+ *   b_w     = L^-1 r,
+ *   kappa_i = h^2 N(x_i | mu, Lambda + Sigma),  S = (Lambda^-1 + Sigma^-1)^-1,
+ *   Q_ij    = h^2 kappa_i kappa_j N(S Lambda^-1 (x_i - x_j) | 0, Lambda + 2 S)
+ *                                                  (bq_int_int_K1_K2_K1 with K1 = K2),
+ *   qq      = alpha^T Q alpha                     (the prior variance of Z):
+ *   *sq  = alpha . r = int m^2 N: the caller's mean is alpha0 + *sq / 2;
+ *   *var = qq - b_w . b_w: latent and NOT clamped at 0, like bq_gp_integral's;
+ *   r    = the n kernel means above.
+ * Any output may be NULL, but not all three.  The sums over pairs of points run on the device
+ * over points transformed once to t1 = x / (sqrt 2 w), t2 = Linv (x - mu) / 2 (Linv^T Linv =
+ * (Lambda / 2 + Sigma)^-1), a pair being exp(-|t1(p) - t1(q)|^2 / 2 - |t2(p) + t2(q)|^2 / 2): one
+ * thread per row point, the columns in fixed slices that are added in ascending order, no
+ * floating-point atomics -- the same inputs give the same bits on every call.  r, b_w, b_w . b_w,
+ * qq and sq are kept with the fit for the measure they were computed for: a call with the same
+ * (mu, Sigma) computes nothing; a call with another measure recomputes them (two pair sums over
+ * n x n, one single-vector forward sweep, three reductions -- enqueued without waiting, one
+ * read-back).  Unlike bq_gp_integral's state this one depends on the targets: bq_gp_set_y
+ * discards it, as do a refit, an append and a removal.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG for mu or cov == NULL, all three
+ * outputs NULL, a non-finite entry of mu or cov, or a diag(w^2) + Sigma, diag(w^2) + 2 Sigma or
+ * diag(w^2) + 2 S that is not positive definite -- all checked before anything is allocated, and
+ * nothing is written. */
+int bq_gp_sqintegral(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov, double *sq,
+                     double *var, double *r);
+/* The greedy design that minimises the posterior variance of Z of bq_gp_sqintegral: which q of A
+ * candidates xc (d x A column-major) to observe so that the variance of the warped integral drops
+ * the most, one point at a time.  The recurrence, its kernels and its bits per step are
+ * bq_gp_zdesign's; what differs is the linear functional it serves.  Sigma_c is the latent
+ * posterior covariance (no s^2) over xc with v_a = L^-1 k(x, xc_a) the rows of the sweep's V;
+ * nugget >= 0 in absolute units is an observation's noise (of g); tol >= 0 in multiples of qq, the
+ * prior variance of Z.
+ * With dc = diag Sigma_c (bq_gp_predict's variance bits), u_a = sum_j W(xc_a, x_j) alpha_j -
+ * v_a . b_w = Cov(Z, g(xc_a) | data) and *zvar0 = bq_gp_sqintegral's var, for t = 0 .. q - 1:
+ *   eligible  a candidate with dc[a] + nugget > 0 that, when nugget == 0, has not been taken;
+ *   score[a] = u_a^2 / (dc[a] + nugget): exactly the drop of var Z when g(xc_a) is observed with
+ *             noise nugget and the posterior mean m, about which l is linearised, is held at its
+ *             current value -- which is what happens when the observation equals the prediction;
+ *   p_t      = the eligible candidate with the largest score, the lowest index among equals; a
+ *             NaN score comes first;
+ *   gain_t   = score[p_t]; the run ends with rank = t unless gain_t > tol qq, is positive and is
+ *             finite;
+ *   den      = sqrt(dc[p] + nugget),
+ *   c        = (K(xc, xc_p) - V V[p]^T - sum_{i<t} c_i c_i[p]) / den;
+ *   u -= c (u_p / den), dc -= c o c (each entry one fma).
+ * nugget == 0: c[p] = den, a taken candidate keeps dc = 0 and u = 0 exactly, has c = 0 from then
+ * on and is never taken twice.  nugget > 0: a candidate may be taken again and nothing is zeroed.
+ * So var Z after t steps is zvar0 - sum_{i<t} gain_i, and with nugget = s^2 that is the var
+ * bq_gp_sqintegral returns after bq_gp_append of the chosen points with targets equal to the
+ * posterior mean there (other targets move m and with it the functional).  Step 0's scores are the
+ * acquisition surface.
+ * Outputs on the host: piv (q, -1 from rank on), gain (q, 0 from rank on), zvar0 and rank (one
+ * value each) are required; resid_u (A: u after the last step), resid_c (A: dc) and score0 (A:
+ * step 0's scores, 0 where a candidate is not eligible) may be NULL.
+ * The same inputs give the same bits on every call, and the first j pivots and gains of a q-step
+ * call are bit for bit those of a j-step call.
+ * Status rules of bq_gp_predict for the handle; BQ_ERR_BAD_ARG as in bq_gp_sqintegral for mu and
+ * cov, and for A < 0, q < 1, q > A (but for A == 0), A > BQ_PIVCHOL_MAX_M, q > BQ_PIVCHOL_MAX_Q, a
+ * negative or non-finite nugget or tol, or piv, gain, zvar0, rank or -- unless A == 0 -- xc ==
+ * NULL: all checked before anything is allocated, and nothing is written.  A == 0 writes
+ * rank = 0, piv = -1, gain = 0 and zvar0 and touches nothing else.  Device memory (bq_gp_zdesign's,
+ * which this call shares, and Ap (2 d + slices) doubles for the candidates' coordinates and pair
+ * sums; kept with the fit) is allocated before anything is enqueued: BQ_ERR_NOMEM leaves the fit as
+ * it was.  bq_gp_sqintegral's state for (mu, Sigma) is computed first where it is not there, with
+ * its one read-back: qq scales the stop level.  After that all steps are enqueued without waiting
+ * for the device; nothing reaches the caller's memory unless every kernel has completed.  The fit
+ * is not disturbed, and bq_gp_zdesign's results on it are bit for bit what they were. */
+int bq_gp_sqdesign(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov, const double *xc,
+                   int64_t A, int64_t q, double nugget, double tol, int64_t *piv, double *gain,
+                   double *zvar0, double *resid_u, double *resid_c, double *score0, int64_t *rank);
 
 /* One pass "fit + posterior + log-ML" of ONE problem without keeping a fit
  * object: the bordered-Cholesky pipeline.  Host in / host out. */
