@@ -133,6 +133,25 @@ Small cov_plus_w2(const Small &cov, const double *w, double cscale)
     return m;
 }
 
+// The conditional covariance S - S (W + S)^-1 S, W = diag(w^2), from WSinv = (W + S)^-1, as
+// W - W (W + S)^-1 W, symmetrised.  The two are equal; the first loses cov / w^2 of its digits
+// where the measure is wide against the length scales (both terms are about S, the result about
+// W), the second loses none there (W alone is about the result) and none where S is small.
+Small cond_cov(const double *w, const Small &WSinv)
+{
+    const int d = WSinv.n;
+    Small t;
+    t.n = d;
+    for (int r = 0; r < d; ++r)
+        for (int c = 0; c <= r; ++c) {
+            const double wr = w[r] * w[r], wc = w[c] * w[c];
+            const double v = (r == c ? wr : 0.0) -
+                             0.5 * ((wr * WSinv(r, c)) * wc + (wc * WSinv(c, r)) * wr);
+            t(r, c) = t(c, r) = v;
+        }
+    return t;
+}
+
 int check_int_args(bq_ctx *c, int64_t d, const double *w, const double *mu, const double *cov)
 {
     if (!c)
@@ -176,28 +195,52 @@ int dev_int_K1_K2(bq_ctx *c, int d, const double *x1_dev, int n1, const double *
                   const double *w1, const double *w2, const double *mu, const Small &cov,
                   double scale, double *out_dev, const double *alpha_dev, double *beta_dev)
 {
-    Small C2;
-    C2.n = 2 * d;
-    double mu2[MAXF];
+    // The factor of C2 by blocks: L11 = chol(S + W1), L21 = S L11^-T, L22 = chol of the Schur
+    // complement S + W2 - S (S + W1)^-1 S = W2 + cond_cov(W1) -- taken from C2's entries, as a
+    // Cholesky sweep over all of C2 takes it, it cancels for a measure wide against w1.
+    Small L11 = cov_plus_w2(cov, w1, 1.0), W1Sinv;
+    if (!small_chol(L11))
+        return fail(c, BQ_ERR_NOT_PD, "matrix is not positive definite");
+    const Small Li11 = small_inv_lower(L11);
+    W1Sinv.n = d;
+    for (int r = 0; r < d; ++r)
+        for (int q = 0; q < d; ++q) {
+            double t = 0.0;
+            for (int k = 0; k < d; ++k)
+                t += Li11(k, r) * Li11(k, q);
+            W1Sinv(r, q) = t;
+        }
+    Small L22 = cond_cov(w1, W1Sinv);
+    for (int r = 0; r < d; ++r)
+        L22(r, r) += w2[r] * w2[r];
+    if (!small_chol(L22))
+        return fail(c, BQ_ERR_NOT_PD, "matrix is not positive definite");
+    const Small Li22 = small_inv_lower(L22);
+    // L^-1 = [[L11^-1, 0], [-L22^-1 L21 L11^-1, L22^-1]],  L21 L11^-1 = S (S + W1)^-1
+    const Small B = small_mul(Li22, small_mul(cov, W1Sinv));
+    Small Linv;
+    Linv.n = 2 * d;
+    double mu2[MAXF], logdet = 0.0;
     for (int r = 0; r < d; ++r) {
         mu2[r] = mu2[r + d] = mu[r];
+        logdet += 2.0 * (std::log(L11(r, r)) + std::log(L22(r, r)));
         for (int q = 0; q < d; ++q) {
-            C2(r, q) = cov(r, q) + (r == q ? w1[r] * w1[r] : 0.0);
-            C2(r + d, q + d) = cov(r, q) + (r == q ? w2[r] * w2[r] : 0.0);
-            C2(r, q + d) = cov(r, q);
-            C2(r + d, q) = cov(r, q);
+            Linv(r, q) = Li11(r, q);
+            Linv(r + d, q) = -B(r, q);
+            Linv(r + d, q + d) = Li22(r, q);
         }
     }
-    bool ok = true;
     BQ_DISPATCH_D(d, {
         GaussForm<2 * D> f;
-        ok = fill_form<2 * D>(f, mu2, C2);
-        if (ok)
-            hipLaunchKernelGGL(int_K1_K2_kernel<D>, dim3((n1 + 63) / 64), dim3(256), 0, c->stream,
-                               x1_dev, n1, x2_dev, n2, f, scale, out_dev, alpha_dev, beta_dev);
+        for (int r = 0; r < 2 * D; ++r) {
+            f.mu[r] = mu2[r];
+            for (int q = 0; q < 2 * D; ++q)
+                f.linv[r * 2 * D + q] = Linv(r, q);
+        }
+        f.logc = -0.5 * (2 * D * LOG_2PI + logdet);
+        hipLaunchKernelGGL(int_K1_K2_kernel<D>, dim3((n1 + 63) / 64), dim3(256), 0, c->stream,
+                           x1_dev, n1, x2_dev, n2, f, scale, out_dev, alpha_dev, beta_dev);
     });
-    if (!ok)
-        return fail(c, BQ_ERR_NOT_PD, "matrix is not positive definite");
     HIPCHK(c, hipGetLastError());
     return BQ_OK;
 }
@@ -213,12 +256,12 @@ int dev_iikk(bq_ctx *c, int d, const double *x_dev, int n, double h1, const doub
     if (!small_spd_inv(W1S, W1Sinv))
         return fail(c, BQ_ERR_NOT_PD, "matrix is not positive definite");
     const Small G = small_mul(cov, W1Sinv); // S (W1 + S)^-1
-    const Small A = small_mul(G, cov);
+    const Small T = cond_cov(w1, W1Sinv);   // S - G S
     Small Cm;
     Cm.n = d;
     for (int r = 0; r < d; ++r)
         for (int q = 0; q < d; ++q)
-            Cm(r, q) = (r == q ? w2[r] * w2[r] : 0.0) + 2.0 * cov(r, q) - 2.0 * A(r, q);
+            Cm(r, q) = (r == q ? w2[r] * w2[r] : 0.0) + 2.0 * T(r, q);
     double *b_dev = work_dev, *n1_dev = work_dev + (size_t)d * n;
     const double scale = (h1 * h1) * (h1 * h1) * (h2 * h2);
     const int gx = (n + 63) / 64, gy = (n + 255) / 256;
@@ -300,12 +343,12 @@ int bqh::sq_forms(bq_ctx *c, int d, double h, const double *w, const double *mu,
     if (!small_chol(L1) || !small_chol(L2) || !small_spd_inv(C1, C1inv))
         return fail(c, BQ_ERR_BAD_ARG,
                     "the measure's covariance plus diag(w^2) is not positive definite");
-    const Small G = small_mul(S, C1inv), GS = small_mul(G, S);
+    const Small G = small_mul(S, C1inv), T = cond_cov(w, C1inv); // T = S - G S
     Small L3;
     L3.n = d;
     for (int r = 0; r < d; ++r)
         for (int q = 0; q < d; ++q)
-            L3(r, q) = (r == q ? w[r] * w[r] : 0.0) + 2.0 * S(r, q) - (GS(r, q) + GS(q, r));
+            L3(r, q) = (r == q ? w[r] * w[r] : 0.0) + 2.0 * T(r, q);
     if (!small_chol(L3))
         return fail(c, BQ_ERR_BAD_ARG,
                     "the measure's covariance gives no positive definite diag(w^2) + 2 (diag(w^-2) "
