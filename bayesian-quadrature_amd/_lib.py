@@ -148,6 +148,7 @@ PROBE_SIGNATURES = {
     "bq_probe_exp": (C.c_int, [_vp, _dp, _i64, _dp]),
     "bq_probe_potf2": (C.c_int, [_vp, _dp, C.c_int, _i64, _dp, _dp, C.POINTER(C.c_int32), _dp,
                                  C.POINTER(C.c_int64)]),
+    "bq_probe_records": (C.c_int, [_vp, _dp, _dp, _dp, _i32p]),
     "bq_probe_mfma_layout": (C.c_int, [_vp, _dp]),
     "bq_probe_panel_solve": (C.c_int, [_vp, _i64, _i64, _i64, _dp, _dp, C.c_int, _i64, _dp]),
     "bq_probe_potrf_batch": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _dp, _i32p, _i32p]),

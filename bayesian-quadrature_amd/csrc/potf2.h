@@ -1,17 +1,23 @@
-// potf2.h -- the 64x64 diagonal Cholesky block (four waves) and its block inverses
+// potf2.h -- the 64x64 diagonal Cholesky block (four or eight waves) and the record it leaves behind
 // Part of the libbqhip.so kernel set; compiled into k_gemm.hip / k_panel.hip / probe.hip (host.h lists the units).
 #pragma once
 #include "common.h"
 
 // ===========================================================================
-// 64 x 64 diagonal Cholesky block by FOUR waves (one per SIMD).  Every wave holds all 64
-// rows (lane = row) and a quarter of the columns: wave w owns the columns 16q + 4w + s
-// (q, s = 0..3), i.e. the matrix is cut into sixteen 4-column panels dealt round-robin to the
-// waves.  Panel p is factored by its owner (in-panel updates by v_readlane) and published to
-// its LDS slot (a full block keeps all sixteen -- the epilogue reads the factor out of them --, a
-// padded one a ring of three); after ONE workgroup barrier per panel every wave applies the
-// rank-4 update to its own later columns.  What was measured on gfx950 and shaped this file
-// (tools/potf2_probe.py, per-wave barrier stamps):
+// 64 x 64 diagonal Cholesky block by NW = 4 waves (one per SIMD) or 8 (two per SIMD).  Every wave
+// holds all 64 rows (lane = row) and 16 / NW four-column panels: the matrix is cut into sixteen
+// 4-column panels dealt round-robin to the waves, panel P to wave P % NW.  Panel P is factored by
+// its owner (in-panel updates by v_readlane) and published to its LDS slot (a full block keeps all
+// sixteen -- the epilogue reads the factor out of them --, a padded one a ring of three); after ONE
+// workgroup barrier per panel every wave applies the rank-4 update to its own later columns.
+// What the factor leaves behind, for its own panel solve and for every sweep over the factor:
+// the factored block in memory and its RECORD, BQ_DINV_HALF doubles -- 64 reciprocal pivots
+// (potf2f_rcp), then the inverses W_b of the four 16 x 16 diagonal sub-blocks, each stored whole and
+// column-major (W_b[r][k] at 64 + 256 b + r + 16 k, the strict upper triangle exact zeros: solve16.h
+// multiplies by the whole block).  ONE function, potf2f_block_inverse, computes W_b for every
+// producer of a record -- both epilogues of potf2f_run and diag_winv_kernel (trsm.h) --, so two
+// records of the same factor agree in every bit.
+// What was measured on gfx950 and shaped this file (tools/potf2_probe.py, tools/c2_timeline.py):
 //   * a wave's time per panel is set by the waves that only update in the early panels
 //     (64 FMAs + 36 LDS reads, ~1100 cycles when every group waited for its own reads) and by
 //     the owner's path (own-panel update + four pivots, ~740 cycles) in the late ones -- not
@@ -19,7 +25,12 @@
 //     moved the 15,000-cycle chain by 2 %;
 //   * published-column counters polled in LDS instead of barriers (every panel its own slot,
 //     the next owner applying columns as they appear) were SLOWER: 24,500 cycles;
-//   * the block inverses and the write-back after the chain were 5,800 cycles, 41 LDS waits.
+//   * the epilogue after the last pivot: 5,800 cycles as row dot products (41 LDS waits), 2,900 as
+//     four VALU slices of forward substitution, 1,400 on the four-block MFMA (LABBOOK, "Diagonal
+//     factor: block inverses on the four-block MFMA");
+//   * a launch cannot end before the factor's stores have drained, and the next launch reads the
+//     factor first: with the short epilogue the write-back has to START before the chain ends
+//     (Potf2FSteps, steps 12-14), or the launch gets longer although workgroup 0 is through sooner.
 // ===========================================================================
 // NW waves (4, or 8: two per SIMD -- potf2f_body): panel P = columns 4P .. 4P + 3 belongs to wave
 // P % NW, which holds it as its group P / NW
@@ -123,19 +134,17 @@ __device__ __forceinline__ void potf2f_update(Potf2FT<NW> &st, const double *slo
 // of a 16-lane group running the same 120 FMAs as the other three groups' lanes.  Now:
 //   * every panel keeps a slot of its own in LDS (16 x 256 doubles -- the region is there; the ring
 //     of three was all the chain needs), so nothing is copied and no barrier follows the chain;
-//   * wave b < 4 inverts sub-block b in four slices of four steps: group g = lane / 16 keeps the rows
-//     4 g .. 4 g + 3 of unit column lane % 16, the group that holds a slice's pivot rows solves
-//     their 4 x 4 triangle, the four multipliers cross to the other groups by ds_bpermute in one
-//     go, and the groups behind apply them -- 6 + 16 FMAs per lane and slice, the same operations
-//     on the same operands in the same order as the sixteen-step form;
+//   * wave b < 4 inverts sub-block b on the four-block MFMA (potf2f_block_inverse below): the four
+//     4 x 4 diagonal inverses on the VALU, then six dependent 4 x 4 x 4 products;
 //   * waves 4-7 write the factor home out of the slots; wave 4 also takes the reciprocal pivots and
 //     the failure report, wave 5 log|K|.
-// Measured and dropped: the same slices INSIDE the chain, on the waves that have run out of columns
-// (wave w from step 8 + w on; they reach every later barrier ~500 cycles before the panel's owner).
-// Whatever those waves did -- slices of 2, 3 or 4 steps, SIMD-aware placement, lower priority, no
-// global stores before the last barrier -- stretched the owners' steps by 150-300 cycles each: the
-// chain grew from 13,700 to 15,500-16,500 cycles and the slab step gained 0.14 us where the factor
-// alone gained 1.0.
+// Measured and dropped: forward substitution in four VALU slices of four steps (sixteen dependent
+// steps and five LDS / ds_bpermute round trips per sub-block, 2,900 cycles), and the same slices
+// INSIDE the chain, on the waves that have run out of columns (wave w from step 8 + w on; they
+// reach every later barrier ~500 cycles before the panel's owner).  Whatever those waves did --
+// slices of 2, 3 or 4 steps, SIMD-aware placement, lower priority, no global stores before the
+// last barrier -- stretched the owners' steps by 150-300 cycles each: the chain grew from 13,700
+// to 15,500-16,500 cycles and the slab step gained 0.14 us where the factor alone gained 1.0.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double potf2f_rcp(double dg)
 {
@@ -146,83 +155,111 @@ __device__ __forceinline__ double potf2f_rcp(double dg)
     return rc;
 }
 
-// steps 4 S .. 4 S + 3 of sub-block b's inversion.  Column 4 S + s of the sub-block is column s of
-// panel 4 b + S, rows 16 b .. 16 b + 15, in that panel's slot.  rcv[r]: 1 / L_ii of this lane's row
-// i = 4 g + r.  Every lane runs the pivot rows' 4 x 4 substitution on a copy of ITS rows with ITS
-// rows' entries (mb) -- in group S those are the pivot rows and the pivot triangle, and it is group
-// S's result that crosses to the others.
-template <int S>
-__device__ __forceinline__ void potf2f_inv_slice(double (&sv4)[4], double (&wc)[12], double (&wl)[4],
-                                                 const double *slots, int b,
-                                                 const double (&rcv)[4], int lane)
+// Where a 16 x 16 diagonal sub-block lies: at(r, k) = L[r][k] of the sub-block.
+// Sub-block b of a full block's factor in the panels' slots: column k is column k % 4 of panel
+// 4 b + k / 4, rows 16 b .. 16 b + 15.
+struct Potf2fInSlots {
+    const double *base;
+    __device__ __forceinline__ Potf2fInSlots(const double *slots, int b) : base(slots + 1040 * b) {}
+    __device__ __forceinline__ double operator()(int r, int k) const { return base[64 * k + r]; }
+};
+// ... and one that lies on its own, column-major with leading dimension 16
+struct Potf2fInBlk {
+    const double *base;
+    __device__ __forceinline__ explicit Potf2fInBlk(const double *blk) : base(blk) {}
+    __device__ __forceinline__ double operator()(int r, int k) const { return base[16 * k + r]; }
+};
+
+// value of lane K of every quad of four lanes
+template <int K>
+__device__ __forceinline__ double potf2f_quad_bcast(double v)
 {
-    const int g = lane >> 4, j = lane & 15;
-    const double *base = slots + (256 * (4 * b + S) + 16 * b);
-    double mb[4][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (S < 3 || r > s)
-                mb[s][r] = base[64 * s + 4 * g + r];
-    double t[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        t[r] = sv4[r];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        wl[s] = t[s] * rcv[s];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (r > s)
-                t[r] = __builtin_fma(-mb[s][r], wl[s], t[r]);
-    }
-    if (S == 3)
-        return; // the last four rows of W stay in group 3: nobody is left to apply them
-    double wk[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        wk[s] = __shfl(wl[s], 16 * S + j, 64);
-        wc[4 * S + s] = wk[s];
-    }
-    // (every group applies them: the rows of the groups up to S are never read again, and
-    // without the branch the compiler is free to issue the next slice's LDS reads early)
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            sv4[r] = __builtin_fma(-mb[s][r], wk[s], sv4[r]);
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_mov_dpp(lo, 0x55 * K, 0xf, 0xf, true); // quad_perm:[K,K,K,K]
+    hi = __builtin_amdgcn_mov_dpp(hi, 0x55 * K, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
 }
 
-// W_b = inverse of sub-block b by one wave, out of the panels' slots
-__device__ __forceinline__ void potf2f_inverse(const double *slots, int b, double *__restrict__ Wb,
-                                               int lane)
+// column c of the inverse of a lower-triangular 4 x 4 block (l[r][k], r > k; rc[k] = 1 / l[k][k]) by
+// forward substitution of the unit vector e_c; the entries above the diagonal come out as exact zeros
+__device__ __forceinline__ void potf2f_inv4_column(const double (&l)[4][4], const double (&rc)[4],
+                                                   int c, double (&w)[4])
 {
-    const int g = lane >> 4, j = lane & 15;
-    // 1 / L_tt of the sub-block's column t in lane t, then this lane's rows' four
-    const double rc = potf2f_rcp(slots[256 * (4 * b + (j >> 2)) + 64 * (j & 3) + 16 * b + j]);
-    double rcv[4];
+    w[0] = (c == 0 ? 1.0 : 0.0) * rc[0];
+    w[1] = __builtin_fma(-l[1][0], w[0], c == 1 ? 1.0 : 0.0) * rc[1];
+    double t = __builtin_fma(-l[2][0], w[0], c == 2 ? 1.0 : 0.0);
+    w[2] = __builtin_fma(-l[2][1], w[1], t) * rc[2];
+    t = __builtin_fma(-l[3][0], w[0], c == 3 ? 1.0 : 0.0);
+    t = __builtin_fma(-l[3][1], w[1], t);
+    w[3] = __builtin_fma(-l[3][2], w[2], t) * rc[3];
+}
+
+// W = L^-1 of one lower-triangular 16 x 16 sub-block by one wave, cut into 4 x 4 blocks:
+//   W_ii = L_ii^-1,   W_ij = -(sum_{j<k<=i} W_ik L_kj) W_jj   (i > j, from W L = I),
+// block sub-diagonal after block sub-diagonal on v_mfma_f64_4x4x4_4b_f64 (A lane = i + 4 blk + 16 k,
+// B lane = j + 4 blk + 16 k, D lane = j + 4 blk + 16 i; LABBOOK "Which fp64 MFMA").  The products
+// run on transposes, W_ij^T = -W_jj^T (sum_k L_kj^T W_ik^T), so that
+//   * slot blk = s of every instruction works on block ROW s of W: a level's independent products
+//     share one instruction (three on the first block sub-diagonal, two on the second, one on the
+//     third; the slots in front of them compute on wrapped-around operands and are thrown away);
+//   * a product's D register is the next product's B operand as it stands, no relayout;
+//   * lane p + 4 s + 16 q ends up with W[4 s + p][4 j + q]: a quad of lanes stores four consecutive
+//     doubles of the record, which is column-major (W[r][k] at r + 16 k, solve16.h reads it so).
+// The diagonal inverses are computed on the VALU twice, once as B operand (W_ss^T, slot s) and once
+// as A operand (W_ss^T again; row_ror moves it to the slots s + 1 .. s + 3 that multiply by it):
+// every lane substitutes the unit column it needs (four steps) and keeps its row.  Their
+// reciprocal pivots: potf2f_rcp of the quad's four pivots, one per lane, spread by quad_perm.
+// The depth: one LDS latency, rcp, four substitution steps, six dependent products.
+// The strict upper triangle of W is stored as exact zeros (solve16_block multiplies by the whole
+// block).  A NaN pivot (a failed factor) makes this sub-block's W NaN and touches no other's:
+// every sub-block is its own wave's.  Every producer of a record calls THIS function on the same
+// values, so that two records of one factor agree in every bit.
+template <class At>
+__device__ __forceinline__ void potf2f_block_inverse(const At &at, double *__restrict__ Wb, int lane)
+{
+    const int p = lane & 3, s = (lane >> 2) & 3, q = lane >> 4;
+    // L_ss below its diagonal (the same for the sixteen lanes of slot s) and this lane's pivot
+    double l[4][4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-        rcv[r] = __shfl(rc, 4 * g + r, 64);
-    double sv4[4], wc[12], wl[4];
+    for (int k = 0; k < 3; ++k)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-        sv4[r] = (4 * g + r == j) ? 1.0 : 0.0;
-    potf2f_inv_slice<0>(sv4, wc, wl, slots, b, rcv, lane);
-    potf2f_inv_slice<1>(sv4, wc, wl, slots, b, rcv, lane);
-    potf2f_inv_slice<2>(sv4, wc, wl, slots, b, rcv, lane);
-    potf2f_inv_slice<3>(sv4, wc, wl, slots, b, rcv, lane);
-    if (lane < 16) {
+        for (int r = k + 1; r < 4; ++r)
+            l[r][k] = at(4 * s + r, 4 * s + k);
+    const double dg = at(4 * s + p, 4 * s + p);
+    // A operands L_kj^T of the products: LT(a, c) holds in slot s the block (s - a, s - c) of L,
+    // lane i + 4 s + 16 k its element [k][i]; block indices wrap in the slots nobody reads
+    double lt[3][4];
 #pragma unroll
-        for (int i = 0; i < 12; ++i)
-            Wb[16 * lane + i] = wc[i];
-    }
-    if (lane >= 48) {
+    for (int a = 0; a < 3; ++a)
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-            Wb[16 * j + 12 + s] = wl[s];
-    }
+        for (int c = a + 1; c < 4; ++c)
+            lt[a][c] = at((4 * (s - a) + q) & 15, (4 * (s - c) + p) & 15);
+    const double rp = potf2f_rcp(dg);
+    const double rc[4] = {potf2f_quad_bcast<0>(rp), potf2f_quad_bcast<1>(rp),
+                          potf2f_quad_bcast<2>(rp), potf2f_quad_bcast<3>(rp)};
+    // W_ss^T as B operand: lane j + 4 s + 16 k holds W_ss^T[k][j] = W_ss[p][q]
+    // W_ss^T as A operand: lane i + 4 s + 16 k holds W_ss^T[i][k] = W_ss[q][p]
+    double wq[4], wp[4];
+    potf2f_inv4_column(l, rc, q, wq);
+    potf2f_inv4_column(l, rc, p, wp);
+    const double u0 = p == 0 ? wq[0] : p == 1 ? wq[1] : p == 2 ? wq[2] : wq[3];
+    const double nwa = -(q == 0 ? wp[0] : q == 1 ? wp[1] : q == 2 ? wp[2] : wp[3]);
+    // u_m: slot s holds W_{s, s-m}^T (D layout: lane p + 4 s + 16 q = W_{s, s-m}[p][q])
+    const double t1 = __builtin_amdgcn_mfma_f64_4x4x4f64(lt[0][1], u0, 0.0, 0, 0, 0);
+    const double t2a = __builtin_amdgcn_mfma_f64_4x4x4f64(lt[0][2], u0, 0.0, 0, 0, 0);
+    const double t3a = __builtin_amdgcn_mfma_f64_4x4x4f64(lt[0][3], u0, 0.0, 0, 0, 0);
+    const double u1 = __builtin_amdgcn_mfma_f64_4x4x4f64(row_ror_quads<1>(nwa), t1, 0.0, 0, 0, 0);
+    const double t2 = __builtin_amdgcn_mfma_f64_4x4x4f64(lt[1][2], u1, t2a, 0, 0, 0);
+    const double t3b = __builtin_amdgcn_mfma_f64_4x4x4f64(lt[1][3], u1, t3a, 0, 0, 0);
+    const double u2 = __builtin_amdgcn_mfma_f64_4x4x4f64(row_ror_quads<2>(nwa), t2, 0.0, 0, 0, 0);
+    const double t3 = __builtin_amdgcn_mfma_f64_4x4x4f64(lt[2][3], u2, t3b, 0, 0, 0);
+    const double u3 = __builtin_amdgcn_mfma_f64_4x4x4f64(row_ror_quads<3>(nwa), t3, 0.0, 0, 0, 0);
+    // block (s, s - m) of W, or zeros into the block (s, s - m + 4) above the diagonal
+    double *Wl = Wb + 4 * s + p + 16 * q;
+    Wl[64 * s] = u0;
+    Wl[64 * ((s - 1) & 3)] = s >= 1 ? u1 : 0.0;
+    Wl[64 * ((s - 2) & 3)] = s >= 2 ? u2 : 0.0;
+    Wl[64 * ((s - 3) & 3)] = s >= 3 ? u3 : 0.0;
 }
 
 // sum over the wave, the same value in every lane: DPP row_shr within the rows of 16, the four row
@@ -257,8 +294,13 @@ struct Potf2FSteps {
     // size is not a multiple of 64): panels that lie wholly in it are neither factored nor applied
     // -- they are what they will be -- and the sweep over the panels ends with the last real one.
     // (An instantiation of its own: the tests cost the full block's straight-line code 0.9 us.)
+    // wb, ldw (eight waves, a full block; else null): where the factor goes home.  Waves 0-3 own
+    // no panel behind panel 11 and have nothing left to update from step 12 on: in steps 12-14 they
+    // write the 48 columns of sub-blocks 0-2 (final since panel 11 was published) out of the slots,
+    // four columns per wave and step, so that these stores have drained when the launch ends.
     static __device__ __forceinline__ void run(Potf2FT<NW> &st, double *slots, int w, int lane,
-                                               long long *wst, int nreal)
+                                               long long *wst, int nreal, double *wb = nullptr,
+                                               long ldw = 0)
     {
         constexpr int NG = 16 / NW;
         constexpr int QP = P / NW, WP = P % NW;
@@ -296,13 +338,27 @@ struct Potf2FSteps {
         } else {
             potf2f_update<LATER, NW>(st, slot, li, w);
         }
+        if (NW == 8 && EARLY && !PAD && P >= 12 && P <= 14 && w < 4) {
+            const int c0 = 12 * w + 4 * (P - 12);
+            const double *ps = slots + 64 * c0 + lane; // column c: panel c / 4, its column c % 4
+            double *pw = wb + lane + (long)c0 * ldw;
+            double col[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                col[c] = ps[64 * c];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (lane >= c0 + c)
+                    pw[(long)c * ldw] = col[c];
+        }
         if (!PAD || 4 * (P + 1) < nreal)
-            Potf2FSteps<P + 1, NW, PAD, EARLY>::run(st, slots, w, lane, wst, nreal);
+            Potf2FSteps<P + 1, NW, PAD, EARLY>::run(st, slots, w, lane, wst, nreal, wb, ldw);
     }
 };
 template <int NW, bool PAD, bool EARLY>
 struct Potf2FSteps<16, NW, PAD, EARLY> {
-    static __device__ __forceinline__ void run(Potf2FT<NW> &, double *, int, int, long long *, int)
+    static __device__ __forceinline__ void run(Potf2FT<NW> &, double *, int, int, long long *, int,
+                                               double *, long)
     {
     }
 };
@@ -318,7 +374,8 @@ struct Potf2FSteps<16, NW, PAD, EARLY> {
 // assemble_first_kernel): *logdet and the failure flag START here.  The factor reads neither, takes
 // both as zero and stores both whatever they come to -- nobody has to clear them in front of it,
 // and no wait or barrier has to order such a store against its reads.
-template <int NW = 4>
+// LATE: see the epilogue (potrf_wg_kernel, where registers are short).
+template <int NW = 4, bool LATE = false>
 __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__ Ab, long lda,
                                            int j0, double *__restrict__ dinv_b,
                                            int *__restrict__ info_b, double *lds,
@@ -342,23 +399,24 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
         const double ld0 = (logdet && !fresh) ? *logdet : 0.0; // one writer per launch, launches in order
         Potf2FSteps<0, NW, false, true>::run(
             st, slots, w, lane,
-            (stamps && stamps[5] != 0) ? stamps + 8 : nullptr, 64);
+            (stamps && stamps[5] != 0) ? stamps + 8 : nullptr, 64, NW == 8 ? Ab : nullptr, lda);
         BQ_STAMP(2);
         BQ_STAMP(3);
-        // The factor goes home (the stores drain under the inverses).  Eight waves: waves 0-3 go
-        // straight to the inverses and waves 4-7 write sixteen columns each out of the panels'
-        // slots; four waves: every wave its own columns out of its registers.
+        // The factor goes home.  Eight waves: columns 0-47 went in steps 12-14 (Potf2FSteps); waves
+        // 0-3 go straight to the inverses and waves 4-7 write four of the last sixteen columns each
+        // out of the panels' slots; four waves: every wave its own columns out of its registers
+        // (the stores drain under the inverses).
         if (NW == 8 && w >= 4) {
-            const int c0 = 16 * (w - 4);
+            const int c0 = 48 + 4 * (w - 4);
             double *pw = Ab + lane + (long)c0 * lda;
             const double *ps = slots + 64 * c0 + lane; // column c: panel c / 4, its column c % 4
             asm volatile("" : "+v"(pw));
-            double col[16];
+            double col[4];
 #pragma unroll
-            for (int c = 0; c < 16; ++c)
+            for (int c = 0; c < 4; ++c)
                 col[c] = ps[64 * c];
 #pragma unroll
-            for (int c = 0; c < 16; ++c)
+            for (int c = 0; c < 4; ++c)
                 if (lane >= c0 + c)
                     pw[(long)c * lda] = col[c];
         }
@@ -376,8 +434,16 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
         }
         // reciprocal pivots + failure report and log|K|: waves 4 and 5 of eight, else 1 and 2
         constexpr int WR = NW == 8 ? 4 : 1, WL = NW == 8 ? 5 : 2;
-        if (w < 4)
-            potf2f_inverse(slots, w, dinv_b + 64 + 256 * w, lane);
+        // (LATE: the inverse's lane arithmetic starts HERE.  The compiler computes it in front of the
+        // chain and keeps it across it; where registers are short -- potrf_wg_kernel -- it came
+        // back from scratch memory right in front of the first product.  Elsewhere keeping it is
+        // the faster form: with it C2 gained 0.0086 ms per step on the parent, without it 0.0095.)
+        if (w < 4) {
+            int il = lane;
+            if (LATE)
+                asm volatile("" : "+v"(il));
+            potf2f_block_inverse(Potf2fInSlots(slots, w), dinv_b + 64 + 256 * w, il);
+        }
         if (w == WR) {
             const double dg = slots[256 * (lane >> 2) + 64 * (lane & 3) + lane];
             dinv_b[lane] = potf2f_rcp(dg);
@@ -444,57 +510,17 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
     }
     // reciprocal pivots (lane = column) and the failure report: a non-positive pivot left a
     // NaN on the diagonal at its own column and at every later one
-    {
+    if (w == 0) {
         const double dg = blk[256 * (lane >> 4) + 17 * (lane & 15)];
-        // 1 / L_cc: v_rcp_f64 + two Newton steps (the IEEE division sequence is three times
-        // as long, and this sits between the pivot chain and the end of the launch)
-        double rc = __builtin_amdgcn_rcp(dg);
-        rc = __builtin_fma(__builtin_fma(-dg, rc, 1.0), rc, rc);
-        rc = __builtin_fma(__builtin_fma(-dg, rc, 1.0), rc, rc);
-        if (w == 0) {
-            dinv_b[lane] = rc;
-            const unsigned long long badm = __ballot(!(dg > 0.0) || !(dg < 1.7e308));
-            if (lane == 0 && fresh)
-                info_b[0] = badm != 0ull ? j0 + __builtin_ctzll(badm) + 1 : 0;
-            else if (lane == 0 && badm != 0ull && info_b[0] == 0)
-                info_b[0] = j0 + __builtin_ctzll(badm) + 1;
-        }
-        // Wave w inverts block w: lane j (mod 16) runs the forward substitution of unit column
-        // j in its right-looking form -- w_k = s_k / L_kk, then s_i -= L_ik w_k for i > k --
-        // so that the dependent chain is two operations per row and column k + 1 of the block
-        // (uniform LDS reads) is in flight while column k is applied.  (The row-by-row dot
-        // products it replaces waited for LDS 41 times: 5,800 cycles for this epilogue.)
-        const double *bw = blk + 256 * w;
-        double sv[16], wc[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            sv[i] = (i == (lane & 15)) ? 1.0 : 0.0;
-        double cur[16], nxt[16];
-#pragma unroll
-        for (int i = 1; i < 16; ++i)
-            cur[i] = bw[i];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (k < 14) {
-#pragma unroll
-                for (int i = k + 2; i < 16; ++i)
-                    nxt[i] = bw[i + 16 * (k + 1)];
-            }
-            wc[k] = sv[k] * readlane_f64(rc, 16 * w + k);
-#pragma unroll
-            for (int i = k + 1; i < 16; ++i)
-                sv[i] = __builtin_fma(-cur[i], wc[k], sv[i]);
-#pragma unroll
-            for (int i = k + 2; i < 16; ++i)
-                cur[i] = nxt[i];
-        }
-        if (lane < 16) {
-            double *Wb = dinv_b + 64 + 256 * w + 16 * lane;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                Wb[i] = wc[i];
-        }
+        dinv_b[lane] = potf2f_rcp(dg);
+        const unsigned long long badm = __ballot(!(dg > 0.0) || !(dg < 1.7e308));
+        if (lane == 0 && fresh)
+            info_b[0] = badm != 0ull ? j0 + __builtin_ctzll(badm) + 1 : 0;
+        else if (lane == 0 && badm != 0ull && info_b[0] == 0)
+            info_b[0] = j0 + __builtin_ctzll(badm) + 1;
     }
+    // wave w inverts sub-block w as the full block's epilogue does, out of its copy in blk
+    potf2f_block_inverse(Potf2fInBlk(blk + 256 * w), dinv_b + 64 + 256 * w, lane);
     if (NW == 4 && logdet && w == 3)
         BQ_POTF2F_LOGDET
 #undef BQ_POTF2F_LOGDET
@@ -507,7 +533,7 @@ __device__ __forceinline__ void potf2f_run(Potf2FT<NW> &st, double *__restrict__
 // NW = 8: the workgroup has EIGHT waves (512 threads), two per SIMD, two panels each: the waves
 // that only update have half the columns to bring up to date per panel (32 FMAs + 20 LDS reads
 // instead of 64 + 36), which is what paces the early panels.
-template <int NW = 4>
+template <int NW = 4, bool LATE = false>
 __device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, int j0,
                                             double *__restrict__ dinv_b,
                                             int *__restrict__ info_b, double *lds,
@@ -529,7 +555,7 @@ __device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, i
                              : Ab[lane + (long)(4 * (NW * q + w) + s) * lda];
     if (src_in_slots)
         __syncthreads(); // the ring overwrites the block: every wave has its columns first
-    potf2f_run<NW>(st, Ab, lda, j0, dinv_b, info_b, lds, stamps, logdet, nreal);
+    potf2f_run<NW, LATE>(st, Ab, lda, j0, dinv_b, info_b, lds, stamps, logdet, nreal);
 }
 #undef BQ_STAMP
 
@@ -540,13 +566,13 @@ __device__ __forceinline__ void potf2f_body(double *__restrict__ Ab, long lda, i
 // ---------------------------------------------------------------------------
 #define BQ_POTF2_LDS_DOUBLES BQ_POTF2F_LDS_DOUBLES
 
-template <int NW = 4>
+template <int NW = 4, bool LATE = false>
 __device__ __forceinline__ void potf2_body(double *__restrict__ Ab, long lda, int j0,
                                            double *__restrict__ dinv_b, int *__restrict__ info_b,
                                            double *lds, const double *src = nullptr,
                                            long lsrc = 0, long long *stamps = nullptr,
                                            double *logdet = nullptr, int nreal = 64)
 {
-    potf2f_body<NW>(Ab, lda, j0, dinv_b, info_b, lds, src, lsrc, src == lds, stamps, logdet,
+    potf2f_body<NW, LATE>(Ab, lda, j0, dinv_b, info_b, lds, src, lsrc, src == lds, stamps, logdet,
                     nreal);
 }

@@ -243,7 +243,8 @@ __global__ __launch_bounds__(64 * NW) void potf2_probe_kernel(const double *__re
                                                           double *__restrict__ A, long lda,
                                                           double *__restrict__ dinv,
                                                           int *__restrict__ info,
-                                                          long long *stamps, int from_lds)
+                                                          long long *stamps, int from_lds,
+                                                          int nreal)
 {
     __shared__ __attribute__((aligned(16))) double lds[BQ_POTF2_LDS_DOUBLES];
     __builtin_amdgcn_s_setprio(3);
@@ -253,12 +254,12 @@ __global__ __launch_bounds__(64 * NW) void potf2_probe_kernel(const double *__re
         for (int e = threadIdx.x; e < 4096; e += 64 * NW)
             Ts[e] = Ain[(e & 63) + (long)(e >> 6) * lda];
         __syncthreads();
-        potf2_body<NW>(A, lda, 0, dinv, info, lds, Ts, 64, stamps);
+        potf2_body<NW>(A, lda, 0, dinv, info, lds, Ts, 64, stamps, nullptr, nreal);
     } else {
         for (int e = threadIdx.x; e < 4096; e += 64 * NW)
             A[(e & 63) + (long)(e >> 6) * lda] = Ain[(e & 63) + (long)(e >> 6) * lda];
         __syncthreads();
-        potf2_body<NW>(A, lda, 0, dinv, info, lds, nullptr, 0, stamps);
+        potf2_body<NW>(A, lda, 0, dinv, info, lds, nullptr, 0, stamps, nullptr, nreal);
     }
 }
 

@@ -360,6 +360,10 @@ extern "C" int bq_probe_potf2(bq_ctx *c, const double *A, int from_lds, int64_t 
 {
     if (!c || !A || reps < 1)
         return BQ_ERR_BAD_ARG;
+    // from_lds bits 8-14: the block's real columns when fewer than 64 (the padded epilogue)
+    const int nreal = ((from_lds >> 8) & 127) ? ((from_lds >> 8) & 127) : 64;
+    if (nreal > 64)
+        return fail(c, BQ_ERR_BAD_ARG, "potf2: at most 64 real columns");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf ain, a, dv, inf, st;
     HIPCHK(c, ain.alloc(sizeof(double) * 4096));
@@ -383,11 +387,11 @@ extern "C" int bq_probe_potf2(bq_ctx *c, const double *A, int from_lds, int64_t 
         if (from_lds & 2)
             hipLaunchKernelGGL(potf2_probe_kernel<8>, dim3(1), dim3(512), 0, c->stream, ain.d(),
                                a.d(), 64L, dv.d(), inf.i(), static_cast<long long *>(st.p),
-                               from_lds & 1);
+                               from_lds & 1, nreal);
         else
             hipLaunchKernelGGL(potf2_probe_kernel<4>, dim3(1), dim3(256), 0, c->stream, ain.d(),
                                a.d(), 64L, dv.d(), inf.i(), static_cast<long long *>(st.p),
-                               from_lds & 1);
+                               from_lds & 1, nreal);
     };
     for (int i = 0; i < 5; ++i)
         launch();
@@ -582,6 +586,45 @@ extern "C" int bq_probe_potrf_batch(bq_ctx *c, int64_t batch, int64_t ntot, int6
     HIPCHK(c, hipMemcpyAsync(A, Ad.p, abytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(info, inf.p, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToHost,
                              c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BQ_OK;
+}
+
+// Both producers of a factor's block-inverse records on one matrix: A (128 x 128 host, column-major,
+// ld 128, SPD) is factored by the one-launch steps, whose two records stay behind in the two halves
+// of the sweep's ping-pong, and the resident factor's records are then built from the factor in
+// memory (diag_winv_kernel) as a fit builds them.
+extern "C" int bq_probe_records(bq_ctx *c, double *A, double *rec_sweep, double *rec_resident,
+                                int32_t *info)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (!A || !rec_sweep || !rec_resident || !info)
+        return fail(c, BQ_ERR_BAD_ARG, "records: null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int ntot = 128;
+    const long lda = ntot, astride = lda * ntot;
+    DevBuf Ad, dinv, dw, ws, inf;
+    HIPCHK(c, Ad.alloc(sizeof(double) * (size_t)astride));
+    HIPCHK(c, dinv.alloc(sizeof(double) * BQ_DINV_STRIDE));
+    HIPCHK(c, dw.alloc(sizeof(double) * BQ_DINV_STRIDE));
+    HIPCHK(c, ws.alloc(sizeof(double) * sweep_route(c, ntot, ntot, 1).ws_doubles));
+    HIPCHK(c, inf.alloc(sizeof(int)));
+    const SweepRoute r = sweep_route(c, ntot, ntot, 1, ws.bytes / sizeof(double));
+    if (r.kind != SweepRoute::Slab)
+        return fail(c, BQ_ERR_BAD_ARG, "records: the context does not run the one-launch steps");
+    HIPCHK(c, hipMemcpyAsync(Ad.p, A, sizeof(double) * (size_t)astride, hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipMemsetAsync(inf.p, 0, sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(dinv.p, 0xA5, dinv.bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(dw.p, 0xA5, dw.bytes, c->stream));
+    BQCHK(enqueue_potrf_partial(c, r, Ad.d(), lda, astride, dinv.d(), inf.i(), ws.d()));
+    BQCHK(launch_diag_winv(c, Ad.d(), lda, ntot, dw.d()));
+    HIPCHK(c, hipMemcpyAsync(A, Ad.p, sizeof(double) * (size_t)astride, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipMemcpyAsync(rec_sweep, dinv.p, dinv.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rec_resident, dw.p, dw.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(info, inf.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BQ_OK;
 }

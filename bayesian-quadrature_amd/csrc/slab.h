@@ -1170,7 +1170,7 @@ __global__ __launch_bounds__(512) void potrf_wg_kernel(double *__restrict__ A, l
     for (int s = 0; s < ns; ++s) {
         double *Ass = A + 64 * s + (long)(64 * s) * lda;
         double *rs = rec + (long)s * BQ_DINV_HALF;
-        potf2_body<8>(Ass, lda, col0 + 64 * s, rs, info + b, plds);
+        potf2_body<8, true>(Ass, lda, col0 + 64 * s, rs, info + b, plds);
         // (explicit: what this workgroup stored is in memory before its other waves read it)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();

@@ -579,6 +579,20 @@ class Engine(object):
             route.ctypes.data_as(L._i32p)))
         return info, (self.SWEEP_KINDS[route[0]], int(route[1]), bool(route[2]))
 
+    def probe_records(self, A):
+        """Both producers of the block-inverse records on one 128 x 128 SPD matrix
+        (bq_probe_records).  Returns (factor, the sweep's two records (2, 1088), the resident
+        factor's two records (2, 1088), info)."""
+        e = self.probe_engine()
+        buf = np.array(A, dtype=np.float64, order="F")
+        if buf.shape != (128, 128):
+            raise ValueError("A must be 128 x 128")
+        rs, rr = np.zeros((2, 1088)), np.zeros((2, 1088))
+        info = np.full(1, -1, dtype=np.int32)
+        e._check(e._lib.bq_probe_records(e._ctx, L.dptr(buf), L.dptr(rs), L.dptr(rr),
+                                         info.ctypes.data_as(L._i32p)))
+        return buf, rs, rr, int(info[0])
+
     def probe_first_launch(self, x, y, xo, h, w, s, stamps=False):
         """The first launch of a small system's sweep alone (bq_probe_first_launch): x (B, d, n),
         y (B, n), xo (B, d, M) as a plan takes them.  Returns a dict of what the launch left in

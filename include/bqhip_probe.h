@@ -94,10 +94,21 @@ int bq_probe_first_launch(bq_ctx *ctx, int64_t batch, int64_t d, int64_t n, int6
  * over through LDS as the one-launch steps do).  Last launch's factor, its
  * BQ_DINV_HALF-double record (64 reciprocal pivots + four 16 x 16 block inverses), info,
  * HIP-event microseconds per launch and 136 in-kernel s_memtime stamps (5 phase
- * boundaries, then per panel and wave the arrival at / release from the panel barrier). */
+ * boundaries, then per panel and wave the arrival at / release from the panel barrier).
+ * from_lds bit 0: through LDS; bit 1: eight waves; bit 2: per-wave stamps; bits 8-14: nreal, the
+ * block's real columns when fewer than 64 (A is then identity from row / column nreal on: the
+ * padded steps and their epilogue); 0 = a full block. */
 int bq_probe_potf2(bq_ctx *ctx, const double *A, int from_lds, int64_t reps, double *L_out,
                    double *dinv_out, int32_t *info_out, double *us_per_launch,
                    int64_t *stamps136);
+/* Both producers of the block-inverse records on one factor: A (128 x 128, host, column-major,
+ * ld 128, in: SPD, out: its factor by the one-launch steps), rec_sweep: the two records the steps
+ * left in the ping-pong halves (2 x BQ_DINV_HALF doubles: block 0, block 1), rec_resident: the
+ * records diag_winv_kernel builds from the factor in memory, as for a resident fit (the same
+ * layout).  BQ_ERR_BAD_ARG when the context would not run the one-launch steps.
+ * (tests/test_block_inverse.py) */
+int bq_probe_records(bq_ctx *ctx, double *A, double *rec_sweep, double *rec_resident,
+                     int32_t *info);
 /* The batched panel solve of one outer block alone (potrf.hip, enqueue_panel_solve): X (m x kb per
  * problem, column-major, in / out) <- X L^-T against `batch` dense lower-triangular kb x kb
  * factors L; mode 0: as the context is configured, 1: recursive products + 64-column solves,
