@@ -318,8 +318,9 @@ def test_staging_routes(engine, oracle):
 
 def test_leaves_the_fit_alone(engine):
     """predict, logml, alpha(), logml_hess() and predict_grad read the same bits before and after
-    a predict_dtheta.  And the pin of the DKZ bit, after test_predict_grad.py: a warm fit that
-    goes through refit, set_y + refit, append and remove, each after predict_dtheta calls on both
+    a predict_dtheta.  And the DKZ bit's own event test at its own shapes (the shared table of
+    test_gp_fit_state.py holds it too, against every event and every other consumer): a warm fit
+    that goes through refit, set_y + refit, append and remove, each after predict_dtheta calls on both
     routes -- so that the solved vectors, every workspace and every piece of derived state are
     there to go stale -- gives the bits of a cold twin that goes through the same events and is
     asked only afterwards.  After the two refits, where the factor is a factorisation from

@@ -262,8 +262,9 @@ def test_staging_routes(engine, oracle):
 
 
 def test_leaves_the_fit_alone(engine):
-    """predict, logml and alpha() read the same bits before and after a predict_grad.  And the
-    pin of test_gp_fit_state.py for this consumer: a warm fit that goes through refit,
+    """predict, logml and alpha() read the same bits before and after a predict_grad.  And this
+    consumer's own event test at its own shapes (the shared table of test_gp_fit_state.py holds
+    it too, against every event and every other consumer): a warm fit that goes through refit,
     set_y + refit, append and remove, each after predict_grad calls on both routes -- so that
     every workspace and every piece of derived state is there to go stale -- gives the bits of a
     cold twin that goes through the same events and is asked only afterwards.  After the two
