@@ -12,6 +12,8 @@ from . import _lib  # noqa: F401
 from . import engine  # noqa: F401
 from . import linalg  # noqa: F401
 from . import linalg as la  # noqa: F401  (the reference's alias, bq.py:10)
+from . import measures  # noqa: F401
+from .measures import BoxMeasure, GaussianMixture  # noqa: F401
 from .engine import Engine, get_engine, set_engine  # noqa: F401
 from .pool import EnginePool  # noqa: F401
 from .gp import GP, GaussianKernel, PeriodicKernel  # noqa: F401

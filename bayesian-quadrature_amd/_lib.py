@@ -28,6 +28,12 @@ _vp = C.c_void_p
 _i64 = C.c_int64
 _dbl = C.c_double
 
+# the arguments of a box (lo, hi) and of a mixture (C, pi, mu, cov), and bq_gp_zdesign's after
+# its measure: xc, A, q, nugget, tol, piv, gain, zvar0, resid_u, resid_c, score0, rank
+_BOX = [_dp, _dp]
+_MIX = [_i64, _dp, _dp, _dp]
+_ZD_TAIL = [_dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp, _dp, _dp, _dp, _i64p]
+
 # name -> (restype, argtypes); every entry point of include/bqhip.h
 SIGNATURES = {
     "bq_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -91,6 +97,11 @@ SIGNATURES = {
     "bq_gp_integral": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "bq_gp_zdesign": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp,
                                 _dp, _dp, _dp, _i64p]),
+    # (the measure's arguments stand where bq_gp_integral's and bq_gp_zdesign's (mu, cov) do)
+    "bq_gp_integral_box": (C.c_int, [_vp, _vp] + _BOX + [_dp, _dp, _dp]),
+    "bq_gp_integral_mix": (C.c_int, [_vp, _vp] + _MIX + [_dp, _dp, _dp]),
+    "bq_gp_zdesign_box": (C.c_int, [_vp, _vp] + _BOX + _ZD_TAIL),
+    "bq_gp_zdesign_mix": (C.c_int, [_vp, _vp] + _MIX + _ZD_TAIL),
     "bq_gp_sqintegral": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "bq_gp_sqdesign": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp,
                                  _dp, _dp, _dp, _i64p]),
@@ -100,6 +111,8 @@ SIGNATURES = {
     "bq_batch_fit_predict": (C.c_int, [_vp, _i64, _dp, _dp, _i64, _i64, _dbl, _dp, _dbl, _dp, _i64,
                                        _dp, _dp, _dp, _i32p]),
     "bq_int_K": (C.c_int, [_vp, _dp, _i64, _i64, _dbl, _dp, _dp, _dp, _dp]),
+    "bq_int_K_box": (C.c_int, [_vp, _dp, _i64, _i64, _dbl, _dp] + _BOX + [_dp, _dp]),
+    "bq_int_K_mix": (C.c_int, [_vp, _dp, _i64, _i64, _dbl, _dp] + _MIX + [_dp, _dp]),
     "bq_int_K1_K2": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _i64, _dbl, _dp, _dbl, _dp, _dp, _dp,
                                _dp]),
     "bq_int_int_K1_K2_K1": (C.c_int, [_vp, _dp, _i64, _i64, _dbl, _dp, _dbl, _dp, _dp, _dp, _dp]),

@@ -20,6 +20,7 @@ from . import linalg as la
 from . import util
 from .engine import get_engine
 from .gp import GP, GaussianKernel, PeriodicKernel
+from .measures import Measure
 
 logger = logging.getLogger("bayesian_quadrature")
 DTYPE = np.dtype("float64")
@@ -175,20 +176,30 @@ class BQ(object):
         return self.gp_log_l.ivr_design(x_c, q, ref=None if x_r is None else ref,
                                         weights=dens / dens.sum())
 
-    def l_integral(self):
+    def _l_measure(self, measure):
+        """The arguments that stand for the measure in ``gp_l``'s integral calls: the prior for
+        None, else the ``measures`` object itself (gp.GP checks its dimension, 1)."""
+        if measure is None:
+            return (self.options["x_mean"], self.options["x_cov"])
+        if not isinstance(measure, Measure):
+            raise TypeError("measure must be None or a measures.BoxMeasure / GaussianMixture")
+        return (measure,)
+
+    def l_integral(self, measure=None):
         """(mean, var): vanilla Bayesian quadrature of the second GP alone, the posterior of
         ``int l(x) N(x | x_mean, x_var) dx`` under ``gp_l`` (gp.GP.integral).  The mean is
         ``Z_mean()`` by another route; the variance ignores the uncertainty of the log-GP that
-        ``Z_var`` carries."""
+        ``Z_var`` carries.  ``measure``: a one-dimensional ``measures.BoxMeasure`` or
+        ``measures.GaussianMixture`` to integrate l against in place of the prior."""
         self._require_exact()
-        return self.gp_l.integral(self.options["x_mean"], self.options["x_cov"])
+        return self.gp_l.integral(*self._l_measure(measure))
 
-    def l_integral_design(self, x_c, q):
+    def l_integral_design(self, x_c, q, measure=None):
         """The indices of the (at most) ``q`` entries of ``x_c`` whose evaluation lowers the
         variance of ``l_integral`` the most (gp.GP.integral_design): sequential Bayesian
-        quadrature on ``gp_l``, with no reference points."""
+        quadrature on ``gp_l``, with no reference points.  ``measure`` as in ``l_integral``."""
         self._require_exact()
-        return self.gp_l.integral_design(x_c, q, self.options["x_mean"], self.options["x_cov"])
+        return self.gp_l.integral_design(x_c, q, *self._l_measure(measure))
 
     def sqrt_bq(self, params, alpha0=None):
         """A ``wsabi.SqrtBQ`` over the samples ``x_s``, ``l_s`` and this object's prior: square-root-

@@ -1830,13 +1830,32 @@ extern "C" int bq_gp_ivr(bq_ctx *c, bq_fit *f, const double *xr, int64_t R, cons
 
 namespace bqh {
 
-// the measure of an integral call as the key of the KMEAN state: [mu d | Sigma d x d], zeros behind,
-// so that two keys compare byte by byte
-static void kmean_key(const bq_fit *f, const double *mu, const double *cov, double *key)
+// the measure of an integral call as the key of the KMEAN state (host.h, bq_fit::km_key, has the
+// three layouts): the kind comes first, so that a box and a Gaussian with the same numbers differ;
+// zeros behind, so that two keys compare byte by byte.  The measure has passed launch_kernel_mean.
+static void kmean_key(const bq_fit *f, const Measure &m, double *key)
 {
+    const size_t d = (size_t)f->d;
     std::memset(key, 0, sizeof f->km_key);
-    std::memcpy(key, mu, sizeof(double) * f->d);
-    std::memcpy(key + f->d, cov, sizeof(double) * f->d * f->d);
+    key[0] = (double)m.kind;
+    switch (m.kind) {
+    case Measure::GAUSS:
+        std::memcpy(key + 1, m.a, sizeof(double) * d);
+        std::memcpy(key + 1 + d, m.b, sizeof(double) * d * d);
+        break;
+    case Measure::BOX:
+        std::memcpy(key + 1, m.a, sizeof(double) * d);
+        std::memcpy(key + 1 + d, m.b, sizeof(double) * d);
+        break;
+    case Measure::MIX: {
+        const size_t C = (size_t)m.C;
+        key[1] = (double)C;
+        std::memcpy(key + 2, m.pi, sizeof(double) * C);
+        std::memcpy(key + 2 + C, m.a, sizeof(double) * d * C);
+        std::memcpy(key + 2 + C + d * C, m.b, sizeof(double) * d * d * C);
+        break;
+    }
+    }
 }
 
 static bool kmean_current(const bq_fit *f, const double *key)
@@ -1844,20 +1863,34 @@ static bool kmean_current(const bq_fit *f, const double *key)
     return (f->have & bq_fit::KMEAN) && std::memcmp(f->km_key, key, sizeof f->km_key) == 0;
 }
 
+// the measure of a warped call as the key of the SQW state: [mu d | Sigma d x d], zeros behind
+static void sqw_key(const bq_fit *f, const double *mu, const double *cov, double *key)
+{
+    std::memset(key, 0, sizeof f->sq_key);
+    std::memcpy(key, mu, sizeof(double) * f->d);
+    std::memcpy(key + f->d, cov, sizeof(double) * f->d * f->d);
+}
+
 // every buffer the producer touches, there before its first launch
-static int kmean_alloc(bq_ctx *c, bq_fit *f)
+static int kmean_alloc(bq_ctx *c, bq_fit *f, const Measure &m)
 {
     BQCHK(fit_grow(c, f->wide, sizeof(double) * wide_alloc_doubles(f->npad), "wide block inverses"));
     BQCHK(fit_vec(c, f));
     BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)f->npad, "contiguous z"));
+    if (m.kind == Measure::MIX) {
+        const size_t len = mix_form_doubles(f->d, BQ_MEASURE_MAX_COMP);
+        BQCHK(fit_grow(c, f->kmform, sizeof(double) * len, "mixture forms"));
+        f->km_hform.resize(len);
+    }
     return fit_grow(c, f->kmean, sizeof(double) * (2 * (size_t)f->npad + 32), "kernel mean state");
 }
 
-// The producer of KMEAN, first half: its launches, nothing read back.  kappa_X by int_K_kernel on
-// the resident points (zero on the padding), a copy into the single-vector workspace, which the
-// sweep consumes, b = L^-1 kappa_X by the fit's forward single-vector sweep, and b.b.  The bit is
-// dropped first: the state belongs to no key until fit_kmean has the sum on the host.
-static int kmean_enqueue(bq_ctx *c, bq_fit *f, const double *mu, const double *cov)
+// The producer of KMEAN, first half: its launches, nothing read back.  A mixture's forms go to the
+// device first; kappa_X by the measure's kernel on the resident points (zero on the padding), a
+// copy into the single-vector workspace, which the sweep consumes, b = L^-1 kappa_X by the fit's
+// forward single-vector sweep, and b.b.  kk is integral_args'.  The bit is dropped first: the
+// state belongs to no key until fit_kmean has the sum on the host.
+static int kmean_enqueue(bq_ctx *c, bq_fit *f, const Measure &m, double kk)
 {
     const int npad = f->npad;
     double *kap = f->kmean.d(), *b = kap + npad, *scal = b + npad;
@@ -1865,7 +1898,15 @@ static int kmean_enqueue(bq_ctx *c, bq_fit *f, const double *mu, const double *c
     WideInv w;
     BQCHK(fit_wide(c, f, w));
     HIPCHK(c, hipMemsetAsync(kap, 0, sizeof(double) * (size_t)npad, c->stream));
-    BQCHK(launch_kernel_mean(c, f->d, f->pts.d(), f->n, f->h, f->w, mu, cov, kap, &f->km_kk));
+    if (m.kind == Measure::MIX) {
+        mix_forms(f->d, f->w, m, f->km_hform.data());
+        HIPCHK(c, hipMemcpyAsync(f->kmform.p, f->km_hform.data(),
+                                 sizeof(double) * mix_form_doubles(f->d, (int)m.C),
+                                 hipMemcpyHostToDevice, c->stream));
+    }
+    BQCHK(launch_kernel_mean(c, f->d, f->pts.d(), f->n, f->h, f->w, m, kap, nullptr,
+                             f->kmform.d()));
+    f->km_kk = kk;
     BQCHK(launch_gather_row(c, f->vec.d(), kap, 1, npad));
     BQCHK(enqueue_forward_vec(c, f->vec.d(), b, f->A.d(), f->ldl, npad, w,
                               f->vec.d() + 2 * (size_t)npad));
@@ -1880,40 +1921,48 @@ static void fit_kmean(bq_fit *f, const double *key, double bb)
     f->have |= bq_fit::KMEAN;
 }
 
-// what the two integral entry points check alike
-static int integral_args(bq_ctx *c, bq_fit *f, const double *mu, const double *cov, double *kk)
+// What the integral and the design entry points check alike: the handle and the measure, before
+// anything is allocated.  Leaves the measure's key, whether the KMEAN state has to be computed for
+// it, and kk -- the state's where it is current (its measure passed this check before), else from
+// the measure, with the factors that only kk needs.
+static int integral_args(bq_ctx *c, bq_fit *f, const Measure &m, double *key, bool *fresh,
+                         double *kk)
 {
     BQCHK(check_fit(c, f));
-    if (!mu || !cov)
-        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
-    return launch_kernel_mean(c, f->d, nullptr, 0, f->h, f->w, mu, cov, nullptr, kk);
+    BQCHK(launch_kernel_mean(c, f->d, nullptr, 0, f->h, f->w, m, nullptr, nullptr));
+    kmean_key(f, m, key);
+    *fresh = !kmean_current(f, key);
+    if (!*fresh) {
+        *kk = f->km_kk;
+        return BQ_OK;
+    }
+    return launch_kernel_mean(c, f->d, nullptr, 0, f->h, f->w, m, nullptr, kk);
 }
 
-} // namespace bqh
-
-// The integral of the fit under N(mu, Sigma) (include/bqhip.h has the contract).  Where the KMEAN
-// state is not there for this measure its producer is enqueued in front; then b.z against the
-// current z, for the weights one backward single-vector sweep from a copy of b, and one read-back
-// of the two sums (and the weights).
-extern "C" int bq_gp_integral(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
-                              double *mean, double *var, double *weights)
+// The integral of the fit under a measure (include/bqhip.h has the contracts): the body of
+// bq_gp_integral and its _box and _mix twins.  Where the KMEAN state is not there for this measure
+// its producer is enqueued in front; then b.z against the current z, for the weights one backward
+// single-vector sweep from a copy of b, and one read-back of the two sums (and the weights).
+static int gp_integral(bq_ctx *c, bq_fit *f, const Measure &m, double *mean, double *var,
+                       double *weights)
 {
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    double key[bq_fit::KM_KEY_LEN];
+    bool fresh;
     double kk;
-    BQCHK(integral_args(c, f, mu, cov, &kk));
+    BQCHK(integral_args(c, f, m, key, &fresh, &kk));
     if (!mean && !var && !weights)
         return fail(c, BQ_ERR_BAD_ARG, "illegal value");
     HIPCHK(c, hipSetDevice(c->device));
-    BQCHK(kmean_alloc(c, f));
-    double key[sizeof f->km_key / sizeof(double)];
-    kmean_key(f, mu, cov, key);
-    const bool fresh = !kmean_current(f, key);
+    BQCHK(kmean_alloc(c, f, m));
     const int n = f->n, npad = f->npad;
     double *b = f->kmean.d() + npad, *scal = b + npad;
     double *hs, *ds;
     BQCHK(ctx_stage(c, 2, &hs, &ds));
     BQCHK(with_flow_fallback(c, [&]() -> int {
         if (fresh)
-            BQCHK(kmean_enqueue(c, f, mu, cov));
+            BQCHK(kmean_enqueue(c, f, m, kk));
         BQCHK(fit_zc(c, f));
         BQCHK(launch_zd_dot(c, b, f->wz.d(), npad, scal + 1));
         if (weights) {
@@ -1938,6 +1987,27 @@ extern "C" int bq_gp_integral(bq_ctx *c, bq_fit *f, const double *mu, const doub
     if (weights)
         std::memcpy(weights, f->hvec, sizeof(double) * n);
     return BQ_OK;
+}
+
+} // namespace bqh
+
+extern "C" int bq_gp_integral(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                              double *mean, double *var, double *weights)
+{
+    return gp_integral(c, f, Measure::gauss(mu, cov), mean, var, weights);
+}
+
+extern "C" int bq_gp_integral_box(bq_ctx *c, bq_fit *f, const double *lo, const double *hi,
+                                  double *mean, double *var, double *weights)
+{
+    return gp_integral(c, f, Measure::box(lo, hi), mean, var, weights);
+}
+
+extern "C" int bq_gp_integral_mix(bq_ctx *c, bq_fit *f, int64_t C, const double *pi,
+                                  const double *mu, const double *cov, double *mean, double *var,
+                                  double *weights)
+{
+    return gp_integral(c, f, Measure::mix(C, pi, mu, cov), mean, var, weights);
 }
 
 namespace bqh {
@@ -2023,20 +2093,27 @@ static int zd_results(bq_ctx *c, const ZdPlan &pl, const double *hs, int64_t A, 
 
 } // namespace bqh
 
+namespace bqh {
+
 // The greedy design that lowers the variance of the integral the most (include/bqhip.h has the
-// contract; zdesign.h the kernels): zd_run with kappa at the staged candidates and b of the KMEAN
-// state, whose producer is enqueued in front where it is not there for this measure (b.b then
-// rides behind the head).  Every device buffer is there before the first launch.
-extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
-                             const double *xc, int64_t A, int64_t q, double nugget, double tol,
-                             int64_t *piv, double *gain, double *zvar0, double *resid_u,
-                             double *resid_c, double *score0, int64_t *rank)
+// contracts; zdesign.h the kernels): the body of bq_gp_zdesign and its _box and _mix twins.
+// zd_run with kappa at the staged candidates and b of the KMEAN state, whose producer is enqueued
+// in front where it is not there for this measure (b.b then rides behind the head).  Every device
+// buffer is there before the first launch.
+static int gp_zdesign(bq_ctx *c, bq_fit *f, const Measure &m, const double *xc, int64_t A,
+                      int64_t q, double nugget, double tol, int64_t *piv, double *gain,
+                      double *zvar0, double *resid_u, double *resid_c, double *score0,
+                      int64_t *rank)
 {
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    double key[bq_fit::KM_KEY_LEN];
+    bool fresh;
     double kk;
-    BQCHK(integral_args(c, f, mu, cov, &kk));
+    BQCHK(integral_args(c, f, m, key, &fresh, &kk));
     BQCHK(zd_args(c, xc, A, q, nugget, tol, piv, gain, zvar0, rank));
     if (A == 0) {
-        BQCHK(bq_gp_integral(c, f, mu, cov, nullptr, zvar0, nullptr));
+        BQCHK(gp_integral(c, f, m, nullptr, zvar0, nullptr));
         for (int64_t j = 0; j < q; ++j)
             piv[j] = -1, gain[j] = 0.0;
         *rank = 0;
@@ -2046,23 +2123,51 @@ extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const doubl
     const int d = f->d, npad = f->npad;
     const ZdPlan pl = zd_plan((int)A, npad, (int)q);
 
-    BQCHK(kmean_alloc(c, f));
+    BQCHK(kmean_alloc(c, f, m));
     BQCHK(zd_alloc(c, f, pl));
-    double key[sizeof f->km_key / sizeof(double)];
-    kmean_key(f, mu, cov, key);
-    const bool fresh = !kmean_current(f, key);
     double *b = f->kmean.d() + npad, *scal = b + npad, *hs;
     BQCHK(zd_run(
         c, f, pl, xc, A, nugget, tol * kk, b, scal,
-        [&]() -> int { return fresh ? kmean_enqueue(c, f, mu, cov) : BQ_OK; },
+        [&]() -> int { return fresh ? kmean_enqueue(c, f, m, kk) : BQ_OK; },
         [&](const double *xq, double *out) -> int {
-            return launch_kernel_mean(c, d, xq, (int)A, f->h, f->w, mu, cov, out, nullptr);
+            return launch_kernel_mean(c, d, xq, (int)A, f->h, f->w, m, out, nullptr,
+                                      f->kmform.d());
         },
         &hs));
     if (fresh)
         fit_kmean(f, key, hs[pl.head]);
     *zvar0 = f->km_kk - f->km_bb;
     return zd_results(c, pl, hs, A, piv, gain, resid_u, resid_c, score0, rank);
+}
+
+} // namespace bqh
+
+extern "C" int bq_gp_zdesign(bq_ctx *c, bq_fit *f, const double *mu, const double *cov,
+                             const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                             int64_t *piv, double *gain, double *zvar0, double *resid_u,
+                             double *resid_c, double *score0, int64_t *rank)
+{
+    return gp_zdesign(c, f, Measure::gauss(mu, cov), xc, A, q, nugget, tol, piv, gain, zvar0,
+                      resid_u, resid_c, score0, rank);
+}
+
+extern "C" int bq_gp_zdesign_box(bq_ctx *c, bq_fit *f, const double *lo, const double *hi,
+                                 const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                                 int64_t *piv, double *gain, double *zvar0, double *resid_u,
+                                 double *resid_c, double *score0, int64_t *rank)
+{
+    return gp_zdesign(c, f, Measure::box(lo, hi), xc, A, q, nugget, tol, piv, gain, zvar0, resid_u,
+                      resid_c, score0, rank);
+}
+
+extern "C" int bq_gp_zdesign_mix(bq_ctx *c, bq_fit *f, int64_t C, const double *pi,
+                                 const double *mu, const double *cov, const double *xc, int64_t A,
+                                 int64_t q, double nugget, double tol, int64_t *piv, double *gain,
+                                 double *zvar0, double *resid_u, double *resid_c, double *score0,
+                                 int64_t *rank)
+{
+    return gp_zdesign(c, f, Measure::mix(C, pi, mu, cov), xc, A, q, nugget, tol, piv, gain, zvar0,
+                      resid_u, resid_c, score0, rank);
 }
 
 namespace bqh {
@@ -2156,8 +2261,9 @@ static int fit_sqw(bq_ctx *c, bq_fit *f, const SqForms &fm, const double *key)
 // what the two warped entry points check alike: the handle, the measure, its forms
 static int sq_args(bq_ctx *c, bq_fit *f, const double *mu, const double *cov, SqForms *fm)
 {
-    double kk;
-    BQCHK(integral_args(c, f, mu, cov, &kk));
+    BQCHK(check_fit(c, f));
+    BQCHK(launch_kernel_mean(c, f->d, nullptr, 0, f->h, f->w, Measure::gauss(mu, cov), nullptr,
+                             nullptr));
     return sq_forms(c, f->d, f->h, f->w, mu, cov, fm);
 }
 
@@ -2176,7 +2282,7 @@ extern "C" int bq_gp_sqintegral(bq_ctx *c, bq_fit *f, const double *mu, const do
     HIPCHK(c, hipSetDevice(c->device));
     BQCHK(sqw_alloc(c, f));
     double key[sizeof f->sq_key / sizeof(double)];
-    kmean_key(f, mu, cov, key);
+    sqw_key(f, mu, cov, key);
     BQCHK(fit_sqw(c, f, fm, key));
     if (r) {
         HIPCHK(c, hipMemcpyAsync(f->hvec, f->sqw.d() + sqw_plan(f->npad, f->d).o_r,
@@ -2224,7 +2330,7 @@ extern "C" int bq_gp_sqdesign(bq_ctx *c, bq_fit *f, const double *mu, const doub
     BQCHK(fit_grow(c, f->wout, sizeof(double) * 2 * Ap, "prediction results"));
     BQCHK(fit_grow(c, f->wz, sizeof(double) * (size_t)npad, "contiguous z"));
     double key[sizeof f->sq_key / sizeof(double)];
-    kmean_key(f, mu, cov, key);
+    sqw_key(f, mu, cov, key);
     BQCHK(fit_sqw(c, f, fm, key));
     const SqwPlan sp = sqw_plan(npad, d);
     const double *st = f->sqw.d();

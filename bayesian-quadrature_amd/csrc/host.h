@@ -769,13 +769,46 @@ int solve_rows_host(bq_ctx *c, const double *L, long ldl, int n, int npad, WideI
                     const double *B, int64_t nrhs, double *X);
 
 // ---- moments.hip ----------------------------------------------------------------------
-// The kernel mean of the measure N(mu, cov) (cov: d x d column-major) under k = h^2 N(. | .,
-// diag(w^2)): out[i] = h^2 N(x_i | mu, diag(w^2) + cov) at the n device points x, d x n, by
-// int_K_kernel on the context's stream (n == 0: no launch), and *kk = h^2 N(0 | 0, diag(w^2) +
-// 2 cov) on the host.  BQ_ERR_BAD_ARG, before anything is enqueued, for a mu or cov that is not
-// finite and for a diag(w^2) + cov or diag(w^2) + 2 cov whose host factor (GaussForm) fails.
+// The measure of an integral, as the caller's host arrays (include/bqhip.h has the three layouts):
+//   GAUSS  N(a, b):                      a = mu, d;      b = Sigma, d x d column-major
+//   BOX    uniform on prod_k [a_k, b_k]: a = lo, d;      b = hi, d
+//   MIX    sum_c pi_c N(a_c, b_c):       a = mu, d x C;  b = C blocks Sigma_c;  pi: C weights
+// This value is the only way a measure reaches launch_kernel_mean and the key of the KMEAN state.
+struct Measure {
+    enum Kind : int { GAUSS = 0, BOX = 1, MIX = 2 };
+    Kind kind;
+    int64_t C; // MIX: the components (as the caller gave them: checked by launch_kernel_mean)
+    const double *pi, *a, *b;
+    static Measure gauss(const double *mu, const double *cov)
+    {
+        return Measure{GAUSS, 1, nullptr, mu, cov};
+    }
+    static Measure box(const double *lo, const double *hi)
+    {
+        return Measure{BOX, 1, nullptr, lo, hi};
+    }
+    static Measure mix(int64_t C, const double *pi, const double *mu, const double *cov)
+    {
+        return Measure{MIX, C, pi, mu, cov};
+    }
+};
+// a mixture's forms as the device reads them: C GaussForm<d> of diag(w^2) + Sigma_c about mu_c,
+// then the C weights
+inline size_t mix_form_doubles(int d, int C) { return (size_t)C * (d + d * d + 1) + C; }
+// The kernel mean of the measure m under k = h^2 N(. | ., diag(w^2)): out[i] = kappa(x_i) at the n
+// device points x, d x n, on the context's stream (n == 0: no launch), and, with kk, *kk = the
+// prior variance of the integral, int int k m m, on the host.  GAUSS: int_K_kernel, kappa = h^2
+// N(x | mu, diag(w^2) + cov), kk = h^2 N(0 | 0, diag(w^2) + 2 cov).  BOX: int_K_box_kernel.  MIX:
+// int_K_mix_kernel over the forms in device memory at `forms` (mix_form_doubles; mix_forms below
+// writes them), kk summed on the host over the GaussForm of diag(w^2) + Sigma_c + Sigma_c'.
+// BQ_ERR_BAD_ARG, before anything is enqueued, for every illegal measure of include/bqhip.h: a
+// NULL array, an entry that is not finite, lo_k >= hi_k, C out of range, a negative weight or
+// weights that sum to zero, and a diag(w^2) + cov, or (with kk; GAUSS: always) a diag(w^2) + 2 cov
+// or + Sigma_c + Sigma_c', whose host factor (GaussForm) fails.
 int launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, const double *w,
-                       const double *mu, const double *cov, double *out, double *kk);
+                       const Measure &m, double *out, double *kk, const double *forms = nullptr);
+// the forms of a legal mixture for int_K_mix_kernel, mix_form_doubles(d, m.C) doubles on the host
+void mix_forms(int d, const double *w, const Measure &m, double *host);
 // the transforms and constants of square-root-warped quadrature (types.h, SqForms) for the kernel
 // (h, w) and the measure N(mu, cov), on the host.  BQ_ERR_BAD_ARG as launch_kernel_mean, and for a
 // diag(w^2) + 2 S, S = (diag(w^-2) + cov^-1)^-1, whose host factor fails.
@@ -902,12 +935,14 @@ struct bq_fit : FitCore {
     //             c, rho) in tr_key; a call with another key
     //             recomputes it
     //   KMEAN     kmean: kappa_X = the kernel mean of the measure   WIDE,       fit_kmean
-    //             N(mu, Sigma) at the fit's points, b = L^-1        the key
-    //             kappa_X, b.b; km_kk = the prior variance of the
-    //             integral, with the key (mu, Sigma) in km_key; a
-    //             call with another key recomputes it.  Nothing of
-    //             it depends on the targets: bq_gp_integral's mean
-    //             is one dot product b.z with the current z
+    //             (a Gaussian, a box or a mixture of Gaussians)     the key
+    //             at the fit's points, b = L^-1 kappa_X, b.b, and
+    //             a mixture's forms; km_kk = the prior variance of
+    //             the integral, with the key (the measure's kind
+    //             and numbers) in km_key; a call with another key
+    //             recomputes it.  Nothing of it depends on the
+    //             targets: bq_gp_integral's mean is one dot product
+    //             b.z with the current z
     //   SQW       sqw: square-root-warped quadrature under the      WIDE, ALPHA, fit_sqw
     //             measure N(mu, Sigma): r = W(X, X) alpha, b_w =    the key
     //             L^-1 r, the fit's transformed points with alpha,
@@ -952,11 +987,18 @@ struct bq_fit : FitCore {
     // designs that minimise the integrated variance (bq_gp_ivr): the steps' workspace (IvrPlan)
     // and T = Sigma(xc, xr), Ap x Rp, grown on demand and kept; the c columns follow V in wV2
     DevBuf ivr, ivrT;
-    // the integral of the fit under a Gaussian measure (bq_gp_integral, bq_gp_zdesign): kappa_X
-    // (npad) | b (npad) | b.b, b.z, allocated on the first call and kept; the measure it was
-    // computed for, [mu d | Sigma d x d] with zeros behind, and the host's share of the state
-    DevBuf kmean;
-    double km_key[BQ_MAXD + BQ_MAXD * BQ_MAXD] = {0};
+    // the integral of the fit under a measure (bq_gp_integral, bq_gp_zdesign and their _box and
+    // _mix twins): kappa_X (npad) | b (npad) | b.b, b.z, allocated on the first call and kept; a
+    // mixture's forms on the device (kmform, mix_form_doubles of the largest mixture) and on their
+    // way there (km_hform: read by a copy on the stream, so it lives as long as the fit),
+    // allocated on the first call with a mixture; the measure the state was computed for --
+    // [kind | mu d | Sigma d x d], [kind | lo d | hi d] or [kind, C | pi C | mu d x C | Sigma
+    // d x d x C], zeros behind, compared byte by byte -- and the host's share of the state
+    DevBuf kmean, kmform;
+    std::vector<double> km_hform;
+    static constexpr size_t KM_KEY_LEN =
+        2 + (size_t)BQ_MEASURE_MAX_COMP * (1 + BQ_MAXD + BQ_MAXD * BQ_MAXD);
+    double km_key[KM_KEY_LEN] = {0};
     double km_kk = 0, km_bb = 0;
     // designs that lower the integral's variance (bq_gp_zdesign): the steps' workspace (ZdPlan),
     // grown on demand and kept; the c columns follow V in wV2

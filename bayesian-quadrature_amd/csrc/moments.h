@@ -28,6 +28,19 @@ __device__ __forceinline__ double gauss_form_eval(const GaussForm<D> &f, const d
     return f.logc - 0.5 * maha;
 }
 
+// scale * exp(add + log N(x_i - mu | 0, C)) at point i of x (d x n): one point of int_K_kernel and
+// one component of int_K_mix_kernel, the same operations in the same order for both
+template <int D>
+__device__ __forceinline__ double int_K_point(const double *__restrict__ x, int i,
+                                              const GaussForm<D> &f, double scale, double add)
+{
+    double z[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+        z[k] = x[k + (long)i * D] - f.mu[k];
+    return scale * exp(add + gauss_form_eval<D>(f, z));
+}
+
 // out_i = scale * exp(add + log N(x_i - mu | 0, C)); also, if alpha != null,
 // accumulates sum_i out_i alpha_i into acc[0] (Z_mean) -- one block per 256 points
 template <int D>
@@ -40,11 +53,7 @@ __global__ __launch_bounds__(256) void int_K_kernel(const double *__restrict__ x
     const int i = blockIdx.x * 256 + threadIdx.x;
     double v = 0.0;
     if (i < n) {
-        double z[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-            z[k] = x[k + (long)i * D] - f.mu[k];
-        v = scale * exp(add + gauss_form_eval<D>(f, z));
+        v = int_K_point<D>(x, i, f, scale, add);
         if (out)
             out[i] = v;
         if (alpha)
@@ -61,6 +70,56 @@ __global__ __launch_bounds__(256) void int_K_kernel(const double *__restrict__ x
         if (threadIdx.x == 0)
             acc[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
     }
+}
+
+// The kernel mean of a mixture of Gaussians, out_i = sum_c pi_c scale exp(log N(x_i - mu_c | 0,
+// C_c)): one thread per point, the components in ascending c.  forms: the C host forms, one per
+// component, pi: their weights, both in device memory.  The first term is the plain product, every
+// later one a single fma: with C = 1 and pi = 1 these are int_K_kernel's bits.
+template <int D>
+__global__ __launch_bounds__(256) void int_K_mix_kernel(const double *__restrict__ x, int n,
+                                                        const GaussForm<D> *__restrict__ forms,
+                                                        const double *__restrict__ pi, int C,
+                                                        double scale, double *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    double v = pi[0] * int_K_point<D>(x, i, forms[0], scale, 0.0);
+    for (int c = 1; c < C; ++c)
+        v = fma(pi[c], int_K_point<D>(x, i, forms[c], scale, 0.0), v);
+    out[i] = v;
+}
+
+// Phi((hi - t) / w) - Phi((lo - t) / w) from a = (lo - t) / (sqrt2 w) < b = (hi - t) / (sqrt2 w),
+// without cancellation in either tail: a difference of two erfc where both arguments lie on one
+// side of the point, a sum of two erf where they straddle it
+__device__ __forceinline__ double box_dphi(double a, double b)
+{
+    if (a > 0.0)
+        return 0.5 * (erfc(a) - erfc(b));
+    if (b < 0.0)
+        return 0.5 * (erfc(-b) - erfc(-a));
+    return 0.5 * (erf(b) + erf(-a));
+}
+
+// The kernel mean of the uniform measure on a box, out_i = scale prod_k dPhi_k(x_ik) / L_k: one
+// thread per point, the factors multiplied in ascending k.  (struct BoxForm<D>: types.h)
+template <int D>
+__global__ __launch_bounds__(256) void int_K_box_kernel(const double *__restrict__ x, int n,
+                                                        BoxForm<D> f, double scale,
+                                                        double *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    double v = scale;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const double t = x[k + (long)i * D];
+        v *= box_dphi((f.lo[k] - t) * f.rw[k], (f.hi[k] - t) * f.rw[k]) * f.rl[k];
+    }
+    out[i] = v;
 }
 
 // out_ij = scale * exp(log N([x1_i - mu; x2_j - mu] | 0, C2)), n1 x n2 column-major.

@@ -293,32 +293,209 @@ int dev_iikk(bq_ctx *c, int d, const double *x_dev, int n, double h1, const doub
 
 } // namespace
 
-// the kernel mean of a Gaussian measure at device points and the prior variance of the integral
-// (host.h; fit.hip, fit_kmean and bq_gp_zdesign)
-int bqh::launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, const double *w,
-                            const double *mu, const double *cov, double *out, double *kk)
+namespace {
+
+// what is wrong with a measure's arrays, before any arithmetic: NULL, not finite, out of range
+int check_measure(bq_ctx *c, int d, const Measure &m)
 {
-    for (int k = 0; k < d; ++k)
-        if (!std::isfinite(mu[k]))
+    if (!m.a || !m.b || (m.kind == Measure::MIX && !m.pi))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    auto finite = [](const double *v, size_t n) {
+        for (size_t k = 0; k < n; ++k)
+            if (!std::isfinite(v[k]))
+                return false;
+        return true;
+    };
+    switch (m.kind) {
+    case Measure::GAUSS:
+        if (!finite(m.a, d))
             return fail(c, BQ_ERR_BAD_ARG, "the measure's mean must be finite");
-    for (int k = 0; k < d * d; ++k)
-        if (!std::isfinite(cov[k]))
+        if (!finite(m.b, (size_t)d * d))
             return fail(c, BQ_ERR_BAD_ARG, "the measure's covariance must be finite");
-    const Small S = small_from_colmajor(cov, d);
-    const Small C1 = cov_plus_w2(S, w, 1.0);
+        return BQ_OK;
+    case Measure::BOX:
+        if (!finite(m.a, d) || !finite(m.b, d))
+            return fail(c, BQ_ERR_BAD_ARG, "the box's ends must be finite");
+        for (int k = 0; k < d; ++k)
+            if (!(m.a[k] < m.b[k]))
+                return fail(c, BQ_ERR_BAD_ARG, "the box needs lo < hi on every axis");
+        return BQ_OK;
+    case Measure::MIX: {
+        if (m.C < 1 || m.C > BQ_MEASURE_MAX_COMP)
+            return fail(c, BQ_ERR_BAD_ARG, "a mixture has 1..%d components", BQ_MEASURE_MAX_COMP);
+        const size_t C = (size_t)m.C;
+        if (!finite(m.pi, C) || !finite(m.a, C * d) || !finite(m.b, C * d * d))
+            return fail(c, BQ_ERR_BAD_ARG, "the mixture's weights, means and covariances must be "
+                                           "finite");
+        double sum = 0.0;
+        for (size_t k = 0; k < C; ++k) {
+            if (m.pi[k] < 0.0)
+                return fail(c, BQ_ERR_BAD_ARG, "the mixture's weights must not be negative");
+            sum += m.pi[k];
+        }
+        if (!(sum > 0.0))
+            return fail(c, BQ_ERR_BAD_ARG, "the mixture's weights sum to zero");
+        return BQ_OK;
+    }
+    }
+    return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+}
+
+// -(d log 2pi + log|C|) / 2 from C's lower factor: the logc of fill_form
+double form_logc(const Small &L)
+{
+    double logdet = 0.0;
+    for (int r = 0; r < L.n; ++r)
+        logdet += 2.0 * std::log(L(r, r));
+    return -0.5 * (L.n * LOG_2PI + logdet);
+}
+
+// N(0 | 0, diag(w^2) + 2 cov) h^2 of a Gaussian, or BQ_ERR_BAD_ARG
+int gauss_measure(bq_ctx *c, int d, double h, const double *w, const Measure &m, Small &C1,
+                  double *kk)
+{
+    const Small S = small_from_colmajor(m.b, d);
+    C1 = cov_plus_w2(S, w, 1.0);
     Small L1 = C1, L2 = cov_plus_w2(S, w, 2.0);
     if (!small_chol(L1) || !small_chol(L2))
         return fail(c, BQ_ERR_BAD_ARG,
                     "the measure's covariance plus diag(w^2) is not positive definite");
-    if (kk) {
-        double logdet = 0.0;
-        for (int r = 0; r < d; ++r)
-            logdet += 2.0 * std::log(L2(r, r));
-        *kk = h * h * std::exp(-0.5 * (d * LOG_2PI + logdet));
+    if (kk)
+        *kk = h * h * std::exp(form_logc(L2));
+    return BQ_OK;
+}
+
+// h^2 prod_k I_k / L_k^2 of a box, I_k = L_k erf(L_k / (sqrt2 w_k)) + w_k sqrt(2 / pi) expm1(-L_k^2
+// / (2 w_k^2)): expm1, since for a box narrow against w_k the two terms are L_k^2 sqrt(2 / pi) /
+// w_k and half of it, and exp(.) - 1 would carry 1's rounding into the second
+double box_kk(int d, double h, const double *w, const Measure &m)
+{
+    double kk = h * h;
+    for (int k = 0; k < d; ++k) {
+        const double Lk = m.b[k] - m.a[k], r = Lk / (M_SQRT2 * w[k]);
+        const double Ik = Lk * std::erf(r) + w[k] * std::sqrt(2.0 / M_PI) * std::expm1(-(r * r));
+        kk *= Ik / (Lk * Lk);
     }
-    if (n == 0)
+    return kk;
+}
+
+// The factors a mixture needs, or BQ_ERR_BAD_ARG: diag(w^2) + Sigma_c for every c, and with kk
+// every diag(w^2) + Sigma_c + Sigma_c', over which *kk is summed in ascending c, then c'.  The
+// terms (c, c') and (c', c) have the same bits -- the sum of the two covariances commutes and the
+// Mahalanobis term squares the difference of the means -- so each pair is factored once.
+int mix_measure(bq_ctx *c, int d, double h, const double *w, const Measure &m, double *kk)
+{
+    const int C = (int)m.C;
+    const size_t dd = (size_t)d * d;
+    for (int p = 0; p < C; ++p) {
+        Small L1 = cov_plus_w2(small_from_colmajor(m.b + p * dd, d), w, 1.0);
+        if (!small_chol(L1))
+            return fail(c, BQ_ERR_BAD_ARG,
+                        "component %d's covariance plus diag(w^2) is not positive definite", p);
+    }
+    if (!kk)
         return BQ_OK;
-    return dev_int_K(c, d, x, n, mu, C1, h * h, 0.0, out, nullptr, nullptr, nullptr);
+    std::vector<double> term((size_t)C * C);
+    for (int p = 0; p < C; ++p)
+        for (int q = p; q < C; ++q) {
+            Small M;
+            M.n = d;
+            for (int r = 0; r < d; ++r)
+                for (int s = 0; s < d; ++s)
+                    M(r, s) = (m.b[p * dd + r + s * d] + m.b[q * dd + r + s * d]) +
+                              (r == s ? w[r] * w[r] : 0.0);
+            if (!small_chol(M))
+                return fail(c, BQ_ERR_BAD_ARG,
+                            "the covariances of components %d and %d plus diag(w^2) are not "
+                            "positive definite", p, q);
+            const Small Li = small_inv_lower(M);
+            double maha = 0.0;
+            for (int r = 0; r < d; ++r) {
+                double y = 0.0;
+                for (int s = 0; s <= r; ++s)
+                    y += Li(r, s) * (m.a[s + (size_t)p * d] - m.a[s + (size_t)q * d]);
+                maha += y * y;
+            }
+            term[(size_t)p * C + q] = term[(size_t)q * C + p] =
+                h * h * std::exp(form_logc(M) - 0.5 * maha);
+        }
+    double sum = 0.0;
+    for (int p = 0; p < C; ++p)
+        for (int q = 0; q < C; ++q) {
+            const double t = m.pi[p] * m.pi[q] * term[(size_t)p * C + q];
+            sum = (p | q) ? sum + t : t;
+        }
+    *kk = sum;
+    return BQ_OK;
+}
+
+} // namespace
+
+// the forms of a legal mixture as int_K_mix_kernel reads them (host.h; fit.hip, kmean_enqueue)
+void bqh::mix_forms(int d, const double *w, const Measure &m, double *host)
+{
+    const int C = (int)m.C;
+    BQ_DISPATCH_D(d, {
+        GaussForm<D> *f = reinterpret_cast<GaussForm<D> *>(host);
+        for (int p = 0; p < C; ++p)
+            (void)fill_form<D>(f[p], m.a + (size_t)p * D,
+                               cov_plus_w2(small_from_colmajor(m.b + (size_t)p * D * D, D), w, 1.0));
+        std::memcpy(f + C, m.pi, sizeof(double) * C);
+    });
+}
+
+// the kernel mean of a measure at device points and the prior variance of the integral
+// (host.h; fit.hip, kmean_enqueue and the designs' bodies)
+int bqh::launch_kernel_mean(bq_ctx *c, int d, const double *x, int n, double h, const double *w,
+                            const Measure &m, double *out, double *kk, const double *forms)
+{
+    BQCHK(check_measure(c, d, m));
+    const int nb = (n + 255) / 256;
+    // (the launch profiler's row of a kernel mean: the points read and the values written)
+    const double work = 8.0 * (d + 1.0) * n;
+    switch (m.kind) {
+    case Measure::GAUSS: {
+        Small C1;
+        BQCHK(gauss_measure(c, d, h, w, m, C1, kk));
+        if (n == 0)
+            return BQ_OK;
+        Bracket br(c, BQ_K_REDUCE, work);
+        return dev_int_K(c, d, x, n, m.a, C1, h * h, 0.0, out, nullptr, nullptr, nullptr);
+    }
+    case Measure::BOX: {
+        if (kk)
+            *kk = box_kk(d, h, w, m);
+        if (n == 0)
+            return BQ_OK;
+        Bracket br(c, BQ_K_REDUCE, work);
+        BQ_DISPATCH_D(d, {
+            BoxForm<D> f;
+            for (int k = 0; k < D; ++k) {
+                f.lo[k] = m.a[k], f.hi[k] = m.b[k];
+                f.rw[k] = 1.0 / (M_SQRT2 * w[k]), f.rl[k] = 1.0 / (m.b[k] - m.a[k]);
+            }
+            hipLaunchKernelGGL(int_K_box_kernel<D>, dim3(nb), dim3(256), 0, c->stream, x, n, f,
+                               h * h, out);
+        });
+        break;
+    }
+    case Measure::MIX: {
+        BQCHK(mix_measure(c, d, h, w, m, kk));
+        if (n == 0)
+            return BQ_OK;
+        if (!forms)
+            return fail(c, BQ_ERR_BAD_ARG, "a mixture's forms are not on the device");
+        Bracket br(c, BQ_K_REDUCE, work);
+        BQ_DISPATCH_D(d, {
+            const GaussForm<D> *f = reinterpret_cast<const GaussForm<D> *>(forms);
+            hipLaunchKernelGGL(int_K_mix_kernel<D>, dim3(nb), dim3(256), 0, c->stream, x, n, f,
+                               reinterpret_cast<const double *>(f + m.C), (int)m.C, h * h, out);
+        });
+        break;
+    }
+    }
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
 }
 
 // the transforms and constants of square-root-warped quadrature (host.h; types.h, SqForms; fit.hip,
@@ -400,6 +577,65 @@ extern "C" int bq_int_K(bq_ctx *c, const double *x, int64_t d, int64_t n, double
     HIPCHK(c, hipMemcpyAsync(out, od.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BQ_OK;
+}
+
+namespace {
+
+// bq_int_K_box and bq_int_K_mix: kappa at n host points, kk on the host
+int int_K_measure(bq_ctx *c, const double *x, int64_t d, int64_t n, double h, const double *w,
+                  const Measure &m, double *out, double *kk)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    if (!w || n < 0 || n > INT32_MAX || (!out && !kk) || (out && n && !x))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    // (the measure is checked, with the factors that only kk needs, before anything is allocated)
+    double kk0 = 0.0;
+    BQCHK(launch_kernel_mean(c, (int)d, nullptr, 0, h, w, m, nullptr, kk ? &kk0 : nullptr));
+    if (!out || n == 0) {
+        if (kk)
+            *kk = kk0;
+        return BQ_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf xd, od, fd;
+    std::vector<double> hf;
+    HIPCHK(c, xd.alloc(sizeof(double) * d * n));
+    HIPCHK(c, od.alloc(sizeof(double) * n));
+    HIPCHK(c, hipMemcpyAsync(xd.p, x, sizeof(double) * d * n, hipMemcpyHostToDevice, c->stream));
+    if (m.kind == Measure::MIX) {
+        hf.resize(mix_form_doubles((int)d, (int)m.C));
+        HIPCHK(c, fd.alloc(sizeof(double) * hf.size()));
+        mix_forms((int)d, w, m, hf.data());
+        HIPCHK(c, hipMemcpyAsync(fd.p, hf.data(), sizeof(double) * hf.size(),
+                                 hipMemcpyHostToDevice, c->stream));
+    }
+    const int st = launch_kernel_mean(c, (int)d, xd.d(), (int)n, h, w, m, od.d(), nullptr, fd.d());
+    if (st == BQ_OK)
+        (void)hipMemcpyAsync(out, od.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (x, hf and the buffers are read until here)
+    HIPCHK(c, hipGetLastError());
+    if (st == BQ_OK && kk)
+        *kk = kk0;
+    return st;
+}
+
+} // namespace
+
+extern "C" int bq_int_K_box(bq_ctx *c, const double *x, int64_t d, int64_t n, double h,
+                            const double *w, const double *lo, const double *hi, double *out,
+                            double *kk)
+{
+    return int_K_measure(c, x, d, n, h, w, Measure::box(lo, hi), out, kk);
+}
+
+extern "C" int bq_int_K_mix(bq_ctx *c, const double *x, int64_t d, int64_t n, double h,
+                            const double *w, int64_t C, const double *pi, const double *mu,
+                            const double *cov, double *out, double *kk)
+{
+    return int_K_measure(c, x, d, n, h, w, Measure::mix(C, pi, mu, cov), out, kk);
 }
 
 extern "C" int bq_int_K1_K2(bq_ctx *c, const double *x1, int64_t n1, const double *x2, int64_t n2,

@@ -202,6 +202,13 @@ struct GaussForm {
     double logc;         // -(D log 2pi + log|C|) / 2
 };
 
+// the uniform measure on a box (moments.h, int_K_box_kernel): per axis the two ends and, from the
+// host, 1 / (sqrt2 w) and 1 / (hi - lo)
+template <int D>
+struct BoxForm {
+    double lo[D], hi[D], rw[D], rl[D];
+};
+
 // one job of rows_step_kernel (gemm.h)
 struct RowsJob {
     double *C;

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .measures import BoxMeasure, GaussianMixture, Measure
 
 _dp = L._dp
 
@@ -47,6 +48,24 @@ def _flat_groups(groups):
     start = np.zeros(len(groups) + 1, dtype=np.int64)
     np.cumsum(np.array([g.size for g in groups], dtype=np.int64), out=start[1:])
     return np.ascontiguousarray(idx), start
+
+
+def _measure_args(m):
+    """("_box" | "_mix", the C arguments that stand for (mu, cov)) of a measure object."""
+    if isinstance(m, BoxMeasure):
+        return "_box", (L.dptr(m.lo), L.dptr(m.hi))
+    if isinstance(m, GaussianMixture):
+        return "_mix", (len(m), L.dptr(m.weights), L.dptr(m.means), L.dptr(m.covs))
+    raise TypeError("unknown measure %r" % (m,))
+
+
+def _sq_gaussian_only(mu):
+    if isinstance(mu, Measure):
+        raise ValueError(
+            "square-root-warped quadrature takes a single Gaussian (mu, cov) only: on a box the "
+            "prior variance alpha^T Q alpha of the warped integral needs a bivariate normal "
+            "distribution function and is not closed form, and for a mixture it is a sum over "
+            "pairs of components that is not built")
 
 
 class Engine(object):
@@ -269,6 +288,31 @@ class Engine(object):
         self._check(self._lib.bq_int_K(self._ctx, L.dptr(x), d, n, float(h), L.dptr(w), L.dptr(mu),
                                        L.dptr(cov), L.dptr(out)))
         return out
+
+    def int_K_box(self, x, h, w, measure, want_kk=False):
+        """kappa(x_i) = int k(x_i, x') dx' / vol over the box of a ``measures.BoxMeasure``, (n,)
+        (bq_int_K_box); ``want_kk`` appends kk, the prior variance of the integral."""
+        return self._int_K_measure(x, h, w, measure, BoxMeasure, want_kk)
+
+    def int_K_mix(self, x, h, w, measure, want_kk=False):
+        """kappa(x_i) = sum_c pi_c int k(x_i, x') N(x' | mu_c, Sigma_c) dx' for a
+        ``measures.GaussianMixture``, (n,) (bq_int_K_mix); ``want_kk`` appends kk."""
+        return self._int_K_measure(x, h, w, measure, GaussianMixture, want_kk)
+
+    def _int_K_measure(self, x, h, w, measure, kind, want_kk):
+        if not isinstance(measure, kind):
+            raise TypeError("measure must be a %s" % kind.__name__)
+        x = _pts(x)
+        d, n = x.shape
+        w = _wvec(w, d)
+        if measure.d != d:
+            raise ValueError("the measure has dimension %d, the points %d" % (measure.d, d))
+        out, kk = np.empty(n), C.c_double()
+        name, margs = _measure_args(measure)
+        self._check(getattr(self._lib, "bq_int_K" + name)(
+            self._ctx, L.dptr(x), d, n, float(h), L.dptr(w), *(margs + (
+                L.dptr(out), C.byref(kk) if want_kk else None))))
+        return (out, float(kk.value)) if want_kk else out
 
     def int_K1_K2(self, x1, x2, h1, w1, h2, w2, mu, cov):
         x1, x2 = _pts(x1), _pts(x2)
@@ -1089,27 +1133,46 @@ class Fit(object):
         res = (piv[:r], gain[:r], float(ivar0.value), resid_c if xr is None else resid_r, resid_c)
         return res + (score0,) if want_scores else res
 
-    def integral(self, mu, cov, want_weights=False):
+    def _measure(self, mu, cov):
+        """("" | "_box" | "_mix", the C arguments of the measure): (mu, cov) spell a Gaussian; a
+        ``measures`` object in place of mu, with no cov, is that measure.  The returned arrays
+        are referenced by the tuple, which the caller holds across the call."""
+        if isinstance(mu, Measure):
+            if cov is not None:
+                raise TypeError("a measure object comes without a cov")
+            if mu.d != self.d:
+                raise ValueError("the measure has dimension %d, the fit %d" % (mu.d, self.d))
+            return _measure_args(mu)
+        if cov is None:
+            raise TypeError("a Gaussian measure needs its cov")
+        mu, cov = self._eng._mc(self.d, mu, cov)
+        return "", (L.dptr(mu), L.dptr(cov))
+
+    def integral(self, mu, cov=None, want_weights=False):
         """(mean, var[, weights]): vanilla Bayesian quadrature of the fit, the posterior mean and
-        variance of Z = int f(x) N(x | mu, cov) dx (bq_gp_integral).  var is latent, like
+        variance of Z = int f(x) N(x | mu, cov) dx (bq_gp_integral) -- or, with a
+        ``measures.BoxMeasure`` or ``measures.GaussianMixture`` in place of mu and no cov, of the
+        integral against that measure (bq_gp_integral_box, bq_gp_integral_mix; TypeError for a
+        measure object with a cov, ValueError for one of another dimension).  var is latent, like
         ``predict``'s, and not clamped at 0.  ``want_weights`` appends the quadrature weights
         Kxx^-1 kappa_X, (n,): mean = weights . y.  The kernel means of the measure at the fit's
         points stay with the fit: a second call with the same measure is one dot product.
         ValueError for a measure that is not finite or whose covariance is not positive
         definite."""
         e = self._eng
-        mu, cov = e._mc(self.d, mu, cov)
+        name, margs = self._measure(mu, cov)
         mean, var = C.c_double(), C.c_double()
         wts = np.empty(self.n) if want_weights else None
-        e._check(e._lib.bq_gp_integral(e._ctx, self._handle(), L.dptr(mu), L.dptr(cov),
-                                       C.byref(mean), C.byref(var), L.dptr(wts)))
+        e._check(getattr(e._lib, "bq_gp_integral" + name)(
+            e._ctx, self._handle(), *(margs + (C.byref(mean), C.byref(var), L.dptr(wts)))))
         res = (float(mean.value), float(var.value))
         return res + (wts,) if want_weights else res
 
-    def integral_design(self, xc, q, mu, cov, nugget=0.0, tol=0.0, want_scores=False):
+    def integral_design(self, xc, q, mu, cov=None, nugget=0.0, tol=0.0, want_scores=False):
         """(piv, gain, zvar0, resid_u, resid_c[, score0]): the greedy design that minimises the
         posterior variance of Z = int f(x) N(x | mu, cov) dx by observing at most q of the
-        candidates xc, on the device (bq_gp_zdesign; sequential Bayesian quadrature).  Each step
+        candidates xc, on the device (bq_gp_zdesign; sequential Bayesian quadrature); a
+        ``measures`` object in place of mu, with no cov, as in ``integral``.  Each step
         takes the candidate whose observation (with noise ``nugget`` >= 0, absolute) lowers var Z
         the most, the lowest index among equals: piv, (rank,) int64; gain, (rank,), the drop each
         step brought; zvar0 is ``integral``'s var, so that zvar0 - gain.sum() is what is left --
@@ -1122,17 +1185,17 @@ class Fit(object):
         if xc.shape[0] != self.d:
             raise ValueError("dimension mismatch")
         e = self._eng
-        mu, cov = e._mc(self.d, mu, cov)
+        name, margs = self._measure(mu, cov)
         A, q = xc.shape[1], int(q)
         piv, gain = np.empty(max(q, 0), dtype=np.int64), np.empty(max(q, 0))
         resid_u, resid_c = np.empty(A), np.empty(A)
         score0 = np.empty(A) if want_scores else None
         zvar0, rank = C.c_double(), C.c_int64()
-        e._check(e._lib.bq_gp_zdesign(e._ctx, self._handle(), L.dptr(mu), L.dptr(cov), L.dptr(xc),
-                                      A, q, float(nugget), float(tol),
-                                      piv.ctypes.data_as(L._i64p), L.dptr(gain), C.byref(zvar0),
-                                      L.dptr(resid_u), L.dptr(resid_c), L.dptr(score0),
-                                      C.byref(rank)))
+        e._check(getattr(e._lib, "bq_gp_zdesign" + name)(
+            e._ctx, self._handle(), *(margs + (
+                L.dptr(xc), A, q, float(nugget), float(tol), piv.ctypes.data_as(L._i64p),
+                L.dptr(gain), C.byref(zvar0), L.dptr(resid_u), L.dptr(resid_c), L.dptr(score0),
+                C.byref(rank)))))
         r = int(rank.value)
         res = (piv[:r], gain[:r], float(zvar0.value), resid_u, resid_c)
         return res + (score0,) if want_scores else res
@@ -1148,6 +1211,7 @@ class Fit(object):
         ValueError for a measure that is not finite or whose covariance is not positive
         definite."""
         e = self._eng
+        _sq_gaussian_only(mu)
         mu, cov = e._mc(self.d, mu, cov)
         sq, var = C.c_double(), C.c_double()
         r = np.empty(self.n) if want_r else None
@@ -1167,6 +1231,7 @@ class Fit(object):
         if xc.shape[0] != self.d:
             raise ValueError("dimension mismatch")
         e = self._eng
+        _sq_gaussian_only(mu)
         mu, cov = e._mc(self.d, mu, cov)
         A, q = xc.shape[1], int(q)
         piv, gain = np.empty(max(q, 0), dtype=np.int64), np.empty(max(q, 0))

@@ -18,7 +18,8 @@ import numpy as np
 import scipy.optimize as optim
 
 from . import util
-from .engine import get_engine
+from .engine import get_engine, _sq_gaussian_only
+from .measures import Measure
 
 DTYPE = np.float64
 
@@ -794,9 +795,18 @@ class GP(object):
         return np.empty(0, dtype=DTYPE) if out is None else out[5]
 
     def _measure(self, mu, cov):
-        """(mu, cov, key): the Gaussian measure of an integral as a (d,) vector and a (d, d)
-        matrix, checked, and its memoisation key."""
+        """(mu, cov, key): the measure of an integral, checked, and its memoisation key.  A
+        Gaussian is a (d,) vector and a (d, d) matrix; a ``measures.BoxMeasure`` or
+        ``measures.GaussianMixture`` in place of mu, with no cov, comes back as (measure, None)."""
         d = 1 if self._x.ndim == 1 else self._x.shape[0]
+        if isinstance(mu, Measure):
+            if cov is not None:
+                raise TypeError("a measure object comes without a cov")
+            if mu.d != d:
+                raise ValueError("the measure has dimension %d, the GP %d" % (mu.d, d))
+            return mu, None, mu.key
+        if cov is None:
+            raise TypeError("a Gaussian measure needs its cov")
         mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=DTYPE)
         cov = np.ascontiguousarray(np.atleast_2d(cov), dtype=DTYPE)
         if mu.shape != (d,):
@@ -807,19 +817,30 @@ class GP(object):
             raise ValueError("the measure must be finite")
         return mu, cov, (mu.tobytes(), cov.tobytes())
 
+    @staticmethod
+    def _margs(mu, cov):
+        """The measure as the positional arguments of the fit's calls: (mu, cov) for a Gaussian,
+        (measure,) for an object."""
+        return (mu,) if cov is None else (mu, cov)
+
     def _integral(self, mu, cov):
         mu, cov, key = self._measure(mu, cov)
         return self._memo(("integral", key),
-                          lambda: self._device_fit().integral(mu, cov, want_weights=True))
+                          lambda: self._device_fit().integral(*self._margs(mu, cov),
+                                                              want_weights=True))
 
-    def integral(self, mu, cov):
+    def integral(self, mu, cov=None):
         """(mean, var): vanilla Bayesian quadrature of the GP, the posterior mean and variance of
         ``Z = int f(x) N(x | mu, cov) dx`` (engine.Fit.integral, bq_gp_integral): for the Gaussian
-        kernel and a Gaussian measure every ingredient is closed form.  ``var`` is latent, like
-        ``var(xo)`` without s^2.  A view of the fit, memoised like ``log_lh``."""
+        kernel and a Gaussian measure every ingredient is closed form.  So it is for the uniform
+        measure on a box and for a mixture of Gaussians: a ``measures.BoxMeasure`` or
+        ``measures.GaussianMixture`` in place of ``mu``, with no ``cov``, integrates against that
+        (here and in ``integral_weights``, ``integral_design`` and ``integral_scores``).  ``var``
+        is latent, like ``var(xo)`` without s^2.  A view of the fit, memoised per measure like
+        ``log_lh``."""
         return self._integral(mu, cov)[:2]
 
-    def integral_weights(self, mu, cov):
+    def integral_weights(self, mu, cov=None):
         """(n,): the quadrature weights ``Kxx^-1 kappa_X`` of ``integral``, whose mean is
         ``integral_weights . y``."""
         return self._integral(mu, cov)[2].copy()
@@ -841,10 +862,10 @@ class GP(object):
         if q > xo.shape[-1]:
             raise ValueError("q = %d steps over %d points" % (q, xo.shape[-1]))
         return self._device_fit().integral_design(
-            xo, q, mu, cov, nugget=float(self._s) ** 2 if noisy else 0.0, tol=float(tol),
+            xo, q, *self._margs(mu, cov), nugget=float(self._s) ** 2 if noisy else 0.0, tol=float(tol),
             want_scores=want_scores)
 
-    def integral_design(self, xo, q, mu, cov, noisy=True, tol=0.0, return_info=False):
+    def integral_design(self, xo, q, mu, cov=None, noisy=True, tol=0.0, return_info=False):
         """The indices into ``xo`` of a batch of at most ``q`` points to evaluate next, chosen to
         lower the posterior variance of ``Z = int f(x) N(x | mu, cov) dx`` the most, one point at
         a time with the points before it counted as observed (sequential Bayesian quadrature) --
@@ -867,7 +888,7 @@ class GP(object):
         info = {"gain": gain, "zvar0": zvar0, "resid": resid_c, "resid_u": resid_u}
         return (piv, info) if return_info else piv
 
-    def integral_scores(self, xo, mu, cov, noisy=True):
+    def integral_scores(self, xo, mu, cov=None, noisy=True):
         """(M,): how much observing each point of ``xo`` alone would lower the posterior variance
         of ``Z = int f(x) N(x | mu, cov) dx`` -- the acquisition surface that
         ``integral_design``'s first step takes the maximum of (arguments as there)."""
@@ -881,6 +902,7 @@ class GP(object):
         ``sq = int m(x)^2 N(x | mu, cov) dx`` -- the integral of l has mean alpha0 + sq / 2 -- and
         ``var`` is its variance, latent like ``integral``'s.  ``wsabi.SqrtBQ`` keeps alpha0.  A view
         of the fit, memoised like ``integral``."""
+        _sq_gaussian_only(mu)
         mu, cov, key = self._measure(mu, cov)
         return self._memo(("sq_integral", key), lambda: self._device_fit().sq_integral(mu, cov))
 
@@ -894,6 +916,7 @@ class GP(object):
             raise ValueError("invalid value for tol: %s" % tol)
         if xo.ndim > 2:
             raise ValueError("points must be a vector or a d x M matrix")
+        _sq_gaussian_only(mu)
         mu, cov, _ = self._measure(mu, cov)
         if xo.size == 0:
             return None

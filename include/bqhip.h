@@ -517,6 +517,50 @@ int bq_gp_integral(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov
 int bq_gp_zdesign(bq_ctx *ctx, bq_fit *fit, const double *mu, const double *cov, const double *xc,
                   int64_t A, int64_t q, double nugget, double tol, int64_t *piv, double *gain,
                   double *zvar0, double *resid_u, double *resid_c, double *score0, int64_t *rank);
+/* bq_gp_integral and bq_gp_zdesign under two more measures.  Everything but kappa and kk is those
+ * two contracts word for word: b = L^-1 kappa_X, mean = b . z, var = kk - b . b not clamped, the
+ * weights, u_a = kappa(xc_a) - v_a . b, the recurrence with its stop, tie and NaN rules, the
+ * outputs that may be NULL, what is allocated when, and the state kept with the fit -- one state,
+ * for the measure of the last call, whatever its kind: a measure of another kind, or other numbers
+ * of the same kind, recomputes it.  A box and a Gaussian with the same numbers are two measures.
+ *
+ * The uniform measure on the box prod_k [lo_k, hi_k] (lo, hi: d doubles each), density 1 / vol.
+ * With L_k = hi_k - lo_k and Phi the standard normal distribution function:
+ *   kappa(x) = h^2 prod_k (Phi((hi_k - x_k) / w_k) - Phi((lo_k - x_k) / w_k)) / L_k,
+ *   kk       = h^2 prod_k (L_k erf(L_k / (sqrt2 w_k)) + w_k sqrt(2 / pi) expm1(-L_k^2 / (2 w_k^2)))
+ *              / L_k^2.
+ * The difference of the two Phi is taken from erfc on the side of x_k where both ends lie, and as a
+ * sum of two erf where x_k lies between them: no cancellation in either tail.
+ * BQ_ERR_BAD_ARG, beyond the Gaussian entry point's: lo or hi == NULL, a non-finite entry, or
+ * lo_k >= hi_k.
+ *
+ * The mixture sum_c pi_c N(mu_c, Sigma_c), c < C <= BQ_MEASURE_MAX_COMP.  pi: C weights, finite,
+ * >= 0 and not all zero, used as given and NOT normalised; mu: d x C column-major; cov: C
+ * column-major d x d blocks, each symmetric, any of which may be zero (a point mass at mu_c: an
+ * empirical measure is a mixture of those).
+ *   kappa(x) = sum_c pi_c h^2 N(x | mu_c, diag(w^2) + Sigma_c)               in ascending c,
+ *   kk       = sum_c sum_c' pi_c pi_c' h^2 N(mu_c - mu_c' | 0, diag(w^2) + Sigma_c + Sigma_c')
+ *                                                                  in ascending c, then c'.
+ * Each component is evaluated as bq_int_K evaluates its measure; the first term of a sum is the
+ * plain product and every later one a single fma.  So C = 1 with pi = 1 gives the bits of the
+ * Gaussian entry point in every output.
+ * BQ_ERR_BAD_ARG, beyond the Gaussian entry point's: pi, mu or cov == NULL, C < 1 or C >
+ * BQ_MEASURE_MAX_COMP, a non-finite entry, a negative weight, weights that sum to zero, or a
+ * diag(w^2) + Sigma_c or diag(w^2) + Sigma_c + Sigma_c' that is not positive definite.
+ * All of it is checked before anything is allocated, and nothing is written. */
+#define BQ_MEASURE_MAX_COMP 64
+int bq_gp_integral_box(bq_ctx *ctx, bq_fit *fit, const double *lo, const double *hi, double *mean,
+                       double *var, double *weights);
+int bq_gp_integral_mix(bq_ctx *ctx, bq_fit *fit, int64_t C, const double *pi, const double *mu,
+                       const double *cov, double *mean, double *var, double *weights);
+int bq_gp_zdesign_box(bq_ctx *ctx, bq_fit *fit, const double *lo, const double *hi,
+                      const double *xc, int64_t A, int64_t q, double nugget, double tol,
+                      int64_t *piv, double *gain, double *zvar0, double *resid_u, double *resid_c,
+                      double *score0, int64_t *rank);
+int bq_gp_zdesign_mix(bq_ctx *ctx, bq_fit *fit, int64_t C, const double *pi, const double *mu,
+                      const double *cov, const double *xc, int64_t A, int64_t q, double nugget,
+                      double tol, int64_t *piv, double *gain, double *zvar0, double *resid_u,
+                      double *resid_c, double *score0, int64_t *rank);
 /* Square-root-warped Bayesian quadrature of a resident fit (WSABI-L, Gunter et al. 2014) for an
  * integrand l >= alpha0: the fit's targets are g = sqrt(2 (l - alpha0)), one zero-mean GP, and
  * l = alpha0 + g^2 / 2 is linearised about the posterior mean m(x) = k(x, X) alpha, alpha =
@@ -628,6 +672,15 @@ int bq_batch_fit_predict(bq_ctx *ctx, int64_t nprob, const double *x, const doub
  * out_i = h^2 N(x_i | mu, diag(w^2) + cov)                       gauss_c.pyx:95-164 */
 int bq_int_K(bq_ctx *ctx, const double *x, int64_t d, int64_t n, double h, const double *w,
              const double *mu, const double *cov, double *out);
+/* The same under the uniform measure on the box [lo, hi] and under the mixture (C, pi, mu, cov):
+ * out_i = kappa(x_i) and *kk (one double on the host) as bq_gp_integral_box and bq_gp_integral_mix
+ * define them.  Either output may be NULL, but not both; kk alone needs no points (n == 0).
+ * BQ_ERR_BAD_ARG for the measures as there. */
+int bq_int_K_box(bq_ctx *ctx, const double *x, int64_t d, int64_t n, double h, const double *w,
+                 const double *lo, const double *hi, double *out, double *kk);
+int bq_int_K_mix(bq_ctx *ctx, const double *x, int64_t d, int64_t n, double h, const double *w,
+                 int64_t C, const double *pi, const double *mu, const double *cov, double *out,
+                 double *kk);
 /* out (n1 x n2) = int K1(x1, x') K2(x', x2) N(x' | mu, cov) dx'    gauss_c.pyx:235-339 */
 int bq_int_K1_K2(bq_ctx *ctx, const double *x1, int64_t n1, const double *x2, int64_t n2,
                  int64_t d, double h1, const double *w1, double h2, const double *w2,

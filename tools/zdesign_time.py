@@ -64,9 +64,11 @@ def kernel_split(tl, Ap, npad, q):
     cols = [i for i in range(start + 1, len(tl))
             if tl[i][4] == 8.0 * Ap * (npad + (i - start - 1) // 2) and (i - start) % 2 == 1]
     out = {"sweep": sum(ms[:start]), "steps": sum(ms[start:]), "per_step": sum(ms[start:]) / q}
-    if start >= 2 and tl[start - 1][4] == 8.0 * Ap * npad:
-        out["rowdot"], out["vb"] = ms[start - 2], ms[start - 1]
-        out["vb_TB_per_s"] = 8.0 * Ap * npad / ms[start - 1] * 1e-9
+    # (the kernel mean at the candidates has a row of its own between the two, work 8 (d + 1) A)
+    big = [i for i in range(start) if tl[i][4] == 8.0 * Ap * npad]
+    if len(big) >= 2 and big[-1] == start - 1:
+        out["rowdot"], out["vb"] = ms[big[-2]], ms[big[-1]]
+        out["vb_TB_per_s"] = 8.0 * Ap * npad / ms[big[-1]] * 1e-9
     if len(cols) == q:
         col_ms = sum(ms[i] for i in cols)
         out["columns"] = col_ms
