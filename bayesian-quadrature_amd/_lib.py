@@ -102,6 +102,13 @@ SIGNATURES = {
     "bq_gp_integral_mix": (C.c_int, [_vp, _vp] + _MIX + [_dp, _dp, _dp]),
     "bq_gp_zdesign_box": (C.c_int, [_vp, _vp] + _BOX + _ZD_TAIL),
     "bq_gp_zdesign_mix": (C.c_int, [_vp, _vp] + _MIX + _ZD_TAIL),
+    # (keep flags, the measure, then xq, M, mean, var, cov)
+    "bq_gp_marginal": (C.c_int, [_vp, _vp, _i32p, _dp, _dp, _dp, _i64, _dp, _dp, _dp]),
+    "bq_gp_marginal_box": (C.c_int, [_vp, _vp, _i32p] + _BOX + [_dp, _i64, _dp, _dp, _dp]),
+    "bq_marginal_K": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _i64, _dbl, _dp, _i32p, _dp, _dp, _dp,
+                                _dp]),
+    "bq_marginal_K_box": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _i64, _dbl, _dp, _i32p] + _BOX
+                          + [_dp, _dp]),
     "bq_gp_sqintegral": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp]),
     "bq_gp_sqdesign": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _i64, _i64, _dbl, _dbl, _i64p, _dp, _dp,
                                  _dp, _dp, _dp, _i64p]),

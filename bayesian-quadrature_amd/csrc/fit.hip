@@ -2012,6 +2012,85 @@ extern "C" int bq_gp_integral_mix(bq_ctx *c, bq_fit *f, int64_t C, const double 
 
 namespace bqh {
 
+// The marginal of the fit under a Gaussian or a box (include/bqhip.h has the contract; marginal.h
+// the kernels): the body of bq_gp_marginal and bq_gp_marginal_box, a posterior call whose cross
+// rows are partial kernel means.  Mean alone: alpha and one fused launch.  Otherwise
+// bq_gp_predict's staging, forward sweep and row reductions over the marginal's own right-hand
+// sides, the prior's diagonal added to -|v|^2 by its producer, and for cov the prior as the seed of
+// posterior_sigma's product.  A box's column factors kappa_box,I(X) live behind the results in
+// f->wout for the length of the call: no state is kept.
+static int gp_marginal(bq_ctx *c, bq_fit *f, const int32_t *keep, const Measure &m,
+                       const double *xq, int64_t M, double *mean, double *var, double *cov)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    BQCHK(check_fit(c, f));
+    if (M < 0 || M > INT32_MAX - 64 || (M && !xq) || (!mean && !var && !cov))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    MargPlan pl;
+    BQCHK(marginal_plan(c, f->d, f->h, f->w, keep, m, xq, M, &pl));
+    if (M == 0)
+        return BQ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int n = f->n, npad = f->npad, Mp = (int)roundup(M, 64);
+    const bool sweep = var || cov;
+    if (!sweep)
+        BQCHK(fit_alpha(c, f));
+    BQCHK(fit_grow(c, f->wout, sizeof(double) * (2 * (size_t)Mp + npad), "prediction results"));
+    PosteriorIO io;
+    BQCHK(io.begin(c, f, xq, M, 0, false));
+    double *colv = f->wout.d() + 2 * (size_t)Mp;
+    if (pl.box)
+        BQCHK(launch_marginal_colv(c, pl, f->pts.d(), n, colv));
+    if (!sweep) {
+        BQCHK(launch_marginal_mean(c, pl, io.xq, (int)M, f->pts.d(), n, colv, f->alpha.d(), io.res));
+        return io.finish(c, (size_t)Mp, mean, nullptr, nullptr, nullptr);
+    }
+    WideInv wi;
+    BQCHK(fit_wide(c, f, wi));
+    DevBuf &V0 = f->wV, &V = f->wV2;
+    BQCHK(fit_grow(c, V0, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(fit_grow(c, V, sizeof(double) * (size_t)Mp * npad, "prediction sweep workspace"));
+    BQCHK(launch_marginal_cross(c, pl, io.xq, (int)M, Mp, f->pts.d(), n, npad, colv, V0.d(), Mp));
+    BQCHK(enqueue_forward_rows(c, V0.d(), V.d(), Mp, Mp, f->A.d(), f->ldl, npad, wi));
+    BQCHK(fit_zc(c, f));
+    BQCHK(launch_rowdot(c, V.d(), (long)Mp, (int)M, Mp, npad, f->wz.d(), 0.0, io.res, io.res + Mp, 1));
+    DevBuf Cd; // (lives until finish has synchronised the stream: one read-back)
+    if (cov) {
+        HIPCHK(c, Cd.alloc(sizeof(double) * (size_t)Mp * Mp));
+        BQCHK(launch_marginal_prior(c, pl, io.xq, (int)M, Mp, Cd.d(), Mp, io.res + Mp, 1));
+        GemmJob vvt;
+        vvt.C = Cd.d(), vvt.ldc = Mp;
+        vvt.P = V.d(), vvt.ldp = Mp;
+        vvt.Q = V.d(), vvt.qsj = 1, vvt.qsk = Mp;
+        vvt.m = Mp, vvt.n = Mp, vvt.k = npad;
+        BQCHK(launch_gemm(c, BQ_K_GEMM, vvt));
+        HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(double) * M, Cd.p, sizeof(double) * Mp,
+                                   sizeof(double) * M, M, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        BQCHK(launch_marginal_prior(c, pl, io.xq, (int)M, Mp, nullptr, 0, io.res + Mp, 1));
+    }
+    return io.finish(c, 2 * (size_t)Mp, mean, var, nullptr, nullptr); // [mean | var], one copy
+}
+
+} // namespace bqh
+
+extern "C" int bq_gp_marginal(bq_ctx *c, bq_fit *f, const int32_t *keep, const double *mu,
+                              const double *cov, const double *xq, int64_t M, double *mean,
+                              double *var, double *cov_out)
+{
+    return gp_marginal(c, f, keep, Measure::gauss(mu, cov), xq, M, mean, var, cov_out);
+}
+
+extern "C" int bq_gp_marginal_box(bq_ctx *c, bq_fit *f, const int32_t *keep, const double *lo,
+                                  const double *hi, const double *xq, int64_t M, double *mean,
+                                  double *var, double *cov_out)
+{
+    return gp_marginal(c, f, keep, Measure::box(lo, hi), xq, M, mean, var, cov_out);
+}
+
+namespace bqh {
+
 // what the two design entry points check alike, after the measure
 static int zd_args(bq_ctx *c, const double *xc, int64_t A, int64_t q, double nugget, double tol,
                    const int64_t *piv, const double *gain, const double *zvar0, const int64_t *rank)

@@ -36,6 +36,7 @@
 //   plan.hip     resident batched plans, batched / grid entry points
 //   fit.hip      resident GP fits
 //   moments.hip  closed-form integrals, BQ moments, the acquisition entry points
+//                marginal.h kernels             the marginal of a fit: partial kernel means, its prior
 //   pair.hip     the stacked pair of GPs at S hyper-parameter sets in one batched pass
 //   probe.hip    hardware probes (libbqhip_probe.so only)
 #pragma once
@@ -814,6 +815,45 @@ void mix_forms(int d, const double *w, const Measure &m, double *host);
 // diag(w^2) + 2 S, S = (diag(w^-2) + cov^-1)^-1, whose host factor fails.
 int sq_forms(bq_ctx *c, int d, double h, const double *w, const double *mu, const double *cov,
              SqForms *out);
+// The marginal of a fit under a Gaussian or a box (marginal.h has the kernels and the one
+// expression both kinds share; include/bqhip.h, bq_gp_marginal, the contract): everything the
+// host works out of (h, w), the measure and the kept axes, as the kernels read it -- d x d
+// matrices row-major with stride d, embedded at the axes' own indices.
+struct MargPlan {
+    int d = 0;
+    bool box = false;
+    unsigned keep = 0;           // bit k: axis k is kept
+    double mu[BQ_MAXD] = {0};    // Gaussian: the measure's mean
+    double lo[BQ_MAXD], hi[BQ_MAXD]; // the box's ends on the kept axes; -inf, +inf elsewhere
+    double ls[BQ_MAXD * BQ_MAXD] = {0}; // inverse factor of Sigma_SS
+    double bm[BQ_MAXD * BQ_MAXD] = {0}; // B = Sigma_IS Sigma_SS^-1
+    double le[BQ_MAXD * BQ_MAXD] = {0}; // diag(1 / w_S), inverse factor of W_I + Sigma_c
+    double g[BQ_MAXD * BQ_MAXD] = {0};  // the prior's transform of q - q'
+    double lq = 0;                      // the constant of log pi_S
+    double logc_e = 0, scale_e = 0;     // a cross entry's constant and factor
+    double logc_p = 0, scale_p = 0, rvol = 1; // the prior's; 1 / vol_S of a box
+    double h2 = 0;
+    // box: int_K_box_kernel's form of kappa_box,I -- the ends on I, -inf and +inf on S, where
+    // rl = 1 and the factor is exactly 1
+    double ilo[BQ_MAXD], ihi[BQ_MAXD], rw[BQ_MAXD] = {0}, rl[BQ_MAXD] = {0};
+};
+// The plan of a call, or BQ_ERR_BAD_ARG before anything is allocated: the measure's own checks
+// (launch_kernel_mean's, on all d axes), keep == NULL, a flag that is not 0 or 1, all flags set or
+// none, a covariance that is not symmetric, and a Sigma_SS, W_I + Sigma_c or W_I + 2 Sigma_c whose
+// host factor fails.  xq (d x M; NULL: not checked): a kept coordinate that is not finite.
+int marginal_plan(bq_ctx *c, int d, double h, const double *w, const int32_t *keep,
+                  const Measure &m, const double *xq, int64_t M, MargPlan *out);
+// colv[j] = kappa_box,I(x_j), h^2 included, at the n device points x (a box's plan only)
+int launch_marginal_colv(bq_ctx *c, const MargPlan &pl, const double *x, int n, double *colv);
+// K (Mp x npad, ld ldk) = c(xq, x) with its zero padding (marginal_cross_kernel)
+int launch_marginal_cross(bq_ctx *c, const MargPlan &pl, const double *xq, int M, int Mp,
+                          const double *x, int n, int npad, const double *colv, double *K, long ldk);
+// mean = c(xq, x) alpha without a matrix (marginal_mean_kernel)
+int launch_marginal_mean(bq_ctx *c, const MargPlan &pl, const double *xq, int M, const double *x,
+                         int n, const double *colv, const double *alpha, double *mean);
+// P (Mp x Mp, ld ldp; NULL: none) and / or its diagonal (diag; accum: added to what is there)
+int launch_marginal_prior(bq_ctx *c, const MargPlan &pl, const double *xq, int M, int Mp, double *P,
+                          long ldp, double *diag, int accum);
 
 // ---- linalg.hip -----------------------------------------------------------------------
 // factor one ntot x ntot device matrix on the context's panel scratch (dinv: BQ_DINV_STRIDE)

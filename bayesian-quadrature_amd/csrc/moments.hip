@@ -6,6 +6,7 @@
 // loops; the per-point / per-pair work runs in the kernels of moments.h.
 #include "host.h"
 #include "moments.h"
+#include "marginal.h"
 
 using namespace bqh;
 
@@ -368,10 +369,13 @@ int gauss_measure(bq_ctx *c, int d, double h, const double *w, const Measure &m,
 // h^2 prod_k I_k / L_k^2 of a box, I_k = L_k erf(L_k / (sqrt2 w_k)) + w_k sqrt(2 / pi) expm1(-L_k^2
 // / (2 w_k^2)): expm1, since for a box narrow against w_k the two terms are L_k^2 sqrt(2 / pi) /
 // w_k and half of it, and exp(.) - 1 would carry 1's rounding into the second
-double box_kk(int d, double h, const double *w, const Measure &m)
+// (skip: bit k set leaves axis k out -- the kept axes of a marginal)
+double box_kk(int d, double h, const double *w, const Measure &m, unsigned skip = 0)
 {
     double kk = h * h;
     for (int k = 0; k < d; ++k) {
+        if ((skip >> k) & 1u)
+            continue;
         const double Lk = m.b[k] - m.a[k], r = Lk / (M_SQRT2 * w[k]);
         const double Ik = Lk * std::erf(r) + w[k] * std::sqrt(2.0 / M_PI) * std::expm1(-(r * r));
         kk *= Ik / (Lk * Lk);
@@ -555,6 +559,226 @@ int bqh::sq_forms(bq_ctx *c, int d, double h, const double *w, const double *mu,
     return BQ_OK;
 }
 
+// the plan of a marginal (host.h, MargPlan; marginal.h has the expression the numbers enter)
+int bqh::marginal_plan(bq_ctx *c, int d, double h, const double *w, const int32_t *keep,
+                       const Measure &m, const double *xq, int64_t M, MargPlan *out)
+{
+    BQCHK(launch_kernel_mean(c, d, nullptr, 0, h, w, m, nullptr, nullptr));
+    if (m.kind == Measure::MIX)
+        return fail(c, BQ_ERR_BAD_ARG, "a mixture has no marginal here");
+    if (!keep)
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    MargPlan p;
+    p.d = d, p.box = m.kind == Measure::BOX, p.h2 = h * h;
+    int S[BQ_MAXD], I[BQ_MAXD], ns = 0, ni = 0;
+    for (int k = 0; k < d; ++k) {
+        if (keep[k] != 0 && keep[k] != 1)
+            return fail(c, BQ_ERR_BAD_ARG, "a keep flag is 0 or 1");
+        if (keep[k])
+            S[ns++] = k, p.keep |= 1u << k;
+        else
+            I[ni++] = k;
+    }
+    if (ns == 0 || ni == 0)
+        return fail(c, BQ_ERR_BAD_ARG, "a marginal keeps between 1 and d - 1 axes");
+    if (xq)
+        for (int64_t j = 0; j < M; ++j)
+            for (int a = 0; a < ns; ++a)
+                if (!std::isfinite(xq[S[a] + j * d]))
+                    return fail(c, BQ_ERR_BAD_ARG, "a kept coordinate of a query point is not finite");
+    const double inf = std::numeric_limits<double>::infinity();
+    double lcS = 0.0; // log N(0 | 0, W_S)
+    for (int k = 0; k < BQ_MAXD; ++k) {
+        p.lo[k] = p.ilo[k] = -inf, p.hi[k] = p.ihi[k] = inf;
+        p.rl[k] = 1.0, p.rw[k] = k < d ? 1.0 / (M_SQRT2 * w[k]) : 1.0;
+    }
+    for (int a = 0; a < ns; ++a) {
+        const int k = S[a];
+        lcS += -0.5 * LOG_2PI - std::log(w[k]);
+        p.le[k * d + k] = p.g[k * d + k] = 1.0 / w[k];
+    }
+    if (p.box) {
+        double vol = 1.0;
+        for (int a = 0; a < ns; ++a) {
+            p.lo[S[a]] = m.a[S[a]], p.hi[S[a]] = m.b[S[a]];
+            vol *= m.b[S[a]] - m.a[S[a]];
+        }
+        for (int i = 0; i < ni; ++i) {
+            p.ilo[I[i]] = m.a[I[i]], p.ihi[I[i]] = m.b[I[i]];
+            p.rl[I[i]] = 1.0 / (m.b[I[i]] - m.a[I[i]]);
+        }
+        p.rvol = 1.0 / vol;
+        p.scale_e = p.rvol, p.logc_e = lcS;
+        p.scale_p = box_kk(d, h, w, m, p.keep), p.logc_p = lcS;
+        *out = p;
+        return BQ_OK;
+    }
+    const double *cov = m.b;
+    for (int r = 0; r < d; ++r)
+        for (int q = 0; q < r; ++q) {
+            const double u = cov[r + q * d], v = cov[q + r * d];
+            if (std::fabs(u - v) > 1e-12 * std::max(std::fabs(u), std::fabs(v)))
+                return fail(c, BQ_ERR_BAD_ARG, "the measure's covariance must be symmetric");
+        }
+    Small Lss;
+    Lss.n = ns;
+    for (int a = 0; a < ns; ++a)
+        for (int b = 0; b < ns; ++b)
+            Lss(a, b) = cov[S[a] + S[b] * d];
+    if (!small_chol(Lss))
+        return fail(c, BQ_ERR_BAD_ARG,
+                    "the measure's covariance is not positive definite on the kept axes");
+    const Small Li = small_inv_lower(Lss);
+    p.lq = form_logc(Lss);
+    double B[BQ_MAXD][BQ_MAXD] = {{0}};
+    for (int a = 0; a < ns; ++a)
+        for (int b = 0; b <= a; ++b)
+            p.ls[S[a] * d + S[b]] = Li(a, b);
+    for (int i = 0; i < ni; ++i)
+        for (int a = 0; a < ns; ++a) {
+            double t = 0.0;
+            for (int b = 0; b < ns; ++b) {
+                double inv = 0.0; // (Sigma_SS^-1)(b, a)
+                for (int k = 0; k < ns; ++k)
+                    inv += Li(k, b) * Li(k, a);
+                t += cov[I[i] + S[b] * d] * inv;
+            }
+            B[i][a] = t;
+            p.bm[I[i] * d + S[a]] = t;
+        }
+    Small E1, E2;
+    E1.n = E2.n = ni;
+    for (int i = 0; i < ni; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double t = 0.0, u = 0.0;
+            for (int a = 0; a < ns; ++a) {
+                t += B[i][a] * cov[S[a] + I[j] * d];
+                u += B[j][a] * cov[S[a] + I[i] * d];
+            }
+            const double sc = cov[I[i] + I[j] * d] - 0.5 * (t + u); // Sigma_c, symmetrised
+            const double wi = i == j ? w[I[i]] * w[I[i]] : 0.0;
+            E1(i, j) = E1(j, i) = wi + sc;
+            E2(i, j) = E2(j, i) = wi + 2.0 * sc;
+        }
+    if (!small_chol(E1) || !small_chol(E2))
+        return fail(c, BQ_ERR_BAD_ARG, "the conditional covariance of the integrated axes plus "
+                                       "diag(w^2) is not positive definite");
+    const Small Li1 = small_inv_lower(E1), Li2 = small_inv_lower(E2);
+    for (int i = 0; i < ni; ++i) {
+        for (int j = 0; j <= i; ++j)
+            p.le[I[i] * d + I[j]] = Li1(i, j);
+        for (int a = 0; a < ns; ++a) {
+            double t = 0.0;
+            for (int j = 0; j <= i; ++j)
+                t += Li2(i, j) * B[j][a];
+            p.g[I[i] * d + S[a]] = t;
+        }
+    }
+    for (int k = 0; k < d; ++k)
+        p.mu[k] = m.a[k];
+    p.scale_e = p.scale_p = h * h;
+    p.logc_e = lcS + form_logc(E1);
+    p.logc_p = lcS + form_logc(E2);
+    *out = p;
+    return BQ_OK;
+}
+
+namespace {
+
+template <int D>
+MargForm<D> marg_form(const MargPlan &p)
+{
+    MargForm<D> f;
+    for (int r = 0; r < D; ++r) {
+        f.mu[r] = p.mu[r], f.lo[r] = p.lo[r], f.hi[r] = p.hi[r];
+        for (int q = 0; q < D; ++q) {
+            f.ls[r * D + q] = p.ls[r * D + q];
+            f.bm[r * D + q] = p.bm[r * D + q];
+            f.le[r * D + q] = p.le[r * D + q];
+        }
+    }
+    f.lq = p.lq, f.logc = p.logc_e, f.scale = p.scale_e, f.keep = p.keep;
+    return f;
+}
+
+} // namespace
+
+int bqh::launch_marginal_colv(bq_ctx *c, const MargPlan &pl, const double *x, int n, double *colv)
+{
+    Bracket br(c, BQ_K_REDUCE, 8.0 * (pl.d + 1.0) * n);
+    BQ_DISPATCH_D(pl.d, {
+        BoxForm<D> f;
+        for (int k = 0; k < D; ++k)
+            f.lo[k] = pl.ilo[k], f.hi[k] = pl.ihi[k], f.rw[k] = pl.rw[k], f.rl[k] = pl.rl[k];
+        hipLaunchKernelGGL(int_K_box_kernel<D>, dim3((n + 255) / 256), dim3(256), 0, c->stream, x, n,
+                           f, pl.h2, colv);
+    });
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int bqh::launch_marginal_cross(bq_ctx *c, const MargPlan &pl, const double *xq, int M, int Mp,
+                               const double *x, int n, int npad, const double *colv, double *K,
+                               long ldk)
+{
+    if (M < 1 || n < 1 || Mp % 64 || npad % 64 || Mp < M || npad < n || ldk < Mp)
+        return fail(c, BQ_ERR_BAD_ARG, "marginal_cross: padded sizes must be multiples of 64");
+    Bracket br(c, BQ_K_GRAM, 8.0 * Mp * npad);
+    const dim3 grid(Mp / 64, npad / 64);
+    BQ_DISPATCH_D(pl.d, {
+        const MargForm<D> f = marg_form<D>(pl);
+        if (pl.box)
+            hipLaunchKernelGGL((marginal_cross_kernel<D, true>), grid, dim3(256), 0, c->stream, xq, M,
+                               x, n, f, colv, K, ldk);
+        else
+            hipLaunchKernelGGL((marginal_cross_kernel<D, false>), grid, dim3(256), 0, c->stream, xq,
+                               M, x, n, f, colv, K, ldk);
+    });
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int bqh::launch_marginal_mean(bq_ctx *c, const MargPlan &pl, const double *xq, int M,
+                              const double *x, int n, const double *colv, const double *alpha,
+                              double *mean)
+{
+    Bracket br(c, BQ_K_REDUCE);
+    const dim3 grid((unsigned)((M + 3) / 4));
+    BQ_DISPATCH_D(pl.d, {
+        const MargForm<D> f = marg_form<D>(pl);
+        if (pl.box)
+            hipLaunchKernelGGL((marginal_mean_kernel<D, true>), grid, dim3(256), 0, c->stream, xq, M,
+                               x, n, f, colv, alpha, mean);
+        else
+            hipLaunchKernelGGL((marginal_mean_kernel<D, false>), grid, dim3(256), 0, c->stream, xq,
+                               M, x, n, f, colv, alpha, mean);
+    });
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
+int bqh::launch_marginal_prior(bq_ctx *c, const MargPlan &pl, const double *xq, int M, int Mp,
+                               double *P, long ldp, double *diag, int accum)
+{
+    if (M < 1 || Mp % 64 || Mp < M || (P && ldp < Mp) || (!P && !diag))
+        return fail(c, BQ_ERR_BAD_ARG, "marginal_prior: the padded size must be a multiple of 64");
+    Bracket br(c, BQ_K_GRAM, P ? 8.0 * Mp * Mp : 8.0 * M);
+    const dim3 grid(Mp / 64, P ? Mp / 64 : 1);
+    BQ_DISPATCH_D(pl.d, {
+        MargPrior<D> f;
+        for (int r = 0; r < D; ++r) {
+            f.mu[r] = pl.mu[r], f.lo[r] = pl.lo[r], f.hi[r] = pl.hi[r];
+            for (int q = 0; q < D; ++q)
+                f.ls[r * D + q] = pl.ls[r * D + q], f.g[r * D + q] = pl.g[r * D + q];
+        }
+        f.lq = pl.lq, f.logc = pl.logc_p, f.scale = pl.scale_p, f.rvol = pl.rvol, f.keep = pl.keep;
+        hipLaunchKernelGGL(marginal_prior_kernel<D>, grid, dim3(256), 0, c->stream, xq, M, f, P, ldp,
+                           diag, accum);
+    });
+    HIPCHK(c, hipGetLastError());
+    return BQ_OK;
+}
+
 // ===========================================================================
 // gauss_c drop-ins: host buffers in and out
 // ===========================================================================
@@ -636,6 +860,76 @@ extern "C" int bq_int_K_mix(bq_ctx *c, const double *x, int64_t d, int64_t n, do
                             const double *cov, double *out, double *kk)
 {
     return int_K_measure(c, x, d, n, h, w, Measure::mix(C, pi, mu, cov), out, kk);
+}
+
+namespace {
+
+// bq_marginal_K and bq_marginal_K_box: the cross matrix c(xq, x), M x n, and the prior's diagonal
+// at host points without a fit, through the kernels bq_gp_marginal runs
+int marginal_K(bq_ctx *c, const double *xq, int64_t M, const double *x, int64_t n, int64_t d,
+               double h, const double *w, const int32_t *keep, const Measure &m, double *out,
+               double *pdiag)
+{
+    if (!c)
+        return BQ_ERR_BAD_ARG;
+    if (d < 1 || d > BQ_MAXD)
+        return fail(c, BQ_ERR_BAD_ARG, "d must be in 1..%d", BQ_MAXD);
+    BQCHK(check_w(c, d, h, w, 0.0));
+    if (M < 0 || n < 0 || M > INT32_MAX - 64 || n > INT32_MAX - 64 || (!out && !pdiag) ||
+        (M && !xq) || (out && M && n && !x))
+        return fail(c, BQ_ERR_BAD_ARG, "illegal value");
+    MargPlan pl;
+    BQCHK(marginal_plan(c, (int)d, h, w, keep, m, xq, M, &pl));
+    if (M == 0)
+        return BQ_OK;
+    const bool cross = out && n;
+    const int Mp = (int)roundup(M, 64), npad = (int)roundup(n, 64);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf qd, xd, Kd, cd, dd;
+    HIPCHK(c, qd.alloc(sizeof(double) * d * M));
+    HIPCHK(c, dd.alloc(sizeof(double) * M));
+    if (cross) {
+        HIPCHK(c, xd.alloc(sizeof(double) * d * n));
+        HIPCHK(c, Kd.alloc(sizeof(double) * (size_t)Mp * npad));
+        HIPCHK(c, cd.alloc(sizeof(double) * npad));
+    }
+    HIPCHK(c, hipMemcpyAsync(qd.p, xq, sizeof(double) * d * M, hipMemcpyHostToDevice, c->stream));
+    int st = BQ_OK;
+    if (cross) {
+        HIPCHK(c, hipMemcpyAsync(xd.p, x, sizeof(double) * d * n, hipMemcpyHostToDevice, c->stream));
+        if (pl.box)
+            st = launch_marginal_colv(c, pl, xd.d(), (int)n, cd.d());
+        if (st == BQ_OK)
+            st = launch_marginal_cross(c, pl, qd.d(), (int)M, Mp, xd.d(), (int)n, npad, cd.d(),
+                                       Kd.d(), Mp);
+        if (st == BQ_OK)
+            (void)hipMemcpy2DAsync(out, sizeof(double) * M, Kd.p, sizeof(double) * Mp,
+                                   sizeof(double) * M, n, hipMemcpyDeviceToHost, c->stream);
+    }
+    if (st == BQ_OK && pdiag) {
+        st = launch_marginal_prior(c, pl, qd.d(), (int)M, Mp, nullptr, 0, dd.d(), 0);
+        if (st == BQ_OK)
+            (void)hipMemcpyAsync(pdiag, dd.p, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host arrays and the buffers are read until here)
+    HIPCHK(c, hipGetLastError());
+    return st;
+}
+
+} // namespace
+
+extern "C" int bq_marginal_K(bq_ctx *c, const double *xq, int64_t M, const double *x, int64_t n,
+                             int64_t d, double h, const double *w, const int32_t *keep,
+                             const double *mu, const double *cov, double *out, double *pdiag)
+{
+    return marginal_K(c, xq, M, x, n, d, h, w, keep, Measure::gauss(mu, cov), out, pdiag);
+}
+
+extern "C" int bq_marginal_K_box(bq_ctx *c, const double *xq, int64_t M, const double *x, int64_t n,
+                                 int64_t d, double h, const double *w, const int32_t *keep,
+                                 const double *lo, const double *hi, double *out, double *pdiag)
+{
+    return marginal_K(c, xq, M, x, n, d, h, w, keep, Measure::box(lo, hi), out, pdiag);
 }
 
 extern "C" int bq_int_K1_K2(bq_ctx *c, const double *x1, int64_t n1, const double *x2, int64_t n2,

@@ -369,15 +369,17 @@ __global__ __launch_bounds__(1024) void trsv_bwd_flow_kernel(const double *__res
 // 2.9): flow_in_kernel brings the right-hand side in from the caller's mapped pinned vector
 // (coalesced, zero padded to npad) and sets every hand-off slot of BOTH sweeps to the sentinel in
 // the same launch; flow_out_kernel takes the solution out.  grid: enough 256-thread blocks for
-// max(npad, nfill).
+// max(npad, nfill), at most 1024 (launch_flow_in): both loops stride over the grid -- the points of
+// a posterior call come in through here too, and past 2^18 doubles (d M of a mean-only call) a
+// copy of one element per thread left the rest of them behind.
 __global__ __launch_bounds__(256) void flow_in_kernel(const double *__restrict__ hsrc, int n,
                                                       double *__restrict__ x, int npad,
                                                       unsigned long long *__restrict__ fill,
                                                       long nfill)
 {
     const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i < npad)
-        x[i] = i < n ? hsrc[i] : 0.0;
+    for (long k = i; k < npad; k += (long)gridDim.x * 256)
+        x[k] = k < n ? hsrc[k] : 0.0;
     for (long k = i; k < nfill; k += (long)gridDim.x * 256)
         fill[k] = BQ_FLOW_SENT;
 }

@@ -59,6 +59,35 @@ def _measure_args(m):
     raise TypeError("unknown measure %r" % (m,))
 
 
+def _marginal_no_mixture(mu):
+    if isinstance(mu, GaussianMixture):
+        raise ValueError(
+            "a marginal takes a single Gaussian (mu, cov) or a BoxMeasure: the conditional of a "
+            "mixture has weights that depend on the kept coordinates, and is not built")
+
+
+def _marginal_points(xq, axes, d):
+    """(keep, xq): the kept axes as d int32 flags (which the library checks for their number) and
+    the query points -- (|S|, M), row a on axis axes[a], or (M,) for one axis -- scattered into the
+    d x M column-major layout of bq_gp_marginal, NaN in the rows that are never read."""
+    try:
+        axes = [int(a) for a in np.atleast_1d(np.asarray(axes)).ravel()]
+    except (TypeError, ValueError):
+        raise ValueError("axes must be integers")
+    if any(a < 0 or a >= d for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError("axes must be distinct and in 0..%d" % (d - 1))
+    keep = np.zeros(d, dtype=np.int32)
+    keep[axes] = 1
+    xq = np.asarray(xq, dtype=np.float64)
+    if xq.ndim == 1 and len(axes) == 1:
+        xq = xq[None, :]
+    if xq.ndim != 2 or xq.shape[0] != len(axes):
+        raise ValueError("query points must be (%d, M), one row per kept axis" % len(axes))
+    full = np.full((d, xq.shape[1]), np.nan, order="F")
+    full[axes, :] = xq
+    return keep, full
+
+
 def _sq_gaussian_only(mu):
     if isinstance(mu, Measure):
         raise ValueError(
@@ -313,6 +342,35 @@ class Engine(object):
             self._ctx, L.dptr(x), d, n, float(h), L.dptr(w), *(margs + (
                 L.dptr(out), C.byref(kk) if want_kk else None))))
         return (out, float(kk.value)) if want_kk else out
+
+    def marginal_K(self, xq, x, h, w, axes, mu, cov=None):
+        """(c, pdiag): the cross matrix c(xq_i, x_j), (M, n), and the prior's diagonal
+        P(xq_i, xq_i), (M,), of ``Fit.marginal`` at host points without a fit (bq_marginal_K,
+        bq_marginal_K_box).  ``axes`` are the kept axes, ``xq`` is (|S|, M) -- or (M,) for one
+        axis --, ``x`` is d x n; (mu, cov) spell a Gaussian, a ``measures.BoxMeasure`` in place
+        of mu the box.  ValueError for a ``measures.GaussianMixture``."""
+        _marginal_no_mixture(mu)
+        x = _pts(x)
+        d, n = x.shape
+        w = _wvec(w, d)
+        keep, xq = _marginal_points(xq, axes, d)
+        if isinstance(mu, Measure):
+            if cov is not None:
+                raise TypeError("a measure object comes without a cov")
+            if mu.d != d:
+                raise ValueError("the measure has dimension %d, the points %d" % (mu.d, d))
+            name, margs = _measure_args(mu)
+        else:
+            if cov is None:
+                raise TypeError("a Gaussian measure needs its cov")
+            mu, cov = self._mc(d, mu, cov)
+            name, margs = "", (L.dptr(mu), L.dptr(cov))
+        M = xq.shape[1]
+        out, pdiag = np.empty((M, n), order="F"), np.empty(M)
+        self._check(getattr(self._lib, "bq_marginal_K" + name)(
+            self._ctx, L.dptr(xq), M, L.dptr(x), n, d, float(h), L.dptr(w),
+            keep.ctypes.data_as(L._i32p), *(margs + (L.dptr(out), L.dptr(pdiag)))))
+        return out, pdiag
 
     def int_K1_K2(self, x1, x2, h1, w1, h2, w2, mu, cov):
         x1, x2 = _pts(x1), _pts(x2)
@@ -731,7 +789,39 @@ class Engine(object):
 SAMPLE_LADDER = (0.0, 1e-12, 1e-10, 1e-8, 1e-6)
 
 
-class Fit(object):
+class FitViews(object):
+    """The stateless views of a fit that keep nothing with it and set no bit of its derived state:
+    ``Fit`` inherits them.  (The table of a fit's consumers and events, tests/test_gp_fit_state.py,
+    is over ``Fit``'s own methods; a view here brings its rows of that table with it in its own
+    test file, which also holds that no other name lives here: tests/test_gp_marginal.py.)"""
+
+    def marginal(self, xq, axes, mu, cov=None, want_mean=True, want_var=True, want_cov=False):
+        """(mean, var, cov): the marginal of the fit, J(q) = int f(q, t) pi(q, t) dt over every
+        axis but ``axes``, as a Gaussian process in q in closed form (bq_gp_marginal,
+        bq_gp_marginal_box): mean and var (M,), cov (M, M), None where not wanted.  ``xq`` is
+        (|S|, M), row a on axis axes[a], or (M,) for one kept axis; the measure pi on all d axes
+        is (mu, cov) or a ``measures.BoxMeasure`` as in ``integral``.  J is the unnormalised
+        marginal: its integral over q is ``integral``'s Z, the double integral of cov is var Z,
+        and J / Z is the marginal posterior density.  var is latent and not clamped at 0.  Mean
+        alone takes a fused route without a sweep.  A view: nothing is kept with the fit.
+        ValueError for a ``measures.GaussianMixture`` (not built), for axes that are not distinct
+        axes of the fit, none of them or all of them, for a kept coordinate that is not finite
+        and for an illegal measure."""
+        _marginal_no_mixture(mu)
+        e = self._eng
+        name, margs = self._measure(mu, cov)
+        keep, xq = _marginal_points(xq, axes, self.d)
+        M = xq.shape[1]
+        mean = np.empty(M) if want_mean else None
+        var = np.empty(M) if want_var else None
+        cov_out = np.empty((M, M), order="F") if want_cov else None
+        e._check(getattr(e._lib, "bq_gp_marginal" + name)(
+            e._ctx, self._handle(), keep.ctypes.data_as(L._i32p), *(margs + (
+                L.dptr(xq), M, L.dptr(mean), L.dptr(var), L.dptr(cov_out)))))
+        return mean, var, cov_out
+
+
+class Fit(FitViews):
     """Device-resident GP fit (bq_fit): L, z = L^-1 y, log-ML; alpha on demand."""
 
     def __init__(self, eng, x, y, h, w, s):

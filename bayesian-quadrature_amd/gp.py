@@ -18,7 +18,7 @@ import numpy as np
 import scipy.optimize as optim
 
 from . import util
-from .engine import get_engine, _sq_gaussian_only
+from .engine import get_engine, _marginal_no_mixture, _sq_gaussian_only
 from .measures import Measure
 
 DTYPE = np.float64
@@ -844,6 +844,32 @@ class GP(object):
         """(n,): the quadrature weights ``Kxx^-1 kappa_X`` of ``integral``, whose mean is
         ``integral_weights . y``."""
         return self._integral(mu, cov)[2].copy()
+
+    def _marginal(self, axes, xo, mu, cov, want_cov):
+        _marginal_no_mixture(mu)
+        mu, cov, key = self._measure(mu, cov)
+        axes = tuple(int(a) for a in np.atleast_1d(np.asarray(axes)).ravel())
+        xo = np.ascontiguousarray(xo, dtype=DTYPE)
+        mkey = ("marginal", want_cov, axes, xo.shape, xo.tobytes(), key)
+        return self._memo(mkey, lambda: self._device_fit().marginal(
+            xo, axes, *self._margs(mu, cov), want_mean=not want_cov, want_var=not want_cov,
+            want_cov=want_cov))
+
+    def marginal(self, axes, xo, mu, cov=None):
+        """(mean, var), (M,) each: the marginal of the GP over every axis but ``axes``,
+        ``J(q) = int f(q, t) pi(q, t) dt`` at the points ``xo`` -- (|S|, M), or (M,) for one kept
+        axis -- under the Gaussian ``(mu, cov)`` or a ``measures.BoxMeasure`` on all d axes
+        (engine.Fit.marginal, bq_gp_marginal).  J is unnormalised: it integrates to
+        ``integral``'s mean, and ``J / Z`` is the marginal posterior density.  ``var`` is latent.
+        A GP over fewer than two axes has no marginal (ValueError); neither has a
+        ``measures.GaussianMixture``.  A view of the fit, memoised like ``integral``."""
+        mean, var, _ = self._marginal(axes, xo, mu, cov, False)
+        return mean.copy(), var.copy()
+
+    def marginal_cov(self, axes, xo, mu, cov=None):
+        """(M, M): the joint covariance of ``marginal`` at the points ``xo``; its double integral
+        over q is ``integral``'s var."""
+        return self._marginal(axes, xo, mu, cov, True)[2].copy()
 
     def _zdesign(self, xo, q, mu, cov, noisy, tol, want_scores):
         """The checked arguments of ``integral_design`` / ``integral_scores`` and the device

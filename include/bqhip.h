@@ -561,6 +561,48 @@ int bq_gp_zdesign_mix(bq_ctx *ctx, bq_fit *fit, int64_t C, const double *pi, con
                       const double *cov, const double *xc, int64_t A, int64_t q, double nugget,
                       double tol, int64_t *piv, double *gain, double *zvar0, double *resid_u,
                       double *resid_c, double *score0, int64_t *rank);
+/* The marginal of a resident fit: some axes integrated, the others kept.  keep: d flags, 1 for a
+ * kept axis (the set S, 1 <= |S| <= d - 1), 0 for an integrated one (I).  For a measure pi on all
+ * d axes,
+ *   J(q) = int f(q, t) pi(q, t) dt,   q on the kept axes, t on the integrated ones,
+ * the UNNORMALISED marginal: int J(q) dq is bq_gp_integral's Z, the double integral of its
+ * covariance is var Z, and J / Z is the marginal posterior density.  J is linear in f, hence a
+ * Gaussian process in closed form: with k(x, x') = h^2 prod_k N(x_k | x'_k, w_k^2), W_S and W_I
+ * the blocks of diag(w^2) and v_q = L^-1 c(q, X)^T,
+ *   mean(q) = c(q, X) alpha,  cov(q, q') = P(q, q') - v_q . v_q',  var(q) = P(q, q) - |v_q|^2,
+ * latent and not clamped, like every variance here.
+ *
+ * bq_gp_marginal: the Gaussian N(mu, Sigma) of bq_gp_integral (mu: d, cov: d x d column-major,
+ * finite and symmetric).  With B = Sigma_IS Sigma_SS^-1, m(q) = mu_I + B (q - mu_S), Sigma_c =
+ * Sigma_II - B Sigma_SI and pi_S(q) = N(q | mu_S, Sigma_SS):
+ *   c(q, x_j) = h^2 pi_S(q) N(q | x_jS, W_S) N(x_jI | m(q), W_I + Sigma_c),
+ *   P(q, q')  = h^2 N(q | q', W_S) pi_S(q) pi_S(q') N(m(q) - m(q') | 0, W_I + 2 Sigma_c).
+ * Every entry is one exponential of the summed exponents: no density underflows on its own.
+ * bq_gp_marginal_box: the uniform measure on prod_k [lo_k, hi_k] of bq_gp_integral_box.  With
+ * kappa_box,I and kk_box,I that entry point's kappa and kk over the integrated axes alone (h^2
+ * included) and vol_S the volume of the kept axes' box:
+ *   c(q, x_j) = 1[q in box_S] / vol_S   N(q | x_jS, W_S) kappa_box,I(x_jI),
+ *   P(q, q')  = 1[q, q' in box_S] / vol_S^2 N(q | q', W_S) kk_box,I.
+ * The closed box counts as inside; a q outside gives exact zeros in mean, var and its row and
+ * column of cov.  There is no entry point for a mixture (its conditional has weights that depend
+ * on q), none for the square-root-warped model, and no design that lowers a marginal's variance.
+ *
+ * xq: d x M column-major like bq_gp_predict's xo; the coordinates of integrated axes are never
+ * read.  mean, var: M; cov_out: M x M column-major; any may be NULL, not all.  Mean alone takes a
+ * fused route (alpha, one launch, no matrix); anything else the forward sweep of bq_gp_predict
+ * over the M x n right-hand sides c(q, X).  M == 0 returns BQ_OK and writes nothing.  The call
+ * keeps no state with the fit and disturbs none; one read-back.
+ * Status rules of bq_gp_predict for the handle.  BQ_ERR_BAD_ARG, all checked before anything is
+ * allocated, nothing written: every illegal measure of bq_gp_integral / bq_gp_integral_box; keep ==
+ * NULL, a flag that is not 0 or 1, all flags set or none; a covariance that is not symmetric, or
+ * whose Sigma_SS, W_I + Sigma_c or W_I + 2 Sigma_c has no Cholesky factor on the host; M < 0, xq
+ * == NULL with M > 0, a kept coordinate of xq that is not finite; all three outputs NULL. */
+int bq_gp_marginal(bq_ctx *ctx, bq_fit *fit, const int32_t *keep, const double *mu,
+                   const double *cov, const double *xq, int64_t M, double *mean, double *var,
+                   double *cov_out);
+int bq_gp_marginal_box(bq_ctx *ctx, bq_fit *fit, const int32_t *keep, const double *lo,
+                       const double *hi, const double *xq, int64_t M, double *mean, double *var,
+                       double *cov_out);
 /* Square-root-warped Bayesian quadrature of a resident fit (WSABI-L, Gunter et al. 2014) for an
  * integrand l >= alpha0: the fit's targets are g = sqrt(2 (l - alpha0)), one zero-mean GP, and
  * l = alpha0 + g^2 / 2 is linearised about the posterior mean m(x) = k(x, X) alpha, alpha =
@@ -681,6 +723,17 @@ int bq_int_K_box(bq_ctx *ctx, const double *x, int64_t d, int64_t n, double h, c
 int bq_int_K_mix(bq_ctx *ctx, const double *x, int64_t d, int64_t n, double h, const double *w,
                  int64_t C, const double *pi, const double *mu, const double *cov, double *out,
                  double *kk);
+/* The cross matrix and the prior's diagonal of bq_gp_marginal and bq_gp_marginal_box at host
+ * points without a fit: out (M x n column-major) = c(xq_i, x_j), pdiag (M) = P(xq_i, xq_i), by the
+ * kernels those entry points run.  xq: d x M (integrated axes' rows never read), x: d x n, keep:
+ * d flags.  Either output may be NULL, but not both; pdiag alone needs no x (n == 0); M == 0
+ * writes nothing.  BQ_ERR_BAD_ARG for h, w, the measure, keep and xq as there. */
+int bq_marginal_K(bq_ctx *ctx, const double *xq, int64_t M, const double *x, int64_t n, int64_t d,
+                  double h, const double *w, const int32_t *keep, const double *mu,
+                  const double *cov, double *out, double *pdiag);
+int bq_marginal_K_box(bq_ctx *ctx, const double *xq, int64_t M, const double *x, int64_t n,
+                      int64_t d, double h, const double *w, const int32_t *keep, const double *lo,
+                      const double *hi, double *out, double *pdiag);
 /* out (n1 x n2) = int K1(x1, x') K2(x', x2) N(x' | mu, cov) dx'    gauss_c.pyx:235-339 */
 int bq_int_K1_K2(bq_ctx *ctx, const double *x1, int64_t n1, const double *x2, int64_t n2,
                  int64_t d, double h1, const double *w1, double h2, const double *w2,
